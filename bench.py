@@ -1,8 +1,19 @@
 #!/usr/bin/env python3
 """bench.py -- the driver's measurement contract for the MY_MMult hot path.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run does what the headline needs and nothing else: set up, a lead-in of untimed launches (the length of
+the --full run's traced ramp, so that `value` is the same sustained rate), W warm-ups, K timed steps, the outputs
+(--dump-outputs), the line.  Everything else the line can carry -- the traced clock ramp (`cold`), the correctness
+checks of the timed C, the roofline object and its counter passes, the CPU baseline, the extras, and for N > 1 the
+broadcast / overlap / per-rank / single-GPU figures -- is measured with --full only (and there --no-extras,
+--no-cpu-baseline and --no-live-traffic leave parts of it out).
+
+--dump-outputs DIR: after the timed steps, what the last of them computed -- C, float32 -- goes to DIR/c.npy
+(DIR/c_rank<r>.npy per rank for N > 1): all of it when it fits DUMP_BYTES (over all ranks), else a fixed, seeded,
+sorted sample of its rows (dump_rows()).  The inputs are seeded, so the same arguments give the same inputs.
 
 A "step" is one MY_MMult call (device flavour, C = A*B) on synthetic inputs
 already resident in HBM (the reference excludes H2D/D2H from its timed region
@@ -24,8 +35,8 @@ too: cuda/test_MMult.cpp:85-98,121).
          (re-executes under torch.distributed.run on 127.0.0.1) and FAILS when
          fewer than N devices are visible -- it never falls back to fewer ranks.
 
-roofline.traffic, roofline.mfma_busy_frac and roofline.hbm_gbps are measured by the run itself (N=1, unless --no-extras /
---no-live-traffic): three rocprofv3 passes -- FETCH_SIZE, WRITE_SIZE, SQ_VALU_MFMA_BUSY_CYCLES + GRBM_GUI_ACTIVE, each in
+roofline.traffic, roofline.mfma_busy_frac and roofline.hbm_gbps are measured by the run itself (N=1 with --full, unless
+--no-extras / --no-live-traffic): three rocprofv3 passes -- FETCH_SIZE, WRITE_SIZE, SQ_VALU_MFMA_BUSY_CYCLES + GRBM_GUI_ACTIVE, each in
 its own run -- over a child process that launches the timed kernel on the same shape, while the host times REF_MMult;
 the committed pass of profiles/pmc_traffic.json rides along as traffic_committed_pass.  extras.sweep_gflops carries the
 metric's whole sweep (cuda/parameters.h:5-7: 25 sizes) for `auto`, rocBLAS, hipBLASLt and the VALU rung, and the literal
@@ -38,12 +49,12 @@ Cold vs sustained.  The reference times NREPEATS = 20 launches with no warm-up
 (cuda/test_MMult.cpp:98-118).  An idle MI355X starts a launch train below its
 sustained clock, so that convention and the contract's (W warm-ups, K timed
 steps at steady state) give different numbers; both are reported:
-  * the run opens with a per-launch trace of the process's first launches (`ramp_launches` of them: up to 400,
+  * a --full run opens with a per-launch trace of the process's first launches (`ramp_launches` of them: up to 400,
     about half a second; --ramp 0 switches it off, --ramp N bounds it) (mmh_trace_sgemm, one hipEvent pair
     each) -> `cold`: launch #1 (nothing but a launch since mmh_create warms the handle), the mean of launches
     1..20 (= the reference convention) and 2..21, and where the ramp ends;
-  * then W warm-up steps and K timed steps: `warmup` = W exactly, `ramp_launches` = the traced launches in
-    front of them, `untimed_launches` = their sum.  With --ramp 0 the W warm-ups are the only untimed
+  * then W warm-up steps and K timed steps: `warmup` = W exactly, `ramp_launches` = the traced (plain run: untraced)
+    launches in front of them, `untimed_launches` = their sum.  With --ramp 0 the W warm-ups are the only untimed
     launches of the process.
   --sweep adds the reference's square sweep (cuda/parameters.h:5-7: 1024 .. 4096 step 128, plus 8192 and
   16384) under the same sharding as the headline workload -> `extras.sweep_gflops_sharded`: the north star's
@@ -76,6 +87,8 @@ ROOFLINE_KEYS = ("bound", "achieved", "peak", "unit", "frac", "traffic", "kernel
 INT8_ROOFLINE_KEYS = ("bound", "achieved", "peak_spec", "peak_measured_random", "frac", "kernel", "kernel_ms", "achieved_8192",
                       "tops_4096_on_v_mfma_i32_16x16x32_i8", "16x16x32_bit_equal_to_16x16x64")
 SETTLE_MS = 150.0                 # sharded runs: untimed launches in front of the W warm-ups of BOTH timed regions (ranks, single-GPU reference)
+DUMP_BYTES = 48 << 20             # --dump-outputs: C's rows written, all ranks together (under 64 MB with the .npy headers)
+DUMP_SEED = 20260924              # ... and the seed of the row sample when C is larger than that
 
 
 def parse_args():
@@ -99,7 +112,25 @@ def parse_args():
                     help="N > 1: skip rank 0's run of the WHOLE problem on one GPU (the denominator of scaling_efficiency)")
     ap.add_argument("--sweep", action="store_true",
                     help="also run the reference's square sweep under this run's sharding (extras.sweep_gflops_sharded)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline: traced clock ramp, correctness of C, roofline "
+                         "and counters, CPU baseline, extras; N > 1: broadcast, overlap, per-rank and single-GPU figures")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write C of the last timed step (float32; a seeded row sample when large) to DIR/c.npy")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
+
+
+def dump_rows(rows: int, n: int, world: int):
+    """Rows of a rank's C (rows x n, float32) that --dump-outputs writes: None = all of them, when they fit the rank's share
+    of DUMP_BYTES; else a sorted sample drawn with DUMP_SEED -- the same rows on every run with the same arguments."""
+    import numpy as np
+    fit = max(1, DUMP_BYTES // world // (4 * n))
+    if rows <= fit:
+        return None
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(rows, fit, replace=False))
 
 
 def launch_ranks(args) -> int:
@@ -425,11 +456,24 @@ def main():
     c = torch.empty((rows, n), device=dev)
     torch.cuda.synchronize()
 
+    def step():
+        if rows:
+            mm.sgemm(rows, n, n, a.data_ptr(), n, b.data_ptr(), n, c.data_ptr(), n, False, stream)
+
     # ---- the clock ramp, traced: the first RAMP launches of this process, one event pair each ----
     # (before the broadcast on purpose: B's contents do not matter for timing, and the chip is as
-    # cold here as it will ever be)
-    trace = []
-    if rows and args.ramp > 0:
+    # cold here as it will ever be).  A plain run launches the same lead-in untraced: bursts of 25
+    # until RAMP_SECONDS or --ramp launches, whichever comes first.
+    trace, lead_in = [], 0
+    if rows and args.ramp > 0 and not (args.full or args.ramp_csv):
+        t_s = time.perf_counter()
+        while lead_in < args.ramp and time.perf_counter() - t_s < RAMP_SECONDS:
+            burst = min(25, args.ramp - lead_in)
+            for _ in range(burst):
+                step()
+            torch.cuda.synchronize()
+            lead_in += burst
+    elif rows and args.ramp > 0:
         trace = mm.trace_sgemm(rows, n, n, a.data_ptr(), n, b.data_ptr(), n, c.data_ptr(), n, count=min(25, args.ramp),
                                stream=stream)
         more = max(0, min(args.ramp - 25, int(RAMP_SECONDS / (max(trace[-1], 1e-3) * 1e-3)) - 25))
@@ -451,6 +495,7 @@ def main():
         torch.cuda.synchronize()
         dist.barrier()
         bcast_ms = (time.perf_counter() - t0) * 1e3
+    if sharded and args.full:
         # second broadcast = steady-state cost without communicator warm-up
         t0 = time.perf_counter()
         sh.broadcast_b(b, src=0, always=True)
@@ -458,14 +503,13 @@ def main():
         dist.barrier()
         bcast_ms = min(bcast_ms, (time.perf_counter() - t0) * 1e3)
 
-    overlap_ms = None
-    if sharded:
+    overlap_ms, streamed_error = None, None
+    if sharded and args.full:
         # broadcast hidden behind the GEMM: B in --b-chunks K-chunks, consumed with accumulate (same bits)
         def gemm_acc(x, y, out, accumulate):
             mm.sgemm(x.shape[0], n, x.shape[1], x.data_ptr(), x.stride(0), y.data_ptr(), y.stride(0),
                      out.data_ptr(), out.stride(0), accumulate, stream)
         c_stream = torch.empty_like(c)
-        streamed_error = None
         try:
             for rep in range(2):
                 dist.barrier()
@@ -483,10 +527,6 @@ def main():
             dist.all_reduce(okf, op=dist.ReduceOp.MIN)
             if not int(okf.item()):
                 overlap_ms = None
-
-    def step():
-        if rows:
-            mm.sgemm(rows, n, n, a.data_ptr(), n, b.data_ptr(), n, c.data_ptr(), n, False, stream)
 
     # N > 1 / --force-shard: the broadcast phases above leave the chip idle between their host synchronisations, and W
     # warm-ups of a sub-millisecond launch do not bring the clock back: untimed launches for ~SETTLE_MS first -- the SAME
@@ -519,17 +559,22 @@ def main():
         elapsed = float(t.item())
     ms_per_step = elapsed * 1e3 / args.steps
     gflops = 2.0 * m * n * n * 1e-9 / (ms_per_step * 1e-3)
+    # --dump-outputs: C as the last timed step left it, held on the device until the line is ready
+    dump, dump_sel = None, None
+    if args.dump_outputs and rows:
+        dump_sel = dump_rows(rows, n, world)
+        dump = c.clone() if dump_sel is None else c.index_select(0, torch.as_tensor(dump_sel, device=dev))
 
     # dominant-kernel duration: hipEvents on the launch stream around K back-to-back launches
     # (issued right behind the timed region so the clock state is the same)
     kern_ms = mm.time_sgemm(rows, n, n, a.data_ptr(), n, b.data_ptr(), n, c.data_ptr(), n,
-                            warmup=1, reps=args.steps, stream=stream) if rows else 0.0
+                            warmup=1, reps=args.steps, stream=stream) if (rows and args.full) else 0.0
     launched = H.last_launch()
 
     # N > 1: every rank's own kernel time, and -- in the SAME process group, right behind the timed region -- the whole
     # problem on rank 0's GPU alone: the denominator of scaling_efficiency = value(N) / (N * value(1)).
     per_rank_ms, single_ms = None, None
-    if sharded:
+    if sharded and args.full:
         t = torch.tensor([kern_ms], device=dev, dtype=torch.float64)
         parts = [torch.zeros_like(t) for _ in range(world)]
         dist.all_gather(parts, t)
@@ -588,7 +633,7 @@ def main():
     #      element at this size (tests/test_gpu_parity.py::test_headline_size_4096);
     #  (2) sampled rows against an fp64 contraction.
     bit_equal = None
-    if rows:
+    if rows and args.full:
         mm.set_kernel("mfma_tiles")
         c_ref = torch.empty_like(c)
         mm.sgemm(rows, n, n, a.data_ptr(), n, b.data_ptr(), n, c_ref.data_ptr(), n, False, stream)
@@ -602,7 +647,7 @@ def main():
         assert err < 2e-7 * n + 1e-6, f"rank {rank}: sampled-row check failed ({err})"
 
     streamed_equal = True
-    if sharded and rows and overlap_ms is not None:
+    if sharded and args.full and rows and overlap_ms is not None:
         streamed_equal = bool(torch.equal(c_stream, c))
         if dist:
             flag = torch.tensor([1 if streamed_equal else 0], device=dev)
@@ -626,33 +671,37 @@ def main():
             "data": "synthetic uniform [-1,1) fp32, seeded on device",
             "config": {"workload": workload, "m": m, "n": n, "k": n, "kernel": H.kernel_name(mm.get_kernel()),
                        "parallelism": parallelism, "rows_per_rank": rows},
-            "ramp_launches": len(trace), "untimed_launches": len(trace) + settle_launches + args.warmup,
-            "cold": {
-                "what": f"per-launch hipEvent trace of this process's first {len(trace)} launches (rank 0's panel)",
-                "launch_1_ms": round(trace[0], 4) if trace else None,
-                "reference_convention_20_launches_no_warmup_tflops": tf(ref20),
-                "launches_2_to_21_tflops": tf(cold20),
-                "launches_2_to_21_pct_of_peak": round(100.0 * tf(cold20) / PEAK_FP32_MFMA_TFLOPS, 2) if cold20 else None,
-                "sustained_median_last_50_tflops": tf(tail),
-                "launches_until_within_1pct_of_sustained": settled,
-            },
-            "value_cold": round(2.0 * m * n * n * 1e-9 / (cold20 * 1e-3), 1) if cold20 else None,   # launches 2..21
+            "ramp_launches": len(trace) + lead_in, "untimed_launches": len(trace) + lead_in + settle_launches + args.warmup,
             "pct_of_fp32_mfma_peak": round(100.0 * gflops / (world * PEAK_FP32_MFMA_TFLOPS * 1e3), 2),
-            "bit_equal_to_128x128_tile_launch": bit_equal,
-            "roofline": {"bound": "mfma", "achieved": round(achieved, 2), "peak": PEAK_FP32_MFMA_TFLOPS,
-                         "unit": "TFLOP/s", "frac": round(achieved / PEAK_FP32_MFMA_TFLOPS, 4),
-                         "traffic": pmc_traffic(n) if not sharded else None,
-                         "traffic_source": "profiles/pmc_traffic.json (committed rocprofv3 --pmc pass of this command; "
-                                           "not re-measured in-run)" if not sharded else None,
-                         "kernel": launched,
-                         "kernel_ms": round(kern_ms, 4),
-                         "algorithmic_flops_per_launch": launch_flops,
-                         "algorithmic_bytes_per_launch": 4.0 * (rows * n + n * n + rows * n)},
         }
         if sharded:
             out["settle_launches"] = settle_launches          # untimed, in front of the W warm-ups (and of the single-GPU reference's)
             out["rccl_ranks"] = dist.get_world_size()
             out["backend"] = str(dist.get_backend())
+        if args.full:
+            out.update({
+                "cold": {
+                    "what": f"per-launch hipEvent trace of this process's first {len(trace)} launches (rank 0's panel)",
+                    "launch_1_ms": round(trace[0], 4) if trace else None,
+                    "reference_convention_20_launches_no_warmup_tflops": tf(ref20),
+                    "launches_2_to_21_tflops": tf(cold20),
+                    "launches_2_to_21_pct_of_peak": round(100.0 * tf(cold20) / PEAK_FP32_MFMA_TFLOPS, 2) if cold20 else None,
+                    "sustained_median_last_50_tflops": tf(tail),
+                    "launches_until_within_1pct_of_sustained": settled,
+                },
+                "value_cold": round(2.0 * m * n * n * 1e-9 / (cold20 * 1e-3), 1) if cold20 else None,   # launches 2..21
+                "bit_equal_to_128x128_tile_launch": bit_equal,
+                "roofline": {"bound": "mfma", "achieved": round(achieved, 2), "peak": PEAK_FP32_MFMA_TFLOPS,
+                             "unit": "TFLOP/s", "frac": round(achieved / PEAK_FP32_MFMA_TFLOPS, 4),
+                             "traffic": pmc_traffic(n) if not sharded else None,
+                             "traffic_source": "profiles/pmc_traffic.json (committed rocprofv3 --pmc pass of this command; "
+                                               "not re-measured in-run)" if not sharded else None,
+                             "kernel": launched,
+                             "kernel_ms": round(kern_ms, 4),
+                             "algorithmic_flops_per_launch": launch_flops,
+                             "algorithmic_bytes_per_launch": 4.0 * (rows * n + n * n + rows * n)},
+            })
+        if sharded and args.full:
             out["bcast_ms"] = round(bcast_ms, 3)
             out["bcast_gbps"] = round(4.0 * n * n / (bcast_ms * 1e-3) / 1e9, 1) if bcast_ms else None
             out["gemm_ms_per_rank"] = per_rank_ms               # each rank's own hipEvent time per launch of its panel
@@ -687,7 +736,7 @@ def main():
                                            "pct_of_peak_at_4096": (round(100.0 * sweep_sharded["4096"] / (world * PEAK_FP32_MFMA_TFLOPS * 1e3), 2)
                                                                    if sweep_sharded.get("4096") else None),
                                            "gflops": sweep_sharded}
-        if not sharded and not args.no_extras:
+        if not sharded and args.full and not args.no_extras:
             extras = {}
             try:
                 # configs[1]/[2]: the square sweep at the BASELINE sizes, LDS-tiled VALU kernel
@@ -758,7 +807,7 @@ def main():
         # The counter passes (three child processes under rocprofv3, GPU) run WHILE the host times REF_MMult (one core):
         # neither needs what the other uses, and the run stays inside its budget.
         pmc_thread, pmc_box = None, {}
-        if not sharded and not args.no_live_traffic and not args.no_extras and "ROCPROFILER_" not in " ".join(os.environ):
+        if not sharded and args.full and not args.no_live_traffic and not args.no_extras and "ROCPROFILER_" not in " ".join(os.environ):
             # (not under a profiler already: gpu_profile.sh runs this script under rocprofv3)
             import threading
             torch.cuda.synchronize()
@@ -768,7 +817,7 @@ def main():
                     pmc_box[lib] = vendor_sweep_via_harness(lib, [p for p in SWEEP_SIZES if p <= n])
             pmc_thread = threading.Thread(target=background)
             pmc_thread.start()
-        if not sharded and not args.no_cpu_baseline:
+        if not sharded and args.full and not args.no_cpu_baseline:
             try:
                 out["cpu_baseline"] = cpu_baseline(n)
             except Exception as e:   # reported, never fatal (the contract wants the object; say why it is missing)
@@ -800,12 +849,19 @@ def main():
             rl["mfma_busy_frac"] = live.get("mfma_busy_frac")
             rl["effective_clock_ghz_under_counters"] = live.get("effective_clock_ghz")
             rl["kernel_us_under_counters"] = live.get("kernel_us_under_counters")
-        if not sharded:
+        if not sharded and args.full:
             rl = out["roofline"]
             rl.setdefault("mfma_busy_frac", None)
             # HBM-side GB/s of the timed kernel: the counters' bytes per launch over the launch's duration
             rl["hbm_gbps"] = round(rl["traffic"] / (kern_ms * 1e-3) / 1e9, 1) if (rl.get("traffic") and kern_ms) else None
             rl["hbm_frac_of_8tbps"] = round(rl["hbm_gbps"] / 8000.0, 4) if rl["hbm_gbps"] else None
+    if dump is not None:
+        import numpy as np
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        name = "c.npy" if world == 1 else f"c_rank{rank}.npy"
+        np.save(os.path.join(args.dump_outputs, name), dump.cpu().numpy())
+        sys.stderr.write(f"bench.py: wrote {name}: C of the last timed step, "
+                         f"{'all' if dump_sel is None else f'{len(dump_sel)} seeded sample rows'} of {rows} x {n}\n")
     mm.close()
     if dist:
         dist.barrier()

@@ -73,13 +73,13 @@ def test_the_committed_line_of_the_round_has_the_schema():
 
 @pytest.mark.gpu
 def test_a_live_default_line_has_the_schema():
-    """`python bench.py` as the driver runs it (N = 1, defaults but fewer steps): one line, every key."""
+    """`python bench.py --full` (N = 1, defaults but fewer steps): one line, every key."""
     import subprocess
     import sys
     import time
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     t0 = time.time()
-    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--steps", "10", "--warmup", "3"], env=env, capture_output=True,
+    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--full", "--steps", "10", "--warmup", "3"], env=env, capture_output=True,
                        text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]

@@ -46,12 +46,12 @@ def test_the_committed_one_rank_line_has_the_sharded_schema():
 
 @pytest.mark.gpu
 def test_a_live_one_rank_sharded_sweep_has_the_schema():
-    """`bench.py --gpus 1 --force-shard --sweep`: process group, RCCL broadcast, streamed B, per-rank times, the
+    """`bench.py --gpus 1 --force-shard --sweep --full`: process group, RCCL broadcast, streamed B, per-rank times, the
     single-GPU reference and the square sweep -- on one rank, the code an N-rank run executes."""
     import subprocess
     import sys
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
-    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--force-shard", "--n", "4096", "--steps", "2",
+    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--full", "--gpus", "1", "--force-shard", "--n", "4096", "--steps", "2",
                         "--warmup", "1", "--sweep", "--b-chunks", "4", "--no-extras", "--no-cpu-baseline"], env=env, capture_output=True,
                        text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]

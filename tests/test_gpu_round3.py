@@ -355,17 +355,19 @@ def test_one_element_off_the_grid_is_not_a_cliff(mm, n0):
     column of tiles start a second round on 33 of 256 CUs (profiles/r04_notes.md section 3, r04_thin_tiles_edge.md)."""
     import torch
     mm.set_kernel("auto")
-    rates = {}
+    # the three sizes' bursts take turns, so that a clock dip of a few hundred ms costs each size one burst of its five,
+    # not one size all of them (3071 once read 0.88 x 3072 while 3073 read 0.93)
+    ops = {}
     for n in (n0, n0 - 1, n0 + 1):
-        a = torch.rand((n, n), device="cuda") * 2 - 1
-        b = torch.rand((n, n), device="cuda") * 2 - 1
-        c = torch.empty((n, n), device="cuda")
-        best = 1e9
-        for _ in range(5):
+        ops[n] = [torch.rand((n, n), device="cuda") * 2 - 1, torch.rand((n, n), device="cuda") * 2 - 1,
+                  torch.empty((n, n), device="cuda")]
+    best = {n: 1e9 for n in ops}
+    for _ in range(5):
+        for n, (a, b, c) in ops.items():
             ms = mm.time_sgemm(n, n, n, a.data_ptr(), n, b.data_ptr(), n, c.data_ptr(), n, warmup=40, reps=40,
                                stream=torch.cuda.current_stream().cuda_stream)
-            best = min(best, ms)
-        rates[n] = 2.0 * n ** 3 / (best * 1e-3) / 1e12
+            best[n] = min(best[n], ms)
+    rates = {n: 2.0 * n ** 3 / (best[n] * 1e-3) / 1e12 for n in ops}
     # measured, round 4 (profiles/r04_offgrid_vs_vendor.json against the harness sweep): N - 1 at 0.87 / 0.96 / 0.97 / 0.95 of
     # N, N + 1 at 0.65 / 0.80 / 0.87 / 0.88 -- the whole-tile instantiation of N has 1-2 us less fixed cost than the guarded
     # one (the cost table carries both), which is 5-10 % of a launch at N = 1024 .. 1536.  The bars leave a box's worth of

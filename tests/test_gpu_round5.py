@@ -126,7 +126,7 @@ def test_the_one_rank_sharded_bench_line_reads_a_scaling_efficiency_of_one():
     import sys
     seen = []
     for attempt in range(2):      # (one retry: two of the round's 125 sustained sweep points read a 15 % transient dip -- a clock excursion of
-        r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--force-shard", "--n", "4096", "--steps", "20",   # tens of ms;
+        r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--full", "--gpus", "1", "--force-shard", "--n", "4096", "--steps", "20",   # tens of ms;
                             "--warmup", "3", "--no-cpu-baseline", "--no-extras"], capture_output=True, text=True, timeout=600,               # 20 steps here are 18 ms)
                            env=dict(os.environ, MASTER_PORT=str(29577 + attempt)))
         assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])

@@ -1,8 +1,9 @@
 """The families that live in the TOOLS build only (libmmult_hip_ab.so, -DMMH_AB_BUILD) -- kept for their measurements,
 not shipped: the rim (round 3), the 32x32x2 LDS-DMA tiles and the one-loader / 160-wide forms of K2W (round 4), the
 16-MFMA-per-phase int8 ping-pong.  Their results are still held to the oracle's bits here, in a process of their own
-that loads the tools library -- when that library has been built (`python -c "import how_to_optimize_gemm_amd as H;
-H.build.build_ab_library()"`, minutes); the product library's side -- it rejects every one of these ids and switches --
+that loads the tools library -- built here on first use when a checkout has not built it yet (`python -c "import
+how_to_optimize_gemm_amd as H; H.build.build_ab_library()"`, minutes; build() compiles the product library only);
+the product library's side -- it rejects every one of these ids and switches --
 is tests/test_abi.py and the last test below."""
 import os
 import subprocess
@@ -12,7 +13,16 @@ import pytest
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 AB_LIB = os.path.join(REPO, "how-to-optimize-gemm_amd", "libmmult_hip_ab.so")
-needs_ab = pytest.mark.skipif(not os.path.exists(AB_LIB), reason="libmmult_hip_ab.so (the tools build) has not been built")
+needs_ab = pytest.mark.usefixtures("ab_library")
+
+
+@pytest.fixture(scope="module")
+def ab_library():
+    """libmmult_hip_ab.so, compiled now if it is missing or older than its sources (a no-op when it is fresh)."""
+    import how_to_optimize_gemm_amd as H
+    path = H.build.build_ab_library()
+    assert os.path.samefile(path, AB_LIB)
+    return path
 
 
 def _run(script, timeout=900):

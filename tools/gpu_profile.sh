@@ -18,7 +18,7 @@ OUT=$REPO/gpurun_out/$TAG
 PASSES=${PASSES:-"trace pmc1 pmc2 pmc3 pmc4"}
 KERNEL=${KERNEL:-mfma}
 rm -rf "$OUT"; mkdir -p "$OUT"
-BENCH="python $REPO/bench.py --no-extras --no-cpu-baseline --kernel $KERNEL ${BENCH_ARGS:-}"
+BENCH="python $REPO/bench.py --full --no-extras --no-cpu-baseline --kernel $KERNEL ${BENCH_ARGS:-}"
 cd /tmp
 declare -A CTRS
 CTRS[pmc1]="SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_ACTIVE_INST_ANY GRBM_GUI_ACTIVE"

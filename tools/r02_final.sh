@@ -20,10 +20,10 @@ sweep auto_ref_convention KERNEL=auto REF=threads WARMUP=0
 sweep auto_splitk KERNEL=auto SPLITK=1 REF=threads WARMUP=30 PLAST=2048
 tail -2 $OUT/output_MMult_hip_auto_ref_convention.m
 # (the sustained-clock sweeps: tools/r02_sweeps.sh)
-timeout 600 python bench.py --gpus 1 --steps 20 --warmup 5 --ramp-csv $OUT/clock_ramp.csv > $OUT/bench.json 2> $OUT/bench.err
+timeout 600 python bench.py --full --gpus 1 --steps 20 --warmup 5 --ramp-csv $OUT/clock_ramp.csv > $OUT/bench.json 2> $OUT/bench.err
 tail -c 300 $OUT/bench.json; echo
-timeout 120 python bench.py --gpus 2 --steps 2 --warmup 1 > $OUT/bench_gpus2.out 2> $OUT/bench_gpus2.err; echo "bench --gpus 2 rc=$?" >> $OUT/bench_gpus2.err
-timeout 300 python bench.py --gpus 1 --force-shard --n 8192 --steps 5 --warmup 2 > $OUT/bench_forceshard.json 2> $OUT/bench_forceshard.err
+timeout 120 python bench.py --full --gpus 2 --steps 2 --warmup 1 > $OUT/bench_gpus2.out 2> $OUT/bench_gpus2.err; echo "bench --gpus 2 rc=$?" >> $OUT/bench_gpus2.err
+timeout 300 python bench.py --full --gpus 1 --force-shard --n 8192 --steps 5 --warmup 2 > $OUT/bench_forceshard.json 2> $OUT/bench_forceshard.err
 timeout 900 python tools/smalln_sweep.py --rounds 3 --sizes $(seq -s, 1024 128 4096) --variants auto,rocblas,hipblaslt,valu > $OUT/sweep_vs_vendor.md 2> $OUT/sweep_vs_vendor.err
 grep -v "^<" $OUT/sweep_vs_vendor.md | tail -26
 for panels in 0 -1; do
@@ -43,7 +43,7 @@ hipcc --offload-arch=gfx950 -O3 tools/probes/hbm_patterns.hip -o /tmp/hbm_patter
 # cold start of the two N=4096 candidates, fresh process each, alternating (auto = the 256x256 tile)
 for i in 1 2 3; do
   for kk in auto mfma_64x64_dma; do
-    timeout 300 python bench.py --steps 20 --warmup 5 --no-extras --no-cpu-baseline --kernel $kk 2> /dev/null | \
+    timeout 300 python bench.py --full --steps 20 --warmup 5 --no-extras --no-cpu-baseline --kernel $kk 2> /dev/null | \
       python -c "import json,sys; d=json.load(sys.stdin); c=d['cold']; print('$kk', 'sustained', d['value'], 'launch1_ms', c['launch_1_ms'], 'first20', c['reference_convention_20_launches_no_warmup_tflops'], 'launches2to21', c['launches_2_to_21_tflops'], 'within1pct_after', c['launches_until_within_1pct_of_sustained'])" >> $OUT/cold_start.txt
     sleep 2
   done

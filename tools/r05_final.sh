@@ -59,14 +59,14 @@ if has nonsquare; then
         <(awk 'NF==3 && $1+0>0{print $2}' $OUT/output_MMult_hip_hipblaslt_nonsquare.m)
 fi
 if has bench; then
-  timeout 600 python bench.py --gpus 1 --steps 20 --warmup 5 --ramp-csv $OUT/clock_ramp.csv > $OUT/bench.json 2> $OUT/bench.err
+  timeout 600 python bench.py --full --gpus 1 --steps 20 --warmup 5 --ramp-csv $OUT/clock_ramp.csv > $OUT/bench.json 2> $OUT/bench.err
   tail -c 300 $OUT/bench.json; echo
-  timeout 300 python bench.py --gpus 1 --steps 20 --warmup 5 --ramp 0 --no-extras --no-cpu-baseline > $OUT/bench_noramp.json 2> $OUT/bench_noramp.err
-  timeout 300 python bench.py --gpus 1 --force-shard --n 8192 --steps 5 --warmup 2 --sweep --b-chunks 4 > $OUT/bench_forceshard.json 2> $OUT/bench_forceshard.err
-  timeout 120 python bench.py --gpus 2 --steps 2 --warmup 1 > $OUT/bench_gpus2.out 2> $OUT/bench_gpus2.err; echo "bench --gpus 2 rc=$?" >> $OUT/bench_gpus2.err
+  timeout 300 python bench.py --full --gpus 1 --steps 20 --warmup 5 --ramp 0 --no-extras --no-cpu-baseline > $OUT/bench_noramp.json 2> $OUT/bench_noramp.err
+  timeout 300 python bench.py --full --gpus 1 --force-shard --n 8192 --steps 5 --warmup 2 --sweep --b-chunks 4 > $OUT/bench_forceshard.json 2> $OUT/bench_forceshard.err
+  timeout 120 python bench.py --full --gpus 2 --steps 2 --warmup 1 > $OUT/bench_gpus2.out 2> $OUT/bench_gpus2.err; echo "bench --gpus 2 rc=$?" >> $OUT/bench_gpus2.err
   for i in 1 2; do
     for kk in auto mfma_128x64_dma mfma_64x64_dma5 mfma_256x256; do
-      timeout 300 python bench.py --steps 20 --warmup 5 --no-extras --no-cpu-baseline --kernel $kk 2> /dev/null | \
+      timeout 300 python bench.py --full --steps 20 --warmup 5 --no-extras --no-cpu-baseline --kernel $kk 2> /dev/null | \
         python -c "import json,sys; d=json.load(sys.stdin); c=d['cold']; print('$kk', 'sustained', d['value'], 'launch1_ms', c['launch_1_ms'], 'first20', c['reference_convention_20_launches_no_warmup_tflops'], 'launches2to21', c['launches_2_to_21_tflops'], 'within1pct_after', c['launches_until_within_1pct_of_sustained'])" >> $OUT/cold_start.txt
       sleep 2
     done
