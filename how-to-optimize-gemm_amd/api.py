@@ -32,6 +32,7 @@ OPT_RIM = 11
 OPT_STREAMK_CHAIN = 12
 OPT_PERSIST = 13
 OPT_RIM5 = 14
+OP_N, OP_T = 0, 1   # mmh_sgemm_op's operand layouts (include/mmult_hip.h)
 KERNELS = {"auto": KERNEL_AUTO, "valu": KERNEL_VALU, "mfma": KERNEL_MFMA,
            "mfma256": KERNEL_MFMA_256, "naive": KERNEL_NAIVE, "mfma_simple": KERNEL_MFMA_SIMPLE,
            "mfma_pipe": KERNEL_MFMA_PIPE, "mfma_tiles": 10, "mfma_128x64": 8, "mfma_64x64": 11, "mfma_256x256": 12,
@@ -58,6 +59,7 @@ EXPORTS = [
     "mmh_rccl_version",
     "mmh_sgemm_sharded", "mmh_time_sgemm", "mmh_time_comparator", "mmh_trace_sgemm", "mmh_probe_mfma_f32", "mmh_probe_valu_f32", "mmh_probe_mfma_i8",
     "mmh_probe_mfma_i8_sustained", "mmh_probe_hbm_copy", "mmh_probe_hbm_read", "mmh_probe_lds_read", "mmh_streamk_plan", "mmh_auto_plan",
+    "mmh_sgemm_op", "mmh_time_sgemm_op", "mmh_auto_plan_op",
 ]
 
 
@@ -103,6 +105,16 @@ def auto_plan(m: int, n: int, k: int, lda: int = 0, ldb: int = 0, ldc: int = 0, 
     kern, grid, tiles = C.c_int(), C.c_int(), C.c_long()
     _check(lib().mmh_auto_plan(m, n, k, lda or k, ldb or n, ldc or n, base_align, cu_count, C.byref(kern), C.byref(tiles),
                                C.byref(grid)), "mmh_auto_plan")
+    names = {v: name for name, v in KERNELS.items() if name != "mfma256"}
+    return names.get(kern.value, str(kern.value)), tiles.value, grid.value
+
+
+def auto_plan_op(transa: int, transb: int, m: int, n: int, k: int, lda: int = 0, ldb: int = 0, ldc: int = 0, base_align: int = 16,
+                 cu_count: int = 256):
+    """auto_plan for mmh_sgemm_op (OP_N / OP_T per operand; lda / ldb default to the dense stored rows: k or m, n or k)."""
+    kern, grid, tiles = C.c_int(), C.c_int(), C.c_long()
+    _check(lib().mmh_auto_plan_op(transa, transb, m, n, k, lda or (m if transa else k), ldb or (k if transb else n), ldc or n,
+                                  base_align, cu_count, C.byref(kern), C.byref(tiles), C.byref(grid)), "mmh_auto_plan_op")
     names = {v: name for name, v in KERNELS.items() if name != "mfma256"}
     return names.get(kern.value, str(kern.value)), tiles.value, grid.value
 
@@ -175,6 +187,9 @@ def lib() -> C.CDLL:
     L.mmh_kernel_name.restype = C.c_char_p
     gemm = [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp, C.c_int, vp, C.c_int]
     L.mmh_sgemm.argtypes = gemm + [C.c_int, vp]
+    L.mmh_sgemm_op.argtypes = [vp, C.c_int, C.c_int] + gemm[1:] + [C.c_int, vp]
+    L.mmh_time_sgemm_op.argtypes = [vp, C.c_int, C.c_int] + gemm[1:] + [C.c_int, C.c_int, vp, fp]
+    L.mmh_auto_plan_op.argtypes = [C.c_int] * 10 + [ip, C.POINTER(C.c_long), ip]
     L.mmh_sgemm_host.argtypes = gemm + [C.c_int]
     L.mmh_sgemm_host_timed.argtypes = gemm + [C.c_int, C.POINTER(C.c_float)]
     L.mmh_igemm_s8.argtypes = gemm + [C.c_int, vp]
@@ -372,6 +387,13 @@ class MMult:
         _check(lib().mmh_sgemm(self._h, m, n, k, dA, lda, dB, ldb, dC, ldc, int(bool(accumulate)),
                                stream), "mmh_sgemm")
 
+    def sgemm_op(self, transa, transb, m, n, k, dA: int, lda, dB: int, ldb, dC: int, ldc, accumulate=False,
+                 stream: int = 0) -> None:
+        """C = op(A) op(B) (+ C), row-major: transa = OP_T reads A stored k x m (lda >= m), transb = OP_T B stored n x k
+        (ldb >= k).  (OP_N, OP_N) is sgemm."""
+        _check(lib().mmh_sgemm_op(self._h, int(transa), int(transb), m, n, k, dA, lda, dB, ldb, dC, ldc, int(bool(accumulate)),
+                                  stream), "mmh_sgemm_op")
+
     def MY_MMult_device(self, m, n, k, d_A: int, lda, d_B: int, ldb, d_C: int, ldc, stream: int = 0):
         """cuda/test_MMult.cpp:102 -- MY_MMult(handle, m, n, k, d_A, k, d_B, n, d_C, n):
         C = A*B on device pointers, asynchronous."""
@@ -444,8 +466,22 @@ class MMult:
         ld = t.stride(0) if rows > 1 else max(cols, 1)
         return t.data_ptr(), max(ld, 1)
 
+    def _operand_args(self, t, rows, cols, what):
+        """(data_ptr, leading dimension, OP_N / OP_T) of a matmul operand: a row-major window as _tensor_args takes it,
+        or else a TRANSPOSED view -- stride(0) == 1, stride(1) >= rows (w.t(), a .t() of a row-strided window) --, whose
+        .t() is such a window.  A tensor both readings take (one row or one column) is read row-major."""
+        import torch
+        try:
+            return self._tensor_args(t, rows, cols, what, torch.float32) + (OP_N,)
+        except MMultError:
+            if not (t.dim() == 2 and tuple(t.shape) == (rows, cols) and cols > 1 and (rows <= 1 or t.stride(0) == 1)
+                    and t.stride(1) >= max(rows, 1)):
+                raise
+        return self._tensor_args(t.t(), cols, rows, what, torch.float32) + (OP_T,)
+
     def matmul(self, a, b, out=None, accumulate: bool = False):
-        """C = A @ B (+ C) for fp32 CUDA tensors, on torch's current stream."""
+        """C = A @ B (+ C) for fp32 CUDA tensors, on torch's current stream.  A and B may be transposed views (x @ w.t(),
+        a.t() @ b): they are read in place through mmh_sgemm_op; `out` is row-major."""
         import torch
         if a.dtype != torch.float32 or b.dtype != torch.float32:
             raise MMultError(ERR_INVALID_ARG, "matmul", "fp32 only")
@@ -457,11 +493,14 @@ class MMult:
             if accumulate:
                 raise MMultError(ERR_INVALID_ARG, "matmul", "accumulate needs out=")
             out = torch.empty((m, n), dtype=torch.float32, device=a.device)
-        pa, lda = self._tensor_args(a, m, k, "matmul(A)", torch.float32)
-        pb, ldb = self._tensor_args(b, k, n, "matmul(B)", torch.float32)
+        pa, lda, ta = self._operand_args(a, m, k, "matmul(A)")
+        pb, ldb, tb = self._operand_args(b, k, n, "matmul(B)")
         pc, ldc = self._tensor_args(out, m, n, "matmul(C)", torch.float32)
         stream = torch.cuda.current_stream(a.device).cuda_stream
-        self.sgemm(m, n, k, pa, lda, pb, ldb, pc, ldc, accumulate, stream)
+        if ta == OP_N and tb == OP_N:
+            self.sgemm(m, n, k, pa, lda, pb, ldb, pc, ldc, accumulate, stream)
+        else:
+            self.sgemm_op(ta, tb, m, n, k, pa, lda, pb, ldb, pc, ldc, accumulate, stream)
         return out
 
     def igemm_s8(self, a, b, out=None, accumulate: bool = False):
@@ -556,6 +595,13 @@ class MMult:
         ms = C.c_float(0)
         _check(lib().mmh_time_sgemm(self._h, m, n, k, dA, lda, dB, ldb, dC, ldc, warmup, reps, stream,
                                     C.byref(ms)), "mmh_time_sgemm")
+        return ms.value
+
+    def time_sgemm_op(self, transa, transb, m, n, k, dA, lda, dB, ldb, dC, ldc, warmup=1, reps=20, stream: int = 0) -> float:
+        """time_sgemm for mmh_sgemm_op (every op pair, (OP_N, OP_N) included)."""
+        ms = C.c_float(0)
+        _check(lib().mmh_time_sgemm_op(self._h, int(transa), int(transb), m, n, k, dA, lda, dB, ldb, dC, ldc, warmup, reps, stream,
+                                       C.byref(ms)), "mmh_time_sgemm_op")
         return ms.value
 
     def time_comparator(self, which: str, m, n, k, dA, lda, dB, ldb, dC, ldc, warmup=1, reps=20, stream: int = 0) -> float:
@@ -699,7 +745,7 @@ def sgemm_sharded(ngpus: int, a: np.ndarray, b: np.ndarray, kernel="mfma"):
 
 
 __all__ = ["MMult", "ShardedMMult", "MMultError", "lib", "use_ab_library", "device_count", "rccl_version", "shard_rows", "shard_chunks",
-           "kernel_name", "last_launch", "use_timeline_library", "streamk_plan", "auto_plan", "sgemm_sharded", "KERNELS", "CHAIN_KERNELS", "AB_LIB_PATH",
+           "kernel_name", "last_launch", "use_timeline_library", "streamk_plan", "auto_plan", "auto_plan_op", "OP_N", "OP_T", "sgemm_sharded", "KERNELS", "CHAIN_KERNELS", "AB_LIB_PATH",
            "OPT_SPLITK", "OPT_HOST_PANELS", "OPT_STREAMK_SPIN_LIMIT", "OPT_FAULT_INJECT", "OPT_STREAMK_ORDER", "OPT_DMA_EDGE", "OPT_STREAMK_DELEGATIONS", "OPT_RIM", "OPT_STREAMK_CHAIN", "OPT_PERSIST", "OPT_RIM5", "KERNEL_AUTO", "KERNEL_VALU", "KERNEL_MFMA", "KERNEL_MFMA_256", "KERNEL_NAIVE", "KERNEL_MFMA_SIMPLE", "KERNEL_MFMA_PIPE",
            "EXPORTS", "LIB_PATH", "OPT_STREAMK", "OPT_STREAMK_TIMEOUTS", "OPT_IGEMM_MODE", "OK", "ERR_INVALID_ARG", "ERR_HIP", "ERR_NO_DEVICE",
            "ERR_UNSUPPORTED", "ERR_ALLOC", "ERR_COMM"]

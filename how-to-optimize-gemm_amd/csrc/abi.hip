@@ -360,22 +360,33 @@ int mmh_sgemm(mmh_handle_t h, int m, int n, int k, const float *dA, int lda, con
   return sgemm_on(h, h->kernel, m, n, k, dA, lda, dB, ldb, dC, ldc, accumulate,
                   static_cast<hipStream_t>(stream));
 }
+int mmh_sgemm_op(mmh_handle_t h, int transa, int transb, int m, int n, int k, const float *dA, int lda, const float *dB,
+                 int ldb, float *dC, int ldc, int accumulate, void *stream) {
+  if (!h) return MMH_ERR_INVALID_ARG;
+  ENTER(h);
+  return sgemm_op_on(h, h->kernel, transa, transb, m, n, k, dA, lda, dB, ldb, dC, ldc, accumulate,
+                     static_cast<hipStream_t>(stream));
+}
 int mmh_time_sgemm(mmh_handle_t h, int m, int n, int k, const float *dA, int lda, const float *dB,
                    int ldb, float *dC, int ldc, int warmup, int reps, void *stream,
                    float *ms_per_call) {
+  return mmh_time_sgemm_op(h, MMH_OP_N, MMH_OP_N, m, n, k, dA, lda, dB, ldb, dC, ldc, warmup, reps, stream, ms_per_call);
+}
+int mmh_time_sgemm_op(mmh_handle_t h, int transa, int transb, int m, int n, int k, const float *dA, int lda, const float *dB,
+                      int ldb, float *dC, int ldc, int warmup, int reps, void *stream, float *ms_per_call) {
   if (!h || reps <= 0 || warmup < 0 || !ms_per_call) return MMH_ERR_INVALID_ARG;
   ENTER(h);
   hipStream_t s = static_cast<hipStream_t>(stream);
   int rc = MMH_OK;
-  for (int i = 0; i < warmup && rc == MMH_OK; ++i) rc = sgemm_on(h, h->kernel, m, n, k, dA, lda, dB, ldb, dC, ldc, 0, s);
+  auto call = [&]() { return sgemm_op_on(h, h->kernel, transa, transb, m, n, k, dA, lda, dB, ldb, dC, ldc, 0, s); };
+  for (int i = 0; i < warmup && rc == MMH_OK; ++i) rc = call();
   if (rc != MMH_OK) return rc;
   // (every exit below destroys what was created: a sticky error or a failed launch inside the loop must not leak events)
   hipEvent_t t0 = nullptr, t1 = nullptr;
   hipError_t e = hipEventCreate(&t0);
   if (e == hipSuccess) e = hipEventCreate(&t1);
   if (e == hipSuccess) e = hipEventRecord(t0, s);
-  for (int i = 0; i < reps && rc == MMH_OK && e == hipSuccess; ++i)
-    rc = sgemm_on(h, h->kernel, m, n, k, dA, lda, dB, ldb, dC, ldc, 0, s);
+  for (int i = 0; i < reps && rc == MMH_OK && e == hipSuccess; ++i) rc = call();
   float ms = 0.f;
   if (rc == MMH_OK && e == hipSuccess) e = hipEventRecord(t1, s);
   if (rc == MMH_OK && e == hipSuccess) e = hipEventSynchronize(t1);
@@ -383,7 +394,7 @@ int mmh_time_sgemm(mmh_handle_t h, int m, int n, int k, const float *dA, int lda
   if (t0) (void)hipEventDestroy(t0);
   if (t1) (void)hipEventDestroy(t1);
   if (rc != MMH_OK) return rc;
-  if (e != hipSuccess) return hip_fail(e, "mmh_time_sgemm");
+  if (e != hipSuccess) return hip_fail(e, "mmh_time_sgemm_op");
   *ms_per_call = ms / reps;
   return check_sticky(h);
 }
@@ -420,6 +431,11 @@ int mmh_streamk_plan(long tiles, int nk, int grid, int *order, int *place) {
 int mmh_auto_plan(int m, int n, int k, int lda, int ldb, int ldc, int base_align, int cu_count, int *kernel, long *tiles,
                   int *streamk_grid) {
   return mmh::auto_plan(m, n, k, lda, ldb, ldc, base_align, cu_count, kernel, tiles, streamk_grid);
+}
+
+int mmh_auto_plan_op(int transa, int transb, int m, int n, int k, int lda, int ldb, int ldc, int base_align, int cu_count,
+                     int *kernel, long *tiles, int *streamk_grid) {
+  return mmh::auto_plan_op(transa, transb, m, n, k, lda, ldb, ldc, base_align, cu_count, kernel, tiles, streamk_grid);
 }
 
 }  // extern "C"

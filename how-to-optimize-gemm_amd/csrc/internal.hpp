@@ -96,6 +96,8 @@ struct GemmArgs {
   int form = 0;
   // ... and the persistent workgroups per CU the table priced that launch on (0: whatever the kernel's residency allows)
   int sk_w = 0;
+  // operand layouts (mmh_sgemm_op): 1 = stored transposed -- A as k x m (lda >= m), B as n x k (ldb >= k)
+  int ta = 0, tb = 0;
 };
 
 }  // namespace mmh
@@ -205,8 +207,18 @@ inline bool window_ok(int BM, int BN, int k, int lda, int ldb) {
   const size_t lim = (1ull << 31) - 4096;
   return ((size_t)BM * lda + k) * 4 < lim && ((size_t)k * ldb + BN) * 4 < lim;
 }
+// ... for the layout the operands are stored in (a tile of A^T is k rows of BM floats, one of B^T BN rows of k floats)
+inline bool window_ok(int BM, int BN, const GemmArgs &g) {
+  if (!g.ta && !g.tb) return window_ok(BM, BN, g.k, g.lda, g.ldb);
+  const size_t lim = (1ull << 31) - 4096;
+  const size_t a = g.ta ? (size_t)g.k * g.lda + BM : (size_t)BM * g.lda + g.k;
+  const size_t b = g.tb ? (size_t)BN * g.ldb + g.k : (size_t)g.k * g.ldb + BN;
+  return a * 4 < lim && b * 4 < lim;
+}
 
-int check_gemm_args(int m, int n, int k, const void *A, int lda, const void *B, int ldb, const void *C, int ldc);
+// ta / tb: the operand layouts of mmh_sgemm_op (A stored k x m needs lda >= m, B stored n x k ldb >= k)
+int check_gemm_args(int m, int n, int k, const void *A, int lda, const void *B, int ldb, const void *C, int ldc, int ta = 0,
+                    int tb = 0);
 bool known_kernel(int kernel);
 
 // ---- stream-K workspaces (state.hip) ----
@@ -222,6 +234,11 @@ int auto_plan(int m, int n, int k, int lda, int ldb, int ldc, int base_align, in
               int *streamk_grid);   // policy.hip: mmh_auto_plan
 int sgemm_on(mmh_context *ctx, int kernel, int m, int n, int k, const float *dA, int lda, const float *dB, int ldb,
              float *dC, int ldc, int accumulate, hipStream_t s);
+// mmh_sgemm_op: C = op(A) op(B) (+ C); ta = tb = 0 is sgemm_on
+int sgemm_op_on(mmh_context *ctx, int kernel, int ta, int tb, int m, int n, int k, const float *dA, int lda, const float *dB,
+                int ldb, float *dC, int ldc, int accumulate, hipStream_t s);
+int auto_plan_op(int ta, int tb, int m, int n, int k, int lda, int ldb, int ldc, int base_align, int cu_count, int *kernel,
+                 long *tiles, int *streamk_grid);   // mmh_auto_plan_op
 // launch_reg.hip: `kernel` is one of the register-staged ids (MFMA, MFMA_TILES, MFMA_256, MFMA_256X256, MFMA_128X64,
 // MFMA_64X64, MFMA_SIMPLE, MFMA_PIPE, the split-K ids and, in the A/B build, the ablation ids)
 int launch_reg(mmh_context *ctx, int kernel, const GemmArgs &g);
@@ -253,8 +270,12 @@ inline bool dma5_rim_dims(int m, int n, int *r_m, int *r_n) {
 }
 // launch_dma5.hip: tile = MMH_KERNEL_MFMA_*_DMA5 (sgemm_dma5.hpp); returns 1 when the shape does not qualify
 int launch_dma5(mmh_context *ctx, int kernel, const GemmArgs &g);
-bool dma5_shape_ok(const mmh_context *ctx, int kernel, const GemmArgs &g);
+bool dma5_shape_ok(const mmh_context *ctx, int kernel, const GemmArgs &g);   // (g.ta / g.tb: the stored layouts' window)
 int warm_dma5(mmh_context *ctx, float *scratch, hipStream_t s);
+// launch_op.hip: the op forms (g.ta / g.tb) of MMH_KERNEL_MFMA_{64X64,128X64,128X128}_DMA5, and of MMH_KERNEL_NAIVE
+int launch_dma5_op(mmh_context *ctx, int kernel, const GemmArgs &g);   // 1: the shape does not qualify
+int launch_naive_op(const GemmArgs &g);
+int warm_dma5_op(mmh_context *ctx);                                     // LDS opt-ins only (nothing is launched)
 // launch_valu.hip
 int launch_valu(mmh_context *ctx, int kernel, const GemmArgs &g);
 int warm_valu(mmh_context *ctx, float *scratch, hipStream_t s);

@@ -13,7 +13,7 @@ namespace {
 
 template <int BM, int BN, int KB>
 int dma5_form(const mmh_context *ctx, const GemmArgs &g) {
-  if (!window_ok(BM, BN, g.k, g.lda, g.ldb)) return -1;
+  if (!window_ok(BM, BN, g)) return -1;   // (g.ta / g.tb: the stored layouts -- launch_op.hip asks through dma5_shape_ok)
   if (fast_shape(BM, BN, KB, g)) return 0;
   if (!ctx || !ctx->dma_edge) return -1;
   const bool rows16 = (g.lda % 4 == 0) && (g.ldb % 4 == 0) && aligned16(g.A) && aligned16(g.B);

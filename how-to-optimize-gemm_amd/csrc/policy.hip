@@ -45,6 +45,10 @@ bool is_k2w(int kernel) {
   return kernel == MMH_KERNEL_MFMA_64X64_DMA5 || kernel == MMH_KERNEL_MFMA_128X64_DMA5 || kernel == MMH_KERNEL_MFMA_128X128_DMA5 ||
          kernel == MMH_KERNEL_MFMA_96X96_DMA5 || kernel == MMH_KERNEL_MFMA_96X64_DMA5 || kernel == MMH_KERNEL_MFMA_160X160_DMA5;
 }
+// the tiles with op forms (launch_op.hip): where the NN table picks one of them the op plan is that very plan
+bool has_op_forms(int kernel) {
+  return kernel == MMH_KERNEL_MFMA_64X64_DMA5 || kernel == MMH_KERNEL_MFMA_128X64_DMA5 || kernel == MMH_KERNEL_MFMA_128X128_DMA5;
+}
 bool is_k2l(int kernel) {
   return kernel == MMH_KERNEL_MFMA_64X64_DMA || kernel == MMH_KERNEL_MFMA_128X64_DMA || kernel == MMH_KERNEL_MFMA_128X128_DMA;
 }
@@ -56,6 +60,7 @@ Plan auto_plan_for(const mmh_context *ctx, const GemmArgs &g) {
   long tiles_rim = 0;
   bool any_dma5 = false;   // did any LDS-DMA family take the shape?
   for (const Family &f : kFamilies) {
+    if ((g.ta || g.tb) && !has_op_forms(f.kernel)) continue;   // op forms: the same table, restricted to their three tiles
     // (Rounds 2-3 kept K > 8192 -- B beyond the Infinity Cache, the config-4 panels -- on the 256x256 tile: K2L's small tiles
     // lost 1-6 % there.  K2W's do not: 2048 .. 4096 x 16384 x 16384 run 152.4-153.2 TFLOP/s on the 128x64 tile against
     // 150.2-150.3, and 2048 x 4096 x 16384 -- half a round of 256x256 tiles -- 151.5 against 74.8: the fence is gone, the
@@ -288,19 +293,77 @@ int sgemm_on(mmh_context *ctx, int kernel, int m, int n, int k, const float *dA,
   }
 }
 
+// mmh_sgemm_op.  NN is mmh_sgemm's own path.  The op forms run on the three K2W tiles that have them (AUTO: the table
+// restricted to those; forced: 29 / 30 / 31) and on the naive kernel; every other kernel, and operands beyond the 2 GiB
+// descriptor window (the register-staged fallback is NN-only), are refused before anything is launched.  Split-K and
+// MMH_OPT_STREAMK_CHAIN = 0 are NN A/B switches: the op forms run the chained stream-K kernels, which keep the bits.
+int sgemm_op_on(mmh_context *ctx, int kernel, int ta, int tb, int m, int n, int k, const float *dA, int lda, const float *dB,
+                int ldb, float *dC, int ldc, int accumulate, hipStream_t s) {
+  if ((ta != MMH_OP_N && ta != MMH_OP_T) || (tb != MMH_OP_N && tb != MMH_OP_T)) {
+    set_last_error("transa / transb must be MMH_OP_N or MMH_OP_T");
+    return MMH_ERR_INVALID_ARG;
+  }
+  if (!ta && !tb) return sgemm_on(ctx, kernel, m, n, k, dA, lda, dB, ldb, dC, ldc, accumulate, s);
+  int rc = check_gemm_args(m, n, k, dA, lda, dB, ldb, dC, ldc, ta, tb);
+  if (rc != MMH_OK) {
+    set_last_error("invalid argument");
+    return rc;
+  }
+  if (m == 0 || n == 0) return MMH_OK;
+  if (kernel != MMH_KERNEL_AUTO && kernel != MMH_KERNEL_NAIVE && !has_op_forms(kernel)) {
+    set_last_error("transposed operands run on MMH_KERNEL_AUTO, the 64x64 / 128x64 / 128x128 LDS-DMA tiles (29 / 30 / 31) and "
+                   "MMH_KERNEL_NAIVE only");
+    return MMH_ERR_UNSUPPORTED;
+  }
+  if (k == 0) {
+    if (!accumulate)
+      HIP_TRY(hipMemset2DAsync(dC, (size_t)ldc * sizeof(float), 0, (size_t)n * sizeof(float), (size_t)m, s));
+    return MMH_OK;
+  }
+  GemmArgs g{m, n, k, dA, lda, dB, ldb, dC, ldc, accumulate ? 1 : 0, s};
+  g.ta = ta;
+  g.tb = tb;
+  if (kernel == MMH_KERNEL_NAIVE) return launch_naive_op(g);
+  if (kernel == MMH_KERNEL_AUTO) {
+    const Plan plan = auto_plan_for(ctx, g);
+    if (plan.kernel >= 0) {
+      g.form = plan.form;
+      g.sk_w = plan.sk_w;
+      kernel = plan.kernel;
+    }
+  }
+  if (has_op_forms(kernel)) {
+    const int d = launch_dma5_op(ctx, kernel, g);
+    if (d <= 0) return d;
+  }
+  set_last_error("transposed operands need the LDS-DMA tiles: an operand lies beyond their 2 GiB descriptor window, or "
+                 "MMH_OPT_DMA_EDGE keeps this shape off them (the register-staged tiles take NN operands only)");
+  return MMH_ERR_UNSUPPORTED;
+}
+
 // What MMH_KERNEL_AUTO would do with a shape, as host arithmetic (mmh_auto_plan: no device, no launch): the tile it
 // picks and, for the tiles whose residency the LDS alone decides, whether the launch would be the persistent
 // stream-K form.  Uses the very functions the launch path uses (auto_kernel, streamk_wanted) on a default handle.
 int auto_plan(int m, int n, int k, int lda, int ldb, int ldc, int base_align, int cu_count, int *kernel, long *tiles,
               int *streamk_grid) {
-  if (m <= 0 || n <= 0 || k <= 0 || lda < k || ldb < n || ldc < n) return MMH_ERR_INVALID_ARG;
+  return auto_plan_op(MMH_OP_N, MMH_OP_N, m, n, k, lda, ldb, ldc, base_align, cu_count, kernel, tiles, streamk_grid);
+}
+
+// mmh_auto_plan_op: the same for C = op(A) op(B); an op form no tile with op forms takes is MMH_ERR_UNSUPPORTED
+int auto_plan_op(int ta, int tb, int m, int n, int k, int lda, int ldb, int ldc, int base_align, int cu_count, int *kernel,
+                 long *tiles, int *streamk_grid) {
+  if ((ta != MMH_OP_N && ta != MMH_OP_T) || (tb != MMH_OP_N && tb != MMH_OP_T)) return MMH_ERR_INVALID_ARG;
+  if (m <= 0 || n <= 0 || k <= 0 || lda < (ta ? m : k) || ldb < (tb ? k : n) || ldc < n) return MMH_ERR_INVALID_ARG;
   mmh_context ctx;
   ctx.cu_count = cu_count > 0 ? cu_count : 256;
   // addresses that are never dereferenced: a 16-byte (or only 4-byte) aligned base for each operand
   const uintptr_t base = (uintptr_t)1 << 32, off = base_align >= 16 ? 0 : 4;
-  const GemmArgs g{m, n, k, reinterpret_cast<const float *>(base + off), lda,
-                   reinterpret_cast<const float *>(2 * base + off), ldb, reinterpret_cast<float *>(3 * base + off), ldc, 0, nullptr};
+  GemmArgs g{m, n, k, reinterpret_cast<const float *>(base + off), lda,
+             reinterpret_cast<const float *>(2 * base + off), ldb, reinterpret_cast<float *>(3 * base + off), ldc, 0, nullptr};
+  g.ta = ta;
+  g.tb = tb;
   const Plan plan = auto_plan_for(&ctx, g);
+  if ((ta || tb) && plan.kernel < 0) return MMH_ERR_UNSUPPORTED;
   const int kern = plan.kernel >= 0 ? plan.kernel : fallback_kernel(&ctx, g);
   int bm = plan.bm, bn = plan.bn;
   if (plan.kernel < 0) {

@@ -145,10 +145,36 @@ struct Dma5ValuFrags {
   f32x4 b[4][RJ];     // k-step mod 4
 };
 
+// OP (operand layouts, bit 0: A is stored k x m -- op(A) = T --, bit 1: B is stored n x k): a transposed operand lands in
+// LDS in the OTHER operand's image -- A^T as [k][m] (B's: k-rows of BM floats, odd rows' 16-float halves of each 32 swapped,
+// so that the kq = 0 / 1 lanes of a ds_read_b32 half take different banks), B^T as [n][k] (A's: 128-byte rows, 16-byte
+// chunk c of row j at c ^ ((j / WTN) & 7) -- the rows one b32 read touches are WTN apart).  The fp32 MFMA takes one float
+// of each operand per lane, A[i][k] and B[k][i]: only the loaders' maps and the fragment addresses change, never the
+// MFMAs, the k order or the accumulators -- the NN bits.  K tail: B^T's columns past k are garbage like A's, and the
+// TAIL slice zeroes both operands.  (Even WTN, MFMA consumers only.)
 template <int BM, int BN, int KB, int WTM, int WTN, int NBUF, bool PART_WT = false, bool EDGE = false, bool CHAIN = false,
-          int NL = 1, int D = 2, bool RIM = false, bool VALU = false, int RS = 1>
+          int NL = 1, int D = 2, bool RIM = false, bool VALU = false, int RS = 1, int OP = 0>
 struct Dma5Segment {
   using T = Dma5Tile<BM, BN, KB, WTM, WTN, NBUF, NL>;
+  static constexpr bool TA = (OP & 1) != 0, TB = (OP & 2) != 0;
+  static_assert(OP == 0 || (!VALU && !RIM && (WTN == 2 || WTN == 4) && (BM == 64 || BM == 128)), "op forms: the 64x64, 128x64 and 128x128 tiles");
+  static constexpr int CPR_AT = BM / 4, RA_T = 64 / CPR_AT;   // A^T: 16-byte chunks per k-row, k-rows per piece
+  static constexpr int PBX = TB ? WTN : T::PB;                // B's pieces until the lane -> (row, chunk) map repeats
+  static constexpr int RBX = TB ? 8 * WTN : T::RB;            // ... and the rows of the stored operand they hold
+  static_assert((T::CHB / PBX) % NL == 0, "B's piece periods divide over the loaders");
+  // A [row][k] image keeps a table of eight fragment offsets per lane, one per k-step of a slice (a_off, and b_off for B^T).
+  // Two NT stream-K kernels cannot hold both tables -- the guarded 128x128 one (256 registers and 8 spilled) and the
+  // whole-tile 128x64 one (129: past the 128 of its NN twin's two workgroups per CU): their A keeps the offset of k-step
+  // 0 only.  The chunk swizzle touches bits 2-4 of a float offset, so k-step ks's is an XOR away: an instruction per read,
+  // which costs those launches 9-17 % (profiles/op_sweep.md; the table costs nothing).  (volatile: hoisted out of the
+  // slice loop it would be the table again)
+  static constexpr bool A_XOR = OP == 2 && CHAIN && BM == 128 && (BN == 64 ? !EDGE : EDGE);
+  template <int KS_>
+  static __device__ __forceinline__ int kstep_off(int base) {
+    int o = base;
+    if constexpr ((KS_ & 7) != 0) asm volatile("v_xor_b32 %0, %1, %2" : "=v"(o) : "n"(4 * (KS_ & 7)), "v"(base));
+    return o + 4 * (KS_ & ~7);
+  }
   static_assert(!VALU || (!EDGE && !RIM && (D == 2 || D == 4) && (BM == 64 || BM == 128) && (BN == 64 || BN == 128)),
                 "the vector-ALU consumer: whole tiles, 16 x 16 threads of 4x4 output blocks");
   static constexpr bool kChain = CHAIN, kPartWt = PART_WT, kValu = VALU;
@@ -178,9 +204,9 @@ struct Dma5Segment {
     int wave, wm, wn, li, kq, ld;
     bool loader, rim;
     int stamp_base = 0;   // timeline build: the stream-K body moves it from part to part
-    int a_off[8], b_off[BBLK ? WTN : 1];
+    int a_off[8], b_off[BBLK ? WTN : TB ? 8 : 1];
     int v_tx = 0, v_wrow = 0, v_a_even = 0, v_a_odd = 0, v_b_col = 0, v_b_col_odd = 0;   // VALU consumers (sgemm_valu_dma5.hpp)
-    uint32_t voff_a, voff_b[T::PB];
+    uint32_t voff_a, voff_b[PBX];
     __device__ __forceinline__ void init(int lda, int ldb) {
       const int tid = threadIdx.x, lane = tid & 63;
       wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -191,9 +217,20 @@ struct Dma5Segment {
       wn = (wave & 3) % T::WAVES_N;
       li = lane & 15;
       kq = lane >> 4;
+      if constexpr (TA) {   // [k][m]: block t of this lane's row at a_off[t & 1] + 32 (t >> 1) (odd k-rows: halves swapped)
+        const int s = 16 * (kq & 1);
+        a_off[0] = kq * BM + wm * 16 * WTM + li + s;
+        a_off[1] = kq * BM + wm * 16 * WTM + li + 16 - s;
+      } else if constexpr (A_XOR) {   // (kstep_off)
+        a_off[0] = (wm * 16 * WTM + li) * KB + 4 * (li & 7) + kq;
+      } else {
 #pragma unroll
       for (int j = 0; j < 8; ++j) a_off[j] = (wm * 16 * WTM + li) * KB + 4 * (j ^ (li & 7)) + kq;
-      if constexpr (BBLK) {
+      }
+      if constexpr (TB) {   // [n][k]: column WTN li + u of the wave is row (wn 16 + li) WTN + u, its chunk swizzle li & 7
+#pragma unroll
+        for (int j = 0; j < 8; ++j) b_off[j] = T::A_FLOATS + (wn * 16 * WTN + WTN * li) * KB + 4 * (j ^ (li & 7)) + kq;
+      } else if constexpr (BBLK) {
 #pragma unroll
         for (int u = 0; u < WTN; ++u) b_off[u] = T::A_FLOATS + kq * BN + 16 * ((wn * WTN + u) ^ (kq & 1)) + li;
       } else {
@@ -201,14 +238,25 @@ struct Dma5Segment {
                             : T::A_FLOATS + kq * BN + 4 * ((wn * 8 + (li >> 1)) ^ ((kq & 1) << 3)) + 2 * (li & 1);
       }
       // loaders: the 16-byte chunk a lane fetches is the one that belongs at its (swizzled) position of the image
-      {
+      if constexpr (TA) {
+        const int r = lane / CPR_AT, pc = lane % CPR_AT;                   // piece j holds k-rows RA_T j + r
+        voff_a = (uint32_t)(r * lda + 4 * (pc ^ ((r & 1) << 2))) * 4u;
+      } else {
         const int r = lane / 8, p = lane % 8;                              // piece j holds A rows 8 j + r
         voff_a = (uint32_t)(r * lda + 4 * (p ^ (VALU ? (r >> 1) & 1 : r & 7))) * 4u;
       }
+      if constexpr (TB) {
+#pragma unroll
+        for (int jj = 0; jj < WTN; ++jj) {
+          const int r = lane / 8, p = lane % 8;                            // piece WTN g + jj holds B^T rows 8 (WTN g + jj) + r
+          voff_b[jj] = (uint32_t)(r * ldb + 4 * (p ^ (((8 * jj + r) / WTN) & 7))) * 4u;
+        }
+      } else {
 #pragma unroll
       for (int jj = 0; jj < T::PB; ++jj) {
         const int c = 64 * jj + lane, r = c / T::CPR_B, pc = c % T::CPR_B; // piece PB g + jj holds k-rows RB g + r
         voff_b[jj] = (uint32_t)(r * ldb + 4 * T::src_chunk_b(r, pc)) * 4u;
+      }
       }
       if constexpr (VALU) {
         // a wave is 16 (tx) x 4 (t) threads: rows (BM / 4) wave + t + 4 i, columns 4 tx + 64 h (sgemm_valu_dma5.hpp)
@@ -257,16 +305,18 @@ struct Dma5Segment {
       // ------------------------------------------------------------------ the loader waves
       // descriptors as base + extent SCALARS, packed where they are used (a select between two 128-bit descriptors goes
       // through scratch memory)
-      auto ext_a = [&](int valid) { return EDGE ? (uint32_t)(((valid - 1) * lda + k) * 4) : 0x7fffffffu; };
-      auto ext_b = [&](int valid) { return EDGE ? (uint32_t)(((k - 1) * ldb + valid) * 4) : 0x7fffffffu; };
-      const float *own_pa = A + (size_t)row0 * lda, *own_pb = B + col0;
+      // (A^T: the extent ends at the last k-row's column m - 1 -- its columns past m feed C rows that are never stored; B^T: at
+      // row n - 1's column k - 1)
+      auto ext_a = [&](int valid) { return EDGE ? (uint32_t)((TA ? (k - 1) * lda + valid : (valid - 1) * lda + k) * 4) : 0x7fffffffu; };
+      auto ext_b = [&](int valid) { return EDGE ? (uint32_t)((TB ? (valid - 1) * ldb + k : (k - 1) * ldb + valid) * 4) : 0x7fffffffu; };
+      const float *own_pa = TA ? A + row0 : A + (size_t)row0 * lda, *own_pb = TB ? B + (size_t)col0 * ldb : B + col0;
       const uint32_t own_ea = ext_a(rows_valid), own_eb = ext_b(cols_valid);
       const float *next_pa = A, *next_pb = B;
       uint32_t next_ea = 0, next_eb = 0;   // no successor: the same instructions against empty descriptors
       if constexpr (CHAIN) {
         if (chain) {
-          next_pa = A + (size_t)(nx.tm * BM) * lda;
-          next_pb = B + nx.tn * BN;
+          next_pa = TA ? A + nx.tm * BM : A + (size_t)(nx.tm * BM) * lda;
+          next_pb = TB ? B + (size_t)(nx.tn * BN) * ldb : B + nx.tn * BN;
           next_ea = ext_a(EDGE ? min(BM, m - nx.tm * BM) : BM);
           next_eb = ext_b(EDGE ? min(BN, n - nx.tn * BN) : BN);
         }
@@ -298,20 +348,25 @@ struct Dma5Segment {
                                                                             own ? own_ea : next_ea, 0x00020000);
         const __amdgpu_buffer_rsrc_t rb = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(own ? own_pb : next_pb), 0,
                                                                             own ? own_eb : next_eb, 0x00020000);
-        const uint32_t off_a = (uint32_t)(ks * KB) * 4u, off_b = (uint32_t)(ks * KB) * (uint32_t)ldb * 4u;
+        const uint32_t off_a = TA ? (uint32_t)(ks * KB) * (uint32_t)lda * 4u : (uint32_t)(ks * KB) * 4u;
+        const uint32_t off_b = TB ? (uint32_t)(ks * KB) * 4u : (uint32_t)(ks * KB) * (uint32_t)ldb * 4u;
         // pieces j = NL i + ld of each image (ld is wave-uniform: scalar arithmetic)
         static_for<T::CHA / NL>([&](auto i_c) {
           constexpr int i = decltype(i_c)::value;
           const int j = NL * i + ld;
-          DmaPiece::one(ra, buf + 256 * j, L.voff_a, off_a + (uint32_t)(8 * j) * (uint32_t)lda * 4u);
+          DmaPiece::one(ra, buf + 256 * j, L.voff_a, off_a + (uint32_t)((TA ? RA_T : 8) * j) * (uint32_t)lda * 4u);
         });
-        // B: whole periods g = NL i2 + ld (PB pieces each, whose lane offsets are compile-time picks)
-        static_for<T::CHB / T::PB / NL>([&](auto i_c) {
+        // B: whole periods g = NL i2 + ld (PBX pieces each, whose lane offsets are compile-time picks)
+        static_for<T::CHB / PBX / NL>([&](auto i_c) {
           constexpr int i2 = decltype(i_c)::value;
           const int g = NL * i2 + ld;
-          static_for<T::PB>([&](auto jj_c) {
+          static_for<PBX>([&](auto jj_c) {
             constexpr int jj = decltype(jj_c)::value;
-            DmaPiece::one(rb, buf + A_FLOATS + 256 * (T::PB * g + jj), L.voff_b[jj], off_b + (uint32_t)(T::RB * g) * (uint32_t)ldb * 4u);
+            if constexpr (TB)
+              DmaPiece::one(rb, buf + A_FLOATS + 256 * (PBX * g + jj), L.voff_b[jj],
+                            off_b + (uint32_t)(RBX * g) * (uint32_t)ldb * 4u + (uint32_t)(8 * jj) * (uint32_t)ldb * 4u);
+            else
+              DmaPiece::one(rb, buf + A_FLOATS + 256 * (T::PB * g + jj), L.voff_b[jj], off_b + (uint32_t)(T::RB * g) * (uint32_t)ldb * 4u);
           });
         });
         if constexpr (RIM) {
@@ -459,12 +514,23 @@ struct Dma5Segment {
     }
     auto frag_a = [&](const float *buf, auto ks_c, float (&a)[WTM]) {
       constexpr int ks = decltype(ks_c)::value;
+      if constexpr (TA) {
+#pragma unroll
+        for (int t = 0; t < WTM; ++t) a[t] = buf[L.a_off[t & 1] + 32 * (t >> 1) + 4 * ks * BM];
+      } else if constexpr (A_XOR) {
+#pragma unroll
+        for (int t = 0; t < WTM; ++t) a[t] = buf[kstep_off<ks>(L.a_off[0]) + t * 16 * KB];
+      } else {
 #pragma unroll
       for (int t = 0; t < WTM; ++t) a[t] = buf[L.a_off[ks & 7] + 4 * (ks & ~7) + t * 16 * KB];
+      }
     };
     auto frag_b = [&](const float *buf, auto ks_c, float (&b)[WTN]) {
       constexpr int ks = decltype(ks_c)::value;
-      if constexpr (BBLK) {
+      if constexpr (TB) {
+#pragma unroll
+        for (int u = 0; u < WTN; ++u) b[u] = buf[L.b_off[ks & 7] + 4 * (ks & ~7) + u * KB];
+      } else if constexpr (BBLK) {
 #pragma unroll
         for (int u = 0; u < WTN; ++u) b[u] = buf[L.b_off[u] + 4 * ks * BN];
       } else {
@@ -511,16 +577,25 @@ struct Dma5Segment {
         // RS (read spread): the fragment reads of k-step ks + D leave ONE AT A TIME behind the first MFMAs of k-step ks,
         // each in the shadow of a matrix instruction, instead of as a block in front of them (a wave alone on its SIMD
         // issues nothing else while eight ds_read instructions leave: the 160x160 tile's 5 + 5 single-float fragments)
-        constexpr int UA = (WTM + 1) / 2, UB = BBLK ? WTN : 1, UNITS = UA + UB;
+        constexpr int UA = (WTM + 1) / 2, UB = BBLK || TB ? WTN : 1, UNITS = UA + UB;
         auto read_unit = [&](auto j_c) {
           constexpr int j = decltype(j_c)::value;
           constexpr int rks = ks + D < KS ? ks + D : ks + D - KS;
           const float *rb = ks + D < KS ? buf : nxt;
           float(&fa)[WTM] = fr.a[(ks + D) % SLOTS];
           float(&fb)[WTN] = fr.b[(ks + D) % SLOTS];
-          if constexpr (j < UA) {
+          if constexpr (j < UA && TA) {
+#pragma unroll
+            for (int t = 2 * j; t < 2 * j + 2 && t < WTM; ++t) fa[t] = rb[L.a_off[t & 1] + 32 * (t >> 1) + 4 * rks * BM];
+          } else if constexpr (j < UA && A_XOR) {
+            const int o = kstep_off<rks>(L.a_off[0]);
+#pragma unroll
+            for (int t = 2 * j; t < 2 * j + 2 && t < WTM; ++t) fa[t] = rb[o + t * 16 * KB];
+          } else if constexpr (j < UA) {
 #pragma unroll
             for (int t = 2 * j; t < 2 * j + 2 && t < WTM; ++t) fa[t] = rb[L.a_off[rks & 7] + 4 * (rks & ~7) + t * 16 * KB];
+          } else if constexpr (TB) {
+            fb[j - UA] = rb[L.b_off[rks & 7] + 4 * (rks & ~7) + (j - UA) * KB];
           } else if constexpr (BBLK) {
             fb[j - UA] = rb[L.b_off[j - UA] + 4 * rks * BN];
           } else {
@@ -544,7 +619,8 @@ struct Dma5Segment {
         for (int u = 0; u < NU; ++u) b[u] = fr.b[ks % SLOTS][u];
         if constexpr (TAIL) {
           // A's columns past k are the next row's floats or the caller's padding (NaN included): zero this lane's
-          // operands of the k's that do not exist (B's rows there are zeros by descriptor; belt and braces)
+          // operands of the k's that do not exist (B's rows there are zeros by descriptor -- B^T's columns are garbage like A's;
+          // A^T's rows there are zeros by descriptor)
           const bool live = 4 * ks + L.kq < krem;
 #pragma unroll
           for (int t = 0; t < NT; ++t) a[t] = live ? a[t] : 0.0f;
@@ -747,6 +823,42 @@ sgemm_mfma_dma5_kernel(int m, int n, int k, const float *__restrict__ A, int lda
   dma_stamp_after_stores(3);
 }
 
+// The op forms (OP: Dma5Segment) of the plain launch: kernels of their own, so that the NN instantiations keep their names
+// and their code (sgemm_mfma_dma5_kernel above stays as it is -- hipcc's output moves with any refactoring of its body);
+// the raster is that kernel's, thin edge tiles last, the tail split's id offset in bits 16-31 of `accumulate`.
+template <int BM, int BN, int KB, int WTM, int WTN, int NBUF, bool EDGE, int NL, int D, int OP>
+__global__ void __launch_bounds__(64 * (4 + NL))
+sgemm_mfma_dma5_op_kernel(int m, int n, int k, const float *__restrict__ A, int lda, const float *__restrict__ B, int ldb,
+                          float *__restrict__ C, int ldc, int accumulate, int nbm, int nbn) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  using S = Dma5Segment<BM, BN, KB, WTM, WTN, NBUF, false, EDGE, false, NL, D, false, false, 1, OP>;
+  constexpr int GM = Dma5Tile<BM, BN, KB, WTM, WTN, NBUF, NL>::GM;
+  asm volatile("" ::"s"(A), "s"(B), "s"(C), "s"(lda), "s"(ldb), "s"(ldc), "s"(k));
+  const unsigned bid = blockIdx.x + (((unsigned)accumulate >> 16) << 3);
+  accumulate &= 0xffff;
+  int tm, tn;
+  const int thin_row = (EDGE && nbm > 1 && m - (nbm - 1) * BM <= 16) ? 1 : 0, thin_col = (EDGE && nbn > 1 && n - (nbn - 1) * BN <= 16) ? 1 : 0;
+  const int n_full = (nbm - thin_row) * (nbn - thin_col);
+  int r = (int)bid - n_full;
+  if (r < 0) {
+    block_to_tile_g(bid, n_full, nbm - thin_row, nbn - thin_col, GM, tm, tn);
+  } else if (thin_col && r < nbm) {
+    tm = r;
+    tn = nbn - 1;
+  } else {
+    if (thin_col) r -= nbm;
+    tm = nbm - 1;
+    tn = r;
+  }
+  typename S::Lane L;
+  L.init(lda, ldb);
+  typename S::Frags fr;
+  Dma5Link link;
+  int no_reply = 0;
+  S::run(lds, L, m, n, k, A, lda, B, ldb, C, ldc, tm, tn, 0, (k + KB - 1) / KB, accumulate != 0, nullptr, nullptr, fr, link,
+         Dma5Next{}, nullptr, no_reply);
+}
+
 
 // ---------------------------------------------------------------------------------------------------------------
 // K2Wp: the chained stream-K body.  Ranges, the order of a range's parts (head of the last tile FIRST, whole tiles, tail
@@ -755,14 +867,15 @@ sgemm_mfma_dma5_kernel(int m, int n, int k, const float *__restrict__ A, int lda
 // looked at (they depend on nobody); should the word say the head's owner is not running (the wait-free path: leave),
 // they are dropped.
 // ---------------------------------------------------------------------------------------------------------------
-template <int BM, int BN, int KB, int WTM, int WTN, int NBUF, bool EDGE, bool CHAINED, int NL, int D, bool VALU = false, int RS = 1>
+template <int BM, int BN, int KB, int WTM, int WTN, int NBUF, bool EDGE, bool CHAINED, int NL, int D, bool VALU = false, int RS = 1,
+          int OP = 0>
 __device__ __forceinline__ void streamk5_body(float *lds, int m, int n, int k, const float *__restrict__ A, int lda,
                                               const float *__restrict__ B, int ldb, float *__restrict__ C, int ldc,
                                               int accumulate, int nbm, int nbn, int *__restrict__ flags,
                                               float *__restrict__ parts, const int *__restrict__ order,
                                               const int *__restrict__ place, int *__restrict__ stats) {
   constexpr bool chained = CHAINED;
-  using S = Dma5Segment<BM, BN, KB, WTM, WTN, NBUF, true, EDGE, true, NL, D, false, VALU, RS>;
+  using S = Dma5Segment<BM, BN, KB, WTM, WTN, NBUF, true, EDGE, true, NL, D, false, VALU, RS, OP>;
   using T = Dma5Tile<BM, BN, KB, WTM, WTN, NBUF, NL>;
   // tools build: bit 1 of `accumulate` = publish every head on the spot, bit 2 = whole-tile ranges, bits 8-15 = raster group height
   const bool ab_nodefer = kAbBuild && (accumulate & 2) != 0;
@@ -991,6 +1104,19 @@ sgemm_dma5_streamk_kernel(int m, int n, int k, const float *__restrict__ A, int 
   asm volatile("" ::"s"(A), "s"(B), "s"(C), "s"(lda), "s"(ldb), "s"(ldc), "s"(k), "s"(flags), "s"(parts), "s"(order), "s"(place));   // (every argument requested at entry: sgemm_mfma_dma5_kernel)
   streamk5_body<BM, BN, KB, WTM, WTN, NBUF, EDGE, CHAINED, NL, D, false, RS>(lds, m, n, k, A, lda, B, ldb, C, ldc, accumulate, nbm, nbn,
                                                                    flags, parts, order, place, stats);
+}
+
+// The op forms of the chained stream-K launch (the only stream-K form they have)
+template <int BM, int BN, int KB, int WTM, int WTN, int NBUF, bool EDGE, int NL, int D, int OP>
+__global__ void __launch_bounds__(64 * (4 + NL))
+sgemm_dma5_op_streamk_kernel(int m, int n, int k, const float *__restrict__ A, int lda, const float *__restrict__ B,
+                             int ldb, float *__restrict__ C, int ldc, int accumulate, int nbm, int nbn,
+                             int *__restrict__ flags, float *__restrict__ parts, const int *__restrict__ order,
+                             const int *__restrict__ place, int *__restrict__ stats) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  asm volatile("" ::"s"(A), "s"(B), "s"(C), "s"(lda), "s"(ldb), "s"(ldc), "s"(k), "s"(flags), "s"(parts), "s"(order), "s"(place));
+  streamk5_body<BM, BN, KB, WTM, WTN, NBUF, EDGE, true, NL, D, false, 1, OP>(lds, m, n, k, A, lda, B, ldb, C, ldc, accumulate, nbm, nbn,
+                                                                          flags, parts, order, place, stats);
 }
 
 }  // namespace mmh

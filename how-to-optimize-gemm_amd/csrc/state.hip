@@ -67,11 +67,11 @@ int check_sticky(mmh_context *h) {
   return MMH_OK;
 }
 
-int check_gemm_args(int m, int n, int k, const void *A, int lda, const void *B, int ldb, const void *C, int ldc) {
+int check_gemm_args(int m, int n, int k, const void *A, int lda, const void *B, int ldb, const void *C, int ldc, int ta, int tb) {
   if (m < 0 || n < 0 || k < 0) return MMH_ERR_INVALID_ARG;
   if (m == 0 || n == 0) return MMH_OK;
   if (!C || ldc < n) return MMH_ERR_INVALID_ARG;
-  if (k > 0 && (!A || !B || lda < k || ldb < n)) return MMH_ERR_INVALID_ARG;
+  if (k > 0 && (!A || !B || lda < (ta ? m : k) || ldb < (tb ? k : n))) return MMH_ERR_INVALID_ARG;
   return MMH_OK;
 }
 
@@ -390,7 +390,7 @@ int warm_context(mmh_context *h) {
   HIP_TRY(hipMemsetAsync(scratch.p, 0, scratch.bytes, nullptr));
   float *p = static_cast<float *>(scratch.p);
   if ((rc = warm_reg(h, p, nullptr)) == MMH_OK && (rc = warm_dma(h, p, nullptr)) == MMH_OK &&
-      (rc = warm_dma5(h, p, nullptr)) == MMH_OK) rc = warm_valu(h, p, nullptr);
+      (rc = warm_dma5(h, p, nullptr)) == MMH_OK && (rc = warm_valu(h, p, nullptr)) == MMH_OK) rc = warm_dma5_op(h);
 #ifdef MMH_AB_BUILD
   if (rc == MMH_OK) rc = warm_dma32(h, p, nullptr);   // (K2M: tools/ab/)
 #endif

@@ -19,6 +19,8 @@
  *                     cuda/MMult_cuda_12.cu:228-235 (C = A*B, overwrite);
  *                     accumulate=1 gives the host flavour's C = A*B + C
  *                     (armv7/MMult0.c:9-24, aarch64/MMult0.cpp:3-19).
+ *   mmh_sgemm_op      cublasSgemm(handle, opA, opB, ...) (cuda/MMult_cuBLAS_1.cpp:11-19) with ROW-MAJOR
+ *                     storage: C = op(A)*op(B) on device pointers, op = N or T per operand.
  *   mmh_sgemm_host    host-pointer MY_MMult (armv7/test_MMult.c:8,76;
  *                     aarch64/test_MMult.cpp:17,113): does H2D, kernel, D2H.
  *   mmh_sgemm_host_timed  the third flavour of the symbol, `float MY_MMult(m, n, k, a, b, c)`
@@ -297,6 +299,11 @@ int mmh_streamk_plan(long tiles, int nk, int grid, int *order, int *place);
  * tools and callers that want to know before they launch. */
 int mmh_auto_plan(int m, int n, int k, int lda, int ldb, int ldc, int base_align, int cu_count, int *kernel, long *tiles,
                   int *streamk_grid);
+/* The same for mmh_sgemm_op's operands (lda / ldb as mmh_sgemm_op reads them).  (N, N) is mmh_auto_plan; the op forms
+ * answer one of MMH_KERNEL_MFMA_{64X64,128X64,128X128}_DMA5, or MMH_ERR_UNSUPPORTED where an operand lies beyond the
+ * descriptor window. */
+int mmh_auto_plan_op(int transa, int transb, int m, int n, int k, int lda, int ldb, int ldc, int base_align, int cu_count,
+                     int *kernel, long *tiles, int *streamk_grid);
 int mmh_get_option(mmh_handle_t handle, int option, int *value);
 
 /* The hot path ------------------------------------------------------------ */
@@ -312,6 +319,28 @@ int mmh_get_option(mmh_handle_t handle, int option, int *value);
 int mmh_sgemm(mmh_handle_t handle, int m, int n, int k, const float *dA, int lda,
               const float *dB, int ldb, float *dC, int ldc, int accumulate,
               void *stream);
+
+/* Transposed operands: C[m x n] = op(A) * op(B) (+ C), everything ROW-MAJOR.
+ *   transa == MMH_OP_N: A is stored m x k, element (i, p) at dA[i * lda + p], lda >= k  (mmh_sgemm's A)
+ *   transa == MMH_OP_T: A is stored k x m, element (i, p) at dA[p * lda + i], lda >= m  (x @ W^T's W, A^T @ dC's A)
+ *   transb == MMH_OP_N: B is stored k x n, element (p, j) at dB[p * ldb + j], ldb >= n
+ *   transb == MMH_OP_T: B is stored n x k, element (p, j) at dB[j * ldb + p], ldb >= k
+ *   C is always m x n, ldc >= n.
+ * The transposed operand is read in place -- no copy, no workspace: it lands in LDS in the other operand's image
+ * (csrc/sgemm_dma5.hpp, OP), and every element is the same fp32 fma chain over ascending k as mmh_sgemm computes on
+ * the materialised transposes, bit for bit.  (N, N) is mmh_sgemm itself.  The op forms run on MMH_KERNEL_AUTO (the
+ * cost table restricted to the 64x64, 128x64 and 128x128 LDS-DMA tiles: where mmh_sgemm's plan is one of those, the
+ * same tile, form and grid), on those three tiles forced, and on MMH_KERNEL_NAIVE; any other kernel, and operands
+ * beyond the tiles' 2 GiB buffer-descriptor window, give MMH_ERR_UNSUPPORTED with nothing launched.  MMH_OPT_SPLITK
+ * and MMH_OPT_STREAMK_CHAIN = 0 do not apply to them.  mmh_reserve_stream covers their launches; k == 0, m == 0,
+ * n == 0 behave as in mmh_sgemm; transa / transb outside {MMH_OP_N, MMH_OP_T}: MMH_ERR_INVALID_ARG.
+ * mmh_last_launch names the instantiation and ends in ", operands NT" (TN, TT).
+ * A column-major caller (cublasSgemm's convention) computes its C = op(A) op(B) as the row-major C^T = op(B)^T op(A)^T:
+ * swap the operands (and m / n), keep the op flags. */
+#define MMH_OP_N 0
+#define MMH_OP_T 1
+int mmh_sgemm_op(mmh_handle_t handle, int transa, int transb, int m, int n, int k, const float *dA, int lda,
+                 const float *dB, int ldb, float *dC, int ldc, int accumulate, void *stream);
 
 /* Host-pointer flavour: stages A, B (and C when accumulating) to the device,
  * runs mmh_sgemm, copies C back, synchronises.  Staging buffers are cached in
@@ -426,6 +455,10 @@ int mmh_sgemm_sharded(int ngpus, int m, int n, int k, const float *A, int lda,
 int mmh_time_sgemm(mmh_handle_t handle, int m, int n, int k, const float *dA, int lda,
                    const float *dB, int ldb, float *dC, int ldc, int warmup, int reps,
                    void *stream, float *ms_per_call);
+/* mmh_time_sgemm for mmh_sgemm_op (every op pair, (N, N) included). */
+int mmh_time_sgemm_op(mmh_handle_t handle, int transa, int transb, int m, int n, int k, const float *dA, int lda,
+                      const float *dB, int ldb, float *dC, int ldc, int warmup, int reps, void *stream,
+                      float *ms_per_call);
 
 /* The same measurement for a vendor comparator (the calls are issued from C, like mmh_time_sgemm's, so that
  * a 20 us kernel is not timed through an interpreter's call overhead). */

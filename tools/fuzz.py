@@ -3,7 +3,9 @@
 independent code path with the same chain semantics -> bit-equal) on random shapes,
 leading dimensions, 4-byte-misaligned bases and accumulate flags; plus a stream-K
 stress loop (ragged tile counts, repeated launches) against the one-tile-per-workgroup
-kernel.  usage: python tools/fuzz.py [cases] [stress_reps] [seed]"""
+kernel.  usage: python tools/fuzz.py [--ops] [cases] [stress_reps] [seed]
+--ops: the transposed-operand forms instead (mmh_sgemm_op: NT / TN / TT on AUTO and the 64x64 / 128x64 / 128x128 LDS-DMA
+tiles, plain and stream-K) against the naive kernel's op form, with NaN in every operand's padding and behind its last row."""
 import os
 import sys
 
@@ -12,9 +14,11 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 import how_to_optimize_gemm_amd as H  # noqa: E402
 
-cases = int(sys.argv[1]) if len(sys.argv) > 1 else 200
-stress = int(sys.argv[2]) if len(sys.argv) > 2 else 30
-seed = int(sys.argv[3]) if len(sys.argv) > 3 else 1
+OPS = "--ops" in sys.argv
+argv = [x for x in sys.argv if x != "--ops"]
+cases = int(argv[1]) if len(argv) > 1 else 200
+stress = int(argv[2]) if len(argv) > 2 else 30
+seed = int(argv[3]) if len(argv) > 3 else 1
 rng = np.random.default_rng(seed)
 mm = H.MMult(0)
 stream = torch.cuda.current_stream().cuda_stream
@@ -36,10 +40,8 @@ def strided(rows, cols, ld, off, fill=None):
     return flat, view
 
 
-bad = 0
-for case in range(cases):
+def random_shape():
     kind = rng.integers(0, 7)
-    aligned = kind == 4
     if kind == 4:      # whole tiles, 16-byte aligned bases and leading dimensions: what the LDS-DMA tiles take
         m, n = (int(rng.integers(1, 12)) * 128 for _ in range(2))
         k = int(rng.integers(1, 24)) * 64
@@ -57,6 +59,55 @@ for case in range(cases):
         k = int(rng.integers(33, 700))
     else:              # thin
         m, n, k = int(rng.integers(1, 40)), int(rng.integers(1, 2000)), int(rng.integers(1, 1500))
+    return kind, m, n, k
+
+
+def fuzz_ops():
+    """C = op(A) op(B) on the op forms' kernels against sgemm_naive_op_kernel (mmh_sgemm_op with MMH_KERNEL_NAIVE)."""
+    variants = ["auto", "mfma_64x64_dma5", "mfma_128x64_dma5", "mfma_128x128_dma5",
+                "mfma_64x64_dma5/sk2", "mfma_128x64_dma5/sk2", "mfma_128x128_dma5/sk2", "mfma_128x128_dma5/sk0"]
+    nbad = 0
+    for case in range(cases):
+        kind, m, n, k = random_shape()
+        ta, tb = [(0, 1), (1, 0), (1, 1)][int(rng.integers(0, 3))]
+        ra, ca = (k, m) if ta else (m, k)   # A as stored
+        rb, cb = (n, k) if tb else (k, n)
+        pad = (lambda: 4 * int(rng.integers(0, 3))) if kind == 4 else (lambda: int(rng.integers(0, 9)))
+        lda, ldb, ldc = ca + pad(), cb + pad(), n + pad()
+        offs = [4 * int(rng.integers(0, 2)) if kind == 4 else int(rng.integers(0, 4)) for _ in range(3)]
+        acc = bool(rng.integers(0, 2))
+        _, av = strided(ra, ca, lda, offs[0], torch.rand((ra, ca), device="cuda") * 2 - 1)
+        _, bv = strided(rb, cb, ldb, offs[1], torch.rand((rb, cb), device="cuda") * 2 - 1)
+        c0 = torch.rand((m, n), device="cuda")
+        results = {}
+        for kern in ["naive"] + variants:
+            mm.set_kernel(kern.split("/")[0])
+            mm.set_streamk({"sk2": 2, "sk0": 0}.get(kern.partition("/")[2], 1))
+            cflat, cv = strided(m, n, ldc, offs[2], c0)
+            mm.sgemm_op(ta, tb, m, n, k, av.data_ptr(), lda, bv.data_ptr(), ldb, cv.data_ptr(), ldc, acc, stream)
+            torch.cuda.synchronize()
+            results[kern] = cv[:, :n].clone()
+            if not (bool(torch.isnan(cv[:, n:]).all()) and bool(torch.isnan(cflat[:offs[2]]).all())):
+                nbad += 1
+                print(f"ops case {case} {kern}: wrote outside C window  m,n,k={m},{n},{k} op={ta}{tb}")
+        for kern in variants:
+            if not torch.equal(results[kern], results["naive"]):
+                nbad += 1
+                d = (results[kern] - results["naive"]).abs().max().item()
+                print(f"ops case {case} {kern}: != naive (max diff {d})  m,n,k={m},{n},{k} op={'NT'[ta]}{'NT'[tb]} "
+                      f"ld={lda},{ldb},{ldc} off={offs} acc={acc}")
+    mm.set_streamk(1)
+    print(f"fuzz --ops: {cases} cases x {len(variants)} variants, {nbad} failures")
+    return nbad
+
+
+if OPS:
+    sys.exit(1 if fuzz_ops() else 0)
+
+bad = 0
+for case in range(cases):
+    kind, m, n, k = random_shape()
+    aligned = kind == 4
     lda, ldb, ldc = k + int(rng.integers(0, 9)), n + int(rng.integers(0, 9)), n + int(rng.integers(0, 9))
     offs = [int(rng.integers(0, 4)) for _ in range(3)]
     if aligned:
