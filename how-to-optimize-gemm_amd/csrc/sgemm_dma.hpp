@@ -336,8 +336,9 @@ static __device__ __forceinline__ void run(float *lds, int m, int n, int k, cons
         afrag_t a = fa[ks & 3];
         bfrag_t b = fb[ks & 3];
         const bool live = 4 * ks + kq < krem;   // this lane's k of the k-step (the same k for its A and its B operand)
+        // (-0 for A, +0 for B: a padded product of -0 leaves every accumulator as it is, a -0 one included)
 #pragma unroll
-        for (int t = 0; t < WTM; ++t) a[t] = live ? a[t] : 0.0f;
+        for (int t = 0; t < WTM; ++t) a[t] = live ? a[t] : -0.0f;
 #pragma unroll
         for (int u = 0; u < WTN; ++u) b[u] = live ? b[u] : 0.0f;   // (zeros by descriptor already; belt and braces)
 #pragma unroll

@@ -151,7 +151,7 @@ struct Dma5ValuFrags {
 // chunk c of row j at c ^ ((j / WTN) & 7) -- the rows one b32 read touches are WTN apart).  The fp32 MFMA takes one float
 // of each operand per lane, A[i][k] and B[k][i]: only the loaders' maps and the fragment addresses change, never the
 // MFMAs, the k order or the accumulators -- the NN bits.  K tail: B^T's columns past k are garbage like A's, and the
-// TAIL slice zeroes both operands.  (Even WTN, MFMA consumers only.)
+// TAIL slice zeroes both operands (A to -0, B to +0).  (Even WTN, MFMA consumers only.)
 template <int BM, int BN, int KB, int WTM, int WTN, int NBUF, bool PART_WT = false, bool EDGE = false, bool CHAIN = false,
           int NL = 1, int D = 2, bool RIM = false, bool VALU = false, int RS = 1, int OP = 0>
 struct Dma5Segment {
@@ -620,10 +620,11 @@ struct Dma5Segment {
         if constexpr (TAIL) {
           // A's columns past k are the next row's floats or the caller's padding (NaN included): zero this lane's
           // operands of the k's that do not exist (B's rows there are zeros by descriptor -- B^T's columns are garbage like A's;
-          // A^T's rows there are zeros by descriptor)
+          // A^T's rows there are zeros by descriptor).  A's dead lanes take -0, B's +0: every padded product is then -0, and
+          // acc + (-0) is acc exactly, -0 included (with +0 * +0 an accumulator of -0 would come out +0: DESIGN section 2)
           const bool live = 4 * ks + L.kq < krem;
 #pragma unroll
-          for (int t = 0; t < NT; ++t) a[t] = live ? a[t] : 0.0f;
+          for (int t = 0; t < NT; ++t) a[t] = live ? a[t] : -0.0f;
 #pragma unroll
           for (int u = 0; u < NU; ++u) b[u] = live ? b[u] : 0.0f;
         }

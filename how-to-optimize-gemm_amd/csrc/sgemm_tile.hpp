@@ -268,9 +268,10 @@ struct Stage {
   }
 
   // K tail of the guarded buffer path: in the last, partial K-slice the A loads
-  // run past column k into the next row (or the caller's padding); zero those
+  // run past column k into the next row (or the caller's padding); -0 into those
   // lanes.  (B needs nothing: its rows >= k lie beyond the descriptor's extent
-  // and read as 0.)  `krem` = number of valid k in this slice.
+  // and read as +0; each padded product is -0, which leaves every accumulator --
+  // -0 included -- as it is.)  `krem` = number of valid k in this slice.
   __device__ __forceinline__ void mask_k_tail(int krem, int tid) {
     const int c = tid % CH;
 #pragma unroll
@@ -279,12 +280,13 @@ struct Stage {
       for (int j = 0; j < 4; ++j)
 #pragma unroll
         for (int s = 0; s < 4; ++s)
-          if (4 * c + s >= krem) a[blk][j][s] = 0.0f;
+          if (4 * c + s >= krem) a[blk][j][s] = -0.0f;
   }
 
-  // Guarded path: any m, n, k, any alignment; out-of-range elements read as 0
-  // (a zero product is an exact no-op on an fmaf chain unless the partner is
-  // inf/nan, which the fast path would not mask either side of the edge).
+  // Guarded path: any m, n, k, any alignment; out-of-range elements read as 0,
+  // -0 for A and +0 for B (a -0 product is an exact no-op on an fmaf chain, a -0
+  // accumulator included, unless the partner is inf/nan, which the fast path
+  // would not mask either side of the edge).
   __device__ __forceinline__ void load_edge(const float *__restrict__ A, int lda,
                                             const float *__restrict__ B, int ldb, int row0,
                                             int col0, int k0, int m, int n, int k, int tid) {
@@ -298,7 +300,7 @@ struct Stage {
 #pragma unroll
         for (int s = 0; s < 4; ++s) {
           const int kk = k0 + 4 * c + s;
-          a[blk][j][s] = (row < m && kk < k) ? A[(size_t)row * lda + kk] : 0.0f;
+          a[blk][j][s] = (row < m && kk < k) ? A[(size_t)row * lda + kk] : -0.0f;
         }
       }
     }

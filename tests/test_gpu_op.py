@@ -188,6 +188,19 @@ def test_all_25_sizes_on_auto_match_the_nn_launch(h):
             assert torch.equal(c, want), (n, name)
 
 
+def test_op_form_fuzz_against_the_naive_op_kernel():
+    """tools/fuzz.py --ops: random shapes, leading dimensions, misaligned bases and accumulate flags on NT / TN / TT, AUTO
+    and the three tiles plain and stream-K, each bit-equal (signed zeros included) to sgemm_naive_op_kernel, with NaN in
+    every operand's padding and nothing written outside C's window."""
+    import subprocess
+    import sys
+    from conftest import REPO
+    r = subprocess.run([sys.executable, os.path.join(REPO, "tools", "fuzz.py"), "--ops", "60", "0", "2027"],
+                       capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    assert "fuzz --ops: 60 cases x 8 variants, 0 failures" in r.stdout, r.stdout[-500:]
+
+
 def test_refusals_leave_c_untouched(h):
     import torch
     import how_to_optimize_gemm_amd as H

@@ -1,9 +1,10 @@
 #!/usr/bin/env python3
 """Differential fuzz on one GPU: every kernel variant against the naive kernel (an
-independent code path with the same chain semantics -> bit-equal) on random shapes,
-leading dimensions, 4-byte-misaligned bases and accumulate flags; plus a stream-K
-stress loop (ragged tile counts, repeated launches) against the one-tile-per-workgroup
-kernel.  usage: python tools/fuzz.py [--ops] [cases] [stress_reps] [seed]
+independent code path with the same chain semantics -> bit-equal, signed zeros included:
+same_bits) on random shapes, leading dimensions, 4-byte-misaligned bases and accumulate
+flags; plus a stream-K stress loop (ragged tile counts, repeated launches; whole rounds
+of the persistent grid) against the one-tile-per-workgroup kernel.
+usage: python tools/fuzz.py [--ops] [cases] [stress_reps] [seed]
 --ops: the transposed-operand forms instead (mmh_sgemm_op: NT / TN / TT on AUTO and the 64x64 / 128x64 / 128x128 LDS-DMA
 tiles, plain and stream-K) against the naive kernel's op form, with NaN in every operand's padding and behind its last row."""
 import os
@@ -29,7 +30,25 @@ VARIANTS = ["auto", "mfma", "mfma256", "mfma_256x256", "mfma_128x64", "mfma_64x6
             "mfma_96x64_dma5", "valu_128x64",                                                     # round 5: the 96x64 K2W tile, K1W's third tile
             "mfma_64x64_dma/sk2", "mfma_128x64_dma/sk2",                                          # ... K2L under stream-K (AUTO's candidates now)
             "valu_64x64/sk2", "valu_128x64/sk2", "valu_128x128/sk2",                             # round 6: K1W under K2W's stream-K body
-            "mfma_160x160_dma5"]                                                                  # round 6: the 160x160 K2W tile (every K2W tile: fragment reads spread)
+            "mfma_160x160_dma5",                                                                  # round 6: the 160x160 K2W tile (every K2W tile: fragment reads spread)
+            "mfma_64x64_dma5/sk2u", "mfma_128x128_dma5/sk2u",                                     # K2W stream-K, parts unchained (MMH_OPT_STREAMK_CHAIN = 0)
+            "mfma_128x64_dma5/persist", "mfma_64x64_dma/persist"]                                 # whole rounds persistent too (MMH_OPT_PERSIST = 1)
+# variant suffix -> (MMH_OPT_STREAMK, MMH_OPT_STREAMK_CHAIN, MMH_OPT_PERSIST)
+FORMS = {"": (1, 1, 0), "sk2": (2, 1, 0), "sk0": (0, 1, 0), "sk2u": (2, 0, 0), "persist": (1, 1, 1)}
+
+
+def set_form(kern):
+    streamk, chain, persist = FORMS[kern.partition("/")[2]]
+    mm.set_kernel(kern.split("/")[0])
+    mm.set_streamk(streamk)
+    mm.set_option(H.OPT_STREAMK_CHAIN, chain)
+    mm.set_option(H.OPT_PERSIST, persist)
+
+
+def same_bits(x, y):
+    """Bit patterns equal wherever y is not NaN (-0.0 is not +0.0), NaN in the same places (payloads not compared)."""
+    nx, ny = torch.isnan(x), torch.isnan(y)
+    return torch.equal(nx, ny) and torch.equal(x.view(torch.int32).masked_fill(nx, 0), y.view(torch.int32).masked_fill(ny, 0))
 
 
 def strided(rows, cols, ld, off, fill=None):
@@ -81,8 +100,7 @@ def fuzz_ops():
         c0 = torch.rand((m, n), device="cuda")
         results = {}
         for kern in ["naive"] + variants:
-            mm.set_kernel(kern.split("/")[0])
-            mm.set_streamk({"sk2": 2, "sk0": 0}.get(kern.partition("/")[2], 1))
+            set_form(kern)
             cflat, cv = strided(m, n, ldc, offs[2], c0)
             mm.sgemm_op(ta, tb, m, n, k, av.data_ptr(), lda, bv.data_ptr(), ldb, cv.data_ptr(), ldc, acc, stream)
             torch.cuda.synchronize()
@@ -91,12 +109,12 @@ def fuzz_ops():
                 nbad += 1
                 print(f"ops case {case} {kern}: wrote outside C window  m,n,k={m},{n},{k} op={ta}{tb}")
         for kern in variants:
-            if not torch.equal(results[kern], results["naive"]):
+            if not same_bits(results[kern], results["naive"]):
                 nbad += 1
                 d = (results[kern] - results["naive"]).abs().max().item()
                 print(f"ops case {case} {kern}: != naive (max diff {d})  m,n,k={m},{n},{k} op={'NT'[ta]}{'NT'[tb]} "
                       f"ld={lda},{ldb},{ldc} off={offs} acc={acc}")
-    mm.set_streamk(1)
+    set_form("mfma")
     print(f"fuzz --ops: {cases} cases x {len(variants)} variants, {nbad} failures")
     return nbad
 
@@ -121,8 +139,7 @@ for case in range(cases):
     _, bv = strided(k, n, ldb, offs[1], b)
     results = {}
     for kern in ["naive"] + VARIANTS:
-        mm.set_kernel(kern.split("/")[0])
-        mm.set_streamk(2 if kern.endswith("/sk2") else 1)
+        set_form(kern)
         cflat, cv = strided(m, n, ldc, offs[2], c0)
         mm.sgemm(m, n, k, av.data_ptr(), lda, bv.data_ptr(), ldb, cv.data_ptr(), ldc, acc, stream)
         torch.cuda.synchronize()
@@ -132,35 +149,54 @@ for case in range(cases):
             bad += 1
             print(f"case {case} {kern}: wrote outside C window  m,n,k={m},{n},{k} ld={lda},{ldb},{ldc}")
     for kern in VARIANTS:
-        if not torch.equal(results[kern], results["naive"]):
+        if not same_bits(results[kern], results["naive"]):
             bad += 1
             d = (results[kern] - results["naive"]).abs().max().item()
             print(f"case {case} {kern}: != naive (max diff {d})  m,n,k={m},{n},{k} ld={lda},{ldb},{ldc} "
                   f"off={offs} acc={acc}")
-mm.set_streamk(1)
+set_form("mfma")
 print(f"fuzz: {cases} cases x {len(VARIANTS)} variants, {bad} failures")
 
 # stream-K stress
 sk_bad = 0
+
+
+def stress_against(a, b, ref, kerns, n, want_word=None):
+    global sk_bad
+    for kern in kerns:
+        set_form(kern)
+        c = torch.empty_like(ref)
+        for rep in range(stress):
+            c.fill_(float("nan"))
+            mm.matmul(a, b, out=c)
+            if want_word and want_word not in H.last_launch():
+                sk_bad += 1
+                print(f"stream-K {kern} N={n}: not a {want_word} launch: {H.last_launch()}")
+                break
+            if not same_bits(c, ref):
+                sk_bad += 1
+                print(f"stream-K {kern} N={n} rep {rep}: mismatch, max diff {(c - ref).abs().max().item()}")
+        if mm.streamk_timeouts():
+            sk_bad += 1
+            print(f"stream-K {kern} N={n}: hand-off timeouts reported")
+
+
 for n in (1152, 1536, 1792, 2176, 2432, 2944, 3072, 3456, 3712, 4352, 4608, 2049, 2305, 3001):   # the last three: guarded stream-K
     a = torch.rand((n, n), device="cuda") * 2 - 1
     b = torch.rand((n, n), device="cuda") * 2 - 1
     mm.set_kernel("mfma_tiles")
     ref = mm.matmul(a, b)
     # "auto": the LDS-DMA tiles under stream-K below 4096, the 256x256 tile above; "mfma": the register-staged 128x128 tile
-    for kern in ("auto", "mfma", "mfma_128x128_dma5/sk2", "mfma_64x64_dma5/sk2", "valu_128x128/sk2", "valu_64x64/sk2", "valu"):
-        mm.set_kernel(kern.split("/")[0])
-        mm.set_streamk(2 if kern.endswith("/sk2") else 1)
-        c = torch.empty_like(ref)
-        for rep in range(stress):
-            c.fill_(float("nan"))
-            mm.matmul(a, b, out=c)
-            if not torch.equal(c, ref):
-                sk_bad += 1
-                print(f"stream-K {kern} N={n} rep {rep}: mismatch, max diff {(c - ref).abs().max().item()}")
-        if mm.streamk_timeouts():
-            sk_bad += 1
-            print(f"stream-K {kern} N={n}: hand-off timeouts reported")
-mm.set_streamk(1)
+    stress_against(a, b, ref, ("auto", "mfma", "mfma_128x128_dma5/sk2", "mfma_64x64_dma5/sk2", "mfma_128x128_dma5/sk2u",
+                               "valu_128x128/sk2", "valu_64x64/sk2", "valu"), n)
+# whole rounds of the persistent grid (MMH_OPT_PERSIST): 6 tiles per CU, a whole number of rounds on 1, 2 or 3 per CU
+cus = mm.device_info()["cu_count"]
+for kern, bm, bn in (("mfma_128x128_dma5/persist", 128, 128), ("mfma_64x64_dma5/persist", 64, 64), ("mfma_128x64_dma/persist", 128, 64)):
+    a = torch.rand((6 * bm, 96), device="cuda") * 2 - 1
+    b = torch.rand((96, cus * bn), device="cuda") * 2 - 1
+    set_form("mfma_tiles")
+    ref = mm.matmul(a, b)
+    stress_against(a, b, ref, (kern,), f"{6 * bm}x{cus * bn}x96", "persistent")
+set_form("mfma")
 print(f"stream-K stress: {sk_bad} failures")
 sys.exit(1 if bad or sk_bad else 0)
