@@ -33,6 +33,8 @@ OPT_STREAMK_CHAIN = 12
 OPT_PERSIST = 13
 OPT_RIM5 = 14
 OP_N, OP_T = 0, 1   # mmh_sgemm_op's operand layouts (include/mmult_hip.h)
+BATCH_FORMS = {1: "fold", 2: "one_launch", 3: "loop"}   # mmh_sgemm_batched's MMH_BATCH_FORM_*
+BATCHED_MAX_WORKGROUPS = 1 << 22   # MMH_BATCHED_MAX_WORKGROUPS: one batched launch holds at most this many workgroups
 KERNELS = {"auto": KERNEL_AUTO, "valu": KERNEL_VALU, "mfma": KERNEL_MFMA,
            "mfma256": KERNEL_MFMA_256, "naive": KERNEL_NAIVE, "mfma_simple": KERNEL_MFMA_SIMPLE,
            "mfma_pipe": KERNEL_MFMA_PIPE, "mfma_tiles": 10, "mfma_128x64": 8, "mfma_64x64": 11, "mfma_256x256": 12,
@@ -60,6 +62,7 @@ EXPORTS = [
     "mmh_sgemm_sharded", "mmh_time_sgemm", "mmh_time_comparator", "mmh_trace_sgemm", "mmh_probe_mfma_f32", "mmh_probe_valu_f32", "mmh_probe_mfma_i8",
     "mmh_probe_mfma_i8_sustained", "mmh_probe_hbm_copy", "mmh_probe_hbm_read", "mmh_probe_lds_read", "mmh_streamk_plan", "mmh_auto_plan",
     "mmh_sgemm_op", "mmh_time_sgemm_op", "mmh_auto_plan_op",
+    "mmh_sgemm_batched", "mmh_time_sgemm_batched", "mmh_auto_plan_batched",
 ]
 
 
@@ -117,6 +120,24 @@ def auto_plan_op(transa: int, transb: int, m: int, n: int, k: int, lda: int = 0,
                                   base_align, cu_count, C.byref(kern), C.byref(tiles), C.byref(grid)), "mmh_auto_plan_op")
     names = {v: name for name, v in KERNELS.items() if name != "mfma256"}
     return names.get(kern.value, str(kern.value)), tiles.value, grid.value
+
+
+def auto_plan_batched(transa: int, transb: int, m: int, n: int, k: int, lda: int = 0, ldb: int = 0, ldc: int = 0,
+                      stride_a: int = -1, stride_b: int = -1, stride_c: int = -1, batch: int = 1, base_align: int = 16,
+                      cu_count: int = 256):
+    """What MMH_KERNEL_AUTO would run for mmh_sgemm_batched (host arithmetic only): (short kernel name, form name --
+    "fold", "one_launch" or "loop" --, workgroups of all its launches).  Strides default to the packed matrices."""
+    lda = lda or (m if transa else k)
+    ldb = ldb or (k if transb else n)
+    ldc = ldc or n
+    sa = (k if transa else m) * lda if stride_a < 0 else stride_a
+    sb = (n if transb else k) * ldb if stride_b < 0 else stride_b
+    sc = m * ldc if stride_c < 0 else stride_c
+    kern, form, wgs = C.c_int(), C.c_int(), C.c_long()
+    _check(lib().mmh_auto_plan_batched(transa, transb, m, n, k, lda, ldb, ldc, sa, sb, sc, batch, base_align, cu_count,
+                                       C.byref(kern), C.byref(form), C.byref(wgs)), "mmh_auto_plan_batched")
+    names = {v: name for name, v in KERNELS.items() if name != "mfma256"}
+    return names.get(kern.value, str(kern.value)), BATCH_FORMS.get(form.value, str(form.value)), wgs.value
 
 
 def use_timeline_library() -> str:
@@ -190,6 +211,11 @@ def lib() -> C.CDLL:
     L.mmh_sgemm_op.argtypes = [vp, C.c_int, C.c_int] + gemm[1:] + [C.c_int, vp]
     L.mmh_time_sgemm_op.argtypes = [vp, C.c_int, C.c_int] + gemm[1:] + [C.c_int, C.c_int, vp, fp]
     L.mmh_auto_plan_op.argtypes = [C.c_int] * 10 + [ip, C.POINTER(C.c_long), ip]
+    ll = C.c_longlong
+    batched = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, ll, vp, C.c_int, ll, vp, C.c_int, ll, C.c_int]
+    L.mmh_sgemm_batched.argtypes = batched + [C.c_int, vp]
+    L.mmh_time_sgemm_batched.argtypes = batched + [C.c_int, C.c_int, vp, fp]
+    L.mmh_auto_plan_batched.argtypes = [C.c_int] * 8 + [ll] * 3 + [C.c_int] * 3 + [ip, ip, C.POINTER(C.c_long)]
     L.mmh_sgemm_host.argtypes = gemm + [C.c_int]
     L.mmh_sgemm_host_timed.argtypes = gemm + [C.c_int, C.POINTER(C.c_float)]
     L.mmh_igemm_s8.argtypes = gemm + [C.c_int, vp]
@@ -394,6 +420,13 @@ class MMult:
         _check(lib().mmh_sgemm_op(self._h, int(transa), int(transb), m, n, k, dA, lda, dB, ldb, dC, ldc, int(bool(accumulate)),
                                   stream), "mmh_sgemm_op")
 
+    def sgemm_batched(self, transa, transb, m, n, k, dA: int, lda, stride_a, dB: int, ldb, stride_b, dC: int, ldc, stride_c,
+                      batch, accumulate=False, stream: int = 0) -> None:
+        """C_i = op(A_i) op(B_i) (+ C_i) for i < batch, row-major as sgemm_op; matrix i at dA + i stride_a (elements), and
+        so on.  A stride of 0 broadcasts an operand; C matrices must not overlap (include/mmult_hip.h)."""
+        _check(lib().mmh_sgemm_batched(self._h, int(transa), int(transb), m, n, k, dA, lda, stride_a, dB, ldb, stride_b, dC, ldc,
+                                       stride_c, batch, int(bool(accumulate)), stream), "mmh_sgemm_batched")
+
     def MY_MMult_device(self, m, n, k, d_A: int, lda, d_B: int, ldb, d_C: int, ldc, stream: int = 0):
         """cuda/test_MMult.cpp:102 -- MY_MMult(handle, m, n, k, d_A, k, d_B, n, d_C, n):
         C = A*B on device pointers, asynchronous."""
@@ -503,6 +536,47 @@ class MMult:
             self.sgemm_op(ta, tb, m, n, k, pa, lda, pb, ldb, pc, ldc, accumulate, stream)
         return out
 
+    def _batched_args(self, t, batch, rows, cols, what, operand):
+        """(data_ptr, leading dimension, op, batch stride) of a 3-D (batch, rows, cols) tensor: each matrix a row-major
+        window or (operands only) a transposed view, as matmul takes them; any batch stride >= 0 (expand() gives 0)."""
+        import torch
+        if t.dim() != 3 or tuple(t.shape) != (batch, rows, cols):
+            raise MMultError(ERR_INVALID_ARG, what, f"need a ({batch},{rows},{cols}) 3-D tensor")
+        if batch == 0:
+            return 0, max(cols, 1), OP_N, 0
+        if operand:
+            p, ld, op = self._operand_args(t[0], rows, cols, what)
+        else:
+            p, ld = self._tensor_args(t[0], rows, cols, what, torch.float32)
+            op = OP_N
+        return p, ld, op, (t.stride(0) if batch > 1 else 0)
+
+    def bmm(self, a, b, out=None, accumulate: bool = False):
+        """C[i] = A[i] @ B[i] (+ C[i]) for 3-D fp32 CUDA tensors [batch, m, k] @ [batch, k, n], on torch's current stream,
+        through mmh_sgemm_batched.  Each operand's matrices may be row-major or transposed views (x.transpose(1, 2)), with
+        any batch stride >= 0 (expand() broadcasts); `out` is row-major per matrix, its matrices must not overlap."""
+        import torch
+        if a.dtype != torch.float32 or b.dtype != torch.float32:
+            raise MMultError(ERR_INVALID_ARG, "bmm", "fp32 only")
+        if a.dim() != 3 or b.dim() != 3:
+            raise MMultError(ERR_INVALID_ARG, "bmm", "need 3-D tensors")
+        batch, m, k = a.shape
+        b2, k2, n = b.shape
+        if k != k2 or batch != b2:
+            raise MMultError(ERR_INVALID_ARG, "bmm", "batch or inner dimensions differ")
+        if out is None:
+            if accumulate:
+                raise MMultError(ERR_INVALID_ARG, "bmm", "accumulate needs out=")
+            out = torch.empty((batch, m, n), dtype=torch.float32, device=a.device)
+        pa, lda, ta, sa = self._batched_args(a, batch, m, k, "bmm(A)", True)
+        pb, ldb, tb, sb = self._batched_args(b, batch, k, n, "bmm(B)", True)
+        pc, ldc, _, sc = self._batched_args(out, batch, m, n, "bmm(C)", False)
+        if batch == 0:
+            return out
+        stream = torch.cuda.current_stream(a.device).cuda_stream
+        self.sgemm_batched(ta, tb, m, n, k, pa, lda, sa, pb, ldb, sb, pc, ldc, sc, batch, accumulate, stream)
+        return out
+
     def igemm_s8(self, a, b, out=None, accumulate: bool = False):
         """int8 x int8 -> int32 for CUDA tensors (inputs expected in [-127,127])."""
         import torch
@@ -602,6 +676,14 @@ class MMult:
         ms = C.c_float(0)
         _check(lib().mmh_time_sgemm_op(self._h, int(transa), int(transb), m, n, k, dA, lda, dB, ldb, dC, ldc, warmup, reps, stream,
                                        C.byref(ms)), "mmh_time_sgemm_op")
+        return ms.value
+
+    def time_sgemm_batched(self, transa, transb, m, n, k, dA, lda, stride_a, dB, ldb, stride_b, dC, ldc, stride_c, batch,
+                           warmup=1, reps=20, stream: int = 0) -> float:
+        """time_sgemm for mmh_sgemm_batched: ms per batched call."""
+        ms = C.c_float(0)
+        _check(lib().mmh_time_sgemm_batched(self._h, int(transa), int(transb), m, n, k, dA, lda, stride_a, dB, ldb, stride_b, dC,
+                                            ldc, stride_c, batch, warmup, reps, stream, C.byref(ms)), "mmh_time_sgemm_batched")
         return ms.value
 
     def time_comparator(self, which: str, m, n, k, dA, lda, dB, ldb, dC, ldc, warmup=1, reps=20, stream: int = 0) -> float:
@@ -745,7 +827,7 @@ def sgemm_sharded(ngpus: int, a: np.ndarray, b: np.ndarray, kernel="mfma"):
 
 
 __all__ = ["MMult", "ShardedMMult", "MMultError", "lib", "use_ab_library", "device_count", "rccl_version", "shard_rows", "shard_chunks",
-           "kernel_name", "last_launch", "use_timeline_library", "streamk_plan", "auto_plan", "auto_plan_op", "OP_N", "OP_T", "sgemm_sharded", "KERNELS", "CHAIN_KERNELS", "AB_LIB_PATH",
+           "kernel_name", "last_launch", "use_timeline_library", "streamk_plan", "auto_plan", "auto_plan_op", "auto_plan_batched", "BATCH_FORMS", "BATCHED_MAX_WORKGROUPS", "OP_N", "OP_T", "sgemm_sharded", "KERNELS", "CHAIN_KERNELS", "AB_LIB_PATH",
            "OPT_SPLITK", "OPT_HOST_PANELS", "OPT_STREAMK_SPIN_LIMIT", "OPT_FAULT_INJECT", "OPT_STREAMK_ORDER", "OPT_DMA_EDGE", "OPT_STREAMK_DELEGATIONS", "OPT_RIM", "OPT_STREAMK_CHAIN", "OPT_PERSIST", "OPT_RIM5", "KERNEL_AUTO", "KERNEL_VALU", "KERNEL_MFMA", "KERNEL_MFMA_256", "KERNEL_NAIVE", "KERNEL_MFMA_SIMPLE", "KERNEL_MFMA_PIPE",
            "EXPORTS", "LIB_PATH", "OPT_STREAMK", "OPT_STREAMK_TIMEOUTS", "OPT_IGEMM_MODE", "OK", "ERR_INVALID_ARG", "ERR_HIP", "ERR_NO_DEVICE",
            "ERR_UNSUPPORTED", "ERR_ALLOC", "ERR_COMM"]

@@ -7,6 +7,32 @@
 
 using namespace mmh;
 
+namespace {
+// warmup + reps calls of `call` between one event pair on s: ms per call (every exit destroys what was created: a sticky
+// error or a failed launch inside the loop must not leak events)
+template <typename F>
+int time_calls(mmh_context *h, hipStream_t s, int warmup, int reps, float *ms_per_call, const char *what, F call) {
+  int rc = MMH_OK;
+  for (int i = 0; i < warmup && rc == MMH_OK; ++i) rc = call();
+  if (rc != MMH_OK) return rc;
+  hipEvent_t t0 = nullptr, t1 = nullptr;
+  hipError_t e = hipEventCreate(&t0);
+  if (e == hipSuccess) e = hipEventCreate(&t1);
+  if (e == hipSuccess) e = hipEventRecord(t0, s);
+  for (int i = 0; i < reps && rc == MMH_OK && e == hipSuccess; ++i) rc = call();
+  float ms = 0.f;
+  if (rc == MMH_OK && e == hipSuccess) e = hipEventRecord(t1, s);
+  if (rc == MMH_OK && e == hipSuccess) e = hipEventSynchronize(t1);
+  if (rc == MMH_OK && e == hipSuccess) e = hipEventElapsedTime(&ms, t0, t1);
+  if (t0) (void)hipEventDestroy(t0);
+  if (t1) (void)hipEventDestroy(t1);
+  if (rc != MMH_OK) return rc;
+  if (e != hipSuccess) return hip_fail(e, what);
+  *ms_per_call = ms / reps;
+  return check_sticky(h);
+}
+}  // namespace
+
 extern "C" {
 
 const char *mmh_strerror(int status) {
@@ -175,6 +201,9 @@ int mmh_set_option(mmh_handle_t h, int option, int value) {
       return MMH_OK;
     case 107:   // A/B (round 6): the tail split of plain K2W launches (launch_dma5.hip) on (product) / off
       h->split_tail = value ? 1 : 0;
+      return MMH_OK;
+    case 108:   // A/B: the batched K2W launch in plain batch-major order instead of XCD-contiguous runs (profiles/batched_sweep.md)
+      h->ab_batch_major = value ? 1 : 0;
       return MMH_OK;
     case 105:   // A/B: the vector-ALU rung as it was before round 5 (register-staged K1) instead of K1W
       h->ab_valu_old = value ? 1 : 0;
@@ -367,6 +396,14 @@ int mmh_sgemm_op(mmh_handle_t h, int transa, int transb, int m, int n, int k, co
   return sgemm_op_on(h, h->kernel, transa, transb, m, n, k, dA, lda, dB, ldb, dC, ldc, accumulate,
                      static_cast<hipStream_t>(stream));
 }
+int mmh_sgemm_batched(mmh_handle_t h, int transa, int transb, int m, int n, int k, const float *dA, int lda, long long strideA,
+                      const float *dB, int ldb, long long strideB, float *dC, int ldc, long long strideC, int batch, int accumulate,
+                      void *stream) {
+  if (!h) return MMH_ERR_INVALID_ARG;
+  ENTER(h);
+  return sgemm_batched_on(h, h->kernel, transa, transb, m, n, k, dA, lda, strideA, dB, ldb, strideB, dC, ldc, strideC, batch,
+                          accumulate, static_cast<hipStream_t>(stream));
+}
 int mmh_time_sgemm(mmh_handle_t h, int m, int n, int k, const float *dA, int lda, const float *dB,
                    int ldb, float *dC, int ldc, int warmup, int reps, void *stream,
                    float *ms_per_call) {
@@ -377,26 +414,18 @@ int mmh_time_sgemm_op(mmh_handle_t h, int transa, int transb, int m, int n, int 
   if (!h || reps <= 0 || warmup < 0 || !ms_per_call) return MMH_ERR_INVALID_ARG;
   ENTER(h);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  int rc = MMH_OK;
-  auto call = [&]() { return sgemm_op_on(h, h->kernel, transa, transb, m, n, k, dA, lda, dB, ldb, dC, ldc, 0, s); };
-  for (int i = 0; i < warmup && rc == MMH_OK; ++i) rc = call();
-  if (rc != MMH_OK) return rc;
-  // (every exit below destroys what was created: a sticky error or a failed launch inside the loop must not leak events)
-  hipEvent_t t0 = nullptr, t1 = nullptr;
-  hipError_t e = hipEventCreate(&t0);
-  if (e == hipSuccess) e = hipEventCreate(&t1);
-  if (e == hipSuccess) e = hipEventRecord(t0, s);
-  for (int i = 0; i < reps && rc == MMH_OK && e == hipSuccess; ++i) rc = call();
-  float ms = 0.f;
-  if (rc == MMH_OK && e == hipSuccess) e = hipEventRecord(t1, s);
-  if (rc == MMH_OK && e == hipSuccess) e = hipEventSynchronize(t1);
-  if (rc == MMH_OK && e == hipSuccess) e = hipEventElapsedTime(&ms, t0, t1);
-  if (t0) (void)hipEventDestroy(t0);
-  if (t1) (void)hipEventDestroy(t1);
-  if (rc != MMH_OK) return rc;
-  if (e != hipSuccess) return hip_fail(e, "mmh_time_sgemm_op");
-  *ms_per_call = ms / reps;
-  return check_sticky(h);
+  return time_calls(h, s, warmup, reps, ms_per_call, "mmh_time_sgemm_op",
+                    [&]() { return sgemm_op_on(h, h->kernel, transa, transb, m, n, k, dA, lda, dB, ldb, dC, ldc, 0, s); });
+}
+int mmh_time_sgemm_batched(mmh_handle_t h, int transa, int transb, int m, int n, int k, const float *dA, int lda,
+                           long long strideA, const float *dB, int ldb, long long strideB, float *dC, int ldc, long long strideC,
+                           int batch, int warmup, int reps, void *stream, float *ms_per_call) {
+  if (!h || reps <= 0 || warmup < 0 || !ms_per_call) return MMH_ERR_INVALID_ARG;
+  ENTER(h);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  return time_calls(h, s, warmup, reps, ms_per_call, "mmh_time_sgemm_batched", [&]() {
+    return sgemm_batched_on(h, h->kernel, transa, transb, m, n, k, dA, lda, strideA, dB, ldb, strideB, dC, ldc, strideC, batch, 0, s);
+  });
 }
 
 // per-launch durations of `count` back-to-back calls (one event pair each): the clock-ramp trace
@@ -436,6 +465,12 @@ int mmh_auto_plan(int m, int n, int k, int lda, int ldb, int ldc, int base_align
 int mmh_auto_plan_op(int transa, int transb, int m, int n, int k, int lda, int ldb, int ldc, int base_align, int cu_count,
                      int *kernel, long *tiles, int *streamk_grid) {
   return mmh::auto_plan_op(transa, transb, m, n, k, lda, ldb, ldc, base_align, cu_count, kernel, tiles, streamk_grid);
+}
+int mmh_auto_plan_batched(int transa, int transb, int m, int n, int k, int lda, int ldb, int ldc, long long strideA,
+                          long long strideB, long long strideC, int batch, int base_align, int cu_count, int *kernel,
+                          int *form, long *workgroups) {
+  return mmh::auto_plan_batched(transa, transb, m, n, k, lda, ldb, ldc, strideA, strideB, strideC, batch, base_align, cu_count,
+                                kernel, form, workgroups);
 }
 
 }  // extern "C"

@@ -151,6 +151,7 @@ struct mmh_context {
   int ab_own_occ = 0;          // tools build only (option 103): a whole-tile stream-K launch is bounded by ITS OWN instantiation's residency
   int split_tail = 1;          // a plain K2W launch whose last round the dispatcher would pack two per CU goes out as two launches (launch_dma5.hip; tools build: option 107 switches it off)
   int ab_group_m = 0;          // tools build only (option 101): raster group height of the plain K2W launch, 0 = GROUP_M
+  int ab_batch_major = 0;      // tools build only (option 108): the batched K2W launch in plain batch-major order, not XCD-contiguous
   int persist = 0;             // whole rounds of the persistent grid run persistent too (MMH_OPT_PERSIST)
   int rim = 0;                 // MMH_KERNEL_AUTO trims up to this many rows / columns past a 64-boundary off the tiles (MMH_OPT_RIM; off: measured, it does not pay)
   // stream-K tables per launch shape (tiles, K-slices, grid): [order: grid ints][place: tiles ints]
@@ -276,6 +277,36 @@ int warm_dma5(mmh_context *ctx, float *scratch, hipStream_t s);
 int launch_dma5_op(mmh_context *ctx, int kernel, const GemmArgs &g);   // 1: the shape does not qualify
 int launch_naive_op(const GemmArgs &g);
 int warm_dma5_op(mmh_context *ctx);                                     // LDS opt-ins only (nothing is launched)
+// launch_batched.hip: mmh_sgemm_batched's one-launch form -- `batch` matrices of g's shape, matrix i at g.A + i sA, g.B + i sB,
+// g.C + i sC (elements) -- on MMH_KERNEL_MFMA_{64X64,128X64,128X128}_DMA5 (1: the matrices do not qualify), and the naive
+// batched kernel (every kernel id, k == 0 included: it zeroes C without reading A or B)
+struct BatchArgs {
+  long long sA = 0, sB = 0, sC = 0;
+  long batch = 1;
+};
+// one launch never holds more workgroups than this; a larger batch goes out as several launches of the same kernel
+constexpr long kBatchedMaxWorkgroups = MMH_BATCHED_MAX_WORKGROUPS;
+// the batched tiles' form for a whole matrix set: 0 whole-tile (fast_shape for EVERY matrix: the bases 16-byte aligned
+// and every stride a multiple of 4 floats), 1 guarded (dma5_form's rules, every matrix), -1 not on this tile
+inline int dma5_batched_form(const mmh_context *ctx, int BM, int BN, const GemmArgs &g, const BatchArgs &b) {
+  if (!window_ok(BM, BN, g)) return -1;   // (per matrix: the descriptors are built per tile from the matrix's base)
+  const bool s4 = b.batch == 1 || (b.sA % 4 == 0 && b.sB % 4 == 0 && b.sC % 4 == 0);
+  if (fast_shape(BM, BN, 32, g) && s4) return 0;
+  if (!ctx || !ctx->dma_edge) return -1;
+  const bool rows16 = (g.lda % 4 == 0) && (g.ldb % 4 == 0) && aligned16(g.A) && aligned16(g.B) &&
+                      (b.batch == 1 || (b.sA % 4 == 0 && b.sB % 4 == 0));
+  if (!rows16 && !ctx->dma_dword_rows) return -1;
+  return 1;
+}
+int launch_dma5_batched(mmh_context *ctx, int kernel, const GemmArgs &g, const BatchArgs &b);
+int launch_naive_batched(const GemmArgs &g, const BatchArgs &b);
+int warm_dma5_batched(mmh_context *ctx);   // LDS opt-ins only (nothing is launched)
+// policy.hip: mmh_sgemm_batched / mmh_auto_plan_batched
+int sgemm_batched_on(mmh_context *ctx, int kernel, int ta, int tb, int m, int n, int k, const float *dA, int lda, long long sA,
+                     const float *dB, int ldb, long long sB, float *dC, int ldc, long long sC, int batch, int accumulate,
+                     hipStream_t s);
+int auto_plan_batched(int ta, int tb, int m, int n, int k, int lda, int ldb, int ldc, long long sA, long long sB, long long sC,
+                      int batch, int base_align, int cu_count, int *kernel, int *form, long *workgroups);
 // launch_valu.hip
 int launch_valu(mmh_context *ctx, int kernel, const GemmArgs &g);
 int warm_valu(mmh_context *ctx, float *scratch, hipStream_t s);

@@ -1,0 +1,164 @@
+// launch_batched.hip -- launchers of mmh_sgemm_batched's one-launch form: the 64x64, 128x64 and 128x128 K2W tiles
+// (sgemm_dma5.hpp, sgemm_mfma_dma5_batched_kernel) over batch x tiles, whole-tile and guarded, every op pair; and the
+// naive batched kernel.  A translation unit of its own, like launch_op.hip: the NN and op instantiations are compiled
+// exactly as before.  Part of libmmult_hip.so (see internal.hpp).
+#include "launch_common.hpp"
+#include "sgemm_dma5.hpp"
+
+namespace mmh {
+
+// K0 batched: sgemm_naive_op_kernel with the matrix in blockIdx.z (+ z0 of the launch's chunk).  One fmaf chain over
+// ascending k per element: the independent reference of tools/fuzz.py --batched.  k == 0 writes 0 (or leaves C) and
+// reads neither A nor B.
+__global__ void __launch_bounds__(256)
+sgemm_naive_batched_kernel(int transa, int transb, int m, int n, int k, const float *__restrict__ A, int lda, long long sA,
+                           const float *__restrict__ B, int ldb, long long sB, float *__restrict__ C, int ldc, long long sC,
+                           int accumulate) {
+  const int col = blockIdx.x * 64 + (threadIdx.x & 63);
+  const int row = blockIdx.y * 4 + (threadIdx.x >> 6);
+  if (row >= m || col >= n) return;
+  A += (long long)blockIdx.z * sA;
+  B += (long long)blockIdx.z * sB;
+  C += (long long)blockIdx.z * sC;
+  const size_t a_i = transa ? 1 : (size_t)lda, a_p = transa ? (size_t)lda : 1;
+  const size_t b_p = transb ? 1 : (size_t)ldb, b_j = transb ? (size_t)ldb : 1;
+  float acc = accumulate ? C[(size_t)row * ldc + col] : 0.0f;
+  for (int p = 0; p < k; ++p) acc = __builtin_fmaf(A[row * a_i + p * a_p], B[p * b_p + col * b_j], acc);
+  C[(size_t)row * ldc + col] = acc;
+}
+
+namespace {
+
+const char *batch_op_tag(const GemmArgs &g) {
+  return g.ta ? (g.tb ? ", operands TT" : ", operands TN") : (g.tb ? ", operands NT" : "");
+}
+
+// One launch (or several of at most kBatchedMaxWorkgroups workgroups each: whole matrices per launch, the pointers
+// advanced to the chunk's first matrix) of one tile over every matrix.  Whole-tile or guarded for the whole matrix set
+// (dma5_batched_form); the tail split of launch_op_tile on the residency of the NN twin.
+template <int BM, int BN, int WTM, int WTN, int NBUF, int NL, int D, int OP>
+int launch_batched_tile(mmh_context *ctx, const GemmArgs &g, const BatchArgs &bt) {
+  constexpr int KB = 32;
+  using T = Dma5Tile<BM, BN, KB, WTM, WTN, NBUF, NL>;
+  const int form = dma5_batched_form(ctx, BM, BN, g, bt);
+  if (form < 0) return 1;
+  const bool edge = form == 1;
+  auto kern = edge ? sgemm_mfma_dma5_batched_kernel<BM, BN, KB, WTM, WTN, NBUF, true, NL, D, OP>
+                   : sgemm_mfma_dma5_batched_kernel<BM, BN, KB, WTM, WTN, NBUF, false, NL, D, OP>;
+  auto twin = edge ? sgemm_mfma_dma5_kernel<BM, BN, KB, WTM, WTN, NBUF, true, NL, D, 1>
+                   : sgemm_mfma_dma5_kernel<BM, BN, KB, WTM, WTN, NBUF, false, NL, D, 1>;
+  const int ok = allow_big_lds(kern, T::LDS_BYTES);
+  if (ok != MMH_OK) return ok;
+  const int nbm = (g.m + BM - 1) / BM, nbn = (g.n + BN - 1) / BN;
+  const long per = (long)nbm * nbn;   // (<= 2^17: a matrix inside the descriptor window)
+  const long mats = std::max(1L, kBatchedMaxWorkgroups / per);   // matrices per launch
+  int acc = g.acc;
+  if constexpr (kAbBuild) acc |= (ctx && ctx->ab_batch_major) ? 2 : 0;
+  long launches = 0;
+  bool split = false;
+  for (long b0 = 0; b0 < bt.batch; b0 += mats) {
+    const long nb = std::min(mats, bt.batch - b0);
+    const long tiles = nb * per;
+    const float *A = g.A + b0 * bt.sA, *B = g.B + b0 * bt.sB;
+    float *C = g.C + b0 * bt.sC;
+    long first = tiles;
+    if (ctx && ctx->split_tail) {   // the tail split of launch_dma5_tile
+      (void)allow_big_lds(twin, T::LDS_BYTES);
+      const long cus = ctx->cu_count > 0 ? ctx->cu_count : 256;
+      const long w = std::min(resident_per_cu(ctx, twin, T::THREADS, T::LDS_BYTES), 3);
+      if (dma5_tail_split(tiles, w, cus, g.k) && (w * cus) % 8 == 0) first = w * cus;
+    }
+    hipLaunchKernelGGL(kern, dim3((unsigned)first), dim3(T::THREADS), T::LDS_BYTES, g.s, g.m, g.n, g.k, A, g.lda, bt.sA, B, g.ldb,
+                       bt.sB, C, g.ldc, bt.sC, acc, nbm, nbn, 0u);
+    ++launches;
+    if (first < tiles) {
+      hipLaunchKernelGGL(kern, dim3((unsigned)(tiles - first)), dim3(T::THREADS), T::LDS_BYTES, g.s, g.m, g.n, g.k, A, g.lda, bt.sA,
+                         B, g.ldb, bt.sB, C, g.ldc, bt.sC, acc, nbm, nbn, (unsigned)first);
+      ++launches;
+      split = true;
+    }
+    HIP_TRY(hipGetLastError());
+  }
+  char what[384];
+  char how[64] = "";
+  if (launches > 1) snprintf(how, sizeof how, " as %ld launches", launches);
+  snprintf(what, sizeof what,
+           "sgemm_mfma_dma5_batched_kernel<%d,%d> wave tile %dx%d, K-slice %d x %d ring buffers by %d loader waves' LDS-DMA, "
+           "fragments %d k-steps ahead, %s%ld workgroups of %d threads%s%s, batch %ld%s",
+           BM, BN, 16 * WTM, 16 * WTN, KB, NBUF, NL, D, edge ? "guarded, " : "", bt.batch * per, T::THREADS,
+           split ? " (the last round as a launch of its own)" : "", batch_op_tag(g), bt.batch, how);
+  set_last_launch(what);
+  return MMH_OK;
+}
+
+// (the NN configurations of launch_dma5: BM BN WTM WTN NBUF NL D)
+template <int OP>
+int launch_batched_family(mmh_context *ctx, int kernel, const GemmArgs &g, const BatchArgs &b) {
+  switch (kernel) {
+    case MMH_KERNEL_MFMA_64X64_DMA5: return launch_batched_tile<64, 64, 2, 2, 3, 2, 2, OP>(ctx, g, b);
+    case MMH_KERNEL_MFMA_128X64_DMA5: return launch_batched_tile<128, 64, 4, 2, 3, 4, 2, OP>(ctx, g, b);
+    case MMH_KERNEL_MFMA_128X128_DMA5: return launch_batched_tile<128, 128, 4, 4, 3, 4, 2, OP>(ctx, g, b);
+    default: return 1;
+  }
+}
+
+template <int BM, int BN, int WTM, int WTN, int NBUF, int NL, int D, int OP>
+int warm_batched_tile() {
+  constexpr int KB = 32;
+  using T = Dma5Tile<BM, BN, KB, WTM, WTN, NBUF, NL>;
+  int rc;
+  if ((rc = allow_big_lds(sgemm_mfma_dma5_batched_kernel<BM, BN, KB, WTM, WTN, NBUF, false, NL, D, OP>, T::LDS_BYTES)) != MMH_OK)
+    return rc;
+  return allow_big_lds(sgemm_mfma_dma5_batched_kernel<BM, BN, KB, WTM, WTN, NBUF, true, NL, D, OP>, T::LDS_BYTES);
+}
+
+template <int OP>
+int warm_batched_families() {
+  int rc;
+  if ((rc = warm_batched_tile<64, 64, 2, 2, 3, 2, 2, OP>()) != MMH_OK) return rc;
+  if ((rc = warm_batched_tile<128, 64, 4, 2, 3, 4, 2, OP>()) != MMH_OK) return rc;
+  return warm_batched_tile<128, 128, 4, 4, 3, 4, 2, OP>();
+}
+
+}  // namespace
+
+int launch_dma5_batched(mmh_context *ctx, int kernel, const GemmArgs &g, const BatchArgs &b) {
+  switch (g.ta | (g.tb << 1)) {
+    case 0: return launch_batched_family<0>(ctx, kernel, g, b);
+    case 1: return launch_batched_family<1>(ctx, kernel, g, b);
+    case 2: return launch_batched_family<2>(ctx, kernel, g, b);
+    default: return launch_batched_family<3>(ctx, kernel, g, b);
+  }
+}
+
+int launch_naive_batched(const GemmArgs &g, const BatchArgs &b) {
+  const long gx = (g.n + 63) / 64, gy = (g.m + 3) / 4;
+  const long mats = std::max(1L, std::min(65535L, kBatchedMaxWorkgroups / (gx * gy)));   // matrices per launch
+  long launches = 0;
+  for (long b0 = 0; b0 < b.batch; b0 += mats) {
+    const long nb = std::min(mats, b.batch - b0);
+    hipLaunchKernelGGL(sgemm_naive_batched_kernel, dim3((unsigned)gx, (unsigned)gy, (unsigned)nb), dim3(256), 0, g.s, g.ta, g.tb, g.m,
+                       g.n, g.k, g.A ? g.A + b0 * b.sA : nullptr, g.lda, b.sA, g.B ? g.B + b0 * b.sB : nullptr, g.ldb, b.sB,
+                       g.C + b0 * b.sC, g.ldc, b.sC, g.acc);
+    ++launches;
+    HIP_TRY(hipGetLastError());
+  }
+  char what[160];
+  snprintf(what, sizeof what, "sgemm_naive_batched_kernel%s, batch %ld", batch_op_tag(g), b.batch);
+  std::string s = what;
+  if (launches > 1) s += " as " + std::to_string(launches) + " launches";
+  set_last_launch(s);
+  return MMH_OK;
+}
+
+// the batched kernels' LDS opt-ins (> 64 KiB), so that a first batched launch can be captured into a graph
+int warm_dma5_batched(mmh_context *ctx) {
+  (void)ctx;
+  int rc;
+  if ((rc = warm_batched_families<0>()) != MMH_OK) return rc;
+  if ((rc = warm_batched_families<1>()) != MMH_OK) return rc;
+  if ((rc = warm_batched_families<2>()) != MMH_OK) return rc;
+  return warm_batched_families<3>();
+}
+
+}  // namespace mmh

@@ -53,6 +53,40 @@ bool is_k2l(int kernel) {
   return kernel == MMH_KERNEL_MFMA_64X64_DMA || kernel == MMH_KERNEL_MFMA_128X64_DMA || kernel == MMH_KERNEL_MFMA_128X128_DMA;
 }
 
+// the tiles of an m x n shape that are not K2W thin edge tiles (a last tile row / column with at most 16 valid rows /
+// columns: a fraction of a tile's MFMAs, dispatched last, beside whole tiles)
+long full_tiles(const Family &f, int m, int n) {
+  const int nbm = (m + f.bm - 1) / f.bm, nbn = (n + f.bn - 1) / f.bn;
+  const int tr = (nbm > 1 && m - (nbm - 1) * f.bm <= 16) ? 1 : 0, tc = (nbn > 1 && n - (nbn - 1) * f.bn <= 16) ? 1 : 0;
+  return (long)(nbm - tr) * (nbn - tc);
+}
+
+// The price of a plain launch (one workgroup per tile) of `tiles` workgroups of the family, `full` of them not thin.
+// The thin edge tiles cost MMH_POLICY_THIN of a round where they add a tile to the fullest CU (N = 1025 against 1024 on
+// the 64x64 tile: 26.3 against 18.1 us; tools/policy_fit.py THIN).
+double plain_us(const mmh_context *ctx, const Family &f, int k, long tiles, long full, bool whole) {
+  const long cus = ctx && ctx->cu_count > 0 ? ctx->cu_count : 256;
+  const double nk = (double)((k + kSliceK - 1) / kSliceK);
+  const long cmax = (tiles + cus - 1) / cus;
+  const int occ = (int)std::min<long>(cmax, f.w);
+  double cmax_p = (double)cmax;
+  if (full < tiles) {
+    const long cfull = (full + cus - 1) / cus;
+    cmax_p = (double)cfull + MMH_POLICY_THIN * (double)(cmax - cfull);
+  }
+  double t = (whole ? f.fix_p_whole : f.fix_p) + cmax_p * (nk * f.s_p[occ - 1] + f.tile_p[occ - 1]);
+  if (cmax > f.w && tiles % ((long)f.w * cus) != 0) {   // a ragged last round
+    // ... of between half a tile and one tile per CU: the dispatcher hands those out one per CU, or in pairs to the
+    // CUs whose workgroups ended together -- a whole extra round (the same launch 142 and 110 TFLOP/s in two passes:
+    // tools/policy_fit.py PAIRING); priced at the risk
+    // (the launches launch_dma5.hip splits -- one round and a last round of just under a tile per CU -- are out of that class)
+    const long rem = tiles % ((long)f.w * cus);
+    const bool split = is_k2w(f.kernel) && (!ctx || ctx->split_tail) && dma5_tail_split(tiles, f.w, cus, k);
+    t *= (2 * rem > cus && rem <= cus && !split) ? std::max(MMH_POLICY_PAIRING_MARGIN, MMH_POLICY_MULTIROUND_MARGIN) : MMH_POLICY_MULTIROUND_MARGIN;
+  }
+  return t;
+}
+
 Plan auto_plan_for(const mmh_context *ctx, const GemmArgs &g) {
   const long cus = ctx && ctx->cu_count > 0 ? ctx->cu_count : 256;
   const double nk = (double)((g.k + kSliceK - 1) / kSliceK);
@@ -80,31 +114,8 @@ Plan auto_plan_for(const mmh_context *ctx, const GemmArgs &g) {
         tiles_rim = 0;
     }
     if (tiles_rim) tiles = tiles_rim;
-    const long cmax = (tiles + cus - 1) / cus;
-    const int occ = (int)std::min<long>(cmax, f.w);
     const bool whole = fast_shape(f.bm, f.bn, kSliceK, g);
-    // K2W's thin edge tiles (a last tile row / column with at most 16 valid rows / columns: a fraction of a tile's MFMAs,
-    // dispatched last, beside whole tiles) cost MMH_POLICY_THIN of a round where they add a tile to the fullest CU
-    // (N = 1025 against 1024 on the 64x64 tile: 26.3 against 18.1 us; tools/policy_fit.py THIN)
-    double cmax_p = (double)cmax;
-    if (is_k2w(f.kernel) && !tiles_rim) {
-      const int nbm = (g.m + f.bm - 1) / f.bm, nbn = (g.n + f.bn - 1) / f.bn;
-      const int tr = (nbm > 1 && g.m - (nbm - 1) * f.bm <= 16) ? 1 : 0, tc = (nbn > 1 && g.n - (nbn - 1) * f.bn <= 16) ? 1 : 0;
-      if (tr || tc) {
-        const long full = (long)(nbm - tr) * (nbn - tc), cfull = (full + cus - 1) / cus;
-        cmax_p = (double)cfull + MMH_POLICY_THIN * (double)(cmax - cfull);
-      }
-    }
-    double t = (whole ? f.fix_p_whole : f.fix_p) + cmax_p * (nk * f.s_p[occ - 1] + f.tile_p[occ - 1]);
-    if (cmax > f.w && tiles % ((long)f.w * cus) != 0) {   // a ragged last round
-      // ... of between half a tile and one tile per CU: the dispatcher hands those out one per CU, or in pairs to the
-      // CUs whose workgroups ended together -- a whole extra round (the same launch 142 and 110 TFLOP/s in two passes:
-      // tools/policy_fit.py PAIRING); priced at the risk
-      // (the launches launch_dma5.hip splits -- one round and a last round of just under a tile per CU -- are out of that class)
-      const long rem = tiles % ((long)f.w * cus);
-      const bool split = is_k2w(f.kernel) && (!ctx || ctx->split_tail) && dma5_tail_split(tiles, f.w, cus, g.k);
-      t *= (2 * rem > cus && rem <= cus && !split) ? std::max(MMH_POLICY_PAIRING_MARGIN, MMH_POLICY_MULTIROUND_MARGIN) : MMH_POLICY_MULTIROUND_MARGIN;
-    }
+    const double t = plain_us(ctx, f, g.k, tiles, is_k2w(f.kernel) && !tiles_rim ? full_tiles(f, g.m, g.n) : tiles, whole);
     if (best.kernel < 0 || t < best.us) best = Plan{f.kernel, 1, t, 0, f.bm, f.bn};
     if (f.has_sk && (!ctx || ctx->streamk) && !tiles_rim) {
       // the grid launch_streamk will launch: the largest w' <= skw workgroups per CU that leaves every one a whole tile
@@ -339,6 +350,153 @@ int sgemm_op_on(mmh_context *ctx, int kernel, int ta, int tb, int m, int n, int 
   set_last_error("transposed operands need the LDS-DMA tiles: an operand lies beyond their 2 GiB descriptor window, or "
                  "MMH_OPT_DMA_EDGE keeps this shape off them (the register-staged tiles take NN operands only)");
   return MMH_ERR_UNSUPPORTED;
+}
+
+// ---- mmh_sgemm_batched ----
+namespace {
+struct BatchPlan {
+  int form = 0;      // MMH_BATCH_FORM_*
+  int kernel = -1;   // one launch: the tile; fold / loop: the per-matrix (folded) plan's kernel, -1 = its fallback
+  Plan per;          // fold / loop: the plan of the one GEMM mmh_sgemm_op runs (the folded one, or one matrix's)
+};
+
+bool fold_ok(const GemmArgs &g, const BatchArgs &b) {
+  return !g.ta && b.sB == 0 && b.sA == (long long)g.m * g.lda && b.sC == (long long)g.m * g.ldc &&
+         (long long)b.batch * g.m <= 0x7fffffff;
+}
+
+// MMH_KERNEL_AUTO for a batch: fold where the matrices ARE one GEMM (B shared, A and C packed); else the cheaper of one
+// batched launch on one of the three tiles -- the plain price of auto_plan_for with batch x tiles per matrix, thin edge
+// tiles and ragged last round included -- and a loop of the per-matrix plan at batch x its price.  A batch of one is the
+// per-matrix plan.
+BatchPlan batched_plan_for(const mmh_context *ctx, const GemmArgs &g, const BatchArgs &b) {
+  BatchPlan bp;
+  if (fold_ok(g, b)) {
+    GemmArgs f = g;
+    f.m = (int)(b.batch * g.m);
+    bp.form = MMH_BATCH_FORM_FOLD;
+    bp.per = auto_plan_for(ctx, f);
+    bp.kernel = bp.per.kernel;
+    return bp;
+  }
+  bp.form = MMH_BATCH_FORM_LOOP;
+  bp.per = auto_plan_for(ctx, g);
+  bp.kernel = bp.per.kernel;
+  if (b.batch == 1) return bp;
+  double best = bp.per.kernel >= 0 ? (double)b.batch * bp.per.us : 0.0;
+  for (const Family &f : kFamilies) {
+    if (!has_op_forms(f.kernel)) continue;
+    const int form = dma5_batched_form(ctx, f.bm, f.bn, g, b);
+    if (form < 0) continue;
+    const long per = (long)((g.m + f.bm - 1) / f.bm) * ((g.n + f.bn - 1) / f.bn);
+    const double t = plain_us(ctx, f, g.k, b.batch * per, b.batch * full_tiles(f, g.m, g.n), form == 0);
+    if (bp.kernel < 0 || t < best) {
+      best = t;
+      bp.form = MMH_BATCH_FORM_ONE_LAUNCH;
+      bp.kernel = f.kernel;
+    }
+  }
+  return bp;
+}
+
+// the argument rules of mmh_sgemm_batched that need no pointer (mmh_auto_plan_batched shares them)
+int check_batch_args(int ta, int tb, int m, int n, int ldc, long long sA, long long sB, long long sC, int batch) {
+  if ((ta != MMH_OP_N && ta != MMH_OP_T) || (tb != MMH_OP_N && tb != MMH_OP_T)) return MMH_ERR_INVALID_ARG;
+  if (batch < 0 || sA < 0 || sB < 0 || sC < 0) return MMH_ERR_INVALID_ARG;
+  if (batch > 1 && m > 0 && n > 0 && ldc >= n && sC < (long long)(m - 1) * ldc + n) return MMH_ERR_INVALID_ARG;   // C matrices overlap
+  return MMH_OK;
+}
+}  // namespace
+
+// mmh_sgemm_batched: the argument rules, the empty cases, then the form (AUTO: batched_plan_for; 29 / 30 / 31: one
+// launch on that tile; MMH_KERNEL_NAIVE: the naive batched kernel; anything else is refused before anything is launched)
+int sgemm_batched_on(mmh_context *ctx, int kernel, int ta, int tb, int m, int n, int k, const float *dA, int lda, long long sA,
+                     const float *dB, int ldb, long long sB, float *dC, int ldc, long long sC, int batch, int accumulate,
+                     hipStream_t s) {
+  int rc = check_batch_args(ta, tb, m, n, ldc, sA, sB, sC, batch);
+  if (rc == MMH_OK && batch > 0) rc = check_gemm_args(m, n, k, dA, lda, dB, ldb, dC, ldc, ta, tb);
+  if (rc != MMH_OK) {
+    set_last_error("invalid argument");
+    return rc;
+  }
+  if (batch == 0 || m == 0 || n == 0) return MMH_OK;
+  if (kernel != MMH_KERNEL_AUTO && kernel != MMH_KERNEL_NAIVE && !has_op_forms(kernel)) {
+    set_last_error("batched GEMMs run on MMH_KERNEL_AUTO, the 64x64 / 128x64 / 128x128 LDS-DMA tiles (29 / 30 / 31) and "
+                   "MMH_KERNEL_NAIVE only");
+    return MMH_ERR_UNSUPPORTED;
+  }
+  GemmArgs g{m, n, k, dA, lda, dB, ldb, dC, ldc, accumulate ? 1 : 0, s};
+  g.ta = ta;
+  g.tb = tb;
+  BatchArgs b;
+  b.sA = sA;
+  b.sB = sB;
+  b.sC = sC;
+  b.batch = batch;
+  if (k == 0) {   // C = 0 (overwrite) or C unchanged (accumulate); the zeros go out through the naive kernel, matrix by matrix
+    if (!accumulate) return launch_naive_batched(g, b);
+    return MMH_OK;
+  }
+  if (kernel == MMH_KERNEL_NAIVE) return launch_naive_batched(g, b);
+  if (kernel == MMH_KERNEL_AUTO) {
+    const BatchPlan bp = batched_plan_for(ctx, g, b);
+    if (bp.form == MMH_BATCH_FORM_FOLD) {
+      rc = sgemm_op_on(ctx, MMH_KERNEL_AUTO, ta, tb, batch * m, n, k, dA, lda, dB, ldb, dC, ldc, accumulate, s);
+      if (rc == MMH_OK)
+        set_last_launch(last_launch_ref() + ", batch " + std::to_string(batch) + " folded into one " + std::to_string(batch * m) +
+                        "-row GEMM");
+      return rc;
+    }
+    if (bp.form == MMH_BATCH_FORM_LOOP) {
+      for (int i = 0; i < batch && rc == MMH_OK; ++i)
+        rc = sgemm_op_on(ctx, MMH_KERNEL_AUTO, ta, tb, m, n, k, dA + i * sA, lda, dB + i * sB, ldb, dC + i * sC, ldc, accumulate, s);
+      if (rc == MMH_OK)
+        set_last_launch(last_launch_ref() + ", batch " + std::to_string(batch) + " as a loop of " + std::to_string(batch) +
+                        " per-matrix launches");
+      return rc;
+    }
+    kernel = bp.kernel;
+  }
+  const int d = launch_dma5_batched(ctx, kernel, g, b);
+  if (d <= 0) return d;
+  set_last_error("batched GEMMs need the LDS-DMA tiles: a matrix lies beyond their 2 GiB descriptor window, or "
+                 "MMH_OPT_DMA_EDGE keeps this shape off them");
+  return MMH_ERR_UNSUPPORTED;
+}
+
+// mmh_auto_plan_batched: batched_plan_for on a default handle, as host arithmetic
+int auto_plan_batched(int ta, int tb, int m, int n, int k, int lda, int ldb, int ldc, long long sA, long long sB, long long sC,
+                      int batch, int base_align, int cu_count, int *kernel, int *form, long *workgroups) {
+  if (check_batch_args(ta, tb, m, n, ldc, sA, sB, sC, batch) != MMH_OK) return MMH_ERR_INVALID_ARG;
+  if (batch < 1 || m <= 0 || n <= 0 || k <= 0 || lda < (ta ? m : k) || ldb < (tb ? k : n) || ldc < n) return MMH_ERR_INVALID_ARG;
+  mmh_context ctx;
+  ctx.cu_count = cu_count > 0 ? cu_count : 256;
+  const uintptr_t base = (uintptr_t)1 << 32, off = base_align >= 16 ? 0 : 4;
+  GemmArgs g{m, n, k, reinterpret_cast<const float *>(base + off), lda,
+             reinterpret_cast<const float *>(2 * base + off), ldb, reinterpret_cast<float *>(3 * base + off), ldc, 0, nullptr};
+  g.ta = ta;
+  g.tb = tb;
+  BatchArgs b;
+  b.sA = sA;
+  b.sB = sB;
+  b.sC = sC;
+  b.batch = batch;
+  const BatchPlan bp = batched_plan_for(&ctx, g, b);
+  if (form) *form = bp.form;
+  if (bp.form == MMH_BATCH_FORM_ONE_LAUNCH) {
+    const int bm = bp.kernel == MMH_KERNEL_MFMA_64X64_DMA5 ? 64 : 128, bn = bp.kernel == MMH_KERNEL_MFMA_128X128_DMA5 ? 128 : 64;
+    if (kernel) *kernel = bp.kernel;
+    if (workgroups) *workgroups = (long)batch * ((m + bm - 1) / bm) * ((n + bn - 1) / bn);
+    return MMH_OK;
+  }
+  // fold / loop: mmh_auto_plan_op on the one GEMM mmh_sgemm_op runs, times the launches
+  const bool fold = bp.form == MMH_BATCH_FORM_FOLD;
+  long tiles = 0;
+  int grid = 0;
+  const int rc = auto_plan_op(ta, tb, fold ? batch * m : m, n, k, lda, ldb, ldc, base_align, cu_count, kernel, &tiles, &grid);
+  if (rc != MMH_OK) return rc;
+  if (workgroups) *workgroups = (fold ? 1L : (long)batch) * (grid > 0 ? grid : tiles);
+  return MMH_OK;
 }
 
 // What MMH_KERNEL_AUTO would do with a shape, as host arithmetic (mmh_auto_plan: no device, no launch): the tile it

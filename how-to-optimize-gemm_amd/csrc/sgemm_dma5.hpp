@@ -860,6 +860,62 @@ sgemm_mfma_dma5_op_kernel(int m, int n, int k, const float *__restrict__ A, int 
          Dma5Next{}, nullptr, no_reply);
 }
 
+// The strided batched form (launch_batched.hip): matrix b of the launch at A + b sA, B + b sB, C + b sC (elements, 64-bit
+// offsets), one workgroup per tile of every matrix.  The launch holds the workgroup ids [first, first + gridDim.x) of its
+// matrix set, matrix after matrix.  The dispatcher deals a launch's blocks round-robin over the eight XCDs; the id is
+// remapped XCD-contiguous first (each XCD takes a run of consecutive ids, so a small matrix's tiles share one L2 and its A
+// and B panels), then split into (matrix, tile).  Inside a matrix: the op kernel's raster, thin edge tiles last.
+// (Tools build: bit 1 of `accumulate` = the plain batch-major order, the A/B baseline of profiles/batched_sweep.md.)
+template <int BM, int BN, int KB, int WTM, int WTN, int NBUF, bool EDGE, int NL, int D, int OP>
+__global__ void __launch_bounds__(64 * (4 + NL))
+sgemm_mfma_dma5_batched_kernel(int m, int n, int k, const float *__restrict__ A, int lda, long long sA,
+                               const float *__restrict__ B, int ldb, long long sB, float *__restrict__ C, int ldc,
+                               long long sC, int accumulate, int nbm, int nbn, unsigned first) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  using S = Dma5Segment<BM, BN, KB, WTM, WTN, NBUF, false, EDGE, false, NL, D, false, false, 1, OP>;
+  constexpr int GM = Dma5Tile<BM, BN, KB, WTM, WTN, NBUF, NL>::GM;
+  asm volatile("" ::"s"(A), "s"(B), "s"(C), "s"(lda), "s"(ldb), "s"(ldc), "s"(k));
+  bool xcd_runs = true;
+  if constexpr (kAbBuild) {
+    xcd_runs = (accumulate & 2) == 0;
+    accumulate &= 1;
+  }
+  const unsigned G = gridDim.x, x = blockIdx.x;
+  unsigned id = x;
+  if (xcd_runs) {   // (block_to_tile_g's remap, a bijection of [0, G) for any G)
+    const unsigned xcd = x % NXCD, local = x / NXCD, q = G / NXCD, r = G % NXCD;
+    id = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + local;
+  }
+  id += first;
+  const unsigned per = (unsigned)nbm * (unsigned)nbn;
+  const unsigned b = id / per;
+  const int bid = (int)(id - b * per);
+  A += (long long)b * sA;
+  B += (long long)b * sB;
+  C += (long long)b * sC;
+  int tm, tn;
+  const int thin_row = (EDGE && nbm > 1 && m - (nbm - 1) * BM <= 16) ? 1 : 0, thin_col = (EDGE && nbn > 1 && n - (nbn - 1) * BN <= 16) ? 1 : 0;
+  const int n_full = (nbm - thin_row) * (nbn - thin_col);
+  int r = bid - n_full;
+  if (r < 0) {
+    block_to_tile_g(bid, n_full, nbm - thin_row, nbn - thin_col, GM, tm, tn);
+  } else if (thin_col && r < nbm) {
+    tm = r;
+    tn = nbn - 1;
+  } else {
+    if (thin_col) r -= nbm;
+    tm = nbm - 1;
+    tn = r;
+  }
+  typename S::Lane L;
+  L.init(lda, ldb);
+  typename S::Frags fr;
+  Dma5Link link;
+  int no_reply = 0;
+  S::run(lds, L, m, n, k, A, lda, B, ldb, C, ldc, tm, tn, 0, (k + KB - 1) / KB, accumulate != 0, nullptr, nullptr, fr, link,
+         Dma5Next{}, nullptr, no_reply);
+}
+
 
 // ---------------------------------------------------------------------------------------------------------------
 // K2Wp: the chained stream-K body.  Ranges, the order of a range's parts (head of the last tile FIRST, whole tiles, tail

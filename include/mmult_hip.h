@@ -304,6 +304,13 @@ int mmh_auto_plan(int m, int n, int k, int lda, int ldb, int ldc, int base_align
  * descriptor window. */
 int mmh_auto_plan_op(int transa, int transb, int m, int n, int k, int lda, int ldb, int ldc, int base_align, int cu_count,
                      int *kernel, long *tiles, int *streamk_grid);
+/* The same for mmh_sgemm_batched (batch >= 1, m, n, k >= 1): *kernel = the tile (or the per-matrix plan's kernel for
+ * the fold and loop forms), *form = MMH_BATCH_FORM_*, *workgroups = what all its launches hold together (fold: the folded
+ * GEMM's tiles or stream-K grid; one launch: batch x tiles; loop: batch x the per-matrix plan's).  The argument rules
+ * of mmh_sgemm_batched (MMH_ERR_INVALID_ARG); MMH_ERR_UNSUPPORTED as mmh_auto_plan_op. */
+int mmh_auto_plan_batched(int transa, int transb, int m, int n, int k, int lda, int ldb, int ldc, long long strideA,
+                          long long strideB, long long strideC, int batch, int base_align, int cu_count, int *kernel,
+                          int *form, long *workgroups);
 int mmh_get_option(mmh_handle_t handle, int option, int *value);
 
 /* The hot path ------------------------------------------------------------ */
@@ -341,6 +348,37 @@ int mmh_sgemm(mmh_handle_t handle, int m, int n, int k, const float *dA, int lda
 #define MMH_OP_T 1
 int mmh_sgemm_op(mmh_handle_t handle, int transa, int transb, int m, int n, int k, const float *dA, int lda,
                  const float *dB, int ldb, float *dC, int ldc, int accumulate, void *stream);
+
+/* Strided batched: C_i = op(A_i) * op(B_i) (+ C_i) for i in [0, batch), everything ROW-MAJOR
+ * (cublasSgemmStridedBatched, rocblas_sgemm_strided_batched, torch.bmm).
+ *   Each matrix's layout follows mmh_sgemm_op: transa / transb, lda, ldb, ldc as there.
+ *   Matrix i is at dA + i * strideA, dB + i * strideB, dC + i * strideC; strides in elements (64-bit).
+ *   strideA, strideB >= 0; a stride of 0 broadcasts one operand to the whole batch.
+ *   batch > 1: strideC >= (m - 1) * ldc + n, so that no two C matrices overlap; a smaller one is MMH_ERR_INVALID_ARG.
+ *   batch == 0, m == 0 or n == 0: MMH_OK, nothing launched.  batch < 0, a negative stride, bad op flags:
+ *   MMH_ERR_INVALID_ARG.
+ *   k == 0: every C matrix is zeroed (left as it is when accumulating); the gaps between matrices are never written.
+ * Every element is the same fp32 fma chain over ascending k as mmh_sgemm_op computes on that matrix alone, bit for bit.
+ * MMH_KERNEL_AUTO picks one of three forms (mmh_auto_plan_batched):
+ *   MMH_BATCH_FORM_FOLD        transa == N, strideB == 0, strideA == m * lda, strideC == m * ldc, batch * m fits an int:
+ *                              ONE mmh_sgemm_op of batch * m rows (B shared, A and C packed)
+ *   MMH_BATCH_FORM_ONE_LAUNCH  one launch of the batched kernel (csrc/sgemm_dma5.hpp) over batch x tiles on the
+ *                              64x64, 128x64 or 128x128 LDS-DMA tile, whichever the cost table prices cheapest
+ *   MMH_BATCH_FORM_LOOP        batch launches of the per-matrix plan mmh_sgemm_op would run (a few large matrices)
+ * A batch of one is the per-matrix plan (fold or loop).  Forced kernels: the 64x64 / 128x64 / 128x128 LDS-DMA tiles
+ * (29 / 30 / 31) run the one-launch form on that tile, MMH_KERNEL_NAIVE a naive batched kernel; every other kernel,
+ * and matrices beyond the tiles' 2 GiB buffer-descriptor window, give MMH_ERR_UNSUPPORTED with nothing launched.
+ * One launch holds at most MMH_BATCHED_MAX_WORKGROUPS workgroups; a larger batch goes out as several launches.
+ * mmh_last_launch names the form and the batch: "..., batch 64", "..., batch 5000000 as 2 launches",
+ * "..., batch 64 folded into one 8192-row GEMM", "..., batch 2 as a loop of 2 per-matrix launches".
+ * A column-major caller of cublasSgemmStridedBatched swaps the operands, m / n and the strides. */
+#define MMH_BATCH_FORM_FOLD 1
+#define MMH_BATCH_FORM_ONE_LAUNCH 2
+#define MMH_BATCH_FORM_LOOP 3
+#define MMH_BATCHED_MAX_WORKGROUPS (1L << 22)
+int mmh_sgemm_batched(mmh_handle_t handle, int transa, int transb, int m, int n, int k, const float *dA, int lda,
+                      long long strideA, const float *dB, int ldb, long long strideB, float *dC, int ldc, long long strideC,
+                      int batch, int accumulate, void *stream);
 
 /* Host-pointer flavour: stages A, B (and C when accumulating) to the device,
  * runs mmh_sgemm, copies C back, synchronises.  Staging buffers are cached in
@@ -459,6 +497,10 @@ int mmh_time_sgemm(mmh_handle_t handle, int m, int n, int k, const float *dA, in
 int mmh_time_sgemm_op(mmh_handle_t handle, int transa, int transb, int m, int n, int k, const float *dA, int lda,
                       const float *dB, int ldb, float *dC, int ldc, int warmup, int reps, void *stream,
                       float *ms_per_call);
+/* mmh_time_sgemm for mmh_sgemm_batched (overwrite; ms per batched call). */
+int mmh_time_sgemm_batched(mmh_handle_t handle, int transa, int transb, int m, int n, int k, const float *dA, int lda,
+                           long long strideA, const float *dB, int ldb, long long strideB, float *dC, int ldc,
+                           long long strideC, int batch, int warmup, int reps, void *stream, float *ms_per_call);
 
 /* The same measurement for a vendor comparator (the calls are issued from C, like mmh_time_sgemm's, so that
  * a 20 us kernel is not timed through an interpreter's call overhead). */

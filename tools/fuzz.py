@@ -4,9 +4,12 @@ independent code path with the same chain semantics -> bit-equal, signed zeros i
 same_bits) on random shapes, leading dimensions, 4-byte-misaligned bases and accumulate
 flags; plus a stream-K stress loop (ragged tile counts, repeated launches; whole rounds
 of the persistent grid) against the one-tile-per-workgroup kernel.
-usage: python tools/fuzz.py [--ops] [cases] [stress_reps] [seed]
+usage: python tools/fuzz.py [--ops | --batched] [cases] [stress_reps] [seed]
 --ops: the transposed-operand forms instead (mmh_sgemm_op: NT / TN / TT on AUTO and the 64x64 / 128x64 / 128x128 LDS-DMA
-tiles, plain and stream-K) against the naive kernel's op form, with NaN in every operand's padding and behind its last row."""
+tiles, plain and stream-K) against the naive kernel's op form, with NaN in every operand's padding and behind its last row.
+--batched: mmh_sgemm_batched on random shapes, batch strides (gaps, strides that are not a multiple of 4, 0 = broadcast),
+ops, bases and accumulate flags -- AUTO (fold, one launch or loop) and the three tiles forced -- against the naive batched
+kernel, with NaN in every padding and gap, none of which may be written."""
 import os
 import sys
 
@@ -16,7 +19,8 @@ import torch  # noqa: E402
 import how_to_optimize_gemm_amd as H  # noqa: E402
 
 OPS = "--ops" in sys.argv
-argv = [x for x in sys.argv if x != "--ops"]
+BATCHED = "--batched" in sys.argv
+argv = [x for x in sys.argv if x not in ("--ops", "--batched")]
 cases = int(argv[1]) if len(argv) > 1 else 200
 stress = int(argv[2]) if len(argv) > 2 else 30
 seed = int(argv[3]) if len(argv) > 3 else 1
@@ -119,8 +123,84 @@ def fuzz_ops():
     return nbad
 
 
+def fuzz_batched():
+    """C_i = op(A_i) op(B_i) (+ C_i) through mmh_sgemm_batched against sgemm_naive_batched_kernel (MMH_KERNEL_NAIVE)."""
+    variants = ["auto", "mfma_64x64_dma5", "mfma_128x64_dma5", "mfma_128x128_dma5"]
+    nbad = 0
+    forms = {}
+    for case in range(cases):
+        shape = int(rng.integers(0, 4))
+        if shape == 0:     # many small matrices
+            m, n, k = (int(rng.integers(1, 140)) for _ in range(3))
+            batch = int(rng.integers(1, 300))
+        elif shape == 1:   # whole tiles: the whole-tile form where the strides allow it
+            m, n = (int(rng.integers(1, 5)) * 128 for _ in range(2))
+            k = int(rng.integers(1, 12)) * 32
+            batch = int(rng.integers(1, 40))
+        elif shape == 2:   # around the tile edges (thin last rows / columns), K tails
+            m, n = (int(rng.integers(1, 5)) * 64 + int(rng.integers(-2, 18)) for _ in range(2))
+            k = int(rng.integers(1, 300))
+            batch = int(rng.integers(1, 24))
+        else:              # a few mid-size matrices
+            m, n, k = (int(rng.integers(300, 1300)) for _ in range(3))
+            batch = int(rng.integers(1, 5))
+        ta, tb = int(rng.integers(0, 2)), int(rng.integers(0, 2))
+        ra, ca = (k, m) if ta else (m, k)
+        rb, cb = (n, k) if tb else (k, n)
+        whole = shape == 1 and bool(rng.integers(0, 2))
+        pad = (lambda: 4 * int(rng.integers(0, 2))) if whole else (lambda: int(rng.integers(0, 5)))
+        lda, ldb, ldc = ca + pad(), cb + pad(), n + pad()
+        def stride(rows, ld, may_broadcast):
+            if may_broadcast and rng.integers(0, 5) == 0:
+                return 0
+            return rows * ld + (4 * int(rng.integers(0, 3)) if whole else int(rng.integers(0, 7)))
+        fold = not ta and rng.integers(0, 4) == 0   # packed A and C, shared B: AUTO folds
+        sa = ra * lda if fold else stride(ra, lda, True)
+        sb = 0 if fold else stride(rb, ldb, True)
+        sc = m * ldc if fold else stride(m, ldc, False)
+        offs = [4 * int(rng.integers(0, 2)) if whole else int(rng.integers(0, 4)) for _ in range(3)]
+        acc = bool(rng.integers(0, 2))
+        size = lambda rows, cols, ld, s, off: off + (batch - 1) * s + (rows - 1) * ld + cols + 8
+        a = torch.full((size(ra, ca, lda, sa, offs[0]),), float("nan"), device="cuda")
+        b = torch.full((size(rb, cb, ldb, sb, offs[1]),), float("nan"), device="cuda")
+        c0 = torch.full((size(m, n, ldc, sc, offs[2]),), float("nan"), device="cuda")
+        inside = torch.zeros(c0.shape, dtype=torch.bool, device="cuda")
+        for i in range(batch):
+            for flat, rows, cols, ld, s, off in ((a, ra, ca, lda, sa, offs[0]), (b, rb, cb, ldb, sb, offs[1])):
+                if s or i == 0:
+                    flat[off + i * s:off + i * s + rows * ld].view(rows, ld)[:, :cols] = torch.rand((rows, cols), device="cuda") * 2 - 1
+            w = c0[offs[2] + i * sc:offs[2] + i * sc + m * ldc].view(m, ldc)[:, :n]
+            w.copy_(torch.rand((m, n), device="cuda"))
+            inside[offs[2] + i * sc:offs[2] + i * sc + m * ldc].view(m, ldc)[:, :n] = True
+        results = {}
+        for kern in ["naive"] + variants:
+            mm.set_kernel(kern)
+            c = c0.clone()
+            mm.sgemm_batched(ta, tb, m, n, k, a.data_ptr() + 4 * offs[0], lda, sa, b.data_ptr() + 4 * offs[1], ldb, sb,
+                             c.data_ptr() + 4 * offs[2], ldc, sc, batch, acc, stream)
+            torch.cuda.synchronize()
+            if kern == "auto":
+                form = "folded" if "folded" in H.last_launch() else "loop" if "loop of" in H.last_launch() else "one launch"
+                forms[form] = forms.get(form, 0) + 1
+            results[kern] = c
+            if not same_bits(c[~inside], c0[~inside]):
+                nbad += 1
+                print(f"batched case {case} {kern}: wrote outside the C matrices  m,n,k={m},{n},{k} batch={batch}")
+        for kern in variants:
+            if not same_bits(results[kern][inside], results["naive"][inside]):
+                nbad += 1
+                print(f"batched case {case} {kern}: != naive  m,n,k={m},{n},{k} batch={batch} op={'NT'[ta]}{'NT'[tb]} "
+                      f"ld={lda},{ldb},{ldc} strides={sa},{sb},{sc} off={offs} acc={acc}: {H.last_launch()}")
+    mm.set_kernel("auto")
+    print(f"fuzz --batched: AUTO forms {forms}")
+    print(f"fuzz --batched: {cases} cases x {len(variants)} variants, {nbad} failures")
+    return nbad
+
+
 if OPS:
     sys.exit(1 if fuzz_ops() else 0)
+if BATCHED:
+    sys.exit(1 if fuzz_batched() else 0)
 
 bad = 0
 for case in range(cases):
