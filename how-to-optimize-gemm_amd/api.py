@@ -578,7 +578,7 @@ class MMult:
         return out
 
     def igemm_s8(self, a, b, out=None, accumulate: bool = False):
-        """int8 x int8 -> int32 for CUDA tensors (inputs expected in [-127,127])."""
+        """int8 x int8 -> int32 for CUDA tensors (any int8; every sum must fit in int32)."""
         import torch
         if a.dtype != torch.int8 or b.dtype != torch.int8:
             raise MMultError(ERR_INVALID_ARG, "igemm_s8", "int8 inputs only")

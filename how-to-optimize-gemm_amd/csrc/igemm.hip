@@ -25,6 +25,9 @@ static int pp_grid_cap(const mmh_context *h, int mode, int k, int cus) {
   return k <= 5120 ? cus : 0;
 }
 
+// mmh_last_launch of the quantiser passes: which path a tensor took (quant_vec_ok: 16-byte rows, float4 loads; else the row loop)
+static const char *quant_path(bool vec) { return vec ? "vector" : "row"; }
+
 // tools build: the rungs that left the product (tools/ab/igemm_s8_k3.hpp).  Returns 1 when `mode` is not one of theirs.
 static int launch_ab_modes(mmh_context *h, int mode, int m, int n, int k, const int8_t *A, int lda, const int8_t *B, int ldb, int32_t *C,
                            int ldc, int acc, hipStream_t s) {
@@ -74,11 +77,13 @@ int mmh_igemm_s8(mmh_handle_t h, int m, int n, int k, const int8_t *dA, int lda,
   // launch form, the A/B switch for the persistent loop), 7 (the same kernel on v_mfma_i32_16x16x32_i8, the instruction
   // BASELINE.json configs[4] names: same bits, half the pipe's rate); 6 stays the lockstep K3t kernel.
   const int cus_ = h->cu_count > 0 ? h->cu_count : 256;
+  std::string what;   // mmh_last_launch: the instantiation and its launch form (the fp32 launchers' cost: one snprintf)
   if (igemm_s8_inplace_ok(dA, lda, dB, ldb, k) &&
       (h->igemm_mode == 7 || h->igemm_mode == 8 || h->igemm_mode == 9 ||
        (h->igemm_mode == 0 && igemm_s8_big_tile(m, n, cus_)))) {
-    if (h->igemm_mode == 7) HIP_TRY(launch_igemm_s8_pp<32>(m, n, k, dA, lda, dB, ldb, dC, ldc, accumulate ? 1 : 0, s, pp_grid_cap(h, 0, k, cus_)));
-    else HIP_TRY(launch_igemm_s8_pp<64>(m, n, k, dA, lda, dB, ldb, dC, ldc, accumulate ? 1 : 0, s, pp_grid_cap(h, h->igemm_mode, k, cus_)));
+    if (h->igemm_mode == 7) HIP_TRY(launch_igemm_s8_pp<32>(m, n, k, dA, lda, dB, ldb, dC, ldc, accumulate ? 1 : 0, s, pp_grid_cap(h, 0, k, cus_), nullptr, &what));
+    else HIP_TRY(launch_igemm_s8_pp<64>(m, n, k, dA, lda, dB, ldb, dC, ldc, accumulate ? 1 : 0, s, pp_grid_cap(h, h->igemm_mode, k, cus_), nullptr, &what));
+    set_last_launch(what);
     return MMH_OK;
   }
   // Default mode: operands the in-place kernel cannot take as they are (an odd leading dimension, a
@@ -100,13 +105,15 @@ int mmh_igemm_s8(mmh_handle_t h, int m, int n, int k, const int8_t *dA, int lda,
       sb = static_cast<const int8_t *>(h->qb.p);
     }
     if (igemm_s8_inplace_ok(sa, ka, sb, nb, k)) {
-      HIP_TRY(launch_igemm_s8(m, n, k, sa, ka, sb, nb, dC, ldc, accumulate ? 1 : 0, s, 0, cus_));
+      HIP_TRY(launch_igemm_s8(m, n, k, sa, ka, sb, nb, dC, ldc, accumulate ? 1 : 0, s, 0, cus_, &what));
+      set_last_launch(what + (a_ok ? "" : ", A copied to workspace") + (b_ok ? "" : ", B copied to workspace"));
       return MMH_OK;
     }
     // (operands beyond the descriptors' 2 GiB window: the correctness-first kernel below)
   }
   if ((rc = launch_ab_modes(h, h->igemm_mode, m, n, k, dA, lda, dB, ldb, dC, ldc, accumulate ? 1 : 0, s)) <= 0) return rc;
-  HIP_TRY(launch_igemm_s8(m, n, k, dA, lda, dB, ldb, dC, ldc, accumulate ? 1 : 0, s, h->igemm_mode, cus_));
+  HIP_TRY(launch_igemm_s8(m, n, k, dA, lda, dB, ldb, dC, ldc, accumulate ? 1 : 0, s, h->igemm_mode, cus_, &what));
+  set_last_launch(what);
   return MMH_OK;
 }
 
@@ -130,6 +137,10 @@ int mmh_quantize_sym_s8(mmh_handle_t h, int rows, int cols, const float *dX, int
   hipLaunchKernelGGL(quantize_kernel, dim3(quant_grid(t, v_out), 1), dim3(256), 0, s, t, none, v_out ? 1 : 0, 0,
                      amax, d_scale);
   HIP_TRY(hipGetLastError());
+  char buf[128];
+  snprintf(buf, sizeof buf, "absmax_kernel (%s path), quantize_kernel (%s path), %u + %u workgroups", quant_path(v_in),
+           quant_path(v_out), quant_grid(t, v_in), quant_grid(t, v_out));
+  set_last_launch(buf);
   return MMH_OK;
 }
 
@@ -164,22 +175,29 @@ int mmh_qgemm_f32(mmh_handle_t h, int m, int n, int k, const float *dA, int lda,
   hipLaunchKernelGGL(absmax_kernel, gmax, dim3(256), 0, s, ta, tb, va_in ? 1 : 0, vb_in ? 1 : 0, amax);
   hipLaunchKernelGGL(quantize_kernel, g, dim3(256), 0, s, ta, tb, va_out ? 1 : 0, vb_out ? 1 : 0, amax, scales);
   const int cus = h->cu_count > 0 ? h->cu_count : 256;
+  char buf[96];
+  snprintf(buf, sizeof buf, "qgemm: absmax_kernel + quantize_kernel (A on the %s path, B on the %s path), then ", quant_path(va_out),
+           quant_path(vb_out));
+  std::string what;
   if (h->igemm_mode == 0 && igemm_s8_inplace_ok(qa, ka, qb, nb, k)) {
     // the int8 GEMM dequantises in its epilogue: no int32 image of C at all
     if (igemm_s8_big_tile(m, n, cus))
-      HIP_TRY(launch_igemm_s8_pp<64>(m, n, k, qa, ka, qb, nb, reinterpret_cast<int32_t *>(dC), ldc, 0, s, pp_grid_cap(h, 0, k, cus), scales));
+      HIP_TRY(launch_igemm_s8_pp<64>(m, n, k, qa, ka, qb, nb, reinterpret_cast<int32_t *>(dC), ldc, 0, s, pp_grid_cap(h, 0, k, cus), scales,
+                                     &what));
     else
-      HIP_TRY(launch_igemm_s8_dequant(m, n, k, qa, ka, qb, nb, dC, ldc, scales, s, cus));
+      HIP_TRY(launch_igemm_s8_dequant(m, n, k, qa, ka, qb, nb, dC, ldc, scales, s, cus, &what));
+    set_last_launch(buf + what + ", dequantised in the epilogue");
     return MMH_OK;
   }
   // two-pass form (A/B modes of the int8 kernel): int32 C, then the dequantisation pass
   if ((rc = h->qc.reserve((size_t)m * nb * sizeof(int32_t))) != MMH_OK) return rc;
   int32_t *qc = static_cast<int32_t *>(h->qc.p);
   if ((rc = launch_ab_modes(h, h->igemm_mode, m, n, k, qa, ka, qb, nb, qc, nb, 0, s)) < 0) return rc;
-  if (rc == 1) HIP_TRY(launch_igemm_s8(m, n, k, qa, ka, qb, nb, qc, nb, 0, s, h->igemm_mode, cus));
+  if (rc == 1) HIP_TRY(launch_igemm_s8(m, n, k, qa, ka, qb, nb, qc, nb, 0, s, h->igemm_mode, cus, &what));
   hipLaunchKernelGGL(dequantize_kernel, dim3(quant_rows_grid(m, 0)), dim3(256), 0, s, qc, m, n, nb,
                      scales, scales + 1, dC, ldc);
   HIP_TRY(hipGetLastError());
+  set_last_launch(buf + what + " into int32 workspace, then dequantize_kernel (two-pass)");
   return MMH_OK;
 }
 

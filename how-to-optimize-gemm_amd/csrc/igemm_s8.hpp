@@ -43,7 +43,9 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdio.h>
 
+#include <string>
 #include <type_traits>
 
 #include "ab_build.hpp"
@@ -541,7 +543,7 @@ igemm_s8_simple_kernel(int m, int n, int k, const int8_t *__restrict__ A, int ld
 template <int BM, int BN, int TM, bool EDGE, int ABLATE, bool BTR = false>
 inline hipError_t launch_igemm_s8_dma_edge(int m, int n, int k, const int8_t *A, int lda, const int8_t *Bt,
                                            int kp, int n_pad, int32_t *C, int ldc, int acc, hipStream_t s,
-                                           const float *deq = nullptr) {
+                                           const float *deq = nullptr, std::string *what = nullptr) {
   const int nbm = (m + BM - 1) / BM, nbn = (n + BN - 1) / BN;
   constexpr int threads = BM / (16 * TM) * (BN / 64) * 64;
   constexpr size_t lds = 2 * (size_t)(BM + BN) * IK;
@@ -552,20 +554,26 @@ inline hipError_t launch_igemm_s8_dma_edge(int m, int n, int k, const int8_t *A,
   }
   hipLaunchKernelGGL((igemm_s8_dma_kernel<BM, BN, TM, EDGE, ABLATE, BTR>), dim3((unsigned)(nbm * nbn)), dim3(threads),
                      lds, s, m, n, k, A, lda, Bt, kp, n_pad, C, ldc, acc, nbm, nbn, deq);
+  if (what) {   // mmh_last_launch: the instantiation, spelled as tools/kernel_resources.py demangles it
+    char buf[96];
+    snprintf(buf, sizeof buf, "igemm_s8_dma_kernel<%d,%d,%d,%s,%d,%s>, %s%d workgroups", BM, BN, TM, EDGE ? "true" : "false",
+             ABLATE, BTR ? "true" : "false", BTR ? "B in place, " : "", nbm * nbn);
+    *what = buf;
+  }
   return hipGetLastError();
 }
 
 template <int BM, int BN, int TM, bool BTR = false>
 inline hipError_t launch_igemm_s8_dma(int m, int n, int k, const int8_t *A, int lda, const int8_t *Bt, int kp,
                                       int n_pad, int32_t *C, int ldc, int acc, hipStream_t s,
-                                      const float *deq = nullptr) {
+                                      const float *deq = nullptr, std::string *what = nullptr) {
   const bool c_fast = (m % BM == 0) && (n % BN == 0) && (ldc % 4 == 0) &&
                       ((reinterpret_cast<uintptr_t>(C) & 15) == 0);
   return c_fast
              ? launch_igemm_s8_dma_edge<BM, BN, TM, false, 0, BTR>(m, n, k, A, lda, Bt, kp, n_pad, C, ldc, acc, s,
-                                                                  deq)
+                                                                  deq, what)
              : launch_igemm_s8_dma_edge<BM, BN, TM, true, 0, BTR>(m, n, k, A, lda, Bt, kp, n_pad, C, ldc, acc, s,
-                                                                 deq);
+                                                                 deq, what);
 }
 
 // K3t (B read in place) needs 4-byte aligned operands and byte offsets inside the descriptors' 2 GiB
@@ -591,11 +599,12 @@ inline bool igemm_s8_big_tile(int m, int n, int num_cus) {
 }
 
 inline hipError_t launch_igemm_s8_dequant(int m, int n, int k, const int8_t *A, int lda, const int8_t *B, int ldb,
-                                          float *C, int ldc, const float *scales, hipStream_t s, int num_cus) {
+                                          float *C, int ldc, const float *scales, hipStream_t s, int num_cus,
+                                          std::string *what = nullptr) {
   int32_t *Ci = reinterpret_cast<int32_t *>(C);
   if (igemm_s8_big_tile(m, n, num_cus))
-    return launch_igemm_s8_dma<256, 256, 8, true>(m, n, k, A, lda, B, ldb, n, Ci, ldc, 0, s, scales);
-  return launch_igemm_s8_dma<128, 128, 4, true>(m, n, k, A, lda, B, ldb, n, Ci, ldc, 0, s, scales);
+    return launch_igemm_s8_dma<256, 256, 8, true>(m, n, k, A, lda, B, ldb, n, Ci, ldc, 0, s, scales, what);
+  return launch_igemm_s8_dma<128, 128, 4, true>(m, n, k, A, lda, B, ldb, n, Ci, ldc, 0, s, scales, what);
 }
 
 // mode: 0 = K3t (B read in place by transposing LDS reads; the tile by igemm_s8_big_tile) when the operands are 4-byte
@@ -604,15 +613,16 @@ inline hipError_t launch_igemm_s8_dequant(int m, int n, int k, const int8_t *A, 
 // (The ping-pong kernel K3p is launched by igemm.hip; K3 and the packed-B kernel K3d -- modes 1, 3, 4, and the timing-only
 // ablations 10..13 -- by tools/ab/igemm_s8_k3.hpp in the tools build.)
 inline hipError_t launch_igemm_s8(int m, int n, int k, const int8_t *A, int lda, const int8_t *B,
-                                  int ldb, int32_t *C, int ldc, int acc, hipStream_t s, int mode = 0, int num_cus = 256) {
+                                  int ldb, int32_t *C, int ldc, int acc, hipStream_t s, int mode = 0, int num_cus = 256,
+                                  std::string *what = nullptr) {
   const int nbm = (m + 127) / 128, nbn = (n + 127) / 128;
   dim3 grid((unsigned)(nbm * nbn)), block(256);
   const bool shape_ok = (m % 128 == 0) && (n % 128 == 0);
   if ((mode == 0 || mode == 5 || mode == 6) && igemm_s8_inplace_ok(A, lda, B, ldb, k)) {
     // K3t: B read in place (no packing, no workspace)
     const bool big = mode == 6 || (mode == 0 && igemm_s8_big_tile(m, n, num_cus));
-    if (big) return launch_igemm_s8_dma<256, 256, 8, true>(m, n, k, A, lda, B, ldb, n, C, ldc, acc, s);
-    return launch_igemm_s8_dma<128, 128, 4, true>(m, n, k, A, lda, B, ldb, n, C, ldc, acc, s);
+    if (big) return launch_igemm_s8_dma<256, 256, 8, true>(m, n, k, A, lda, B, ldb, n, C, ldc, acc, s, nullptr, what);
+    return launch_igemm_s8_dma<128, 128, 4, true>(m, n, k, A, lda, B, ldb, n, C, ldc, acc, s, nullptr, what);
   }
   const bool fast = shape_ok && (k % IBK == 0) && (lda % 16 == 0) && (ldb % 4 == 0) && (ldc % 4 == 0) &&
                     ((reinterpret_cast<uintptr_t>(A) & 15) == 0) &&
@@ -624,6 +634,11 @@ inline hipError_t launch_igemm_s8(int m, int n, int k, const int8_t *A, int lda,
   else
     hipLaunchKernelGGL(igemm_s8_simple_kernel<true>, grid, block, 0, s, m, n, k, A, lda, B, ldb, C,
                        ldc, acc, nbm, nbn);
+  if (what) {
+    char buf[64];
+    snprintf(buf, sizeof buf, "igemm_s8_simple_kernel<%s>, %d workgroups", fast ? "false" : "true", nbm * nbn);
+    *what = buf;
+  }
   return hipGetLastError();
 }
 

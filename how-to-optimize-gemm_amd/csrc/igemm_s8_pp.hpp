@@ -283,6 +283,9 @@ igemm_s8_pp_kernel(int m, int n, int k, const int8_t *__restrict__ A, int lda, c
       request_prologue(cur);
     }
     __builtin_amdgcn_sched_barrier(0);
+    // (sched_barrier binds the machine scheduler only: the empty asm keeps the IR passes from moving a store above the
+    // prologue's requests either -- the counted waits below rely on that order; tests/test_int8_kernel_isa.py checks it)
+    asm volatile("" ::: "memory");
     // The accumulators leave through a per-wave 4 KiB transposer behind the ring.  Lane (li, g) holds
     // tile[16 t + li][16 u + 4 g .. + 3] (the MFMA operands are swapped: D = tile^T): stored as they are, the sixteen
     // lanes of a quarter-wave hit sixteen ROWS with 16 bytes each -- 64 requests per instruction, and a tile's 256
@@ -351,6 +354,7 @@ igemm_s8_pp_kernel(int m, int n, int k, const int8_t *__restrict__ A, int lda, c
       for (int q = 0; q < 4; ++q) put(drow + 16 * t + 4 * q, dcol, out[q]);
       __builtin_amdgcn_sched_barrier(0);   // (one row of tiles through the transposer at a time)
     }
+    asm volatile("" ::: "memory");   // (and nothing of the next tile moves in front of the stores)
     // a ragged tile's store count varies, an accumulating one has loads in the queue: their successor waits them out
     stores_in_flight = counted;
     if (!counted) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -362,7 +366,8 @@ igemm_s8_pp_kernel(int m, int n, int k, const int8_t *__restrict__ A, int lda, c
 // round 5's launch form (MMH_OPT_IGEMM_MODE 9, the A/B switch).
 template <int MFMA_K = 64>
 inline hipError_t launch_igemm_s8_pp(int m, int n, int k, const int8_t *A, int lda, const int8_t *B, int ldb, int32_t *C,
-                                     int ldc, int acc, hipStream_t s, int grid_cap, const float *deq = nullptr) {
+                                     int ldc, int acc, hipStream_t s, int grid_cap, const float *deq = nullptr,
+                                     std::string *what = nullptr) {
   constexpr int BM = 256, BN = 256;
   const int nbm = (m + BM - 1) / BM, nbn = (n + BN - 1) / BN;
   constexpr size_t lds = 2 * (size_t)(BM + BN) * IK + 8 * 4096;   // the ring and the eight waves' C transposers: 160 KiB
@@ -390,6 +395,15 @@ inline hipError_t launch_igemm_s8_pp(int m, int n, int k, const int8_t *A, int l
     else MMH_PP_LAUNCH(true, false);
   }
 #undef MMH_PP_LAUNCH
+  if (what) {   // mmh_last_launch: the instantiation, spelled as tools/kernel_resources.py demangles it, and its launch form
+    char buf[128];
+    const char *e = c_fast ? "false" : "true", *d = deq ? "true" : "false";
+    if (grid < nbm * nbn)
+      snprintf(buf, sizeof buf, "igemm_s8_pp_kernel<%s,%s,%d>, persistent: %d workgroups walk %d tiles", e, d, MFMA_K, grid, nbm * nbn);
+    else
+      snprintf(buf, sizeof buf, "igemm_s8_pp_kernel<%s,%s,%d>, %d workgroups, one per tile", e, d, MFMA_K, grid);
+    *what = buf;
+  }
   return hipGetLastError();
 }
 

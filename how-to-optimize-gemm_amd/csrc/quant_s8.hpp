@@ -53,7 +53,10 @@ constexpr int QU = 4;                    // float4 per thread and chunk
 constexpr int QCHUNK = 256 * QU;         // float4 per chunk
 constexpr int QG = 4;                    // chunks per workgroup
 
-__host__ __device__ inline int quant_chunks_per_row(int cols) { return (cols / 4 + QCHUNK - 1) / QCHUNK; }
+// (at least one for 1 - 3 columns: the per-row tail loop of a row's first chunk reads the columns past its float4s)
+__host__ __device__ inline int quant_chunks_per_row(int cols) {
+  return cols >= 4 ? (cols / 4 + QCHUNK - 1) / QCHUNK : (cols > 0 ? 1 : 0);
+}
 
 // chunk `id` (0 .. rows * cpr - 1) of tensor t -> its row pointer offset and first float4 column of this thread
 struct QuantChunk {

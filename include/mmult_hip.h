@@ -394,8 +394,8 @@ int mmh_sgemm_host(mmh_handle_t handle, int m, int n, int k, const float *A, int
 int mmh_sgemm_host_timed(mmh_handle_t handle, int m, int n, int k, const float *A, int lda,
                          const float *B, int ldb, float *C, int ldc, int accumulate, float *kernel_ms);
 
-/* int8 x int8 -> int32, C = A*B (+ C), row-major, inputs expected in
- * [-127,127]; bit-exact integer arithmetic on v_mfma_i32_16x16x64_i8.  4-byte aligned operands
+/* int8 x int8 -> int32, C = A*B (+ C), row-major, any int8 (-128 included); every sum must fit in
+ * int32.  Bit-exact integer arithmetic on v_mfma_i32_16x16x64_i8.  4-byte aligned operands
  * (bases and leading dimensions) are read in place; others are first copied into dense aligned
  * images in a handle-owned workspace (or, for B only, packed transposed) -- see MMH_OPT_IGEMM_MODE. */
 int mmh_igemm_s8(mmh_handle_t handle, int m, int n, int k, const int8_t *dA, int lda,
