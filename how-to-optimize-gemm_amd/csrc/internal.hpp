@@ -8,7 +8,9 @@
 //                    makefile switch (cuda/makefile:1-3) made a run-time choice.  Pure host code.
 //   launch_reg.hip   register-staged MFMA tiles (sgemm_mfma.hpp): plain, stream-K, split-K
 //   launch_dma.hip   LDS-DMA tiles (sgemm_dma.hpp): plain, stream-K; whole and guarded shapes
-//   launch_dma5.hip  LDS-DMA tiles with a loader wave (sgemm_dma5.hpp): plain, chained stream-K
+//   launch_dma5.hip  LDS-DMA tiles with loader waves (K2W, sgemm_dma5.hpp): plain, chained stream-K -- the NN forms;
+//   launch_op.hip    ... their transposed-operand forms, launch_batched.hip their strided batched form: each TU
+//                    instantiates launch_dma5.hpp's one launcher for its own kernels (built in parallel)
 //   launch_valu.hip  K1 / K0 (sgemm_valu.hpp)
 //   host_flavour.hip mmh_sgemm_host(_timed): the host-pointer MY_MMult, row-panel pipeline
 //   shard.hip        mmh_shard_*: single-process row-panel shard over RCCL
@@ -253,15 +255,16 @@ int warm_dma(mmh_context *ctx, float *scratch, hipStream_t s);
 int launch_dma32(mmh_context *ctx, int kernel, const GemmArgs &g);
 bool dma32_shape_ok(const mmh_context *ctx, int kernel, const GemmArgs &g);
 int warm_dma32(mmh_context *ctx, float *scratch, hipStream_t s);
-// The RIM launch of the 64x64 K2W tile (sgemm_dma5.hpp, rim_wave): m and / or n ONE element past a multiple of 64, at
-// least one whole tile each way.  *r_m / *r_n: rim rows / columns (0 or 1).
-// Which plain K2W launches go out as two (launch_dma5.hip, "the tail split"): one whole round of w workgroups per CU and a
-// last round of just under one tile per CU, deep enough in K.  Shared with the cost table (policy.hip).
+// Which plain K2W launches go out as two (launch_dma5.hpp, "the tail split"): one whole round of w workgroups per CU and a
+// last round of just under one tile per CU, deep enough in K -- and a first launch of a multiple of 8 workgroups (the second
+// one's id offset travels / 8).  Shared with the cost table (policy.hip) and tools/policy_fit.py tail_split.
 inline bool dma5_tail_split(long tiles, long w, long cus, int k) {
   const long rem = tiles - w * cus;
-  return w >= 2 && k >= 512 && 100 * rem > 85 * cus && rem <= cus;
+  return w >= 2 && k >= 512 && 100 * rem > 85 * cus && rem <= cus && (w * cus) % 8 == 0;
 }
 
+// The RIM launch of the 64x64 K2W tile (sgemm_dma5.hpp, rim_wave): m and / or n ONE element past a multiple of 64, at
+// least one whole tile each way.  *r_m / *r_n: rim rows / columns (0 or 1).
 inline bool dma5_rim_dims(int m, int n, int *r_m, int *r_n) {
   const int rm = m % 64, rn = n % 64;
   const int a = (rm == 1 && m > 64) ? 1 : 0, b = (rn == 1 && n > 64) ? 1 : 0;
@@ -269,27 +272,59 @@ inline bool dma5_rim_dims(int m, int n, int *r_m, int *r_n) {
   if (r_n) *r_n = b;
   return a > 0 || b > 0;
 }
-// launch_dma5.hip: tile = MMH_KERNEL_MFMA_*_DMA5 (sgemm_dma5.hpp); returns 1 when the shape does not qualify
-int launch_dma5(mmh_context *ctx, int kernel, const GemmArgs &g);
-bool dma5_shape_ok(const mmh_context *ctx, int kernel, const GemmArgs &g);   // (g.ta / g.tb: the stored layouts' window)
-int warm_dma5(mmh_context *ctx, float *scratch, hipStream_t s);
-// launch_op.hip: the op forms (g.ta / g.tb) of MMH_KERNEL_MFMA_{64X64,128X64,128X128}_DMA5, and of MMH_KERNEL_NAIVE
-int launch_dma5_op(mmh_context *ctx, int kernel, const GemmArgs &g);   // 1: the shape does not qualify
-int launch_naive_op(const GemmArgs &g);
-int warm_dma5_op(mmh_context *ctx);                                     // LDS opt-ins only (nothing is launched)
+// The K2W tiles (sgemm_dma5.hpp) of the product's kernel ids -- the one place an id meets its configuration: BM BN, wave
+// tile WTM x WTN MFMA blocks, NBUF ring buffers, NL loader waves, fragments D k-steps ahead, RS the fragment reads' form;
+// SK: a stream-K form (the whole-round tiles run one workgroup per tile only); OPS: op and batched forms.
+// (Loader counts as measured, profiles/r04_notes.md: one loader wave on a consumer's SIMD holds that consumer back -- and
+// the workgroup, at every barrier; two or four spread the pieces -- 128x128 under chained stream-K at N = 2560: 127.9 /
+// 144.4 / 145.2 TFLOP/s with 1 / 2 / 4 loaders, 128x64 at N = 2432: 139.5 / 139.7 / 143.5.)
+template <int ID_, int BM_, int BN_, int WTM_, int WTN_, int NBUF_, int NL_, int D_, bool SK_, bool OPS_, int RS_ = 1>
+struct K2wTile {
+  static constexpr int ID = ID_, BM = BM_, BN = BN_, WTM = WTM_, WTN = WTN_, NBUF = NBUF_, NL = NL_, D = D_, RS = RS_;
+  static constexpr bool SK = SK_, OPS = OPS_;
+};
+template <class... Tile>
+struct K2wTiles {
+  // f(Tile{}) for the tile of `kernel`; `none` when it is no K2W id
+  template <class F>
+  static int with(int kernel, F &&f, int none) {
+    int r = none;
+    (void)((kernel == Tile::ID && ((r = f(Tile{})), true)) || ...);
+    return r;
+  }
+  // f(Tile{}) for every tile in table order, up to the first that does not return MMH_OK
+  template <class F>
+  static int each(F &&f) {
+    int rc = MMH_OK;
+    (void)(((rc = f(Tile{})) == MMH_OK) && ...);
+    return rc;
+  }
+};
+using k2w_tiles = K2wTiles<
+    //      id                            BM   BN WTM WTN NBUF NL D  SK     OPS
+    K2wTile<MMH_KERNEL_MFMA_64X64_DMA5,   64,  64, 2, 2, 3, 2, 2, true,  true>,    // 32x32 consumers + two loaders, 48 KiB ring: 3 per CU
+    K2wTile<MMH_KERNEL_MFMA_128X64_DMA5,  128, 64, 4, 2, 3, 4, 2, true,  true>,    // 64x32 consumers, 72 KiB ring: 2 per CU
+    K2wTile<MMH_KERNEL_MFMA_128X128_DMA5, 128, 128, 4, 4, 3, 4, 2, true, true>,    // 64x64 consumers, 96 KiB ring
+    K2wTile<MMH_KERNEL_MFMA_96X96_DMA5,   96,  96, 3, 3, 3, 1, 2, false, false>,   // 48x48 (column-blocked B), 72 KiB ring: 2 per CU
+    K2wTile<MMH_KERNEL_MFMA_160X160_DMA5, 160, 160, 5, 5, 3, 4, 2, false, false>,  // 80x80 (column-blocked B), 120 KiB ring: 1 per CU (N = 2560: 256 of them)
+    K2wTile<MMH_KERNEL_MFMA_96X64_DMA5,   96,  64, 3, 2, 3, 4, 2, false, false>>;  // 48x32, 60 KiB ring: 2 per CU (round 5; N = 1152: 110.5 against 106.6 TFLOP/s)
+
 // launch_batched.hip: mmh_sgemm_batched's one-launch form -- `batch` matrices of g's shape, matrix i at g.A + i sA, g.B + i sB,
-// g.C + i sC (elements) -- on MMH_KERNEL_MFMA_{64X64,128X64,128X128}_DMA5 (1: the matrices do not qualify), and the naive
-// batched kernel (every kernel id, k == 0 included: it zeroes C without reading A or B)
+// g.C + i sC (elements) -- on the K2W tiles with op forms (1: the matrices do not qualify), and the naive batched kernel
+// (every kernel id, k == 0 included: it zeroes C without reading A or B)
 struct BatchArgs {
   long long sA = 0, sB = 0, sC = 0;
   long batch = 1;
 };
 // one launch never holds more workgroups than this; a larger batch goes out as several launches of the same kernel
 constexpr long kBatchedMaxWorkgroups = MMH_BATCHED_MAX_WORKGROUPS;
-// the batched tiles' form for a whole matrix set: 0 whole-tile (fast_shape for EVERY matrix: the bases 16-byte aligned
-// and every stride a multiple of 4 floats), 1 guarded (dma5_form's rules, every matrix), -1 not on this tile
-inline int dma5_batched_form(const mmh_context *ctx, int BM, int BN, const GemmArgs &g, const BatchArgs &b) {
-  if (!window_ok(BM, BN, g)) return -1;   // (per matrix: the descriptors are built per tile from the matrix's base)
+
+// A K2W tile's form for a shape (for every matrix of a batch): 0 whole-tile (fast_shape; the bases 16-byte aligned and every
+// stride a multiple of 4 floats), 1 guarded (any m, n, k; 4-byte aligned operands unless MMH_OPT_DMA_DWORD_ROWS), -1 not on
+// this tile.  g.ta / g.tb: the stored layouts' descriptor window (per matrix: the descriptors are built per tile from the
+// matrix's base).
+inline int dma5_form(const mmh_context *ctx, int BM, int BN, const GemmArgs &g, const BatchArgs &b = BatchArgs{}) {
+  if (!window_ok(BM, BN, g)) return -1;
   const bool s4 = b.batch == 1 || (b.sA % 4 == 0 && b.sB % 4 == 0 && b.sC % 4 == 0);
   if (fast_shape(BM, BN, 32, g) && s4) return 0;
   if (!ctx || !ctx->dma_edge) return -1;
@@ -298,6 +333,16 @@ inline int dma5_batched_form(const mmh_context *ctx, int BM, int BN, const GemmA
   if (!rows16 && !ctx->dma_dword_rows) return -1;
   return 1;
 }
+inline bool dma5_shape_ok(const mmh_context *ctx, int kernel, const GemmArgs &g) {
+  return k2w_tiles::with(kernel, [&](auto t) { return (int)(dma5_form(ctx, t.BM, t.BN, g) >= 0); }, 0);
+}
+// launch_dma5.hip: tile = MMH_KERNEL_MFMA_*_DMA5 (sgemm_dma5.hpp); returns 1 when the shape does not qualify
+int launch_dma5(mmh_context *ctx, int kernel, const GemmArgs &g);
+int warm_dma5(mmh_context *ctx, float *scratch, hipStream_t s);
+// launch_op.hip: the op forms (g.ta / g.tb) of the K2W tiles with op forms, and of MMH_KERNEL_NAIVE
+int launch_dma5_op(mmh_context *ctx, int kernel, const GemmArgs &g);   // 1: the shape does not qualify
+int launch_naive_op(const GemmArgs &g);
+int warm_dma5_op(mmh_context *ctx);                                     // LDS opt-ins only (nothing is launched)
 int launch_dma5_batched(mmh_context *ctx, int kernel, const GemmArgs &g, const BatchArgs &b);
 int launch_naive_batched(const GemmArgs &g, const BatchArgs &b);
 int warm_dma5_batched(mmh_context *ctx);   // LDS opt-ins only (nothing is launched)

@@ -1,9 +1,8 @@
-// launch_batched.hip -- launchers of mmh_sgemm_batched's one-launch form: the 64x64, 128x64 and 128x128 K2W tiles
-// (sgemm_dma5.hpp, sgemm_mfma_dma5_batched_kernel) over batch x tiles, whole-tile and guarded, every op pair; and the
-// naive batched kernel.  A translation unit of its own, like launch_op.hip: the NN and op instantiations are compiled
-// exactly as before.  Part of libmmult_hip.so (see internal.hpp).
-#include "launch_common.hpp"
-#include "sgemm_dma5.hpp"
+// launch_batched.hip -- launches of mmh_sgemm_batched's one-launch form: the K2W tiles with op forms (k2w_tiles,
+// internal.hpp; sgemm_dma5.hpp, sgemm_mfma_dma5_batched_kernel) over batch x tiles, whole-tile and guarded, every op pair,
+// with launch_dma5.hpp's form, tail split and description; and the naive batched kernel.  A translation unit of its own,
+// like launch_op.hip, so that build.py compiles its instantiations in parallel.  Part of libmmult_hip.so (see internal.hpp).
+#include "launch_dma5.hpp"
 
 namespace mmh {
 
@@ -29,18 +28,14 @@ sgemm_naive_batched_kernel(int transa, int transb, int m, int n, int k, const fl
 
 namespace {
 
-const char *batch_op_tag(const GemmArgs &g) {
-  return g.ta ? (g.tb ? ", operands TT" : ", operands TN") : (g.tb ? ", operands NT" : "");
-}
-
 // One launch (or several of at most kBatchedMaxWorkgroups workgroups each: whole matrices per launch, the pointers
-// advanced to the chunk's first matrix) of one tile over every matrix.  Whole-tile or guarded for the whole matrix set
-// (dma5_batched_form); the tail split of launch_op_tile on the residency of the NN twin.
-template <int BM, int BN, int WTM, int WTN, int NBUF, int NL, int D, int OP>
+// advanced to the chunk's first matrix) of tile K over every matrix.  Whole-tile or guarded for the whole matrix set
+// (dma5_form with the strides); the tail split of launch_dma5_tile on the residency of the NN twin.
+template <class K, int OP>
 int launch_batched_tile(mmh_context *ctx, const GemmArgs &g, const BatchArgs &bt) {
-  constexpr int KB = 32;
+  constexpr int BM = K::BM, BN = K::BN, KB = 32, WTM = K::WTM, WTN = K::WTN, NBUF = K::NBUF, NL = K::NL, D = K::D;
   using T = Dma5Tile<BM, BN, KB, WTM, WTN, NBUF, NL>;
-  const int form = dma5_batched_form(ctx, BM, BN, g, bt);
+  const int form = dma5_form(ctx, BM, BN, g, bt);
   if (form < 0) return 1;
   const bool edge = form == 1;
   auto kern = edge ? sgemm_mfma_dma5_batched_kernel<BM, BN, KB, WTM, WTN, NBUF, true, NL, D, OP>
@@ -61,13 +56,7 @@ int launch_batched_tile(mmh_context *ctx, const GemmArgs &g, const BatchArgs &bt
     const long tiles = nb * per;
     const float *A = g.A + b0 * bt.sA, *B = g.B + b0 * bt.sB;
     float *C = g.C + b0 * bt.sC;
-    long first = tiles;
-    if (ctx && ctx->split_tail) {   // the tail split of launch_dma5_tile
-      (void)allow_big_lds(twin, T::LDS_BYTES);
-      const long cus = ctx->cu_count > 0 ? ctx->cu_count : 256;
-      const long w = std::min(resident_per_cu(ctx, twin, T::THREADS, T::LDS_BYTES), 3);
-      if (dma5_tail_split(tiles, w, cus, g.k) && (w * cus) % 8 == 0) first = w * cus;
-    }
+    const long first = dma5_split_first(ctx, twin, T::THREADS, T::LDS_BYTES, tiles, g.k);
     hipLaunchKernelGGL(kern, dim3((unsigned)first), dim3(T::THREADS), T::LDS_BYTES, g.s, g.m, g.n, g.k, A, g.lda, bt.sA, B, g.ldb,
                        bt.sB, C, g.ldc, bt.sC, acc, nbm, nbn, 0u);
     ++launches;
@@ -86,38 +75,35 @@ int launch_batched_tile(mmh_context *ctx, const GemmArgs &g, const BatchArgs &bt
            "sgemm_mfma_dma5_batched_kernel<%d,%d> wave tile %dx%d, K-slice %d x %d ring buffers by %d loader waves' LDS-DMA, "
            "fragments %d k-steps ahead, %s%ld workgroups of %d threads%s%s, batch %ld%s",
            BM, BN, 16 * WTM, 16 * WTN, KB, NBUF, NL, D, edge ? "guarded, " : "", bt.batch * per, T::THREADS,
-           split ? " (the last round as a launch of its own)" : "", batch_op_tag(g), bt.batch, how);
+           split ? " (the last round as a launch of its own)" : "", op_tag(g), bt.batch, how);
   set_last_launch(what);
   return MMH_OK;
 }
 
-// (the NN configurations of launch_dma5: BM BN WTM WTN NBUF NL D)
 template <int OP>
 int launch_batched_family(mmh_context *ctx, int kernel, const GemmArgs &g, const BatchArgs &b) {
-  switch (kernel) {
-    case MMH_KERNEL_MFMA_64X64_DMA5: return launch_batched_tile<64, 64, 2, 2, 3, 2, 2, OP>(ctx, g, b);
-    case MMH_KERNEL_MFMA_128X64_DMA5: return launch_batched_tile<128, 64, 4, 2, 3, 4, 2, OP>(ctx, g, b);
-    case MMH_KERNEL_MFMA_128X128_DMA5: return launch_batched_tile<128, 128, 4, 4, 3, 4, 2, OP>(ctx, g, b);
-    default: return 1;
-  }
+  return k2w_tiles::with(kernel, [&](auto t) {
+    using K = decltype(t);
+    if constexpr (K::OPS) return launch_batched_tile<K, OP>(ctx, g, b);
+    return 1;
+  }, 1);
 }
 
-template <int BM, int BN, int WTM, int WTN, int NBUF, int NL, int D, int OP>
-int warm_batched_tile() {
-  constexpr int KB = 32;
-  using T = Dma5Tile<BM, BN, KB, WTM, WTN, NBUF, NL>;
-  int rc;
-  if ((rc = allow_big_lds(sgemm_mfma_dma5_batched_kernel<BM, BN, KB, WTM, WTN, NBUF, false, NL, D, OP>, T::LDS_BYTES)) != MMH_OK)
-    return rc;
-  return allow_big_lds(sgemm_mfma_dma5_batched_kernel<BM, BN, KB, WTM, WTN, NBUF, true, NL, D, OP>, T::LDS_BYTES);
-}
-
+// the LDS opt-ins of one op pair's batched instantiations, tile by tile
 template <int OP>
 int warm_batched_families() {
-  int rc;
-  if ((rc = warm_batched_tile<64, 64, 2, 2, 3, 2, 2, OP>()) != MMH_OK) return rc;
-  if ((rc = warm_batched_tile<128, 64, 4, 2, 3, 4, 2, OP>()) != MMH_OK) return rc;
-  return warm_batched_tile<128, 128, 4, 4, 3, 4, 2, OP>();
+  return k2w_tiles::each([](auto t) {
+    using K = decltype(t);
+    if constexpr (K::OPS) {
+      constexpr int BM = K::BM, BN = K::BN, KB = 32, WTM = K::WTM, WTN = K::WTN, NBUF = K::NBUF, NL = K::NL, D = K::D;
+      constexpr size_t lds = Dma5Tile<BM, BN, KB, WTM, WTN, NBUF, NL>::LDS_BYTES;
+      const int rc = allow_big_lds(sgemm_mfma_dma5_batched_kernel<BM, BN, KB, WTM, WTN, NBUF, false, NL, D, OP>, lds);
+      if (rc != MMH_OK) return rc;
+      return allow_big_lds(sgemm_mfma_dma5_batched_kernel<BM, BN, KB, WTM, WTN, NBUF, true, NL, D, OP>, lds);
+    } else {
+      return (int)MMH_OK;
+    }
+  });
 }
 
 }  // namespace
@@ -144,7 +130,7 @@ int launch_naive_batched(const GemmArgs &g, const BatchArgs &b) {
     HIP_TRY(hipGetLastError());
   }
   char what[160];
-  snprintf(what, sizeof what, "sgemm_naive_batched_kernel%s, batch %ld", batch_op_tag(g), b.batch);
+  snprintf(what, sizeof what, "sgemm_naive_batched_kernel%s, batch %ld", op_tag(g), b.batch);
   std::string s = what;
   if (launches > 1) s += " as " + std::to_string(launches) + " launches";
   set_last_launch(s);

@@ -16,6 +16,16 @@ int allow_big_lds(K kernel, size_t bytes) {
   return MMH_OK;
 }
 
+// A last K2W tile row (column) of at most 16 valid rows (columns) is THIN: a fraction of a tile's MFMAs, dispatched after
+// the whole tiles (sgemm_dma5.hpp dma5_raster, which spells this test out on the device).  0 or 1.
+inline int thin_last(int m, int nb, int bm) { return (nb > 1 && m - (nb - 1) * bm <= 16) ? 1 : 0; }
+// the tiles of an m x n shape that are not thin: the count the launchers (launch_dma5.hpp) and the cost table (policy.hip)
+// decide on
+inline long full_tiles(int m, int n, int bm, int bn) {
+  const int nbm = (m + bm - 1) / bm, nbn = (n + bn - 1) / bn;
+  return (long)(nbm - thin_last(m, nbm, bm)) * (nbn - thin_last(n, nbn, bn));
+}
+
 // resident workgroups per CU of a persistent kernel: what the runtime reports, never more than the
 // LDS allows; computed once per handle (= per device) and kernel
 template <typename K>

@@ -41,24 +41,11 @@ struct Plan {
   int bm = 0, bn = 0;
 };
 
-bool is_k2w(int kernel) {
-  return kernel == MMH_KERNEL_MFMA_64X64_DMA5 || kernel == MMH_KERNEL_MFMA_128X64_DMA5 || kernel == MMH_KERNEL_MFMA_128X128_DMA5 ||
-         kernel == MMH_KERNEL_MFMA_96X96_DMA5 || kernel == MMH_KERNEL_MFMA_96X64_DMA5 || kernel == MMH_KERNEL_MFMA_160X160_DMA5;
-}
+bool is_k2w(int kernel) { return k2w_tiles::with(kernel, [](auto) { return 1; }, 0); }
 // the tiles with op forms (launch_op.hip): where the NN table picks one of them the op plan is that very plan
-bool has_op_forms(int kernel) {
-  return kernel == MMH_KERNEL_MFMA_64X64_DMA5 || kernel == MMH_KERNEL_MFMA_128X64_DMA5 || kernel == MMH_KERNEL_MFMA_128X128_DMA5;
-}
+bool has_op_forms(int kernel) { return k2w_tiles::with(kernel, [](auto t) { return (int)t.OPS; }, 0); }
 bool is_k2l(int kernel) {
   return kernel == MMH_KERNEL_MFMA_64X64_DMA || kernel == MMH_KERNEL_MFMA_128X64_DMA || kernel == MMH_KERNEL_MFMA_128X128_DMA;
-}
-
-// the tiles of an m x n shape that are not K2W thin edge tiles (a last tile row / column with at most 16 valid rows /
-// columns: a fraction of a tile's MFMAs, dispatched last, beside whole tiles)
-long full_tiles(const Family &f, int m, int n) {
-  const int nbm = (m + f.bm - 1) / f.bm, nbn = (n + f.bn - 1) / f.bn;
-  const int tr = (nbm > 1 && m - (nbm - 1) * f.bm <= 16) ? 1 : 0, tc = (nbn > 1 && n - (nbn - 1) * f.bn <= 16) ? 1 : 0;
-  return (long)(nbm - tr) * (nbn - tc);
 }
 
 // The price of a plain launch (one workgroup per tile) of `tiles` workgroups of the family, `full` of them not thin.
@@ -79,7 +66,7 @@ double plain_us(const mmh_context *ctx, const Family &f, int k, long tiles, long
     // ... of between half a tile and one tile per CU: the dispatcher hands those out one per CU, or in pairs to the
     // CUs whose workgroups ended together -- a whole extra round (the same launch 142 and 110 TFLOP/s in two passes:
     // tools/policy_fit.py PAIRING); priced at the risk
-    // (the launches launch_dma5.hip splits -- one round and a last round of just under a tile per CU -- are out of that class)
+    // (the launches launch_dma5.hpp splits -- one round and a last round of just under a tile per CU -- are out of that class)
     const long rem = tiles % ((long)f.w * cus);
     const bool split = is_k2w(f.kernel) && (!ctx || ctx->split_tail) && dma5_tail_split(tiles, f.w, cus, k);
     t *= (2 * rem > cus && rem <= cus && !split) ? std::max(MMH_POLICY_PAIRING_MARGIN, MMH_POLICY_MULTIROUND_MARGIN) : MMH_POLICY_MULTIROUND_MARGIN;
@@ -115,7 +102,7 @@ Plan auto_plan_for(const mmh_context *ctx, const GemmArgs &g) {
     }
     if (tiles_rim) tiles = tiles_rim;
     const bool whole = fast_shape(f.bm, f.bn, kSliceK, g);
-    const double t = plain_us(ctx, f, g.k, tiles, is_k2w(f.kernel) && !tiles_rim ? full_tiles(f, g.m, g.n) : tiles, whole);
+    const double t = plain_us(ctx, f, g.k, tiles, is_k2w(f.kernel) && !tiles_rim ? full_tiles(g.m, g.n, f.bm, f.bn) : tiles, whole);
     if (best.kernel < 0 || t < best.us) best = Plan{f.kernel, 1, t, 0, f.bm, f.bn};
     if (f.has_sk && (!ctx || ctx->streamk) && !tiles_rim) {
       // the grid launch_streamk will launch: the largest w' <= skw workgroups per CU that leaves every one a whole tile
@@ -386,10 +373,10 @@ BatchPlan batched_plan_for(const mmh_context *ctx, const GemmArgs &g, const Batc
   double best = bp.per.kernel >= 0 ? (double)b.batch * bp.per.us : 0.0;
   for (const Family &f : kFamilies) {
     if (!has_op_forms(f.kernel)) continue;
-    const int form = dma5_batched_form(ctx, f.bm, f.bn, g, b);
+    const int form = dma5_form(ctx, f.bm, f.bn, g, b);
     if (form < 0) continue;
     const long per = (long)((g.m + f.bm - 1) / f.bm) * ((g.n + f.bn - 1) / f.bn);
-    const double t = plain_us(ctx, f, g.k, b.batch * per, b.batch * full_tiles(f, g.m, g.n), form == 0);
+    const double t = plain_us(ctx, f, g.k, b.batch * per, b.batch * full_tiles(g.m, g.n, f.bm, f.bn), form == 0);
     if (bp.kernel < 0 || t < best) {
       best = t;
       bp.form = MMH_BATCH_FORM_ONE_LAUNCH;
@@ -484,9 +471,9 @@ int auto_plan_batched(int ta, int tb, int m, int n, int k, int lda, int ldb, int
   const BatchPlan bp = batched_plan_for(&ctx, g, b);
   if (form) *form = bp.form;
   if (bp.form == MMH_BATCH_FORM_ONE_LAUNCH) {
-    const int bm = bp.kernel == MMH_KERNEL_MFMA_64X64_DMA5 ? 64 : 128, bn = bp.kernel == MMH_KERNEL_MFMA_128X128_DMA5 ? 128 : 64;
     if (kernel) *kernel = bp.kernel;
-    if (workgroups) *workgroups = (long)batch * ((m + bm - 1) / bm) * ((n + bn - 1) / bn);
+    if (workgroups)
+      *workgroups = (long)batch * k2w_tiles::with(bp.kernel, [&](auto t) { return ((m + t.BM - 1) / t.BM) * ((n + t.BN - 1) / t.BN); }, 0);
     return MMH_OK;
   }
   // fold / loop: mmh_auto_plan_op on the one GEMM mmh_sgemm_op runs, times the launches

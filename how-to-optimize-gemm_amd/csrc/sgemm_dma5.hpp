@@ -763,24 +763,46 @@ struct Dma5Segment {
   }
 };
 
-// One workgroup per C tile (XCD-aware block -> tile map), whole K range.
+// The raster of a plain launch (sgemm_mfma_dma5_kernel and its op form; the batched form spells it out): workgroup `bid`
+// -> tile (tm, tn).
 // EDGE: a last tile row / column that is THIN (at most 16 valid rows / columns: its waves run the thin copies of the
 // consumer) is taken out of the raster and dispatched LAST: the whole tiles fill the CUs first, in the order a launch
-// of the trimmed shape would, and the thin tiles -- a fraction of a whole tile's matrix-pipe time each -- land beside
-// them as second workgroups.  In raster order they would take first-round slots and push whole tiles into a second
-// round (N = 1025: 289 tiles of 64x64 for 256 CUs, 33 of them thin).
+// of the trimmed shape would (block_to_tile_g), and the thin tiles -- a fraction of a whole tile's matrix-pipe time each --
+// land beside them as second workgroups: the thin column top to bottom (its corner with a thin row included), then the
+// thin row left to right.  In raster order they would take first-round slots and push whole tiles into a second round
+// (N = 1025: 289 tiles of 64x64 for 256 CUs, 33 of them thin).  (The thin test is launch_common.hpp's thin_last, spelled
+// out: called, it moves the 96x96 and 160x160 kernels' code.)
+template <int BM, int BN, bool EDGE>
+__device__ __forceinline__ void dma5_raster(int bid, int m, int n, int nbm, int nbn, int gm, int &tm, int &tn) {
+  const int thin_row = (EDGE && nbm > 1 && m - (nbm - 1) * BM <= 16) ? 1 : 0, thin_col = (EDGE && nbn > 1 && n - (nbn - 1) * BN <= 16) ? 1 : 0;
+  const int n_full = (nbm - thin_row) * (nbn - thin_col);
+  int r = bid - n_full;
+  if (r < 0) {
+    block_to_tile_g(bid, n_full, nbm - thin_row, nbn - thin_col, gm, tm, tn);
+  } else if (thin_col && r < nbm) {
+    tm = r;
+    tn = nbn - 1;
+  } else {
+    if (thin_col) r -= nbm;
+    tm = nbm - 1;
+    tn = r;
+  }
+}
+
+// One workgroup per C tile (dma5_raster), whole K range.
 template <int BM, int BN, int KB, int WTM, int WTN, int NBUF, bool EDGE = false, int NL = 1, int D = 2, int RS = 1>
 __global__ void __launch_bounds__(64 * (4 + NL))
 sgemm_mfma_dma5_kernel(int m, int n, int k, const float *__restrict__ A, int lda, const float *__restrict__ B, int ldb,
                        float *__restrict__ C, int ldc, int accumulate, int nbm, int nbn) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   using S = Dma5Segment<BM, BN, KB, WTM, WTN, NBUF, false, EDGE, false, NL, D, false, false, RS>;
+  constexpr int GM = Dma5Tile<BM, BN, KB, WTM, WTN, NBUF, NL>::GM;
   int tm, tn;
   // (round 5: every kernel argument is requested HERE -- left alone hipcc loads the operands' pointers and leading
   // dimensions only behind the branch to the loader path, a second scalar-memory round trip in front of the first DMA)
   asm volatile("" ::"s"(A), "s"(B), "s"(C), "s"(lda), "s"(ldb), "s"(ldc), "s"(k));
   dma_stamp(0);
-  // TAIL SPLIT (bits 16-31 of `accumulate`: the id of this launch's first workgroup, / 8; launch_dma5.hip decides).  The
+  // TAIL SPLIT (bits 16-31 of `accumulate`: the id of this launch's first workgroup, / 8; launch_dma5.hpp decides).  The
   // dispatcher hands a launch's first workgroups out one per CU -- ids 0 .. CUs - 1 --, then the second slot of every CU, then
   // the third; they start together and, the kernels being what they are, the ones that share a CU END together: all slots of
   // a CU are refilled at once, and a last round of fewer tiles than CUs lands two (three) per CU on a part of the chip instead
@@ -792,21 +814,9 @@ sgemm_mfma_dma5_kernel(int m, int n, int k, const float *__restrict__ A, int lda
   const unsigned bid = blockIdx.x + (((unsigned)accumulate >> 16) << 3);
   accumulate &= 0xffff;
   if constexpr (EDGE) {
-    const int thin_row = (nbm > 1 && m - (nbm - 1) * BM <= 16) ? 1 : 0, thin_col = (nbn > 1 && n - (nbn - 1) * BN <= 16) ? 1 : 0;
-    const int nbm_f = nbm - thin_row, nbn_f = nbn - thin_col, n_full = nbm_f * nbn_f;
-    int r = (int)bid - n_full;
-    if (r < 0) {
-      block_to_tile_g(bid, n_full, nbm_f, nbn_f, Dma5Tile<BM, BN, KB, WTM, WTN, NBUF, NL>::GM, tm, tn);
-    } else if (thin_col && r < nbm) {   // the thin column, top to bottom (its corner with a thin row included)
-      tm = r;
-      tn = nbn - 1;
-    } else {                            // the thin row, left to right
-      if (thin_col) r -= nbm;
-      tm = nbm - 1;
-      tn = r;
-    }
-  } else {
-    int gm = Dma5Tile<BM, BN, KB, WTM, WTN, NBUF, NL>::GM;
+    dma5_raster<BM, BN, true>(bid, m, n, nbm, nbn, GM, tm, tn);
+  } else {   // (whole tiles: no thin ones -- the raster is block_to_tile_g's)
+    int gm = GM;
     if constexpr (kAbBuild) {   // tools build: the raster group height rides in bits 8-15 of `accumulate` (0: the tile's own)
       const int ab_gm = (accumulate >> 8) & 0xff;
       accumulate &= 1;
@@ -824,9 +834,8 @@ sgemm_mfma_dma5_kernel(int m, int n, int k, const float *__restrict__ A, int lda
   dma_stamp_after_stores(3);
 }
 
-// The op forms (OP: Dma5Segment) of the plain launch: kernels of their own, so that the NN instantiations keep their names
-// and their code (sgemm_mfma_dma5_kernel above stays as it is -- hipcc's output moves with any refactoring of its body);
-// the raster is that kernel's, thin edge tiles last, the tail split's id offset in bits 16-31 of `accumulate`.
+// The op forms (OP: Dma5Segment) of the plain launch: kernels of their own, so that the NN instantiations keep their names;
+// the raster is dma5_raster, the tail split's id offset in bits 16-31 of `accumulate` (launch_dma5.hpp, one launcher for both).
 template <int BM, int BN, int KB, int WTM, int WTN, int NBUF, bool EDGE, int NL, int D, int OP>
 __global__ void __launch_bounds__(64 * (4 + NL))
 sgemm_mfma_dma5_op_kernel(int m, int n, int k, const float *__restrict__ A, int lda, const float *__restrict__ B, int ldb,
@@ -838,19 +847,7 @@ sgemm_mfma_dma5_op_kernel(int m, int n, int k, const float *__restrict__ A, int 
   const unsigned bid = blockIdx.x + (((unsigned)accumulate >> 16) << 3);
   accumulate &= 0xffff;
   int tm, tn;
-  const int thin_row = (EDGE && nbm > 1 && m - (nbm - 1) * BM <= 16) ? 1 : 0, thin_col = (EDGE && nbn > 1 && n - (nbn - 1) * BN <= 16) ? 1 : 0;
-  const int n_full = (nbm - thin_row) * (nbn - thin_col);
-  int r = (int)bid - n_full;
-  if (r < 0) {
-    block_to_tile_g(bid, n_full, nbm - thin_row, nbn - thin_col, GM, tm, tn);
-  } else if (thin_col && r < nbm) {
-    tm = r;
-    tn = nbn - 1;
-  } else {
-    if (thin_col) r -= nbm;
-    tm = nbm - 1;
-    tn = r;
-  }
+  dma5_raster<BM, BN, EDGE>(bid, m, n, nbm, nbn, GM, tm, tn);
   typename S::Lane L;
   L.init(lda, ldb);
   typename S::Frags fr;
@@ -864,7 +861,7 @@ sgemm_mfma_dma5_op_kernel(int m, int n, int k, const float *__restrict__ A, int 
 // offsets), one workgroup per tile of every matrix.  The launch holds the workgroup ids [first, first + gridDim.x) of its
 // matrix set, matrix after matrix.  The dispatcher deals a launch's blocks round-robin over the eight XCDs; the id is
 // remapped XCD-contiguous first (each XCD takes a run of consecutive ids, so a small matrix's tiles share one L2 and its A
-// and B panels), then split into (matrix, tile).  Inside a matrix: the op kernel's raster, thin edge tiles last.
+// and B panels), then split into (matrix, tile).  Inside a matrix: dma5_raster's map.
 // (Tools build: bit 1 of `accumulate` = the plain batch-major order, the A/B baseline of profiles/batched_sweep.md.)
 template <int BM, int BN, int KB, int WTM, int WTN, int NBUF, bool EDGE, int NL, int D, int OP>
 __global__ void __launch_bounds__(64 * (4 + NL))
@@ -894,6 +891,7 @@ sgemm_mfma_dma5_batched_kernel(int m, int n, int k, const float *__restrict__ A,
   B += (long long)b * sB;
   C += (long long)b * sC;
   int tm, tn;
+  // dma5_raster, written out: every form of the call measured moves this kernel's code (its pointer offsets' schedule)
   const int thin_row = (EDGE && nbm > 1 && m - (nbm - 1) * BM <= 16) ? 1 : 0, thin_col = (EDGE && nbn > 1 && n - (nbn - 1) * BN <= 16) ? 1 : 0;
   const int n_full = (nbm - thin_row) * (nbn - thin_col);
   int r = bid - n_full;

@@ -73,7 +73,7 @@ FAMILIES = {
 def tail_split(tiles, w, cus, k):
     """csrc/internal.hpp dma5_tail_split: the plain K2W launches that go out as one whole round + the last round as a launch of its own."""
     rem = tiles - w * cus
-    return w >= 2 and k >= 512 and 100 * rem > 85 * cus and rem <= cus
+    return w >= 2 and k >= 512 and 100 * rem > 85 * cus and rem <= cus and (w * cus) % 8 == 0
 
 
 def rim_dims(m, n):
