@@ -1,9 +1,13 @@
 // abi.hip -- the extern "C" entry points of include/mmult_hip.h that are not tied to one kernel family: library
-// and handle queries, options, the device-pointer MY_MMult (mmh_sgemm), the measurement helpers.
+// and handle queries, options, the device-pointer MY_MMult (mmh_sgemm), the measurement helpers -- and the catalogue
+// of kernel ids (kKernels) behind mmh_kernel_name, mmh_kernel_id and kernel_row().
 // Part of libmmult_hip.so (see internal.hpp).
 #include <algorithm>
 
 #include "internal.hpp"
+#ifdef MMH_AB_BUILD
+#include "ab_kernels.hpp"   // tools/ab/: the MMH_KERNEL_* numbers of the tools build's tile families
+#endif
 
 using namespace mmh;
 
@@ -31,7 +35,70 @@ int time_calls(mmh_context *h, hipStream_t s, int warmup, int reps, float *ms_pe
   *ms_per_call = ms / reps;
   return check_sticky(h);
 }
+
+// The catalogue (internal.hpp, KernelRow): every id this build accepts.  A new kernel id is one row here -- name, the family
+// whose launcher takes it, the register-staged tile that takes the shapes the family refuses -- plus its tile's row in
+// internal.hpp's tile table and its number in mmult_hip.h.
+constexpr KernelRow kKernels[] = {
+    {MMH_KERNEL_AUTO, "MMult_hip_auto", Launcher::Auto, -1},
+    {MMH_KERNEL_VALU, "MMult_hip_valu", Launcher::Valu, -1},
+    {MMH_KERNEL_VALU_128X128, "MMult_hip_valu_128x128", Launcher::Valu, -1},
+    {MMH_KERNEL_VALU_64X64, "MMult_hip_valu_64x64", Launcher::Valu, -1},
+    {MMH_KERNEL_VALU_128X64, "MMult_hip_valu_128x64", Launcher::Valu, -1},
+    {MMH_KERNEL_MFMA, "MMult_hip_mfma", Launcher::Reg, -1},
+    {MMH_KERNEL_MFMA_256, "MMult_hip_mfma256", Launcher::Reg, -1},
+    {MMH_KERNEL_NAIVE, "MMult_hip_naive", Launcher::Naive, -1},
+    {MMH_KERNEL_MFMA_SIMPLE, "MMult_hip_mfma_simple", Launcher::Reg, -1},
+    {MMH_KERNEL_MFMA_PIPE, "MMult_hip_mfma_pipe", Launcher::Reg, -1},
+    {MMH_KERNEL_MFMA_TILES, "MMult_hip_mfma_tiles", Launcher::Reg, -1},
+    {MMH_KERNEL_MFMA_128X64, "MMult_hip_mfma_128x64", Launcher::Reg, -1},
+    {MMH_KERNEL_MFMA_64X64, "MMult_hip_mfma_64x64", Launcher::Reg, -1},
+    {MMH_KERNEL_MFMA_256X256, "MMult_hip_mfma_256x256", Launcher::Reg, -1},
+    {MMH_KERNEL_MFMA_64X64_DMA, "MMult_hip_mfma_64x64_dma", Launcher::K2L, MMH_KERNEL_MFMA_64X64},
+    {MMH_KERNEL_MFMA_128X64_DMA, "MMult_hip_mfma_128x64_dma", Launcher::K2L, MMH_KERNEL_MFMA_128X64},
+    {MMH_KERNEL_MFMA_128X128_DMA, "MMult_hip_mfma_128x128_dma", Launcher::K2L, MMH_KERNEL_MFMA},
+    {MMH_KERNEL_MFMA_64X64_DMA5, "MMult_hip_mfma_64x64_dma5", Launcher::K2W, MMH_KERNEL_MFMA_64X64},
+    {MMH_KERNEL_MFMA_128X64_DMA5, "MMult_hip_mfma_128x64_dma5", Launcher::K2W, MMH_KERNEL_MFMA_128X64},
+    {MMH_KERNEL_MFMA_128X128_DMA5, "MMult_hip_mfma_128x128_dma5", Launcher::K2W, MMH_KERNEL_MFMA},
+    {MMH_KERNEL_MFMA_96X96_DMA5, "MMult_hip_mfma_96x96_dma5", Launcher::K2W, MMH_KERNEL_MFMA},
+    {MMH_KERNEL_MFMA_96X64_DMA5, "MMult_hip_mfma_96x64_dma5", Launcher::K2W, MMH_KERNEL_MFMA},
+    {MMH_KERNEL_MFMA_160X160_DMA5, "MMult_hip_mfma_160x160_dma5", Launcher::K2W, MMH_KERNEL_MFMA},
+    {MMH_KERNEL_MFMA_SPLITK, "MMult_hip_mfma_splitk", Launcher::SplitK, MMH_KERNEL_MFMA},
+    {MMH_KERNEL_MFMA_SPLITK_128X64, "MMult_hip_mfma_splitk_128x64", Launcher::SplitK, MMH_KERNEL_MFMA_128X64},
+#ifdef MMH_AB_BUILD
+#include "ab_kernels.inc"   // tools/ab/: the A/B ids and the tile families that were measured and lost
+#endif
+};
+// id -> row (ids are small numbers: MMH_KERNEL_* and the tools build's stay below 128), so that the launch path's
+// look-ups cost an index; -1: no such id.  Building it checks the catalogue: no id twice, every fall-back a
+// register-staged id.
+constexpr int kMaxKernelId = 127;
+struct KernelIndex {
+  signed char row[kMaxKernelId + 1];
+  bool ok;
+};
+constexpr KernelIndex kernel_index() {
+  KernelIndex ix{};
+  ix.ok = true;
+  for (signed char &r : ix.row) r = -1;
+  int n = 0;
+  for (const KernelRow &r : kKernels) {
+    if (r.id < 0 || r.id > kMaxKernelId || ix.row[r.id] >= 0) ix.ok = false;
+    else ix.row[r.id] = (signed char)n;
+    ++n;
+  }
+  for (const KernelRow &r : kKernels)
+    if (r.fallback >= 0 && (ix.row[r.fallback] < 0 || kKernels[ix.row[r.fallback]].launcher != Launcher::Reg)) ix.ok = false;
+  return ix;
+}
+constexpr KernelIndex kKernelIndex = kernel_index();
+static_assert(kKernelIndex.ok, "kKernels: an id twice or out of range, or a fall-back that is no register-staged id");
 }  // namespace
+
+const KernelRow *mmh::kernel_row(int kernel) {
+  if (kernel < 0 || kernel > kMaxKernelId || kKernelIndex.row[kernel] < 0) return nullptr;
+  return &kKernels[kKernelIndex.row[kernel]];
+}
 
 extern "C" {
 
@@ -264,109 +331,16 @@ int mmh_get_kernel(mmh_handle_t h, int *kernel) {
 }
 
 const char *mmh_kernel_name(int kernel) {
-  switch (kernel) {
-    case MMH_KERNEL_AUTO: return "MMult_hip_auto";
-    case MMH_KERNEL_VALU: return "MMult_hip_valu";
-    case MMH_KERNEL_VALU_128X128: return "MMult_hip_valu_128x128";
-    case MMH_KERNEL_VALU_64X64: return "MMult_hip_valu_64x64";
-    case MMH_KERNEL_VALU_128X64: return "MMult_hip_valu_128x64";
-    case MMH_KERNEL_MFMA: return "MMult_hip_mfma";
-    case MMH_KERNEL_MFMA_256: return "MMult_hip_mfma256";
-    case MMH_KERNEL_NAIVE: return "MMult_hip_naive";
-    case MMH_KERNEL_MFMA_SIMPLE: return "MMult_hip_mfma_simple";
-    case MMH_KERNEL_MFMA_PIPE: return "MMult_hip_mfma_pipe";
-    case MMH_KERNEL_MFMA_TILES: return "MMult_hip_mfma_tiles";
-    case MMH_KERNEL_MFMA_128X64: return "MMult_hip_mfma_128x64";
-    case MMH_KERNEL_MFMA_64X64: return "MMult_hip_mfma_64x64";
-    case MMH_KERNEL_MFMA_256X256: return "MMult_hip_mfma_256x256";
-    case MMH_KERNEL_MFMA_64X64_DMA: return "MMult_hip_mfma_64x64_dma";
-    case MMH_KERNEL_MFMA_128X64_DMA: return "MMult_hip_mfma_128x64_dma";
-    case MMH_KERNEL_MFMA_128X128_DMA: return "MMult_hip_mfma_128x128_dma";
-    case MMH_KERNEL_MFMA_64X64_DMA5: return "MMult_hip_mfma_64x64_dma5";
-    case MMH_KERNEL_MFMA_128X64_DMA5: return "MMult_hip_mfma_128x64_dma5";
-    case MMH_KERNEL_MFMA_128X128_DMA5: return "MMult_hip_mfma_128x128_dma5";
-    case MMH_KERNEL_MFMA_96X96_DMA5: return "MMult_hip_mfma_96x96_dma5";
-    case MMH_KERNEL_MFMA_96X64_DMA5: return "MMult_hip_mfma_96x64_dma5";
-    case MMH_KERNEL_MFMA_160X160_DMA5: return "MMult_hip_mfma_160x160_dma5";
-    case MMH_KERNEL_MFMA_SPLITK: return "MMult_hip_mfma_splitk";
-    case MMH_KERNEL_MFMA_SPLITK_128X64: return "MMult_hip_mfma_splitk_128x64";
-#ifdef MMH_AB_BUILD
-    case MMH_KERNEL_MFMA32_64X64_DMA: return "MMult_hip_mfma32_64x64_dma";
-    case MMH_KERNEL_MFMA32_128X64_DMA: return "MMult_hip_mfma32_128x64_dma";
-    case MMH_KERNEL_MFMA32_64X128_DMA: return "MMult_hip_mfma32_64x128_dma";
-    case MMH_KERNEL_MFMA32_128X128_DMA: return "MMult_hip_mfma32_128x128_dma";
-    case MMH_KERNEL_MFMA32B_128X64_DMA: return "MMult_hip_mfma32b_128x64_dma";
-    case MMH_KERNEL_MFMA32B_64X128_DMA: return "MMult_hip_mfma32b_64x128_dma";
-    case MMH_KERNEL_MFMA32B_128X128_DMA: return "MMult_hip_mfma32b_128x128_dma";
-    case 19: return "exp_dma_b";
-    case 16: return "cadence_3";
-    case 17: return "cadence_4";
-    case 18: return "cadence_1";
-    case 32: return "ablate_no_gload";
-    case 33: return "ablate_no_gload_no_ldswrite";
-    case 34: return "ablate_no_gload_no_ldswrite_no_barrier";
-    case 35: return "ablate_mfma_only";
-    case 21: return "ablate256_no_gload";
-    case 22: return "ablate256_no_gload_no_ldswrite";
-    case 23: return "ablate256_no_gload_no_ldswrite_no_barrier";
-    case 24: return "ablate256_mfma_only";
-    case 36: return "ablate128x64_hot_loads";
-    case 37: return "ablate128x64_no_gload";
-    case 38: return "ablate128x64_no_gload_no_ldswrite";
-    case 39: return "ablate128x64_no_gload_no_ldswrite_no_barrier";
-    case 40: return "ablate128x64_mfma_only";
-    case 41: return "ablate64x64_no_gload";
-    case 42: return "ablate64x64_no_gload_no_ldswrite";
-    case 43: return "ablate64x64_no_gload_no_ldswrite_no_barrier";
-    case 44: return "ablate64x64_mfma_only";
-    case 45: return "exp_dma_64x64_8waves";
-    case 46: return "exp_dma_128x64_8waves";
-    case 47: return "exp_dma_128x128_8waves";
-    case 52: return "abl32_128x64_no_swap";
-    case 53: return "abl32_128x64_no_dma";
-    case 54: return "abl32_128x64_no_a_reads";
-    case 55: return "abl32_128x64_mfma_only";
-    case 56: return "abl32_64x64_no_swap";
-    case 57: return "abl32_64x64_no_dma";
-    case 58: return "abl32_64x64_no_a_reads";
-    case 59: return "abl32_64x64_mfma_only";
-    case 64: return "exp5_64x64_l1d2";
-    case 65: return "exp5_64x64_ring6";
-    case 66: return "exp5_64x64_ring4";
-    case 67: return "exp5_64x64_ring6_l4";
-    case 68: return "exp5_128x64_l1d2";
-    case 69: return "exp5_128x64_ring4";
-    case 72: return "exp5_128x128_l1d2";
-    case 79: return "exp5_160x96_l1d2";
-    case 80: return "exp5_160x160_l1d2";
-    case 82: return "exp5_160x160_l2";
-    case 83: return "exp5_96x64_l4";
-    case 84: return "exp5_96x64_l2";
-    case 85: return "exp5_64x96_l2";
-    case 87: return "k1w_128x128_b3l2a4";
-    case 89: return "k1w_64x64_a2";
-    case 91: return "k1w_64x128";
-    case 92: return "k1w_64x64_a4";
-    case 93: return "k1w_128x128_b2l4a2";
-    case 94: return "k1w_128x128_b2l1a2";
-    case 95: return "exp5_160x160_rs0";
-    case 96: return "exp5_128x128_rs0";
-    case 97: return "exp5_128x64_rs0";
-    case 98: return "exp5_64x64_rs0";
-    case 99: return "exp5_96x96_rs0";
-#endif
-    default: return nullptr;
-  }
+  const KernelRow *r = kernel_row(kernel);
+  return r ? r->name : nullptr;
 }
 
 // the inverse of mmh_kernel_name, on the short names the harness, MMULT_KERNEL and the Python API use
 int mmh_kernel_id(const char *name) {
   if (!name) return -1;
   const std::string want = std::string("MMult_hip_") + name;
-  for (int id = 0; id < 128; ++id) {
-    const char *s = mmh_kernel_name(id);
-    if (s && (want == s || strcmp(name, s) == 0)) return id;   // (the A/B ids of the tools build carry bare names)
-  }
+  for (const KernelRow &r : kKernels)
+    if (want == r.name || strcmp(name, r.name) == 0) return r.id;   // (the A/B ids of the tools build carry bare names)
   return -1;
 }
 

@@ -33,18 +33,6 @@
 #include "ab_build.hpp"
 #include "../../include/mmult_hip.h"
 
-// Kernel ids of the tools build (libmmult_hip_ab.so) that name whole tile families; the product library neither
-// defines nor accepts them.  K2M (tools/ab/sgemm_dma32.hpp, round 4): the LDS-DMA ring feeding v_mfma_f32_32x32x2_f32 -- 64-cycle
-// matrix instructions, one conflict-free ds_read_b128 + two v_permlane32_swap per eight k's of A -- and the two-block
-// form v_mfma_f32_32x32x1_2b_f32; measured slower than the 16x16x4 tiles (profiles/r04_notes.md).
-#define MMH_KERNEL_MFMA32_64X64_DMA 48
-#define MMH_KERNEL_MFMA32_128X64_DMA 49
-#define MMH_KERNEL_MFMA32_128X128_DMA 50
-#define MMH_KERNEL_MFMA32_64X128_DMA 51
-#define MMH_KERNEL_MFMA32B_128X64_DMA 60
-#define MMH_KERNEL_MFMA32B_64X128_DMA 61
-#define MMH_KERNEL_MFMA32B_128X128_DMA 62
-
 namespace mmh {
 
 // ---- error text (thread-local, state.hip) ----
@@ -222,7 +210,24 @@ inline bool window_ok(int BM, int BN, const GemmArgs &g) {
 // ta / tb: the operand layouts of mmh_sgemm_op (A stored k x m needs lda >= m, B stored n x k ldb >= k)
 int check_gemm_args(int m, int n, int k, const void *A, int lda, const void *B, int ldb, const void *C, int ldc, int ta = 0,
                     int tb = 0);
-bool known_kernel(int kernel);
+
+// ---- the catalogue of kernel ids (abi.hip) ----
+// One row per id the library accepts: the name mmh_kernel_name returns, the family whose launcher takes the id (sgemm_on,
+// policy.hip) and the register-staged tile (an id of reg_tiles) that takes the shape when that launcher answers 1 = "does
+// not qualify" (-1: none -- the launcher's answer is the call's).  The tools build appends tools/ab/ab_kernels.inc.
+enum class Launcher { Auto, Valu, Naive, Reg, SplitK, K2L, K2W, K2M /* tools/ab/launch_dma32.hip */ };
+struct KernelRow {
+  int id;
+  const char *name;
+  Launcher launcher;
+  int fallback;
+};
+const KernelRow *kernel_row(int kernel);   // NULL: no such id in this build
+inline bool known_kernel(int kernel) { return kernel_row(kernel) != nullptr; }
+inline bool is_family(int kernel, Launcher l) {
+  const KernelRow *r = kernel_row(kernel);
+  return r && r->launcher == l;
+}
 
 // ---- stream-K workspaces (state.hip) ----
 // the stream's own hand-off words (>= tiles of them, all zero) and partial-tile slots (>= parts_bytes)
@@ -245,9 +250,9 @@ int auto_plan_op(int ta, int tb, int m, int n, int k, int lda, int ldb, int ldc,
 // launch_reg.hip: `kernel` is one of the register-staged ids (MFMA, MFMA_TILES, MFMA_256, MFMA_256X256, MFMA_128X64,
 // MFMA_64X64, MFMA_SIMPLE, MFMA_PIPE, the split-K ids and, in the A/B build, the ablation ids)
 int launch_reg(mmh_context *ctx, int kernel, const GemmArgs &g);
-int launch_reg_splitk(mmh_context *ctx, int tile /* 128 or 64 = BN */, int S, const GemmArgs &g);
+int launch_reg_splitk(mmh_context *ctx, int tile /* MMH_KERNEL_MFMA or MMH_KERNEL_MFMA_128X64 */, int S, const GemmArgs &g);
 int warm_reg(mmh_context *ctx, float *scratch, hipStream_t s);
-// launch_dma.hip: tile = MMH_KERNEL_MFMA_{64X64,128X64,128X128}_DMA; returns 1 when the shape does not qualify
+// launch_dma.hip: the tiles of k2l_tiles; returns 1 when the shape does not qualify
 int launch_dma(mmh_context *ctx, int kernel, const GemmArgs &g);
 bool dma_shape_ok(const mmh_context *ctx, int kernel, const GemmArgs &g);
 int warm_dma(mmh_context *ctx, float *scratch, hipStream_t s);
@@ -272,20 +277,13 @@ inline bool dma5_rim_dims(int m, int n, int *r_m, int *r_n) {
   if (r_n) *r_n = b;
   return a > 0 || b > 0;
 }
-// The K2W tiles (sgemm_dma5.hpp) of the product's kernel ids -- the one place an id meets its configuration: BM BN, wave
-// tile WTM x WTN MFMA blocks, NBUF ring buffers, NL loader waves, fragments D k-steps ahead, RS the fragment reads' form;
-// SK: a stream-K form (the whole-round tiles run one workgroup per tile only); OPS: op and batched forms.
-// (Loader counts as measured, profiles/r04_notes.md: one loader wave on a consumer's SIMD holds that consumer back -- and
-// the workgroup, at every barrier; two or four spread the pieces -- 128x128 under chained stream-K at N = 2560: 127.9 /
-// 144.4 / 145.2 TFLOP/s with 1 / 2 / 4 loaders, 128x64 at N = 2432: 139.5 / 139.7 / 143.5.)
-template <int ID_, int BM_, int BN_, int WTM_, int WTN_, int NBUF_, int NL_, int D_, bool SK_, bool OPS_, int RS_ = 1>
-struct K2wTile {
-  static constexpr int ID = ID_, BM = BM_, BN = BN_, WTM = WTM_, WTN = WTN_, NBUF = NBUF_, NL = NL_, D = D_, RS = RS_;
-  static constexpr bool SK = SK_, OPS = OPS_;
-};
+// ---- the tile tables: the one place a kernel id meets its template arguments ----
+// A table is a list of tile types, each with a static ID; the launchers, the warm-up and the plan code reach a tile's
+// configuration through with() / each() and never spell it out again.  A new tile of a family is one row here, one row in
+// the catalogue (abi.hip) and its MMH_KERNEL_* number.
 template <class... Tile>
-struct K2wTiles {
-  // f(Tile{}) for the tile of `kernel`; `none` when it is no K2W id
+struct TileTable {
+  // f(Tile{}) for the tile of `kernel`; `none` when the table has no such id
   template <class F>
   static int with(int kernel, F &&f, int none) {
     int r = none;
@@ -300,7 +298,52 @@ struct K2wTiles {
     return rc;
   }
 };
-using k2w_tiles = K2wTiles<
+
+// The register-staged tiles (sgemm_mfma.hpp) that have a stream-K form and are warmed: what MMH_KERNEL_AUTO falls back to
+// and what the LDS-DMA ids run a shape on that they do not take.  Wave tile WTM x WTN MFMA blocks, KB-deep K-slices.
+template <int ID_, int BM_, int BN_, int WTN_, int WTM_, int KB_>
+struct RegTile {
+  static constexpr int ID = ID_, BM = BM_, BN = BN_, WTN = WTN_, WTM = WTM_, KB = KB_;
+};
+using reg_tiles = TileTable<
+    //      id                       BM   BN  WTN WTM KB
+    RegTile<MMH_KERNEL_MFMA,         128, 128, 4, 4, 32>,
+    RegTile<MMH_KERNEL_MFMA_256X256, 256, 256, 4, 8, 32>,    // 8 waves of 128x64 (one workgroup per CU)
+    RegTile<MMH_KERNEL_MFMA_128X64,  128, 64,  2, 4, 32>,    // 4 waves of 64x32
+    RegTile<MMH_KERNEL_MFMA_64X64,   64,  64,  2, 2, 128>>;  // 4 waves of 32x32, 128-deep K-slices
+// the tiles an m x n shape takes of a register-staged tile (0: no such tile)
+inline long reg_tile_count(int kernel, int m, int n) {
+  long tiles = 0;
+  reg_tiles::with(kernel, [&](auto t) {
+    tiles = (long)((m + t.BM - 1) / t.BM) * ((n + t.BN - 1) / t.BN);
+    return 0;
+  }, 0);
+  return tiles;
+}
+
+// The K2L tiles (sgemm_dma.hpp): 4 waves, NBUF ring buffers of KB-deep K-slices filled by the consumers' own LDS-DMA.
+template <int ID_, int BM_, int BN_, int KB_, int WTM_, int WTN_, int NBUF_>
+struct K2lTile {
+  static constexpr int ID = ID_, BM = BM_, BN = BN_, KB = KB_, WTM = WTM_, WTN = WTN_, NBUF = NBUF_;
+};
+using k2l_tiles = TileTable<
+    //      id                           BM   BN  KB WTM WTN NBUF
+    K2lTile<MMH_KERNEL_MFMA_64X64_DMA,   64,  64,  32, 2, 2, 3>,    // 4 waves of 32x32, 48 KiB ring: 3 workgroups per CU
+    K2lTile<MMH_KERNEL_MFMA_128X64_DMA,  128, 64,  32, 4, 2, 3>,    // 4 waves of 64x32, 72 KiB ring: 2 workgroups per CU
+    K2lTile<MMH_KERNEL_MFMA_128X128_DMA, 128, 128, 32, 4, 4, 3>>;   // 4 waves of 64x64, 96 KiB ring
+
+// The K2W tiles (sgemm_dma5.hpp) of the product's kernel ids: BM BN, wave
+// tile WTM x WTN MFMA blocks, NBUF ring buffers, NL loader waves, fragments D k-steps ahead, RS the fragment reads' form;
+// SK: a stream-K form (the whole-round tiles run one workgroup per tile only); OPS: op and batched forms.
+// (Loader counts as measured, profiles/r04_notes.md: one loader wave on a consumer's SIMD holds that consumer back -- and
+// the workgroup, at every barrier; two or four spread the pieces -- 128x128 under chained stream-K at N = 2560: 127.9 /
+// 144.4 / 145.2 TFLOP/s with 1 / 2 / 4 loaders, 128x64 at N = 2432: 139.5 / 139.7 / 143.5.)
+template <int ID_, int BM_, int BN_, int WTM_, int WTN_, int NBUF_, int NL_, int D_, bool SK_, bool OPS_, int RS_ = 1>
+struct K2wTile {
+  static constexpr int ID = ID_, BM = BM_, BN = BN_, WTM = WTM_, WTN = WTN_, NBUF = NBUF_, NL = NL_, D = D_, RS = RS_;
+  static constexpr bool SK = SK_, OPS = OPS_;
+};
+using k2w_tiles = TileTable<
     //      id                            BM   BN WTM WTN NBUF NL D  SK     OPS
     K2wTile<MMH_KERNEL_MFMA_64X64_DMA5,   64,  64, 2, 2, 3, 2, 2, true,  true>,    // 32x32 consumers + two loaders, 48 KiB ring: 3 per CU
     K2wTile<MMH_KERNEL_MFMA_128X64_DMA5,  128, 64, 4, 2, 3, 4, 2, true,  true>,    // 64x32 consumers, 72 KiB ring: 2 per CU

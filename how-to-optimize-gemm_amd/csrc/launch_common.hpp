@@ -1,5 +1,5 @@
-// launch_common.hpp -- what the kernel-launching translation units (launch_reg.hip, launch_dma.hip) share:
-// the > 64 KiB LDS opt-in, per-kernel residency, and the persistent stream-K launch (sgemm_mfma.hpp, K2p).
+// launch_common.hpp -- what the kernel-launching translation units (launch_reg.hip, launch_dma.hip, launch_dma5.hpp) share:
+// the > 64 KiB LDS opt-in, per-kernel residency, the persistent stream-K launch (sgemm_mfma.hpp, K2p), one-tile warm-ups.
 #pragma once
 #include <algorithm>
 
@@ -135,6 +135,16 @@ int launch_streamk(mmh_context *ctx, K kern, K occ_kern, int BM, int BN, int KB,
              order ? ", phase-ordered" : "");
     set_last_launch(buf);
   }
+  return MMH_OK;
+}
+
+// One-tile warm-up of a plain instantiation, on scratch: code object loaded, LDS opted into.
+template <typename K>
+int warm_plain_kernel(K kern, int BM, int BN, int KB, int threads, size_t lds, float *scratch, hipStream_t s) {
+  const int ok = allow_big_lds(kern, lds);
+  if (ok != MMH_OK) return ok;
+  hipLaunchKernelGGL(kern, dim3(1), dim3(threads), lds, s, BM, BN, KB, scratch, KB, scratch, BN, scratch + 65536, BN, 0, 1, 1);
+  HIP_TRY(hipGetLastError());
   return MMH_OK;
 }
 

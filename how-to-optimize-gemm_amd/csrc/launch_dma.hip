@@ -1,4 +1,4 @@
-// launch_dma.hip -- launchers of the LDS-DMA tiles (sgemm_dma.hpp, K2L): 64x64, 128x64 and 128x128, each as one
+// launch_dma.hip -- launchers of the LDS-DMA tiles (sgemm_dma.hpp, K2L; k2l_tiles, internal.hpp): 64x64, 128x64 and 128x128, each as one
 // workgroup per tile or as the persistent stream-K form, each in a whole-tile (round 2) and a guarded (EDGE,
 // round 3: any m, n, k, 4-byte aligned operands) instantiation.  Part of libmmult_hip.so (see internal.hpp).
 #include "launch_common.hpp"
@@ -12,8 +12,7 @@ namespace {
 
 // Which instantiation a shape runs: 0 = whole tiles, 16-byte aligned (the unguarded kernel), 1 = guarded,
 // -1 = not on this family (descriptor window, or the guarded form is switched off / cannot take the rows).
-template <int BM, int BN, int KB>
-int dma_form(const mmh_context *ctx, const GemmArgs &g) {
+int dma_form(const mmh_context *ctx, int BM, int BN, int KB, const GemmArgs &g) {
   if (!window_ok(BM, BN, g.k, g.lda, g.ldb)) return -1;
   if (fast_shape(BM, BN, KB, g)) return 0;
   if (!ctx || !ctx->dma_edge) return -1;
@@ -22,10 +21,12 @@ int dma_form(const mmh_context *ctx, const GemmArgs &g) {
   return 1;
 }
 
-template <int BM, int BN, int KB, int WTM, int WTN, int NBUF>
+// One launch of tile K (a K2lTile, internal.hpp).  Returns MMH_OK, an error, or 1: the shape does not qualify.
+template <class K>
 int launch_dma_tile(mmh_context *ctx, const GemmArgs &g) {
+  constexpr int BM = K::BM, BN = K::BN, KB = K::KB, WTM = K::WTM, WTN = K::WTN, NBUF = K::NBUF;
   using T = DmaTile<BM, BN, KB, WTM, WTN, NBUF>;
-  const int form = dma_form<BM, BN, KB>(ctx, g);
+  const int form = dma_form(ctx, BM, BN, KB, g);
   if (form < 0) return 1;
   const bool edge = form == 1;
   char what[224];
@@ -89,18 +90,12 @@ int launch_dma_tile(mmh_context *ctx, const GemmArgs &g) {
   return MMH_OK;
 }
 
-template <int BM, int BN, int KB, int WTM, int WTN, int NBUF>
+template <class K>
 int warm_dma_tile(mmh_context *ctx, float *scratch, hipStream_t s) {
+  constexpr int BM = K::BM, BN = K::BN, KB = K::KB, WTM = K::WTM, WTN = K::WTN, NBUF = K::NBUF;
   using T = DmaTile<BM, BN, KB, WTM, WTN, NBUF>;
   int rc;
-  auto plain = [&](auto kern) {
-    const int ok = allow_big_lds(kern, T::LDS_BYTES);
-    if (ok != MMH_OK) return ok;
-    hipLaunchKernelGGL(kern, dim3(1), dim3(T::THREADS), T::LDS_BYTES, s, BM, BN, KB, scratch, KB, scratch, BN, scratch + 65536, BN, 0,
-                       1, 1);
-    HIP_TRY(hipGetLastError());
-    return (int)MMH_OK;
-  };
+  auto plain = [&](auto kern) { return warm_plain_kernel(kern, BM, BN, KB, T::THREADS, T::LDS_BYTES, scratch, s); };
   if ((rc = plain(sgemm_mfma_dma_kernel<BM, BN, KB, WTM, WTN, NBUF, false>)) != MMH_OK) return rc;
   if ((rc = plain(sgemm_mfma_dma_kernel<BM, BN, KB, WTM, WTN, NBUF, true>)) != MMH_OK) return rc;
 #ifdef MMH_AB_BUILD
@@ -127,39 +122,27 @@ int warm_dma_tile(mmh_context *ctx, float *scratch, hipStream_t s) {
 }  // namespace
 
 bool dma_shape_ok(const mmh_context *ctx, int kernel, const GemmArgs &g) {
-  switch (kernel) {
-    case MMH_KERNEL_MFMA_64X64_DMA: return dma_form<64, 64, 32>(ctx, g) >= 0;
-    case MMH_KERNEL_MFMA_128X64_DMA: return dma_form<128, 64, 32>(ctx, g) >= 0;
-    case MMH_KERNEL_MFMA_128X128_DMA: return dma_form<128, 128, 32>(ctx, g) >= 0;
-    default: return false;
-  }
+  return k2l_tiles::with(kernel, [&](auto t) { return (int)(dma_form(ctx, t.BM, t.BN, t.KB, g) >= 0); }, 0);
 }
 
 int launch_dma(mmh_context *ctx, int kernel, const GemmArgs &g) {
-  switch (kernel) {
-    case MMH_KERNEL_MFMA_64X64_DMA:   // 64x64 tile, 4 waves of 32x32, 48 KiB ring: 3 workgroups per CU
-      return launch_dma_tile<64, 64, 32, 2, 2, 3>(ctx, g);
-    case MMH_KERNEL_MFMA_128X64_DMA:  // 128x64 tile, 4 waves of 64x32, 72 KiB ring: 2 workgroups per CU
-      return launch_dma_tile<128, 64, 32, 4, 2, 3>(ctx, g);
-    case MMH_KERNEL_MFMA_128X128_DMA: // 128x128 tile, 4 waves of 64x64, 96 KiB ring
-      return launch_dma_tile<128, 128, 32, 4, 4, 3>(ctx, g);
+  constexpr int kNone = 1 << 30;
+  const int rc = k2l_tiles::with(kernel, [&](auto t) { return launch_dma_tile<decltype(t)>(ctx, g); }, kNone);
+  if (rc != kNone) return rc;
 #ifdef MMH_AB_BUILD
-    // A/B (valid results): the LDS-DMA tiles as EIGHT waves -- two waves per SIMD from one workgroup
-    case 45: return launch_dma_tile<64, 64, 32, 1, 2, 3>(ctx, g) <= 0 ? MMH_OK : MMH_ERR_UNSUPPORTED;
-    case 46: return launch_dma_tile<128, 64, 32, 2, 2, 3>(ctx, g) <= 0 ? MMH_OK : MMH_ERR_UNSUPPORTED;
-    case 47: return launch_dma_tile<128, 128, 32, 4, 2, 3>(ctx, g) <= 0 ? MMH_OK : MMH_ERR_UNSUPPORTED;
-#endif
-    default:
-      set_last_error("unknown kernel variant");
-      return MMH_ERR_INVALID_ARG;
+  auto ab = [&](auto t) { return launch_dma_tile<decltype(t)>(ctx, g) <= 0 ? MMH_OK : MMH_ERR_UNSUPPORTED; };
+  switch (kernel) {   // A/B (valid results): the LDS-DMA tiles as EIGHT waves -- two waves per SIMD from one workgroup
+    case 45: return ab(K2lTile<45, 64, 64, 32, 1, 2, 3>{});
+    case 46: return ab(K2lTile<46, 128, 64, 32, 2, 2, 3>{});
+    case 47: return ab(K2lTile<47, 128, 128, 32, 4, 2, 3>{});
   }
+#endif
+  set_last_error("unknown kernel variant");
+  return MMH_ERR_INVALID_ARG;
 }
 
 int warm_dma(mmh_context *ctx, float *scratch, hipStream_t s) {
-  int rc;
-  if ((rc = warm_dma_tile<64, 64, 32, 2, 2, 3>(ctx, scratch, s)) != MMH_OK) return rc;
-  if ((rc = warm_dma_tile<128, 64, 32, 4, 2, 3>(ctx, scratch, s)) != MMH_OK) return rc;
-  return warm_dma_tile<128, 128, 32, 4, 4, 3>(ctx, scratch, s);
+  return k2l_tiles::each([&](auto t) { return warm_dma_tile<decltype(t)>(ctx, scratch, s); });
 }
 
 #ifdef MMH_DMA_TIMELINE

@@ -16,14 +16,7 @@ int warm_dma5_tile(mmh_context *ctx, float *scratch, hipStream_t s) {
   constexpr int BM = K::BM, BN = K::BN, KB = 32, WTM = K::WTM, WTN = K::WTN, NBUF = K::NBUF, NL = K::NL, D = K::D;
   using T = Dma5Tile<BM, BN, KB, WTM, WTN, NBUF, NL>;
   int rc;
-  auto plain = [&](auto kern) {
-    const int ok = allow_big_lds(kern, T::LDS_BYTES);
-    if (ok != MMH_OK) return ok;
-    hipLaunchKernelGGL(kern, dim3(1), dim3(T::THREADS), T::LDS_BYTES, s, BM, BN, KB, scratch, KB, scratch, BN, scratch + 65536, BN, 0,
-                       1, 1);
-    HIP_TRY(hipGetLastError());
-    return (int)MMH_OK;
-  };
+  auto plain = [&](auto kern) { return warm_plain_kernel(kern, BM, BN, KB, T::THREADS, T::LDS_BYTES, scratch, s); };
   if ((rc = plain(sgemm_mfma_dma5_kernel<BM, BN, KB, WTM, WTN, NBUF, false, NL, D>)) != MMH_OK) return rc;
   if ((rc = plain(sgemm_mfma_dma5_kernel<BM, BN, KB, WTM, WTN, NBUF, true, NL, D>)) != MMH_OK) return rc;
   if constexpr (K::SK) {

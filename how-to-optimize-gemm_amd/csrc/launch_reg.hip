@@ -18,28 +18,26 @@ int launch_mfma(const GemmArgs &g) {
   constexpr size_t lds = lds_bytes(BM, BN, KB);
   dim3 grid((unsigned)(nbm * nbn)), block(threads);
   const bool win = window_ok(BM, BN, g.k, g.lda, g.ldb);
-#define MMH_LAUNCH(KERN)                                                                   \
-  do {                                                                                     \
-    auto kern = KERN;                                                                      \
-    const int ok = allow_big_lds(kern, lds);                                               \
-    if (ok != MMH_OK) return ok;                                                           \
-    hipLaunchKernelGGL(kern, grid, block, lds, g.s, g.m, g.n, g.k, g.A, g.lda, g.B, g.ldb, g.C, g.ldc, g.acc, nbm, nbn); \
-  } while (0)
+  auto launch = [&](auto kern) {
+    const int ok = allow_big_lds(kern, lds);
+    if (ok != MMH_OK) return ok;
+    hipLaunchKernelGGL(kern, grid, block, lds, g.s, g.m, g.n, g.k, g.A, g.lda, g.B, g.ldb, g.C, g.ldc, g.acc, nbm, nbn);
+    HIP_TRY(hipGetLastError());
+    return (int)MMH_OK;
+  };
+  int rc;
   if constexpr (SIMPLE) {
-    if (fast) MMH_LAUNCH((sgemm_mfma_simple_kernel<BM, BN, false>));
-    else      MMH_LAUNCH((sgemm_mfma_simple_kernel<BM, BN, true>));
+    rc = fast ? launch(sgemm_mfma_simple_kernel<BM, BN, false>) : launch(sgemm_mfma_simple_kernel<BM, BN, true>);
   } else if (!fast) {
     // guarded launch: buffer descriptors bound the reads (any alignment >= 4 B);
     // operands larger than the descriptor window use the per-element path
-    if (BUFLD && win) MMH_LAUNCH((sgemm_mfma_kernel<BM, BN, true, SCHED, 0, true, WTN, WTM, KB>));
-    else              MMH_LAUNCH((sgemm_mfma_kernel<BM, BN, true, SCHED, 0, false, WTN, WTM, KB>));
-  } else if (BUFLD && win) {
-    MMH_LAUNCH((sgemm_mfma_kernel<BM, BN, false, SCHED, ABL, BUFLD, WTN, WTM, KB>));
+    rc = BUFLD && win ? launch(sgemm_mfma_kernel<BM, BN, true, SCHED, 0, true, WTN, WTM, KB>)
+                      : launch(sgemm_mfma_kernel<BM, BN, true, SCHED, 0, false, WTN, WTM, KB>);
   } else {
-    MMH_LAUNCH((sgemm_mfma_kernel<BM, BN, false, SCHED, ABL, false, WTN, WTM, KB>));
+    rc = BUFLD && win ? launch(sgemm_mfma_kernel<BM, BN, false, SCHED, ABL, BUFLD, WTN, WTM, KB>)
+                      : launch(sgemm_mfma_kernel<BM, BN, false, SCHED, ABL, false, WTN, WTM, KB>);
   }
-#undef MMH_LAUNCH
-  HIP_TRY(hipGetLastError());
+  if (rc != MMH_OK) return rc;
   {
     char buf[160];
     snprintf(buf, sizeof buf, "%s<%d,%d> wave tile %dx%d, K-slice %d, %s%d workgroups of %d threads",
@@ -50,9 +48,10 @@ int launch_mfma(const GemmArgs &g) {
   return MMH_OK;
 }
 
-// persistent stream-K launch of the register-staged tile config <BM, BN, WTN>
-template <int BM, int BN, int WTN, int WTM = 4, int KB = BK>
+// persistent stream-K launch of the register-staged tile T (a RegTile of reg_tiles, internal.hpp)
+template <class T>
 int try_launch_streamk(mmh_context *ctx, const GemmArgs &g) {
+  constexpr int BM = T::BM, BN = T::BN, WTN = T::WTN, WTM = T::WTM, KB = T::KB;
   if (!ctx || !ctx->streamk) return 1;
   if (!window_ok(BM, BN, g.k, g.lda, g.ldb)) return 1;   // descriptor window
   // whole, 16-byte-aligned shapes run the unguarded kernel; everything else the guarded one (partial
@@ -107,23 +106,42 @@ int try_launch_splitk(mmh_context *ctx, int S, const GemmArgs &g) {
   return MMH_OK;
 }
 
-// one tile of a plain register-staged instantiation, on scratch: code object loaded, LDS opted into
-template <typename K>
-int warm_plain(K kern, int BM, int BN, int KB, int threads, size_t lds, float *scratch, hipStream_t s) {
-  const int ok = allow_big_lds(kern, lds);
-  if (ok != MMH_OK) return ok;
-  hipLaunchKernelGGL(kern, dim3(1), dim3(threads), lds, s, BM, BN, KB, scratch, KB, scratch, BN, scratch + 65536, BN, 0, 1, 1);
-  HIP_TRY(hipGetLastError());
-  return MMH_OK;
+// What MMH_KERNEL_AUTO can reach of tile T, run once on one tile of scratch (and the residency of its persistent
+// form asked for)
+template <class T>
+int warm_reg_tile(mmh_context *ctx, float *scratch, hipStream_t s) {
+  constexpr int BM = T::BM, BN = T::BN, WTN = T::WTN, WTM = T::WTM, KB = T::KB;
+  constexpr int threads = (BM / (16 * WTM)) * (BN / (16 * WTN)) * 64;
+  constexpr size_t lds = lds_bytes(BM, BN, KB);
+  int rc;
+  if ((rc = warm_plain_kernel(sgemm_mfma_kernel<BM, BN, false, 4, 0, true, WTN, WTM, KB>, BM, BN, KB, threads, lds, scratch, s)) != MMH_OK)
+    return rc;
+  if ((rc = warm_plain_kernel(sgemm_mfma_kernel<BM, BN, true, 4, 0, true, WTN, WTM, KB>, BM, BN, KB, threads, lds, scratch, s)) != MMH_OK)
+    return rc;
+  auto sk = sgemm_mfma_streamk_kernel<BM, BN, false, WTN, WTM, KB>;
+  auto ske = sgemm_mfma_streamk_kernel<BM, BN, true, WTN, WTM, KB>;
+  (void)resident_per_cu(ctx, ske, threads, lds);
+  if ((rc = warm_streamk_kernel(sk, BM, BN, KB, threads, 160 * 1024, scratch, s)) != MMH_OK) return rc;
+  return warm_streamk_kernel(ske, BM, BN, KB, threads, 160 * 1024, scratch, s);
 }
 
 }  // namespace
 
-int launch_reg_splitk(mmh_context *ctx, int bn, int S, const GemmArgs &g) {
-  return bn == 64 ? try_launch_splitk<128, 64, 2>(ctx, S, g) : try_launch_splitk<128, 128, 4>(ctx, S, g);
+int launch_reg_splitk(mmh_context *ctx, int tile, int S, const GemmArgs &g) {
+  return tile == MMH_KERNEL_MFMA_128X64 ? try_launch_splitk<128, 64, 2>(ctx, S, g) : try_launch_splitk<128, 128, 4>(ctx, S, g);
 }
 
 int launch_reg(mmh_context *ctx, int kernel, const GemmArgs &g) {
+  // the tiles of reg_tiles: ragged tile counts go to the persistent stream-K launch (same arithmetic, same bits);
+  // everything else is one workgroup per tile
+  constexpr int kNone = 1 << 30;
+  const int rc = reg_tiles::with(kernel, [&](auto t) {
+    using T = decltype(t);
+    const int sk = try_launch_streamk<T>(ctx, g);
+    if (sk <= 0) return sk;
+    return launch_mfma<T::BM, T::BN, false, 4, 0, true, T::WTN, T::WTM, T::KB>(g);
+  }, kNone);
+  if (rc != kNone) return rc;
   switch (kernel) {
     case MMH_KERNEL_MFMA_SIMPLE:
       return launch_mfma<128, 128, true>(g);
@@ -131,30 +149,8 @@ int launch_reg(mmh_context *ctx, int kernel, const GemmArgs &g) {
       return launch_mfma<128, 128, false, 0, 0, false>(g);
     case MMH_KERNEL_MFMA_256:
       return launch_mfma<256, 128>(g);
-    case MMH_KERNEL_MFMA: {
-      // ragged tile counts go to the persistent stream-K launch (same arithmetic,
-      // same bits); everything else is one workgroup per tile
-      const int sk = try_launch_streamk<128, 128, 4>(ctx, g);
-      if (sk <= 0) return sk;
-      return launch_mfma<128, 128>(g);
-    }
     case MMH_KERNEL_MFMA_TILES:   // K2 without stream-K (one workgroup per tile, always)
       return launch_mfma<128, 128>(g);
-    case MMH_KERNEL_MFMA_256X256: {  // 256x256 tile, 8 waves of 128x64 (one workgroup per CU)
-      const int sk = try_launch_streamk<256, 256, 4, 8, 32>(ctx, g);
-      if (sk <= 0) return sk;
-      return launch_mfma<256, 256, false, 4, 0, true, 4, 8, 32>(g);
-    }
-    case MMH_KERNEL_MFMA_64X64: {    // 64x64 tile, 4 waves of 32x32, 128-deep K-slices
-      const int sk = try_launch_streamk<64, 64, 2, 2, 128>(ctx, g);
-      if (sk <= 0) return sk;
-      return launch_mfma<64, 64, false, 4, 0, true, 2, 2, 128>(g);
-    }
-    case MMH_KERNEL_MFMA_128X64: {   // 128x64 tile, 4 waves of 64x32
-      const int sk = try_launch_streamk<128, 64, 2>(ctx, g);
-      if (sk <= 0) return sk;
-      return launch_mfma<128, 64, false, 4, 0, true, 2>(g);
-    }
 #ifdef MMH_AB_BUILD
     // ---- tools-only variants (libmmult_hip_ab.so); never part of the product library ----
     case 19: {  // A/B: B through LDS-DMA (buffer_load ... lds)
@@ -199,32 +195,9 @@ int launch_reg(mmh_context *ctx, int kernel, const GemmArgs &g) {
   }
 }
 
-// What MMH_KERNEL_AUTO can reach of this family, run once on one tile of scratch (and the residency of
-// the persistent forms asked for): a first real launch then loads nothing and sets no attribute.
+// a first real launch of what MMH_KERNEL_AUTO can reach of this family then loads nothing and sets no attribute
 int warm_reg(mmh_context *ctx, float *scratch, hipStream_t s) {
-  int rc;
-#define WARM_TILE(BM, BN, WTN, WTM, KB)                                                                                  \
-  do {                                                                                                                   \
-    constexpr int threads = (BM / (16 * WTM)) * (BN / (16 * WTN)) * 64;                                                  \
-    constexpr size_t lds = lds_bytes(BM, BN, KB);                                                                        \
-    if ((rc = warm_plain(sgemm_mfma_kernel<BM, BN, false, 4, 0, true, WTN, WTM, KB>, BM, BN, KB, threads, lds, scratch, \
-                         s)) != MMH_OK)                                                                                  \
-      return rc;                                                                                                         \
-    if ((rc = warm_plain(sgemm_mfma_kernel<BM, BN, true, 4, 0, true, WTN, WTM, KB>, BM, BN, KB, threads, lds, scratch,  \
-                         s)) != MMH_OK)                                                                                  \
-      return rc;                                                                                                         \
-    auto sk = sgemm_mfma_streamk_kernel<BM, BN, false, WTN, WTM, KB>;                                                    \
-    auto ske = sgemm_mfma_streamk_kernel<BM, BN, true, WTN, WTM, KB>;                                                    \
-    (void)resident_per_cu(ctx, ske, threads, lds);                                                                       \
-    if ((rc = warm_streamk_kernel(sk, BM, BN, KB, threads, 160 * 1024, scratch, s)) != MMH_OK) return rc;                \
-    if ((rc = warm_streamk_kernel(ske, BM, BN, KB, threads, 160 * 1024, scratch, s)) != MMH_OK) return rc;               \
-  } while (0)
-  WARM_TILE(128, 128, 4, 4, 32);
-  WARM_TILE(256, 256, 4, 8, 32);
-  WARM_TILE(128, 64, 2, 4, 32);
-  WARM_TILE(64, 64, 2, 2, 128);
-#undef WARM_TILE
-  return MMH_OK;
+  return reg_tiles::each([&](auto t) { return warm_reg_tile<decltype(t)>(ctx, scratch, s); });
 }
 
 }  // namespace mmh

@@ -41,12 +41,9 @@ struct Plan {
   int bm = 0, bn = 0;
 };
 
-bool is_k2w(int kernel) { return k2w_tiles::with(kernel, [](auto) { return 1; }, 0); }
+bool is_k2w(int kernel) { return is_family(kernel, Launcher::K2W); }
 // the tiles with op forms (launch_op.hip): where the NN table picks one of them the op plan is that very plan
 bool has_op_forms(int kernel) { return k2w_tiles::with(kernel, [](auto t) { return (int)t.OPS; }, 0); }
-bool is_k2l(int kernel) {
-  return kernel == MMH_KERNEL_MFMA_64X64_DMA || kernel == MMH_KERNEL_MFMA_128X64_DMA || kernel == MMH_KERNEL_MFMA_128X128_DMA;
-}
 
 // The price of a plain launch (one workgroup per tile) of `tiles` workgroups of the family, `full` of them not thin.
 // The thin edge tiles cost MMH_POLICY_THIN of a round where they add a tile to the fullest CU (N = 1025 against 1024 on
@@ -132,13 +129,39 @@ Plan auto_plan_for(const mmh_context *ctx, const GemmArgs &g) {
 // register-staged tiles, by how many tiles the shape has (rounds 1-2)
 int fallback_kernel(const mmh_context *ctx, const GemmArgs &g) {
   const long cus = ctx && ctx->cu_count > 0 ? ctx->cu_count : 256;
-  const long tiles128 = (long)((g.m + 127) / 128) * ((g.n + 127) / 128);
-  const long tiles128x64 = (long)((g.m + 127) / 128) * ((g.n + 63) / 64);
-  const long tiles256 = (long)((g.m + 255) / 256) * ((g.n + 255) / 256);
-  if (tiles256 >= cus) return MMH_KERNEL_MFMA_256X256;
-  if (tiles128x64 * 2 <= cus) return MMH_KERNEL_MFMA_64X64;
-  if (tiles128 * 10 < cus * 8) return MMH_KERNEL_MFMA_128X64;
+  if (reg_tile_count(MMH_KERNEL_MFMA_256X256, g.m, g.n) >= cus) return MMH_KERNEL_MFMA_256X256;
+  if (reg_tile_count(MMH_KERNEL_MFMA_128X64, g.m, g.n) * 2 <= cus) return MMH_KERNEL_MFMA_64X64;
+  if (reg_tile_count(MMH_KERNEL_MFMA, g.m, g.n) * 10 < cus * 8) return MMH_KERNEL_MFMA_128X64;
   return MMH_KERNEL_MFMA;
+}
+
+// split-K's "auto" part count: fill two workgroups per CU, keep >= 8 K-slices per part, at most 8 parts
+int splitk_auto_parts(long cus, long tiles, int k) {
+  const int S = (int)((2 * cus) / (tiles > 0 ? tiles : 1));
+  return std::min(std::min(S, k / (8 * kSliceK)), 8);
+}
+
+// The launcher of a catalogue row's family.  Split-K (K2s) runs on the row's fall-back tile, ctx->splitk parts (auto when
+// <= 1).  MMH_OK, an error, or 1: the shape does not qualify.
+int launch_family(mmh_context *ctx, const KernelRow &row, const GemmArgs &g) {
+  switch (row.launcher) {
+    case Launcher::Valu:
+    case Launcher::Naive: return launch_valu(ctx, row.id, g);
+    case Launcher::Reg: return launch_reg(ctx, row.id, g);
+    case Launcher::K2L: return launch_dma(ctx, row.id, g);
+    case Launcher::K2W: return launch_dma5(ctx, row.id, g);
+#ifdef MMH_AB_BUILD
+    case Launcher::K2M: return launch_dma32(ctx, row.id, g);
+#endif
+    case Launcher::SplitK: {
+      int S = ctx ? ctx->splitk : 0;
+      if (S <= 1) S = splitk_auto_parts(ctx && ctx->cu_count > 0 ? ctx->cu_count : 256, reg_tile_count(row.fallback, g.m, g.n), g.k);
+      return launch_reg_splitk(ctx, row.fallback, S, g);
+    }
+    default: break;   // (MMH_KERNEL_AUTO: resolved by the caller)
+  }
+  set_last_error("unknown kernel variant");
+  return MMH_ERR_INVALID_ARG;
 }
 }  // namespace
 
@@ -158,19 +181,15 @@ int sgemm_on(mmh_context *ctx, int kernel, int m, int n, int k, const float *dA,
   }
   const GemmArgs g{m, n, k, dA, lda, dB, ldb, dC, ldc, accumulate ? 1 : 0, s};
   const long cus = ctx && ctx->cu_count > 0 ? ctx->cu_count : 256;
-  const long tiles128 = (long)((m + 127) / 128) * ((n + 127) / 128);
   if (kernel == MMH_KERNEL_AUTO) {
+    const long tiles128 = reg_tile_count(MMH_KERNEL_MFMA, m, n);
     // OPT-IN split-K (default off: it gives up the one-chain-per-element bits, see sgemm_mfma.hpp K2s):
     // shapes with fewer 128x128 tiles than workgroup slots run their K ranges concurrently
-    const long tiles256 = (long)((m + 255) / 256) * ((n + 255) / 256);
-    if (ctx && ctx->splitk > 0 && tiles128 < cus && tiles256 < cus) {
+    if (ctx && ctx->splitk > 0 && tiles128 < cus && reg_tile_count(MMH_KERNEL_MFMA_256X256, m, n) < cus) {
       int S = ctx->splitk;
-      if (S == 1) {   // auto: fill two workgroups per CU, keep >= 8 K-slices per part
-        S = (int)((2 * cus) / (tiles128 > 0 ? tiles128 : 1));
-        S = std::min(std::min(S, k / (8 * kSliceK)), 8);
-      }
+      if (S == 1) S = splitk_auto_parts(cus, tiles128, k);
       if (S >= 2) {
-        const int sk = launch_reg_splitk(ctx, 128, S, g);
+        const int sk = launch_reg_splitk(ctx, MMH_KERNEL_MFMA, S, g);
         if (sk <= 0) return sk;
       }
     }
@@ -197,98 +216,19 @@ int sgemm_on(mmh_context *ctx, int kernel, int m, int n, int k, const float *dA,
       GemmArgs ga = g;
       ga.form = plan.form;
       ga.sk_w = plan.sk_w;
-      if (plan.kernel == MMH_KERNEL_MFMA_256X256) return launch_reg(ctx, plan.kernel, ga);
-      const int d = is_k2l(plan.kernel) ? launch_dma(ctx, plan.kernel, ga) : launch_dma5(ctx, plan.kernel, ga);
+      const int d = launch_family(ctx, *kernel_row(plan.kernel), ga);   // (refused: fallback_kernel's tile, not the row's)
       if (d <= 0) return d;
     }
     kernel = fallback_kernel(ctx, g);
   }
-  switch (kernel) {
-    case MMH_KERNEL_VALU:
-    case MMH_KERNEL_VALU_128X128:
-    case MMH_KERNEL_VALU_64X64:
-    case MMH_KERNEL_VALU_128X64:
-    case MMH_KERNEL_NAIVE:
-      return launch_valu(ctx, kernel, g);
-    case MMH_KERNEL_MFMA_64X64_DMA: {   // K2L; shapes it does not take run the register-staged tile of the same size
-      const int d = launch_dma(ctx, kernel, g);
-      return d <= 0 ? d : launch_reg(ctx, MMH_KERNEL_MFMA_64X64, g);
-    }
-    case MMH_KERNEL_MFMA_128X64_DMA: {
-      const int d = launch_dma(ctx, kernel, g);
-      return d <= 0 ? d : launch_reg(ctx, MMH_KERNEL_MFMA_128X64, g);
-    }
-    case MMH_KERNEL_MFMA_128X128_DMA: {
-      const int d = launch_dma(ctx, kernel, g);
-      return d <= 0 ? d : launch_reg(ctx, MMH_KERNEL_MFMA, g);
-    }
-    case MMH_KERNEL_MFMA_64X64_DMA5: {   // K2W; shapes it does not take run the register-staged tile of the same size
-      const int d = launch_dma5(ctx, kernel, g);
-      return d <= 0 ? d : launch_reg(ctx, MMH_KERNEL_MFMA_64X64, g);
-    }
-    case MMH_KERNEL_MFMA_128X64_DMA5: {
-      const int d = launch_dma5(ctx, kernel, g);
-      return d <= 0 ? d : launch_reg(ctx, MMH_KERNEL_MFMA_128X64, g);
-    }
-    case MMH_KERNEL_MFMA_128X128_DMA5:
-    case MMH_KERNEL_MFMA_96X64_DMA5:
-    case MMH_KERNEL_MFMA_160X160_DMA5:
-    case MMH_KERNEL_MFMA_96X96_DMA5: {
-      const int d = launch_dma5(ctx, kernel, g);
-      return d <= 0 ? d : launch_reg(ctx, MMH_KERNEL_MFMA, g);
-    }
-#ifdef MMH_AB_BUILD
-    case MMH_KERNEL_MFMA32_64X64_DMA: {   // K2M; shapes it does not take run the register-staged tile of the same size
-      const int d = launch_dma32(ctx, kernel, g);
-      return d <= 0 ? d : launch_reg(ctx, MMH_KERNEL_MFMA_64X64, g);
-    }
-    case MMH_KERNEL_MFMA32_128X64_DMA:
-    case MMH_KERNEL_MFMA32B_128X64_DMA:
-    case MMH_KERNEL_MFMA32B_64X128_DMA:
-    case MMH_KERNEL_MFMA32_64X128_DMA: {
-      const int d = launch_dma32(ctx, kernel, g);
-      return d <= 0 ? d : launch_reg(ctx, MMH_KERNEL_MFMA_128X64, g);
-    }
-    case MMH_KERNEL_MFMA32B_128X128_DMA:
-    case MMH_KERNEL_MFMA32_128X128_DMA: {
-      const int d = launch_dma32(ctx, kernel, g);
-      return d <= 0 ? d : launch_reg(ctx, MMH_KERNEL_MFMA, g);
-    }
-#endif
-    case MMH_KERNEL_MFMA_SPLITK: {   // K2s forced: 128x128 tiles, ctx->splitk parts (auto when <= 1)
-      int S = ctx ? ctx->splitk : 0;
-      if (S <= 1) {
-        S = (int)((2 * cus) / (tiles128 > 0 ? tiles128 : 1));
-        S = std::min(std::min(S, k / (8 * kSliceK)), 8);
-      }
-      const int sk = launch_reg_splitk(ctx, 128, S, g);
-      return sk <= 0 ? sk : launch_reg(ctx, MMH_KERNEL_MFMA, g);
-    }
-    case MMH_KERNEL_MFMA_SPLITK_128X64: {   // K2s on 128x64 tiles
-      int S = ctx ? ctx->splitk : 0;
-      const long tiles = (long)((m + 127) / 128) * ((n + 63) / 64);
-      if (S <= 1) {
-        S = (int)((2 * cus) / (tiles > 0 ? tiles : 1));
-        S = std::min(std::min(S, k / (8 * kSliceK)), 8);
-      }
-      const int sk = launch_reg_splitk(ctx, 64, S, g);
-      return sk <= 0 ? sk : launch_reg(ctx, MMH_KERNEL_MFMA_128X64, g);
-    }
-#ifdef MMH_AB_BUILD
-    case 45:
-    case 46:
-    case 47:
-      return launch_dma(ctx, kernel, g);
-    case 52: case 53: case 54: case 55: case 56: case 57: case 58: case 59:
-      return launch_dma32(ctx, kernel, g);
-    case 64: case 65: case 66: case 67: case 68: case 69: case 72: case 79: case 80: case 82: case 83: case 84: case 85: case 95: case 96: case 97: case 98: case 99:
-      return launch_dma5(ctx, kernel, g);
-    case 87: case 89: case 91: case 92: case 93: case 94:
-      return launch_valu(ctx, kernel, g);
-#endif
-    default:
-      return launch_reg(ctx, kernel, g);
+  // a forced kernel (or AUTO's fall-back): its family's launcher, else the register-staged tile its row names
+  const KernelRow *row = kernel_row(kernel);
+  if (!row) {
+    set_last_error("unknown kernel variant");
+    return MMH_ERR_INVALID_ARG;
   }
+  const int d = launch_family(ctx, *row, g);
+  return (d <= 0 || row->fallback < 0) ? d : launch_reg(ctx, row->fallback, g);
 }
 
 // mmh_sgemm_op.  NN is mmh_sgemm's own path.  The op forms run on the three K2W tiles that have them (AUTO: the table
@@ -393,6 +333,22 @@ int check_batch_args(int ta, int tb, int m, int n, int ldc, long long sA, long l
   if (batch > 1 && m > 0 && n > 0 && ldc >= n && sC < (long long)(m - 1) * ldc + n) return MMH_ERR_INVALID_ARG;   // C matrices overlap
   return MMH_OK;
 }
+
+// What the plan entry points (mmh_auto_plan*) run the launch path's own functions on: a default handle of `cu_count` CUs and
+// operands at addresses that are never dereferenced -- a 16-byte (or only 4-byte) aligned base each.  MMH_ERR_INVALID_ARG
+// for a shape mmh_sgemm_op refuses.
+int plan_inputs(int ta, int tb, int m, int n, int k, int lda, int ldb, int ldc, int base_align, int cu_count, mmh_context *ctx,
+                GemmArgs *g) {
+  if ((ta != MMH_OP_N && ta != MMH_OP_T) || (tb != MMH_OP_N && tb != MMH_OP_T)) return MMH_ERR_INVALID_ARG;
+  if (m <= 0 || n <= 0 || k <= 0 || lda < (ta ? m : k) || ldb < (tb ? k : n) || ldc < n) return MMH_ERR_INVALID_ARG;
+  ctx->cu_count = cu_count > 0 ? cu_count : 256;
+  const uintptr_t base = (uintptr_t)1 << 32, off = base_align >= 16 ? 0 : 4;
+  *g = GemmArgs{m, n, k, reinterpret_cast<const float *>(base + off), lda,
+                reinterpret_cast<const float *>(2 * base + off), ldb, reinterpret_cast<float *>(3 * base + off), ldc, 0, nullptr};
+  g->ta = ta;
+  g->tb = tb;
+  return MMH_OK;
+}
 }  // namespace
 
 // mmh_sgemm_batched: the argument rules, the empty cases, then the form (AUTO: batched_plan_for; 29 / 30 / 31: one
@@ -415,11 +371,7 @@ int sgemm_batched_on(mmh_context *ctx, int kernel, int ta, int tb, int m, int n,
   GemmArgs g{m, n, k, dA, lda, dB, ldb, dC, ldc, accumulate ? 1 : 0, s};
   g.ta = ta;
   g.tb = tb;
-  BatchArgs b;
-  b.sA = sA;
-  b.sB = sB;
-  b.sC = sC;
-  b.batch = batch;
+  const BatchArgs b{sA, sB, sC, batch};
   if (k == 0) {   // C = 0 (overwrite) or C unchanged (accumulate); the zeros go out through the naive kernel, matrix by matrix
     if (!accumulate) return launch_naive_batched(g, b);
     return MMH_OK;
@@ -454,20 +406,11 @@ int sgemm_batched_on(mmh_context *ctx, int kernel, int ta, int tb, int m, int n,
 // mmh_auto_plan_batched: batched_plan_for on a default handle, as host arithmetic
 int auto_plan_batched(int ta, int tb, int m, int n, int k, int lda, int ldb, int ldc, long long sA, long long sB, long long sC,
                       int batch, int base_align, int cu_count, int *kernel, int *form, long *workgroups) {
-  if (check_batch_args(ta, tb, m, n, ldc, sA, sB, sC, batch) != MMH_OK) return MMH_ERR_INVALID_ARG;
-  if (batch < 1 || m <= 0 || n <= 0 || k <= 0 || lda < (ta ? m : k) || ldb < (tb ? k : n) || ldc < n) return MMH_ERR_INVALID_ARG;
   mmh_context ctx;
-  ctx.cu_count = cu_count > 0 ? cu_count : 256;
-  const uintptr_t base = (uintptr_t)1 << 32, off = base_align >= 16 ? 0 : 4;
-  GemmArgs g{m, n, k, reinterpret_cast<const float *>(base + off), lda,
-             reinterpret_cast<const float *>(2 * base + off), ldb, reinterpret_cast<float *>(3 * base + off), ldc, 0, nullptr};
-  g.ta = ta;
-  g.tb = tb;
-  BatchArgs b;
-  b.sA = sA;
-  b.sB = sB;
-  b.sC = sC;
-  b.batch = batch;
+  GemmArgs g;
+  if (check_batch_args(ta, tb, m, n, ldc, sA, sB, sC, batch) != MMH_OK || batch < 1) return MMH_ERR_INVALID_ARG;
+  if (plan_inputs(ta, tb, m, n, k, lda, ldb, ldc, base_align, cu_count, &ctx, &g) != MMH_OK) return MMH_ERR_INVALID_ARG;
+  const BatchArgs b{sA, sB, sC, batch};
   const BatchPlan bp = batched_plan_for(&ctx, g, b);
   if (form) *form = bp.form;
   if (bp.form == MMH_BATCH_FORM_ONE_LAUNCH) {
@@ -497,31 +440,15 @@ int auto_plan(int m, int n, int k, int lda, int ldb, int ldc, int base_align, in
 // mmh_auto_plan_op: the same for C = op(A) op(B); an op form no tile with op forms takes is MMH_ERR_UNSUPPORTED
 int auto_plan_op(int ta, int tb, int m, int n, int k, int lda, int ldb, int ldc, int base_align, int cu_count, int *kernel,
                  long *tiles, int *streamk_grid) {
-  if ((ta != MMH_OP_N && ta != MMH_OP_T) || (tb != MMH_OP_N && tb != MMH_OP_T)) return MMH_ERR_INVALID_ARG;
-  if (m <= 0 || n <= 0 || k <= 0 || lda < (ta ? m : k) || ldb < (tb ? k : n) || ldc < n) return MMH_ERR_INVALID_ARG;
   mmh_context ctx;
-  ctx.cu_count = cu_count > 0 ? cu_count : 256;
-  // addresses that are never dereferenced: a 16-byte (or only 4-byte) aligned base for each operand
-  const uintptr_t base = (uintptr_t)1 << 32, off = base_align >= 16 ? 0 : 4;
-  GemmArgs g{m, n, k, reinterpret_cast<const float *>(base + off), lda,
-             reinterpret_cast<const float *>(2 * base + off), ldb, reinterpret_cast<float *>(3 * base + off), ldc, 0, nullptr};
-  g.ta = ta;
-  g.tb = tb;
+  GemmArgs g;
+  if (plan_inputs(ta, tb, m, n, k, lda, ldb, ldc, base_align, cu_count, &ctx, &g) != MMH_OK) return MMH_ERR_INVALID_ARG;
   const Plan plan = auto_plan_for(&ctx, g);
   if ((ta || tb) && plan.kernel < 0) return MMH_ERR_UNSUPPORTED;
   const int kern = plan.kernel >= 0 ? plan.kernel : fallback_kernel(&ctx, g);
-  int bm = plan.bm, bn = plan.bn;
-  if (plan.kernel < 0) {
-    switch (kern) {   // the register-staged fall-back tiles
-      case MMH_KERNEL_MFMA_256X256: bm = 256; bn = 256; break;
-      case MMH_KERNEL_MFMA: bm = 128; bn = 128; break;
-      case MMH_KERNEL_MFMA_128X64: bm = 128; bn = 64; break;
-      case MMH_KERNEL_MFMA_64X64: bm = 64; bn = 64; break;
-      default: break;
-    }
-  }
   if (kernel) *kernel = kern;
-  const long t = bm ? (long)((m + bm - 1) / bm) * ((n + bn - 1) / bn) : 0;
+  const long t = plan.kernel >= 0 ? (long)((m + plan.bm - 1) / plan.bm) * ((n + plan.bn - 1) / plan.bn)
+                                  : reg_tile_count(kern, m, n);   // (the register-staged fall-back tiles)
   if (tiles) *tiles = t;
   if (streamk_grid) {
     *streamk_grid = -1;

@@ -75,8 +75,6 @@ int check_gemm_args(int m, int n, int k, const void *A, int lda, const void *B, 
   return MMH_OK;
 }
 
-bool known_kernel(int kernel) { return mmh_kernel_name(kernel) != nullptr; }
-
 // ---------------------------------------------------------------------------------------------------
 // The hand-off workspaces (flags, partial tiles) exist once PER STREAM the handle has launched on.  Launches on
 // one stream are ordered by the stream; launches on different streams use different sets, so they may overlap and

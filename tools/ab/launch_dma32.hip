@@ -5,6 +5,7 @@
 // TOOLS build only: since round 5 it lives here, under tools/ab/, and only build_ab_library() compiles it, with
 // -I csrc for the product's headers.)
 #ifdef MMH_AB_BUILD
+#include "ab_kernels.hpp"
 #include "launch_common.hpp"
 #include "sgemm_dma32.hpp"
 #include "sgemm_mfma.hpp"   // streamk_body
@@ -62,14 +63,7 @@ template <int BM, int BN, int KB, int WM, int WN, int NBUF, int MB = 1>
 int warm_dma32_tile(mmh_context *ctx, float *scratch, hipStream_t s) {
   using T = Dma32Tile<BM, BN, KB, WM, WN, NBUF, MB>;
   int rc;
-  auto plain = [&](auto kern) {
-    const int ok = allow_big_lds(kern, T::LDS_BYTES);
-    if (ok != MMH_OK) return ok;
-    hipLaunchKernelGGL(kern, dim3(1), dim3(T::THREADS), T::LDS_BYTES, s, BM, BN, KB, scratch, KB, scratch, BN, scratch + 65536, BN, 0,
-                       1, 1);
-    HIP_TRY(hipGetLastError());
-    return (int)MMH_OK;
-  };
+  auto plain = [&](auto kern) { return warm_plain_kernel(kern, BM, BN, KB, T::THREADS, T::LDS_BYTES, scratch, s); };
   if ((rc = plain(sgemm_mfma32_dma_kernel<BM, BN, KB, WM, WN, NBUF, false, 0, MB>)) != MMH_OK) return rc;
   if ((rc = plain(sgemm_mfma32_dma_kernel<BM, BN, KB, WM, WN, NBUF, true, 0, MB>)) != MMH_OK) return rc;
   auto sk = sgemm_dma32_streamk_kernel<BM, BN, KB, WM, WN, NBUF, false, MB>;
