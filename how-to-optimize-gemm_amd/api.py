@@ -33,6 +33,8 @@ OPT_STREAMK_CHAIN = 12
 OPT_PERSIST = 13
 OPT_RIM5 = 14
 OP_N, OP_T = 0, 1   # mmh_sgemm_op's operand layouts (include/mmult_hip.h)
+BIAS_NONE, BIAS_COL, BIAS_ROW = 0, 1, 2   # mmh_sgemm_ex's MMH_BIAS_*: no bias, bias[j] (n floats), bias[i] (m floats)
+ACT_NONE, ACT_RELU = 0, 1                 # ... and MMH_ACT_*
 BATCH_FORMS = {1: "fold", 2: "one_launch", 3: "loop"}   # mmh_sgemm_batched's MMH_BATCH_FORM_*
 BATCHED_MAX_WORKGROUPS = 1 << 22   # MMH_BATCHED_MAX_WORKGROUPS: one batched launch holds at most this many workgroups
 KERNELS = {"auto": KERNEL_AUTO, "valu": KERNEL_VALU, "mfma": KERNEL_MFMA,
@@ -63,6 +65,7 @@ EXPORTS = [
     "mmh_probe_mfma_i8_sustained", "mmh_probe_hbm_copy", "mmh_probe_hbm_read", "mmh_probe_lds_read", "mmh_streamk_plan", "mmh_auto_plan",
     "mmh_sgemm_op", "mmh_time_sgemm_op", "mmh_auto_plan_op",
     "mmh_sgemm_batched", "mmh_time_sgemm_batched", "mmh_auto_plan_batched",
+    "mmh_sgemm_ex", "mmh_time_sgemm_ex", "mmh_auto_plan_ex",
 ]
 
 
@@ -118,6 +121,17 @@ def auto_plan_op(transa: int, transb: int, m: int, n: int, k: int, lda: int = 0,
     kern, grid, tiles = C.c_int(), C.c_int(), C.c_long()
     _check(lib().mmh_auto_plan_op(transa, transb, m, n, k, lda or (m if transa else k), ldb or (k if transb else n), ldc or n,
                                   base_align, cu_count, C.byref(kern), C.byref(tiles), C.byref(grid)), "mmh_auto_plan_op")
+    names = {v: name for name, v in KERNELS.items() if name != "mfma256"}
+    return names.get(kern.value, str(kern.value)), tiles.value, grid.value
+
+
+def auto_plan_ex(transa: int, transb: int, m: int, n: int, k: int, lda: int = 0, ldb: int = 0, ldc: int = 0, base_align: int = 16,
+                 cu_count: int = 256):
+    """auto_plan for mmh_sgemm_ex: planned like an op form -- one of the 64x64 / 128x64 / 128x128 LDS-DMA tiles -- for
+    (OP_N, OP_N) too."""
+    kern, tiles, grid = C.c_int(), C.c_long(), C.c_int()
+    _check(lib().mmh_auto_plan_ex(transa, transb, m, n, k, lda or (m if transa else k), ldb or (k if transb else n), ldc or n,
+                                  base_align, cu_count, C.byref(kern), C.byref(tiles), C.byref(grid)), "mmh_auto_plan_ex")
     names = {v: name for name, v in KERNELS.items() if name != "mfma256"}
     return names.get(kern.value, str(kern.value)), tiles.value, grid.value
 
@@ -211,6 +225,10 @@ def lib() -> C.CDLL:
     L.mmh_sgemm_op.argtypes = [vp, C.c_int, C.c_int] + gemm[1:] + [C.c_int, vp]
     L.mmh_time_sgemm_op.argtypes = [vp, C.c_int, C.c_int] + gemm[1:] + [C.c_int, C.c_int, vp, fp]
     L.mmh_auto_plan_op.argtypes = [C.c_int] * 10 + [ip, C.POINTER(C.c_long), ip]
+    L.mmh_auto_plan_ex.argtypes = L.mmh_auto_plan_op.argtypes
+    ex = [vp] + [C.c_int] * 5 + [C.c_float, vp, C.c_int, vp, C.c_int, C.c_float, vp, C.c_int, vp, C.c_int, C.c_int]
+    L.mmh_sgemm_ex.argtypes = ex + [vp]
+    L.mmh_time_sgemm_ex.argtypes = ex + [C.c_int, C.c_int, vp, fp]
     ll = C.c_longlong
     batched = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, ll, vp, C.c_int, ll, vp, C.c_int, ll, C.c_int]
     L.mmh_sgemm_batched.argtypes = batched + [C.c_int, vp]
@@ -420,6 +438,13 @@ class MMult:
         _check(lib().mmh_sgemm_op(self._h, int(transa), int(transb), m, n, k, dA, lda, dB, ldb, dC, ldc, int(bool(accumulate)),
                                   stream), "mmh_sgemm_op")
 
+    def sgemm_ex(self, transa, transb, m, n, k, alpha, dA: int, lda, dB: int, ldb, beta, dC: int, ldc, dBias: int = 0,
+                 bias_mode: int = BIAS_NONE, activation: int = ACT_NONE, stream: int = 0) -> None:
+        """C = act(alpha op(A) op(B) + beta C + bias) in one launch, row-major device pointers as sgemm_op (include/mmult_hip.h,
+        mmh_sgemm_ex: every rounding is defined there).  beta == 0: C is not read."""
+        _check(lib().mmh_sgemm_ex(self._h, int(transa), int(transb), m, n, k, float(alpha), dA, lda, dB, ldb, float(beta), dC, ldc,
+                                  dBias or None, int(bias_mode), int(activation), stream), "mmh_sgemm_ex")
+
     def sgemm_batched(self, transa, transb, m, n, k, dA: int, lda, stride_a, dB: int, ldb, stride_b, dC: int, ldc, stride_c,
                       batch, accumulate=False, stream: int = 0) -> None:
         """C_i = op(A_i) op(B_i) (+ C_i) for i < batch, row-major as sgemm_op; matrix i at dA + i stride_a (elements), and
@@ -535,6 +560,63 @@ class MMult:
         else:
             self.sgemm_op(ta, tb, m, n, k, pa, lda, pb, ldb, pc, ldc, accumulate, stream)
         return out
+
+    def _ex(self, what, a, b, out, alpha, beta, bias, bias_mode, activation):
+        """out = act(alpha a @ b + beta out + bias) through mmh_sgemm_ex on torch's current stream; a / b as matmul takes them."""
+        import torch
+        if a.dtype != torch.float32 or b.dtype != torch.float32:
+            raise MMultError(ERR_INVALID_ARG, what, "fp32 only")
+        if a.dim() != 2 or b.dim() != 2 or a.shape[1] != b.shape[0]:
+            raise MMultError(ERR_INVALID_ARG, what, "need 2-D operands whose inner dimensions agree")
+        (m, k), n = a.shape, b.shape[1]
+        pa, lda, ta = self._operand_args(a, m, k, what + "(A)")
+        pb, ldb, tb = self._operand_args(b, k, n, what + "(B)")
+        pc, ldc = self._tensor_args(out, m, n, what + "(C)", torch.float32)
+        pbias = 0
+        if bias is not None:
+            if not bias.is_cuda or bias.device.index != self.device or bias.dtype != torch.float32 or bias.dim() != 1 or \
+                    bias.shape[0] != (n if bias_mode == BIAS_COL else m) or (bias.shape[0] > 1 and bias.stride(0) != 1):
+                raise MMultError(ERR_INVALID_ARG, what, "the bias is a dense 1-D fp32 tensor on the handle's device, one float per "
+                                 "output column")
+            pbias = bias.data_ptr()
+        stream = torch.cuda.current_stream(a.device).cuda_stream
+        self.sgemm_ex(ta, tb, m, n, k, alpha, pa, lda, pb, ldb, beta, pc, ldc, pbias, bias_mode if bias is not None else BIAS_NONE,
+                      activation, stream)
+        return out
+
+    def addmm(self, input, a, b, *, beta=1.0, alpha=1.0, out=None):
+        """torch.addmm: out = beta input + alpha a @ b in ONE launch (mmh_sgemm_ex: fl(fl(alpha s) + fl(beta input)), s the fp32
+        fma chain).  `input` (m, n): in place when `out is input`, otherwise copied into `out` first; `input` (n,) with
+        beta == 1: the kernel's column bias (no copy); any other 1-D `input` is broadcast into `out` first.  a, b may be
+        transposed views, read in place."""
+        import torch
+        if a.dim() != 2 or b.dim() != 2:
+            raise MMultError(ERR_INVALID_ARG, "addmm", "need 2-D operands")
+        m, n = a.shape[0], b.shape[1]
+        if input.dim() == 1 and input.shape[0] == n and float(beta) == 1.0 and out is not input:
+            if out is None:
+                out = torch.empty((m, n), dtype=torch.float32, device=a.device)
+            return self._ex("addmm", a, b, out, alpha, 0.0, input, BIAS_COL, ACT_NONE)
+        if input.dim() == 1 and input.shape[0] != n or input.dim() == 2 and tuple(input.shape) != (m, n) or input.dim() not in (1, 2):
+            raise MMultError(ERR_INVALID_ARG, "addmm", f"input must be ({m},{n}) or ({n},)")
+        if out is None:
+            out = torch.empty((m, n), dtype=torch.float32, device=a.device)
+        if out is not input:
+            if float(beta) != 0.0:
+                out.copy_(input)   # (1-D: broadcast over the rows)
+        return self._ex("addmm", a, b, out, alpha, beta, None, BIAS_NONE, ACT_NONE)
+
+    def linear(self, x, w, bias=None, activation=None, out=None):
+        """torch.nn.functional.linear (+ ReLU) in ONE launch: y = act(x @ w.t() + bias), `w` stored out x in and read in place
+        (NT), `bias` (out,), activation None or "relu"."""
+        import torch
+        if activation not in (None, "relu"):
+            raise MMultError(ERR_INVALID_ARG, "linear", "activation is None or 'relu'")
+        if x.dim() != 2 or w.dim() != 2:
+            raise MMultError(ERR_INVALID_ARG, "linear", "need a 2-D x (batch, in) and a 2-D w (out, in)")
+        if out is None:
+            out = torch.empty((x.shape[0], w.shape[0]), dtype=torch.float32, device=x.device)
+        return self._ex("linear", x, w.t(), out, 1.0, 0.0, bias, BIAS_COL, ACT_RELU if activation == "relu" else ACT_NONE)
 
     def _batched_args(self, t, batch, rows, cols, what, operand):
         """(data_ptr, leading dimension, op, batch stride) of a 3-D (batch, rows, cols) tensor: each matrix a row-major
@@ -676,6 +758,15 @@ class MMult:
         ms = C.c_float(0)
         _check(lib().mmh_time_sgemm_op(self._h, int(transa), int(transb), m, n, k, dA, lda, dB, ldb, dC, ldc, warmup, reps, stream,
                                        C.byref(ms)), "mmh_time_sgemm_op")
+        return ms.value
+
+    def time_sgemm_ex(self, transa, transb, m, n, k, alpha, dA, lda, dB, ldb, beta, dC, ldc, dBias=0, bias_mode=BIAS_NONE,
+                      activation=ACT_NONE, warmup=1, reps=20, stream: int = 0) -> float:
+        """time_sgemm for mmh_sgemm_ex."""
+        ms = C.c_float()
+        _check(lib().mmh_time_sgemm_ex(self._h, int(transa), int(transb), m, n, k, float(alpha), dA, lda, dB, ldb, float(beta), dC, ldc,
+                                       dBias or None, int(bias_mode), int(activation), warmup, reps, stream, C.byref(ms)),
+               "mmh_time_sgemm_ex")
         return ms.value
 
     def time_sgemm_batched(self, transa, transb, m, n, k, dA, lda, stride_a, dB, ldb, stride_b, dC, ldc, stride_c, batch,
@@ -827,7 +918,7 @@ def sgemm_sharded(ngpus: int, a: np.ndarray, b: np.ndarray, kernel="mfma"):
 
 
 __all__ = ["MMult", "ShardedMMult", "MMultError", "lib", "use_ab_library", "device_count", "rccl_version", "shard_rows", "shard_chunks",
-           "kernel_name", "last_launch", "use_timeline_library", "streamk_plan", "auto_plan", "auto_plan_op", "auto_plan_batched", "BATCH_FORMS", "BATCHED_MAX_WORKGROUPS", "OP_N", "OP_T", "sgemm_sharded", "KERNELS", "CHAIN_KERNELS", "AB_LIB_PATH",
+           "kernel_name", "last_launch", "use_timeline_library", "streamk_plan", "auto_plan", "auto_plan_op", "auto_plan_ex", "auto_plan_batched", "BIAS_NONE", "BIAS_COL", "BIAS_ROW", "ACT_NONE", "ACT_RELU", "BATCH_FORMS", "BATCHED_MAX_WORKGROUPS", "OP_N", "OP_T", "sgemm_sharded", "KERNELS", "CHAIN_KERNELS", "AB_LIB_PATH",
            "OPT_SPLITK", "OPT_HOST_PANELS", "OPT_STREAMK_SPIN_LIMIT", "OPT_FAULT_INJECT", "OPT_STREAMK_ORDER", "OPT_DMA_EDGE", "OPT_STREAMK_DELEGATIONS", "OPT_RIM", "OPT_STREAMK_CHAIN", "OPT_PERSIST", "OPT_RIM5", "KERNEL_AUTO", "KERNEL_VALU", "KERNEL_MFMA", "KERNEL_MFMA_256", "KERNEL_NAIVE", "KERNEL_MFMA_SIMPLE", "KERNEL_MFMA_PIPE",
            "EXPORTS", "LIB_PATH", "OPT_STREAMK", "OPT_STREAMK_TIMEOUTS", "OPT_IGEMM_MODE", "OK", "ERR_INVALID_ARG", "ERR_HIP", "ERR_NO_DEVICE",
            "ERR_UNSUPPORTED", "ERR_ALLOC", "ERR_COMM"]

@@ -119,7 +119,7 @@ const char *mmh_last_error(void) { return last_error_ref().c_str(); }
 
 const char *mmh_last_launch(void) { return last_launch_ref().c_str(); }
 
-int mmh_version(void) { return 300; }
+int mmh_version(void) { return 301; }
 
 int mmh_is_ab_build(void) {
 #ifdef MMH_AB_BUILD
@@ -370,6 +370,14 @@ int mmh_sgemm_op(mmh_handle_t h, int transa, int transb, int m, int n, int k, co
   return sgemm_op_on(h, h->kernel, transa, transb, m, n, k, dA, lda, dB, ldb, dC, ldc, accumulate,
                      static_cast<hipStream_t>(stream));
 }
+int mmh_sgemm_ex(mmh_handle_t h, int transa, int transb, int m, int n, int k, float alpha, const float *dA, int lda,
+                 const float *dB, int ldb, float beta, float *dC, int ldc, const float *dBias, int bias_mode, int activation,
+                 void *stream) {
+  if (!h) return MMH_ERR_INVALID_ARG;
+  ENTER(h);
+  return sgemm_ex_on(h, h->kernel, transa, transb, m, n, k, alpha, dA, lda, dB, ldb, beta, dC, ldc, dBias, bias_mode, activation,
+                     static_cast<hipStream_t>(stream));
+}
 int mmh_sgemm_batched(mmh_handle_t h, int transa, int transb, int m, int n, int k, const float *dA, int lda, long long strideA,
                       const float *dB, int ldb, long long strideB, float *dC, int ldc, long long strideC, int batch, int accumulate,
                       void *stream) {
@@ -390,6 +398,16 @@ int mmh_time_sgemm_op(mmh_handle_t h, int transa, int transb, int m, int n, int 
   hipStream_t s = static_cast<hipStream_t>(stream);
   return time_calls(h, s, warmup, reps, ms_per_call, "mmh_time_sgemm_op",
                     [&]() { return sgemm_op_on(h, h->kernel, transa, transb, m, n, k, dA, lda, dB, ldb, dC, ldc, 0, s); });
+}
+int mmh_time_sgemm_ex(mmh_handle_t h, int transa, int transb, int m, int n, int k, float alpha, const float *dA, int lda,
+                      const float *dB, int ldb, float beta, float *dC, int ldc, const float *dBias, int bias_mode, int activation,
+                      int warmup, int reps, void *stream, float *ms_per_call) {
+  if (!h || reps <= 0 || warmup < 0 || !ms_per_call) return MMH_ERR_INVALID_ARG;
+  ENTER(h);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  return time_calls(h, s, warmup, reps, ms_per_call, "mmh_time_sgemm_ex", [&]() {
+    return sgemm_ex_on(h, h->kernel, transa, transb, m, n, k, alpha, dA, lda, dB, ldb, beta, dC, ldc, dBias, bias_mode, activation, s);
+  });
 }
 int mmh_time_sgemm_batched(mmh_handle_t h, int transa, int transb, int m, int n, int k, const float *dA, int lda,
                            long long strideA, const float *dB, int ldb, long long strideB, float *dC, int ldc, long long strideC,
@@ -439,6 +457,10 @@ int mmh_auto_plan(int m, int n, int k, int lda, int ldb, int ldc, int base_align
 int mmh_auto_plan_op(int transa, int transb, int m, int n, int k, int lda, int ldb, int ldc, int base_align, int cu_count,
                      int *kernel, long *tiles, int *streamk_grid) {
   return mmh::auto_plan_op(transa, transb, m, n, k, lda, ldb, ldc, base_align, cu_count, kernel, tiles, streamk_grid);
+}
+int mmh_auto_plan_ex(int transa, int transb, int m, int n, int k, int lda, int ldb, int ldc, int base_align, int cu_count,
+                     int *kernel, long *tiles, int *streamk_grid) {
+  return mmh::auto_plan_op(transa, transb, m, n, k, lda, ldb, ldc, base_align, cu_count, kernel, tiles, streamk_grid, 1);
 }
 int mmh_auto_plan_batched(int transa, int transb, int m, int n, int k, int lda, int ldb, int ldc, long long strideA,
                           long long strideB, long long strideC, int batch, int base_align, int cu_count, int *kernel,

@@ -9,8 +9,9 @@
 //   launch_reg.hip   register-staged MFMA tiles (sgemm_mfma.hpp): plain, stream-K, split-K
 //   launch_dma.hip   LDS-DMA tiles (sgemm_dma.hpp): plain, stream-K; whole and guarded shapes
 //   launch_dma5.hip  LDS-DMA tiles with loader waves (K2W, sgemm_dma5.hpp): plain, chained stream-K -- the NN forms;
-//   launch_op.hip    ... their transposed-operand forms, launch_batched.hip their strided batched form: each TU
-//                    instantiates launch_dma5.hpp's one launcher for its own kernels (built in parallel)
+//   launch_op.hip    ... their transposed-operand forms, launch_batched.hip their strided batched form, launch_ex.hip /
+//                    launch_ex_t.hip their fused-epilogue forms (mmh_sgemm_ex): each TU instantiates launch_dma5.hpp's one
+//                    launcher for its own kernels (built in parallel)
 //   launch_valu.hip  K1 / K0 (sgemm_valu.hpp)
 //   host_flavour.hip mmh_sgemm_host(_timed): the host-pointer MY_MMult, row-panel pipeline
 //   shard.hip        mmh_shard_*: single-process row-panel shard over RCCL
@@ -88,6 +89,12 @@ struct GemmArgs {
   int sk_w = 0;
   // operand layouts (mmh_sgemm_op): 1 = stored transposed -- A as k x m (lda >= m), B as n x k (ldb >= k)
   int ta = 0, tb = 0;
+  // the fused epilogue (mmh_sgemm_ex, ex = 1): C = act(alpha op(A) op(B) + beta C + bias) on the `ex` kernels (launch_ex.hip);
+  // acc is 0 there -- the chain starts at +0, beta C is the epilogue's
+  int ex = 0;
+  float alpha = 1.0f, beta = 0.0f;
+  const float *bias = nullptr;
+  int bias_mode = MMH_BIAS_NONE, act = MMH_ACT_NONE;
 };
 
 }  // namespace mmh
@@ -246,7 +253,11 @@ int sgemm_on(mmh_context *ctx, int kernel, int m, int n, int k, const float *dA,
 int sgemm_op_on(mmh_context *ctx, int kernel, int ta, int tb, int m, int n, int k, const float *dA, int lda, const float *dB,
                 int ldb, float *dC, int ldc, int accumulate, hipStream_t s);
 int auto_plan_op(int ta, int tb, int m, int n, int k, int lda, int ldb, int ldc, int base_align, int cu_count, int *kernel,
-                 long *tiles, int *streamk_grid);   // mmh_auto_plan_op
+                 long *tiles, int *streamk_grid, int ex = 0);   // mmh_auto_plan_op; ex: mmh_auto_plan_ex
+// mmh_sgemm_ex: C = act(alpha op(A) op(B) + beta C + bias)
+int sgemm_ex_on(mmh_context *ctx, int kernel, int ta, int tb, int m, int n, int k, float alpha, const float *dA, int lda,
+                const float *dB, int ldb, float beta, float *dC, int ldc, const float *dBias, int bias_mode, int activation,
+                hipStream_t s);
 // launch_reg.hip: `kernel` is one of the register-staged ids (MFMA, MFMA_TILES, MFMA_256, MFMA_256X256, MFMA_128X64,
 // MFMA_64X64, MFMA_SIMPLE, MFMA_PIPE, the split-K ids and, in the A/B build, the ablation ids)
 int launch_reg(mmh_context *ctx, int kernel, const GemmArgs &g);
@@ -386,6 +397,13 @@ int warm_dma5(mmh_context *ctx, float *scratch, hipStream_t s);
 int launch_dma5_op(mmh_context *ctx, int kernel, const GemmArgs &g);   // 1: the shape does not qualify
 int launch_naive_op(const GemmArgs &g);
 int warm_dma5_op(mmh_context *ctx);                                     // LDS opt-ins only (nothing is launched)
+// launch_ex.hip (A stored m x k) / launch_ex_t.hip (A stored k x m): the epilogue forms (g.ex, every g.ta / g.tb) of the same
+// three tiles; the naive kernel with the epilogue written out (k == 0 included: A and B are not read)
+int launch_dma5_ex(mmh_context *ctx, int kernel, const GemmArgs &g);   // 1: the shape does not qualify
+int launch_dma5_ex_ta(mmh_context *ctx, int kernel, const GemmArgs &g);
+int launch_naive_ex(const GemmArgs &g);
+int warm_dma5_ex(mmh_context *ctx);                                     // LDS opt-ins only
+int warm_dma5_ex_ta(mmh_context *ctx);
 int launch_dma5_batched(mmh_context *ctx, int kernel, const GemmArgs &g, const BatchArgs &b);
 int launch_naive_batched(const GemmArgs &g, const BatchArgs &b);
 int warm_dma5_batched(mmh_context *ctx);   // LDS opt-ins only (nothing is launched)

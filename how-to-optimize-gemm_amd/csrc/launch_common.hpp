@@ -80,9 +80,10 @@ inline int streamk_wanted(const mmh_context *ctx, long tiles, int BM, int BN, in
 // to launch (`occ_kern` the one whose residency bounds the grid).  Returns MMH_OK if it launched, 1 if
 // the shape does not qualify (caller then uses the plain one-tile-per-workgroup launch).  `force`: launch
 // even when the policy below prefers the plain launch (warm-up, tools).
-template <typename K>
-int launch_streamk(mmh_context *ctx, K kern, K occ_kern, int BM, int BN, int KB, int threads, size_t lds, const char *what,
-                   const GemmArgs &g, long decide_tiles = 0, int order_min10 = 0) {
+// (`extra`: what an `ex` kernel takes behind the common arguments -- its epilogue)
+template <typename K, typename KO, typename... X>
+int launch_streamk(mmh_context *ctx, K kern, KO occ_kern, int BM, int BN, int KB, int threads, size_t lds, const char *what,
+                   const GemmArgs &g, long decide_tiles = 0, int order_min10 = 0, X... extra) {
   const int nbm = (g.m + BM - 1) / BM, nbn = (g.n + BN - 1) / BN;
   const long tiles = (long)nbm * nbn;
   const int cus = ctx->cu_count > 0 ? ctx->cu_count : 256;
@@ -127,7 +128,7 @@ int launch_streamk(mmh_context *ctx, K kern, K occ_kern, int BM, int BN, int KB,
   const int *order = nullptr, *place = nullptr;
   if ((rc = sk_tables_for(ctx, tiles, (g.k + KB - 1) / KB, grid, g.s, &order, &place, order_min10)) != MMH_OK) return rc;
   hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(threads), lds_launch, g.s, g.m, g.n, g.k, g.A, g.lda, g.B, g.ldb, g.C,
-                     g.ldc, g.acc, nbm, nbn, flags, parts, order, place, ctx->sk_stats);
+                     g.ldc, g.acc, nbm, nbn, flags, parts, order, place, ctx->sk_stats, extra...);
   HIP_TRY(hipGetLastError());
   {
     char buf[224];

@@ -78,7 +78,7 @@ Plan auto_plan_for(const mmh_context *ctx, const GemmArgs &g) {
   long tiles_rim = 0;
   bool any_dma5 = false;   // did any LDS-DMA family take the shape?
   for (const Family &f : kFamilies) {
-    if ((g.ta || g.tb) && !has_op_forms(f.kernel)) continue;   // op forms: the same table, restricted to their three tiles
+    if ((g.ta || g.tb || g.ex) && !has_op_forms(f.kernel)) continue;   // op forms, and every epilogue call: the same table, restricted to their three tiles
     // (Rounds 2-3 kept K > 8192 -- B beyond the Infinity Cache, the config-4 panels -- on the 256x256 tile: K2L's small tiles
     // lost 1-6 % there.  K2W's do not: 2048 .. 4096 x 16384 x 16384 run 152.4-153.2 TFLOP/s on the 128x64 tile against
     // 150.2-150.3, and 2048 x 4096 x 16384 -- half a round of 256x256 tiles -- 151.5 against 74.8: the fence is gone, the
@@ -279,6 +279,59 @@ int sgemm_op_on(mmh_context *ctx, int kernel, int ta, int tb, int m, int n, int 
   return MMH_ERR_UNSUPPORTED;
 }
 
+// mmh_sgemm_ex: C = act(alpha op(A) op(B) + beta C + bias).  Planned like an op call, NN included (auto_plan_for, g.ex): the
+// `ex` kernels exist on the three tiles with op forms; MMH_KERNEL_NAIVE and the empty contraction (s = +0: A and B are not
+// read) run the naive kernel with the same epilogue.  Everything else is refused before anything is launched.
+int sgemm_ex_on(mmh_context *ctx, int kernel, int ta, int tb, int m, int n, int k, float alpha, const float *dA, int lda,
+                const float *dB, int ldb, float beta, float *dC, int ldc, const float *dBias, int bias_mode, int activation,
+                hipStream_t s) {
+  if ((ta != MMH_OP_N && ta != MMH_OP_T) || (tb != MMH_OP_N && tb != MMH_OP_T)) {
+    set_last_error("transa / transb must be MMH_OP_N or MMH_OP_T");
+    return MMH_ERR_INVALID_ARG;
+  }
+  if (bias_mode < MMH_BIAS_NONE || bias_mode > MMH_BIAS_ROW || (activation != MMH_ACT_NONE && activation != MMH_ACT_RELU) ||
+      (bias_mode != MMH_BIAS_NONE && !dBias)) {
+    set_last_error("bias_mode must be MMH_BIAS_NONE / _COL / _ROW (with a bias pointer), activation MMH_ACT_NONE / _RELU");
+    return MMH_ERR_INVALID_ARG;
+  }
+  int rc = check_gemm_args(m, n, k, dA, lda, dB, ldb, dC, ldc, ta, tb);
+  if (rc != MMH_OK) {
+    set_last_error("invalid argument");
+    return rc;
+  }
+  if (m == 0 || n == 0) return MMH_OK;
+  if (kernel != MMH_KERNEL_AUTO && kernel != MMH_KERNEL_NAIVE && !has_op_forms(kernel)) {
+    set_last_error("the fused epilogue runs on MMH_KERNEL_AUTO, the 64x64 / 128x64 / 128x128 LDS-DMA tiles (29 / 30 / 31) and "
+                   "MMH_KERNEL_NAIVE only");
+    return MMH_ERR_UNSUPPORTED;
+  }
+  GemmArgs g{m, n, k, dA, lda, dB, ldb, dC, ldc, 0, s};
+  g.ta = ta;
+  g.tb = tb;
+  g.ex = 1;
+  g.alpha = alpha;
+  g.beta = beta;
+  g.bias = bias_mode != MMH_BIAS_NONE ? dBias : nullptr;
+  g.bias_mode = bias_mode;
+  g.act = activation;
+  if (k == 0 || kernel == MMH_KERNEL_NAIVE) return launch_naive_ex(g);
+  if (kernel == MMH_KERNEL_AUTO) {
+    const Plan plan = auto_plan_for(ctx, g);
+    if (plan.kernel >= 0) {
+      g.form = plan.form;
+      g.sk_w = plan.sk_w;
+      kernel = plan.kernel;
+    }
+  }
+  if (has_op_forms(kernel)) {
+    const int d = ta ? launch_dma5_ex_ta(ctx, kernel, g) : launch_dma5_ex(ctx, kernel, g);
+    if (d <= 0) return d;
+  }
+  set_last_error("the fused epilogue needs the LDS-DMA tiles: an operand lies beyond their 2 GiB descriptor window, or "
+                 "MMH_OPT_DMA_EDGE keeps this shape off them");
+  return MMH_ERR_UNSUPPORTED;
+}
+
 // ---- mmh_sgemm_batched ----
 namespace {
 struct BatchPlan {
@@ -438,13 +491,15 @@ int auto_plan(int m, int n, int k, int lda, int ldb, int ldc, int base_align, in
 }
 
 // mmh_auto_plan_op: the same for C = op(A) op(B); an op form no tile with op forms takes is MMH_ERR_UNSUPPORTED
+// (ex: mmh_auto_plan_ex -- an epilogue call is planned like an op form, NN too)
 int auto_plan_op(int ta, int tb, int m, int n, int k, int lda, int ldb, int ldc, int base_align, int cu_count, int *kernel,
-                 long *tiles, int *streamk_grid) {
+                 long *tiles, int *streamk_grid, int ex) {
   mmh_context ctx;
   GemmArgs g;
   if (plan_inputs(ta, tb, m, n, k, lda, ldb, ldc, base_align, cu_count, &ctx, &g) != MMH_OK) return MMH_ERR_INVALID_ARG;
+  g.ex = ex;
   const Plan plan = auto_plan_for(&ctx, g);
-  if ((ta || tb) && plan.kernel < 0) return MMH_ERR_UNSUPPORTED;
+  if ((ta || tb || ex) && plan.kernel < 0) return MMH_ERR_UNSUPPORTED;
   const int kern = plan.kernel >= 0 ? plan.kernel : fallback_kernel(&ctx, g);
   if (kernel) *kernel = kern;
   const long t = plan.kernel >= 0 ? (long)((m + plan.bm - 1) / plan.bm) * ((n + plan.bn - 1) / plan.bn)

@@ -152,10 +152,50 @@ struct Dma5ValuFrags {
 // of each operand per lane, A[i][k] and B[k][i]: only the loaders' maps and the fragment addresses change, never the
 // MFMAs, the k order or the accumulators -- the NN bits.  K tail: B^T's columns past k are garbage like A's, and the
 // TAIL slice zeroes both operands (A to -0, B to +0).  (Even WTN, MFMA consumers only.)
+//
+// EP (the fused epilogue of mmh_sgemm_ex): Dma5NoEpilogue -- every kernel but the `ex` ones -- compiles to what was here before.
+// With Dma5Epilogue a finished tile's chain values s become act(alpha s + beta C + bias) in the one place they sit in
+// registers: behind the K loop of the part that stores C.  Partial tiles (part_in / part_out) carry bare chain values, the
+// chain starts at +0 (init_from_c is never used), and C is read -- only when beta != 0 -- the way init_from_c reads it.
+// The arithmetic is DESIGN.md section 2's: one rounding per operation, nothing contracted (dma5_epilogue_apply).
+struct Dma5NoEpilogue {};
+struct Dma5Epilogue {
+  float alpha, beta;
+  const float *bias;   // MMH_BIAS_COL: n floats, MMH_BIAS_ROW: m floats; any 4-byte aligned address
+  int bias_mode, act;  // MMH_BIAS_*, MMH_ACT_*
+};
+// r1 = fl(alpha s); r2 = fl(r1 + fl(beta c)) unless beta == 0; r3 = fl(r2 + bias) with a bias; ReLU: r3 > 0 or NaN keeps r3,
+// everything else (-0 included) gives +0.  The switches are wave-uniform; an operation that is switched off is SKIPPED, never
+// run on a neutral value (r + (+0) would turn a -0 into +0).  The pragma keeps hipcc from fusing a product into the sum
+// behind it: each line rounds once.
+template <int N>
+__device__ __forceinline__ void dma5_epilogue_apply(const Dma5Epilogue &ep, float (&v)[N], const float (&c)[N], const float (&b)[N]) {
+#pragma clang fp contract(off)
+#pragma unroll
+  for (int i = 0; i < N; ++i) v[i] = ep.alpha * v[i];
+  if (ep.beta != 0.0f) {
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+      const float bc = ep.beta * c[i];
+      v[i] = v[i] + bc;
+    }
+  }
+  if (ep.bias_mode != 0) {
+#pragma unroll
+    for (int i = 0; i < N; ++i) v[i] = v[i] + b[i];
+  }
+  if (ep.act != 0) {
+#pragma unroll
+    for (int i = 0; i < N; ++i) v[i] = !(v[i] <= 0.0f) ? v[i] : 0.0f;   // (NaN: not <= 0, stays)
+  }
+}
+
 template <int BM, int BN, int KB, int WTM, int WTN, int NBUF, bool PART_WT = false, bool EDGE = false, bool CHAIN = false,
-          int NL = 1, int D = 2, bool RIM = false, bool VALU = false, int RS = 1, int OP = 0>
+          int NL = 1, int D = 2, bool RIM = false, bool VALU = false, int RS = 1, int OP = 0, class EP = Dma5NoEpilogue>
 struct Dma5Segment {
   using T = Dma5Tile<BM, BN, KB, WTM, WTN, NBUF, NL>;
+  static constexpr bool EX = !std::is_same<EP, Dma5NoEpilogue>::value;
+  static_assert(!EX || (!VALU && !RIM && (WTN == 2 || WTN == 4) && (BM == 64 || BM == 128)), "the epilogue: the 64x64, 128x64 and 128x128 tiles");
   static constexpr bool TA = (OP & 1) != 0, TB = (OP & 2) != 0;
   static_assert(OP == 0 || (!VALU && !RIM && (WTN == 2 || WTN == 4) && (BM == 64 || BM == 128)), "op forms: the 64x64, 128x64 and 128x128 tiles");
   static constexpr int CPR_AT = BM / 4, RA_T = 64 / CPR_AT;   // A^T: 16-byte chunks per k-row, k-rows per piece
@@ -275,7 +315,7 @@ struct Dma5Segment {
                                              int lda, const float *__restrict__ B, int ldb, float *__restrict__ C, int ldc,
                                              int tm, int tn, int kb, int ke, bool init_from_c, const float *part_in,
                                              float *part_out, Frags &fr, Dma5Link &link, const Dma5Next nx, int *pub_flag,
-                                             int &pub_reply, const Dma5Rim rim = Dma5Rim{}) {
+                                             int &pub_reply, const Dma5Rim rim = Dma5Rim{}, const EP ep = EP{}) {
     constexpr int KS = T::KS, STAGE = T::STAGE, A_FLOATS = T::A_FLOATS, NPL = NPL_R, LA = T::LA;
     const int row0 = tm * BM, col0 = tn * BN;
     const int rows_valid = EDGE ? min(BM, m - row0) : BM;
@@ -424,22 +464,22 @@ struct Dma5Segment {
       const bool thin_n = __builtin_amdgcn_readfirstlane((int)(BBLK ? cv <= 16 : cv <= 1)) != 0;
       if (thin_m && thin_n) {
         consume(std::true_type{}, std::true_type{}, lds, L, m, n, k, C, ldc, row0, col0, rows_valid, cols_valid, kb, ke, pos, primed, chain,
-                init_from_c, part_in, part_out, fr, pub_flag, pub_reply);
+                init_from_c, part_in, part_out, fr, pub_flag, pub_reply, ep);
         return;
       }
       if (thin_m) {
         consume(std::true_type{}, std::false_type{}, lds, L, m, n, k, C, ldc, row0, col0, rows_valid, cols_valid, kb, ke, pos, primed, chain,
-                init_from_c, part_in, part_out, fr, pub_flag, pub_reply);
+                init_from_c, part_in, part_out, fr, pub_flag, pub_reply, ep);
         return;
       }
       if (thin_n) {
         consume(std::false_type{}, std::true_type{}, lds, L, m, n, k, C, ldc, row0, col0, rows_valid, cols_valid, kb, ke, pos, primed, chain,
-                init_from_c, part_in, part_out, fr, pub_flag, pub_reply);
+                init_from_c, part_in, part_out, fr, pub_flag, pub_reply, ep);
         return;
       }
     }
     consume(std::false_type{}, std::false_type{}, lds, L, m, n, k, C, ldc, row0, col0, rows_valid, cols_valid, kb, ke, pos, primed, chain,
-            init_from_c, part_in, part_out, fr, pub_flag, pub_reply);
+            init_from_c, part_in, part_out, fr, pub_flag, pub_reply, ep);
   }   // (!VALU)
   }
 
@@ -449,7 +489,7 @@ struct Dma5Segment {
   static __device__ __forceinline__ void consume(TM1, TN1, float *lds, const Lane &L, int m, int n, int k, float *__restrict__ C,
                                                  int ldc, int row0, int col0, int rows_valid, int cols_valid, int kb, int ke,
                                                  int pos, bool primed, bool chain, bool init_from_c, const float *part_in,
-                                                 float *part_out, Frags &fr, int *pub_flag, int &pub_reply) {
+                                                 float *part_out, Frags &fr, int *pub_flag, int &pub_reply, const EP ep) {
     constexpr int KS = T::KS, STAGE = T::STAGE;
     constexpr bool THIN = TM1::value || TN1::value;
     constexpr int NT = TM1::value ? 1 : WTM, NU = TN1::value ? 1 : WTN;   // blocks kept
@@ -479,7 +519,7 @@ struct Dma5Segment {
             for (int u = 0; u < NU; ++u) acc[t][u][r] = src[BBLK ? 16 * u : u];
           }
         }
-    } else if (init_from_c) {
+    } else if (!EX && init_from_c) {
 #pragma unroll
       for (int t = 0; t < NT; ++t)
 #pragma unroll
@@ -703,6 +743,85 @@ struct Dma5Segment {
     dma_stamp(L.stamp_base + 2);
     if constexpr (THIN) __builtin_amdgcn_s_setprio(0);
 
+    if constexpr (EX) {
+      // The epilogue (mmh_sgemm_ex): the part that finishes a tile stores act(alpha s + beta C + bias) instead of its chain
+      // values (a partial tile goes out bare, below).  One ROW of the lane's block (NU columns) at a time, and nothing of the
+      // next row is requested before this one is done (the scheduling barrier): the guarded stream-K kernels of the 128-wide
+      // tiles have no registers to hold more of C than that beside the accumulators and the next part's fragments.  C is read
+      // only when beta != 0 -- a vector per row on whole tiles, single elements at clamped indices on edge tiles.
+      if (!part_out) {
+        // (the epilogue's arguments pass through an empty asm: what hipcc can derive from them -- the switches as lane masks, the
+        // bias addresses -- it otherwise computes in front of a persistent workgroup's part loop and keeps in scalar registers
+        // it does not have: 66-78 spilled on the guarded 128x128 stream-K kernels instead of 50-55; 64 is the suite's bound)
+        EP e = ep;
+        asm volatile("" : "+s"(e.alpha), "+s"(e.beta), "+s"(e.bias), "+s"(e.bias_mode), "+s"(e.act));
+        const bool rd_c = e.beta != 0.0f;
+        // an edge tile's rows >= m and columns >= n are never stored: what the epilogue reads for them is row m - 1's /
+        // column n - 1's value -- a clamped index instead of a branch per element (no lane masks to keep)
+        auto row_in = [&](int row) { return whole_c ? row : min(row, m - 1); };
+        auto col_in = [&](int u) { return whole_c ? col_of(u) : min(col_of(u), n - 1); };
+        float bcol[NU];
+#pragma unroll
+        for (int u = 0; u < NU; ++u) bcol[u] = 0.0f;
+        if (e.bias_mode == 1) {
+#pragma unroll
+          for (int u = 0; u < NU; ++u) bcol[u] = e.bias[col_in(u)];
+        }
+#pragma unroll
+        for (int t = 0; t < NT; ++t)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const int row = crow + 16 * t + r;
+            float v[NU], c[NU], b[NU];
+#pragma unroll
+            for (int u = 0; u < NU; ++u) {
+              v[u] = acc[t][u][r];
+              c[u] = 0.0f;
+              b[u] = bcol[u];
+            }
+            if (e.bias_mode == 2) {
+              const float brow = e.bias[row_in(row)];
+#pragma unroll
+              for (int u = 0; u < NU; ++u) b[u] = brow;
+            }
+            if (rd_c) {
+              bool vec = false;
+              if constexpr (VEC) {
+                if (whole_c) {
+                  vec = true;
+                  const bfrag_t w = *reinterpret_cast<const c_vec *>(C + (size_t)row * ldc + ccol);
+#pragma unroll
+                  for (int u = 0; u < NU; ++u) c[u] = w[u];
+                }
+              }
+              if (!vec) {
+                const float *crow_p = C + (size_t)row_in(row) * ldc;
+#pragma unroll
+                for (int u = 0; u < NU; ++u) c[u] = crow_p[col_in(u)];
+              }
+            }
+            dma5_epilogue_apply(e, v, c, b);
+            // ... and the row goes out: the vector store of a whole tile, guarded elements otherwise (the stores below, row by row)
+            bool stored = false;
+            if constexpr (VEC) {
+              if (whole_c) {
+                stored = true;
+                bfrag_t w;
+#pragma unroll
+                for (int u = 0; u < WTN; ++u) w[u] = v[u < NU ? u : 0];
+                *reinterpret_cast<c_vec *>(C + (size_t)row * ldc + ccol) = w;
+              }
+            }
+            if (!stored && row < m) {
+#pragma unroll
+              for (int u = 0; u < NU; ++u)
+                if (col_of(u) < n) C[(size_t)row * ldc + col_of(u)] = v[u];
+            }
+            if constexpr (CHAIN) __builtin_amdgcn_sched_barrier(0);
+          }
+        return;
+      }
+    }
     auto out_vec = [&](int t, int r) {
       bfrag_t v;
 #pragma unroll
@@ -923,14 +1042,14 @@ sgemm_mfma_dma5_batched_kernel(int m, int n, int k, const float *__restrict__ A,
 // they are dropped.
 // ---------------------------------------------------------------------------------------------------------------
 template <int BM, int BN, int KB, int WTM, int WTN, int NBUF, bool EDGE, bool CHAINED, int NL, int D, bool VALU = false, int RS = 1,
-          int OP = 0>
+          int OP = 0, class EP = Dma5NoEpilogue>
 __device__ __forceinline__ void streamk5_body(float *lds, int m, int n, int k, const float *__restrict__ A, int lda,
                                               const float *__restrict__ B, int ldb, float *__restrict__ C, int ldc,
                                               int accumulate, int nbm, int nbn, int *__restrict__ flags,
                                               float *__restrict__ parts, const int *__restrict__ order,
-                                              const int *__restrict__ place, int *__restrict__ stats) {
+                                              const int *__restrict__ place, int *__restrict__ stats, const EP ep = EP{}) {
   constexpr bool chained = CHAINED;
-  using S = Dma5Segment<BM, BN, KB, WTM, WTN, NBUF, true, EDGE, true, NL, D, false, VALU, RS, OP>;
+  using S = Dma5Segment<BM, BN, KB, WTM, WTN, NBUF, true, EDGE, true, NL, D, false, VALU, RS, OP, EP>;
   using T = Dma5Tile<BM, BN, KB, WTM, WTN, NBUF, NL>;
   // tools build: bit 1 of `accumulate` = publish every head on the spot, bit 2 = whole-tile ranges, bits 8-15 = raster group height
   const bool ab_nodefer = kAbBuild && (accumulate & 2) != 0;
@@ -1125,7 +1244,7 @@ __device__ __forceinline__ void streamk5_body(float *lds, int m, int n, int k, c
     int *const pub_flag = pending;
     pending = nullptr;
     S::run(lds, L, m, n, k, A, lda, B, ldb, C, ldc, tm, tn, pkb, pke, pkb == 0 && accumulate != 0, part_in,
-           p.kind == HEAD ? my_slot : nullptr, fr, link, nx, pub_flag, head_reply);
+           p.kind == HEAD ? my_slot : nullptr, fr, link, nx, pub_flag, head_reply, Dma5Rim{}, ep);
     if (p.kind == HEAD) {
       if (chained && !ab_nodefer && next_kind == WHOLE && nk >= 3) {
         // a whole tile follows, which depends on nobody: the publish rides on its first slice's barrier (Dma5Publish)
@@ -1172,6 +1291,41 @@ sgemm_dma5_op_streamk_kernel(int m, int n, int k, const float *__restrict__ A, i
   asm volatile("" ::"s"(A), "s"(B), "s"(C), "s"(lda), "s"(ldb), "s"(ldc), "s"(k), "s"(flags), "s"(parts), "s"(order), "s"(place));
   streamk5_body<BM, BN, KB, WTM, WTN, NBUF, EDGE, true, NL, D, false, 1, OP>(lds, m, n, k, A, lda, B, ldb, C, ldc, accumulate, nbm, nbn,
                                                                           flags, parts, order, place, stats);
+}
+
+// The epilogue forms (mmh_sgemm_ex; Dma5Segment, EP) of the plain and of the chained stream-K launch, OP = 0 .. 3 (NN, NT, TN,
+// TT): kernels of their own again, so that every other instantiation keeps its name and its code.  `accumulate` carries the
+// tail split's id offset only (bits 16-31): the chain starts at +0 and beta C is the epilogue's.
+template <int BM, int BN, int KB, int WTM, int WTN, int NBUF, bool EDGE, int NL, int D, int OP>
+__global__ void __launch_bounds__(64 * (4 + NL))
+sgemm_mfma_dma5_ex_kernel(int m, int n, int k, const float *__restrict__ A, int lda, const float *__restrict__ B, int ldb,
+                          float *__restrict__ C, int ldc, int accumulate, int nbm, int nbn, const Dma5Epilogue ep) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  using S = Dma5Segment<BM, BN, KB, WTM, WTN, NBUF, false, EDGE, false, NL, D, false, false, 1, OP, Dma5Epilogue>;
+  constexpr int GM = Dma5Tile<BM, BN, KB, WTM, WTN, NBUF, NL>::GM;
+  asm volatile("" ::"s"(A), "s"(B), "s"(C), "s"(lda), "s"(ldb), "s"(ldc), "s"(k));
+  const unsigned bid = blockIdx.x + (((unsigned)accumulate >> 16) << 3);
+  int tm, tn;
+  dma5_raster<BM, BN, EDGE>(bid, m, n, nbm, nbn, GM, tm, tn);
+  typename S::Lane L;
+  L.init(lda, ldb);
+  typename S::Frags fr;
+  Dma5Link link;
+  int no_reply = 0;
+  S::run(lds, L, m, n, k, A, lda, B, ldb, C, ldc, tm, tn, 0, (k + KB - 1) / KB, false, nullptr, nullptr, fr, link, Dma5Next{},
+         nullptr, no_reply, Dma5Rim{}, ep);
+}
+
+template <int BM, int BN, int KB, int WTM, int WTN, int NBUF, bool EDGE, int NL, int D, int OP>
+__global__ void __launch_bounds__(64 * (4 + NL))
+sgemm_dma5_ex_streamk_kernel(int m, int n, int k, const float *__restrict__ A, int lda, const float *__restrict__ B,
+                             int ldb, float *__restrict__ C, int ldc, int accumulate, int nbm, int nbn,
+                             int *__restrict__ flags, float *__restrict__ parts, const int *__restrict__ order,
+                             const int *__restrict__ place, int *__restrict__ stats, const Dma5Epilogue ep) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  asm volatile("" ::"s"(A), "s"(B), "s"(C), "s"(lda), "s"(ldb), "s"(ldc), "s"(k), "s"(flags), "s"(parts), "s"(order), "s"(place));
+  streamk5_body<BM, BN, KB, WTM, WTN, NBUF, EDGE, true, NL, D, false, 1, OP, Dma5Epilogue>(lds, m, n, k, A, lda, B, ldb, C, ldc, 0, nbm, nbn,
+                                                                                      flags, parts, order, place, stats, ep);
 }
 
 }  // namespace mmh

@@ -21,6 +21,9 @@
  *                     (armv7/MMult0.c:9-24, aarch64/MMult0.cpp:3-19).
  *   mmh_sgemm_op      cublasSgemm(handle, opA, opB, ...) (cuda/MMult_cuBLAS_1.cpp:11-19) with ROW-MAJOR
  *                     storage: C = op(A)*op(B) on device pointers, op = N or T per operand.
+ *   mmh_sgemm_ex      the same call with its `&alpha` and `&beta` (cuda/MMult_cuBLAS_1.cpp:14-18,
+ *                     cuda/MMult_cuBLAS_2.cpp:14-25), and the linear layer's bias and ReLU, in ONE launch:
+ *                     C = act(alpha*op(A)*op(B) + beta*C + bias).
  *   mmh_sgemm_host    host-pointer MY_MMult (armv7/test_MMult.c:8,76;
  *                     aarch64/test_MMult.cpp:17,113): does H2D, kernel, D2H.
  *   mmh_sgemm_host_timed  the third flavour of the symbol, `float MY_MMult(m, n, k, a, b, c)`
@@ -311,6 +314,11 @@ int mmh_auto_plan_op(int transa, int transb, int m, int n, int k, int lda, int l
 int mmh_auto_plan_batched(int transa, int transb, int m, int n, int k, int lda, int ldb, int ldc, long long strideA,
                           long long strideB, long long strideC, int batch, int base_align, int cu_count, int *kernel,
                           int *form, long *workgroups);
+/* The same for mmh_sgemm_ex: planned like an op call -- the cost table restricted to the 64x64, 128x64 and 128x128 LDS-DMA
+ * tiles -- for (N, N) too; where mmh_auto_plan answers one of those three, the same tile, form and grid (the epilogue is
+ * not priced).  Host arithmetic only. */
+int mmh_auto_plan_ex(int transa, int transb, int m, int n, int k, int lda, int ldb, int ldc, int base_align, int cu_count,
+                     int *kernel, long *tiles, int *streamk_grid);
 int mmh_get_option(mmh_handle_t handle, int option, int *value);
 
 /* The hot path ------------------------------------------------------------ */
@@ -348,6 +356,41 @@ int mmh_sgemm(mmh_handle_t handle, int m, int n, int k, const float *dA, int lda
 #define MMH_OP_T 1
 int mmh_sgemm_op(mmh_handle_t handle, int transa, int transb, int m, int n, int k, const float *dA, int lda,
                  const float *dB, int ldb, float *dC, int ldc, int accumulate, void *stream);
+
+/* Fused epilogue: C[m x n] = act(alpha * op(A) * op(B) + beta * C + bias) in ONE launch, everything ROW-MAJOR, operands as
+ * mmh_sgemm_op reads them (cublasSgemm's `&alpha`, `&beta`; torch.addmm; the linear layer y = relu(x W^T + b)).
+ * For every element (i, j), all arithmetic fp32, round-to-nearest-even, NO contraction between the epilogue's operations:
+ *   s   = the chain every other entry point computes: s_0 = +0, s_(p+1) = fma(A(i,p), B(p,j), s_p), p ascending (k = 0: +0)
+ *   r1  = fl(alpha * s)
+ *   r2  = r1                      if beta == 0  -- C is NOT read: NaN / Inf in C never reach the result
+ *         fl(r1 + fl(beta * c))   otherwise, c = C(i,j) before the call
+ *   r3  = r2                      bias_mode == MMH_BIAS_NONE
+ *         fl(r2 + dBias[j])       MMH_BIAS_COL (dBias has n floats: the linear layer's bias)
+ *         fl(r2 + dBias[i])       MMH_BIAS_ROW (dBias has m floats: what a column-major caller's per-column bias becomes
+ *                                 after the operand swap of INTEGRATION.md)
+ *   out = r3                      MMH_ACT_NONE
+ *         r3 if (r3 > 0 or r3 is NaN) else +0     MMH_ACT_RELU (-0 and negatives give +0, NaN stays NaN)
+ * So: alpha == 1, beta == 0, no bias, no activation is mmh_sgemm_op(accumulate = 0) bit for bit (1 * s = s).
+ * alpha == 1, beta == 1 is NOT accumulate = 1: there C is the first term of the chain, here it is added behind it.
+ * alpha == 0 is not special (0 * s: NaN / Inf of the product propagate); only beta == 0 skips a read.  Signed zeros,
+ * subnormals and infinities count, NaN payloads do not.
+ * The epilogue runs where a finished tile sits in registers (csrc/sgemm_dma5.hpp, EP) -- no second pass over C, no
+ * workspace; dBias: any 4-byte aligned device pointer.
+ * Arguments as mmh_sgemm_op, plus: bias_mode / activation outside their sets, or bias_mode != MMH_BIAS_NONE with a NULL
+ * dBias: MMH_ERR_INVALID_ARG.  m == 0 or n == 0: MMH_OK, nothing launched.  k == 0: the formula with s = +0 (A and B are
+ * not read).  Kernels: MMH_KERNEL_AUTO (mmh_auto_plan_ex), the 64x64 / 128x64 / 128x128 LDS-DMA tiles (29 / 30 / 31) and
+ * MMH_KERNEL_NAIVE; any other kernel, and operands beyond the tiles' 2 GiB buffer-descriptor window, give
+ * MMH_ERR_UNSUPPORTED with nothing launched and C untouched.  MMH_OPT_SPLITK and MMH_OPT_STREAMK_CHAIN = 0 do not apply;
+ * mmh_reserve_stream covers the launches.  mmh_last_launch names the `ex` instantiation and ends in the operand pair and
+ * a readable epilogue tag: "..., operands NT, epilogue alpha beta bias(col) relu" ("..., epilogue identity"). */
+#define MMH_BIAS_NONE 0
+#define MMH_BIAS_COL 1
+#define MMH_BIAS_ROW 2
+#define MMH_ACT_NONE 0
+#define MMH_ACT_RELU 1
+int mmh_sgemm_ex(mmh_handle_t handle, int transa, int transb, int m, int n, int k, float alpha, const float *dA, int lda,
+                 const float *dB, int ldb, float beta, float *dC, int ldc, const float *dBias, int bias_mode,
+                 int activation, void *stream);
 
 /* Strided batched: C_i = op(A_i) * op(B_i) (+ C_i) for i in [0, batch), everything ROW-MAJOR
  * (cublasSgemmStridedBatched, rocblas_sgemm_strided_batched, torch.bmm).
@@ -497,6 +540,10 @@ int mmh_time_sgemm(mmh_handle_t handle, int m, int n, int k, const float *dA, in
 int mmh_time_sgemm_op(mmh_handle_t handle, int transa, int transb, int m, int n, int k, const float *dA, int lda,
                       const float *dB, int ldb, float *dC, int ldc, int warmup, int reps, void *stream,
                       float *ms_per_call);
+/* mmh_time_sgemm for mmh_sgemm_ex (with beta != 0 every call reads what the call before it wrote). */
+int mmh_time_sgemm_ex(mmh_handle_t handle, int transa, int transb, int m, int n, int k, float alpha, const float *dA, int lda,
+                      const float *dB, int ldb, float beta, float *dC, int ldc, const float *dBias, int bias_mode,
+                      int activation, int warmup, int reps, void *stream, float *ms_per_call);
 /* mmh_time_sgemm for mmh_sgemm_batched (overwrite; ms per batched call). */
 int mmh_time_sgemm_batched(mmh_handle_t handle, int transa, int transb, int m, int n, int k, const float *dA, int lda,
                            long long strideA, const float *dB, int ldb, long long strideB, float *dC, int ldc,

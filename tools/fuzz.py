@@ -4,12 +4,15 @@ independent code path with the same chain semantics -> bit-equal, signed zeros i
 same_bits) on random shapes, leading dimensions, 4-byte-misaligned bases and accumulate
 flags; plus a stream-K stress loop (ragged tile counts, repeated launches; whole rounds
 of the persistent grid) against the one-tile-per-workgroup kernel.
-usage: python tools/fuzz.py [--ops | --batched] [cases] [stress_reps] [seed]
+usage: python tools/fuzz.py [--ops | --batched | --ex] [cases] [stress_reps] [seed]
 --ops: the transposed-operand forms instead (mmh_sgemm_op: NT / TN / TT on AUTO and the 64x64 / 128x64 / 128x128 LDS-DMA
 tiles, plain and stream-K) against the naive kernel's op form, with NaN in every operand's padding and behind its last row.
 --batched: mmh_sgemm_batched on random shapes, batch strides (gaps, strides that are not a multiple of 4, 0 = broadcast),
 ops, bases and accumulate flags -- AUTO (fold, one launch or loop) and the three tiles forced -- against the naive batched
-kernel, with NaN in every padding and gap, none of which may be written."""
+kernel, with NaN in every padding and gap, none of which may be written.
+--ex: mmh_sgemm_ex (C = act(alpha op(A) op(B) + beta C + bias)) on random shapes, op pairs (NN included), leading dimensions,
+misaligned bases and bias pointers and random epilogues -- AUTO and the three tiles, plain and stream-K -- against the naive
+kernel's epilogue form, with NaN in every padding (and in C itself when beta == 0)."""
 import os
 import sys
 
@@ -20,7 +23,8 @@ import how_to_optimize_gemm_amd as H  # noqa: E402
 
 OPS = "--ops" in sys.argv
 BATCHED = "--batched" in sys.argv
-argv = [x for x in sys.argv if x not in ("--ops", "--batched")]
+EX = "--ex" in sys.argv
+argv = [x for x in sys.argv if x not in ("--ops", "--batched", "--ex")]
 cases = int(argv[1]) if len(argv) > 1 else 200
 stress = int(argv[2]) if len(argv) > 2 else 30
 seed = int(argv[3]) if len(argv) > 3 else 1
@@ -123,6 +127,54 @@ def fuzz_ops():
     return nbad
 
 
+def fuzz_ex():
+    """The fused epilogue on the `ex` kernels against sgemm_naive_ex_kernel (mmh_sgemm_ex with MMH_KERNEL_NAIVE)."""
+    variants = ["auto", "mfma_64x64_dma5", "mfma_128x64_dma5", "mfma_128x128_dma5",
+                "mfma_64x64_dma5/sk2", "mfma_128x64_dma5/sk2", "mfma_128x128_dma5/sk2", "mfma_128x128_dma5/sk0"]
+    nbad = 0
+    for case in range(cases):
+        kind, m, n, k = random_shape()
+        ta, tb = int(rng.integers(0, 2)), int(rng.integers(0, 2))
+        ra, ca = (k, m) if ta else (m, k)   # A as stored
+        rb, cb = (n, k) if tb else (k, n)
+        pad = (lambda: 4 * int(rng.integers(0, 3))) if kind == 4 else (lambda: int(rng.integers(0, 9)))
+        lda, ldb, ldc = ca + pad(), cb + pad(), n + pad()
+        offs = [4 * int(rng.integers(0, 2)) if kind == 4 else int(rng.integers(0, 4)) for _ in range(3)]
+        alpha = float(rng.choice([1.0, 0.0, -1.0, 0.7, -1.3, 3.0]))
+        beta = float(rng.choice([0.0, 0.0, 1.0, 0.5, -2.0]))
+        mode, act = int(rng.integers(0, 3)), int(rng.integers(0, 2))
+        boff = int(rng.integers(0, 4))
+        nb = n if mode == H.BIAS_COL else m
+        bias = (torch.rand((nb + boff,), device="cuda") * 2 - 1)[boff:]
+        _, av = strided(ra, ca, lda, offs[0], torch.rand((ra, ca), device="cuda") * 2 - 1)
+        _, bv = strided(rb, cb, ldb, offs[1], torch.rand((rb, cb), device="cuda") * 2 - 1)
+        c0 = torch.rand((m, n), device="cuda") * 2 - 1 if beta != 0.0 else None   # beta == 0: C is NaN all over
+        results = {}
+        for kern in ["naive"] + variants:
+            set_form(kern)
+            cflat, cv = strided(m, n, ldc, offs[2], c0)
+            mm.sgemm_ex(ta, tb, m, n, k, alpha, av.data_ptr(), lda, bv.data_ptr(), ldb, beta, cv.data_ptr(), ldc,
+                        bias.data_ptr() if mode else 0, mode, act, stream)
+            torch.cuda.synchronize()
+            results[kern] = cv[:, :n].clone()
+            if not (bool(torch.isnan(cv[:, n:]).all()) and bool(torch.isnan(cflat[:offs[2]]).all()) and
+                    bool(torch.isnan(cflat[offs[2] + m * ldc:]).all())):
+                nbad += 1
+                print(f"ex case {case} {kern}: wrote outside C window  m,n,k={m},{n},{k} op={ta}{tb}")
+        if bool(torch.isnan(results["naive"]).any()):
+            nbad += 1
+            print(f"ex case {case} naive: NaN in the result  m,n,k={m},{n},{k}")
+        for kern in variants:
+            if not same_bits(results[kern], results["naive"]):
+                nbad += 1
+                d = (results[kern] - results["naive"]).abs().max().item()
+                print(f"ex case {case} {kern}: != naive (max diff {d})  m,n,k={m},{n},{k} op={'NT'[ta]}{'NT'[tb]} "
+                      f"ld={lda},{ldb},{ldc} off={offs} alpha={alpha} beta={beta} bias={mode}+{boff} act={act}")
+    set_form("mfma")
+    print(f"fuzz --ex: {cases} cases x {len(variants)} variants, {nbad} failures")
+    return nbad
+
+
 def fuzz_batched():
     """C_i = op(A_i) op(B_i) (+ C_i) through mmh_sgemm_batched against sgemm_naive_batched_kernel (MMH_KERNEL_NAIVE)."""
     variants = ["auto", "mfma_64x64_dma5", "mfma_128x64_dma5", "mfma_128x128_dma5"]
@@ -201,6 +253,8 @@ if OPS:
     sys.exit(1 if fuzz_ops() else 0)
 if BATCHED:
     sys.exit(1 if fuzz_batched() else 0)
+if EX:
+    sys.exit(1 if fuzz_ex() else 0)
 
 bad = 0
 for case in range(cases):
