@@ -49,6 +49,7 @@ KERNELS = {"auto": KERNEL_AUTO, "valu": KERNEL_VALU, "mfma": KERNEL_MFMA,
 # their names resolve through the library's own table, mmh_kernel_id)
 # kernels that keep the one-chain-per-element contract (bit-identical results); the split-K ids do not
 CHAIN_KERNELS = [k for k in KERNELS if "splitk" not in k]
+_SHORT_NAMES = {v: name for name, v in KERNELS.items() if name != "mfma256"}   # what the plan functions (auto_plan*) call a kernel id
 
 # every symbol include/mmult_hip.h declares (tests assert the .so exports them all)
 EXPORTS = [
@@ -105,24 +106,26 @@ def streamk_plan(tiles: int, nk: int, grid: int):
     return order, place
 
 
+def _dense_ld(transa, transb, m, n, k, lda, ldb, ldc):   # the plan functions' (lda, ldb, ldc): 0 = the dense stored row (k or m, n or k, n)
+    return lda or (m if transa else k), ldb or (k if transb else n), ldc or n
+
+
 def auto_plan(m: int, n: int, k: int, lda: int = 0, ldb: int = 0, ldc: int = 0, base_align: int = 16, cu_count: int = 256):
     """What MMH_KERNEL_AUTO would run for a shape (host arithmetic only, no device): (short kernel name, tiles,
     stream-K grid) -- grid 0 = one workgroup per tile, -1 = needs the device's occupancy query."""
     kern, grid, tiles = C.c_int(), C.c_int(), C.c_long()
-    _check(lib().mmh_auto_plan(m, n, k, lda or k, ldb or n, ldc or n, base_align, cu_count, C.byref(kern), C.byref(tiles),
-                               C.byref(grid)), "mmh_auto_plan")
-    names = {v: name for name, v in KERNELS.items() if name != "mfma256"}
-    return names.get(kern.value, str(kern.value)), tiles.value, grid.value
+    _check(lib().mmh_auto_plan(m, n, k, *_dense_ld(OP_N, OP_N, m, n, k, lda, ldb, ldc), base_align, cu_count, C.byref(kern),
+                               C.byref(tiles), C.byref(grid)), "mmh_auto_plan")
+    return _SHORT_NAMES.get(kern.value, str(kern.value)), tiles.value, grid.value
 
 
 def auto_plan_op(transa: int, transb: int, m: int, n: int, k: int, lda: int = 0, ldb: int = 0, ldc: int = 0, base_align: int = 16,
                  cu_count: int = 256):
     """auto_plan for mmh_sgemm_op (OP_N / OP_T per operand; lda / ldb default to the dense stored rows: k or m, n or k)."""
     kern, grid, tiles = C.c_int(), C.c_int(), C.c_long()
-    _check(lib().mmh_auto_plan_op(transa, transb, m, n, k, lda or (m if transa else k), ldb or (k if transb else n), ldc or n,
-                                  base_align, cu_count, C.byref(kern), C.byref(tiles), C.byref(grid)), "mmh_auto_plan_op")
-    names = {v: name for name, v in KERNELS.items() if name != "mfma256"}
-    return names.get(kern.value, str(kern.value)), tiles.value, grid.value
+    _check(lib().mmh_auto_plan_op(transa, transb, m, n, k, *_dense_ld(transa, transb, m, n, k, lda, ldb, ldc), base_align, cu_count,
+                                  C.byref(kern), C.byref(tiles), C.byref(grid)), "mmh_auto_plan_op")
+    return _SHORT_NAMES.get(kern.value, str(kern.value)), tiles.value, grid.value
 
 
 def auto_plan_ex(transa: int, transb: int, m: int, n: int, k: int, lda: int = 0, ldb: int = 0, ldc: int = 0, base_align: int = 16,
@@ -130,10 +133,9 @@ def auto_plan_ex(transa: int, transb: int, m: int, n: int, k: int, lda: int = 0,
     """auto_plan for mmh_sgemm_ex: planned like an op form -- one of the 64x64 / 128x64 / 128x128 LDS-DMA tiles -- for
     (OP_N, OP_N) too."""
     kern, tiles, grid = C.c_int(), C.c_long(), C.c_int()
-    _check(lib().mmh_auto_plan_ex(transa, transb, m, n, k, lda or (m if transa else k), ldb or (k if transb else n), ldc or n,
-                                  base_align, cu_count, C.byref(kern), C.byref(tiles), C.byref(grid)), "mmh_auto_plan_ex")
-    names = {v: name for name, v in KERNELS.items() if name != "mfma256"}
-    return names.get(kern.value, str(kern.value)), tiles.value, grid.value
+    _check(lib().mmh_auto_plan_ex(transa, transb, m, n, k, *_dense_ld(transa, transb, m, n, k, lda, ldb, ldc), base_align, cu_count,
+                                  C.byref(kern), C.byref(tiles), C.byref(grid)), "mmh_auto_plan_ex")
+    return _SHORT_NAMES.get(kern.value, str(kern.value)), tiles.value, grid.value
 
 
 def auto_plan_batched(transa: int, transb: int, m: int, n: int, k: int, lda: int = 0, ldb: int = 0, ldc: int = 0,
@@ -141,17 +143,14 @@ def auto_plan_batched(transa: int, transb: int, m: int, n: int, k: int, lda: int
                       cu_count: int = 256):
     """What MMH_KERNEL_AUTO would run for mmh_sgemm_batched (host arithmetic only): (short kernel name, form name --
     "fold", "one_launch" or "loop" --, workgroups of all its launches).  Strides default to the packed matrices."""
-    lda = lda or (m if transa else k)
-    ldb = ldb or (k if transb else n)
-    ldc = ldc or n
+    lda, ldb, ldc = _dense_ld(transa, transb, m, n, k, lda, ldb, ldc)
     sa = (k if transa else m) * lda if stride_a < 0 else stride_a
     sb = (n if transb else k) * ldb if stride_b < 0 else stride_b
     sc = m * ldc if stride_c < 0 else stride_c
     kern, form, wgs = C.c_int(), C.c_int(), C.c_long()
     _check(lib().mmh_auto_plan_batched(transa, transb, m, n, k, lda, ldb, ldc, sa, sb, sc, batch, base_align, cu_count,
                                        C.byref(kern), C.byref(form), C.byref(wgs)), "mmh_auto_plan_batched")
-    names = {v: name for name, v in KERNELS.items() if name != "mfma256"}
-    return names.get(kern.value, str(kern.value)), BATCH_FORMS.get(form.value, str(form.value)), wgs.value
+    return _SHORT_NAMES.get(kern.value, str(kern.value)), BATCH_FORMS.get(form.value, str(form.value)), wgs.value
 
 
 def use_timeline_library() -> str:

@@ -12,18 +12,21 @@
 using namespace mmh;
 
 namespace {
-// warmup + reps calls of `call` between one event pair on s: ms per call (every exit destroys what was created: a sticky
-// error or a failed launch inside the loop must not leak events)
+// mmh_time_sgemm_*: warmup + reps calls of `call(stream)` between one event pair on the stream: ms per call (every exit
+// destroys what was created: a sticky error or a failed launch inside the loop must not leak events).  `what`: the entry point.
 template <typename F>
-int time_calls(mmh_context *h, hipStream_t s, int warmup, int reps, float *ms_per_call, const char *what, F call) {
+int time_calls(mmh_context *h, void *stream, int warmup, int reps, float *ms_per_call, const char *what, F call) {
+  if (!h || reps <= 0 || warmup < 0 || !ms_per_call) return MMH_ERR_INVALID_ARG;
+  ENTER(h);
+  hipStream_t s = static_cast<hipStream_t>(stream);
   int rc = MMH_OK;
-  for (int i = 0; i < warmup && rc == MMH_OK; ++i) rc = call();
+  for (int i = 0; i < warmup && rc == MMH_OK; ++i) rc = call(s);
   if (rc != MMH_OK) return rc;
   hipEvent_t t0 = nullptr, t1 = nullptr;
   hipError_t e = hipEventCreate(&t0);
   if (e == hipSuccess) e = hipEventCreate(&t1);
   if (e == hipSuccess) e = hipEventRecord(t0, s);
-  for (int i = 0; i < reps && rc == MMH_OK && e == hipSuccess; ++i) rc = call();
+  for (int i = 0; i < reps && rc == MMH_OK && e == hipSuccess; ++i) rc = call(s);
   float ms = 0.f;
   if (rc == MMH_OK && e == hipSuccess) e = hipEventRecord(t1, s);
   if (rc == MMH_OK && e == hipSuccess) e = hipEventSynchronize(t1);
@@ -393,29 +396,21 @@ int mmh_time_sgemm(mmh_handle_t h, int m, int n, int k, const float *dA, int lda
 }
 int mmh_time_sgemm_op(mmh_handle_t h, int transa, int transb, int m, int n, int k, const float *dA, int lda, const float *dB,
                       int ldb, float *dC, int ldc, int warmup, int reps, void *stream, float *ms_per_call) {
-  if (!h || reps <= 0 || warmup < 0 || !ms_per_call) return MMH_ERR_INVALID_ARG;
-  ENTER(h);
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  return time_calls(h, s, warmup, reps, ms_per_call, "mmh_time_sgemm_op",
-                    [&]() { return sgemm_op_on(h, h->kernel, transa, transb, m, n, k, dA, lda, dB, ldb, dC, ldc, 0, s); });
+  return time_calls(h, stream, warmup, reps, ms_per_call, "mmh_time_sgemm_op", [&](hipStream_t s) {
+    return sgemm_op_on(h, h->kernel, transa, transb, m, n, k, dA, lda, dB, ldb, dC, ldc, 0, s);
+  });
 }
 int mmh_time_sgemm_ex(mmh_handle_t h, int transa, int transb, int m, int n, int k, float alpha, const float *dA, int lda,
                       const float *dB, int ldb, float beta, float *dC, int ldc, const float *dBias, int bias_mode, int activation,
                       int warmup, int reps, void *stream, float *ms_per_call) {
-  if (!h || reps <= 0 || warmup < 0 || !ms_per_call) return MMH_ERR_INVALID_ARG;
-  ENTER(h);
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  return time_calls(h, s, warmup, reps, ms_per_call, "mmh_time_sgemm_ex", [&]() {
+  return time_calls(h, stream, warmup, reps, ms_per_call, "mmh_time_sgemm_ex", [&](hipStream_t s) {
     return sgemm_ex_on(h, h->kernel, transa, transb, m, n, k, alpha, dA, lda, dB, ldb, beta, dC, ldc, dBias, bias_mode, activation, s);
   });
 }
 int mmh_time_sgemm_batched(mmh_handle_t h, int transa, int transb, int m, int n, int k, const float *dA, int lda,
                            long long strideA, const float *dB, int ldb, long long strideB, float *dC, int ldc, long long strideC,
                            int batch, int warmup, int reps, void *stream, float *ms_per_call) {
-  if (!h || reps <= 0 || warmup < 0 || !ms_per_call) return MMH_ERR_INVALID_ARG;
-  ENTER(h);
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  return time_calls(h, s, warmup, reps, ms_per_call, "mmh_time_sgemm_batched", [&]() {
+  return time_calls(h, stream, warmup, reps, ms_per_call, "mmh_time_sgemm_batched", [&](hipStream_t s) {
     return sgemm_batched_on(h, h->kernel, transa, transb, m, n, k, dA, lda, strideA, dB, ldb, strideB, dC, ldc, strideC, batch, 0, s);
   });
 }

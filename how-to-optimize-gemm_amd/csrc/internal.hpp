@@ -11,7 +11,7 @@
 //   launch_dma5.hip  LDS-DMA tiles with loader waves (K2W, sgemm_dma5.hpp): plain, chained stream-K -- the NN forms;
 //   launch_op.hip    ... their transposed-operand forms, launch_batched.hip their strided batched form, launch_ex.hip /
 //                    launch_ex_t.hip their fused-epilogue forms (mmh_sgemm_ex): each TU instantiates launch_dma5.hpp's one
-//                    launcher for its own kernels (built in parallel)
+//                    launcher for the kernels of its own form (NnForm / OpForm / ExForm / BatchedForm; built in parallel)
 //   launch_valu.hip  K1 / K0 (sgemm_valu.hpp)
 //   host_flavour.hip mmh_sgemm_host(_timed): the host-pointer MY_MMult, row-panel pipeline
 //   shard.hip        mmh_shard_*: single-process row-panel shard over RCCL
@@ -354,6 +354,9 @@ struct K2wTile {
   static constexpr int ID = ID_, BM = BM_, BN = BN_, WTM = WTM_, WTN = WTN_, NBUF = NBUF_, NL = NL_, D = D_, RS = RS_;
   static constexpr bool SK = SK_, OPS = OPS_;
 };
+// the template arguments every kernel of sgemm_dma5.hpp starts with, for a K2wTile K (KB = 32): `kernel<MMH_K2W_ARGS(K), ...>` in
+// launch_dma5.hpp's forms and launch_batched.hip's (the kernels are function templates over bare numbers: no alias can name them)
+#define MMH_K2W_ARGS(K) K::BM, K::BN, 32, K::WTM, K::WTN, K::NBUF
 using k2w_tiles = TileTable<
     //      id                            BM   BN WTM WTN NBUF NL D  SK     OPS
     K2wTile<MMH_KERNEL_MFMA_64X64_DMA5,   64,  64, 2, 2, 3, 2, 2, true,  true>,    // 32x32 consumers + two loaders, 48 KiB ring: 3 per CU
@@ -396,17 +399,18 @@ int warm_dma5(mmh_context *ctx, float *scratch, hipStream_t s);
 // launch_op.hip: the op forms (g.ta / g.tb) of the K2W tiles with op forms, and of MMH_KERNEL_NAIVE
 int launch_dma5_op(mmh_context *ctx, int kernel, const GemmArgs &g);   // 1: the shape does not qualify
 int launch_naive_op(const GemmArgs &g);
-int warm_dma5_op(mmh_context *ctx);                                     // LDS opt-ins only (nothing is launched)
-// launch_ex.hip (A stored m x k) / launch_ex_t.hip (A stored k x m): the epilogue forms (g.ex, every g.ta / g.tb) of the same
-// three tiles; the naive kernel with the epilogue written out (k == 0 included: A and B are not read)
+int warm_dma5_op();                                                     // LDS opt-ins only (nothing is launched)
+// launch_ex.hip: the epilogue forms (g.ex, every g.ta / g.tb) of the same three tiles; the naive kernel with the epilogue
+// written out (k == 0 included: A and B are not read)
 int launch_dma5_ex(mmh_context *ctx, int kernel, const GemmArgs &g);   // 1: the shape does not qualify
-int launch_dma5_ex_ta(mmh_context *ctx, int kernel, const GemmArgs &g);
 int launch_naive_ex(const GemmArgs &g);
-int warm_dma5_ex(mmh_context *ctx);                                     // LDS opt-ins only
-int warm_dma5_ex_ta(mmh_context *ctx);
+int warm_dma5_ex();                                                     // LDS opt-ins only
+// (launch_ex_t.hip: the half of those two with A stored k x m -- launch_ex.hip's own callees)
+int launch_dma5_ex_ta(mmh_context *ctx, int kernel, const GemmArgs &g);
+int warm_dma5_ex_ta();
 int launch_dma5_batched(mmh_context *ctx, int kernel, const GemmArgs &g, const BatchArgs &b);
 int launch_naive_batched(const GemmArgs &g, const BatchArgs &b);
-int warm_dma5_batched(mmh_context *ctx);   // LDS opt-ins only (nothing is launched)
+int warm_dma5_batched();   // LDS opt-ins only (nothing is launched)
 // policy.hip: mmh_sgemm_batched / mmh_auto_plan_batched
 int sgemm_batched_on(mmh_context *ctx, int kernel, int ta, int tb, int m, int n, int k, const float *dA, int lda, long long sA,
                      const float *dB, int ldb, long long sB, float *dC, int ldc, long long sC, int batch, int accumulate,

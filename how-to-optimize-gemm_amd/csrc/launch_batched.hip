@@ -1,6 +1,6 @@
 // launch_batched.hip -- launches of mmh_sgemm_batched's one-launch form: the K2W tiles with op forms (k2w_tiles,
 // internal.hpp; sgemm_dma5.hpp, sgemm_mfma_dma5_batched_kernel) over batch x tiles, whole-tile and guarded, every op pair,
-// with launch_dma5.hpp's form, tail split and description; and the naive batched kernel.  A translation unit of its own,
+// as a BatchedForm through launch_dma5.hpp's launch_form, tail split and description; and the naive batched kernel.  A translation unit of its own,
 // like launch_op.hip, so that build.py compiles its instantiations in parallel.  Part of libmmult_hip.so (see internal.hpp).
 #include "launch_dma5.hpp"
 
@@ -28,23 +28,31 @@ sgemm_naive_batched_kernel(int transa, int transb, int m, int n, int k, const fl
 
 namespace {
 
+// the batched kernels of tile K, operand form OP (0 = NN included): plain launches only; `first` is an argument of its own
+template <class K_, int OP>
+struct BatchedForm {
+  using K = K_;
+  static constexpr bool SK = false;
+  static auto plain(bool edge) {
+    return edge ? sgemm_mfma_dma5_batched_kernel<MMH_K2W_ARGS(K), true, K::NL, K::D, OP>
+                : sgemm_mfma_dma5_batched_kernel<MMH_K2W_ARGS(K), false, K::NL, K::D, OP>;
+  }
+};
+
 // One launch (or several of at most kBatchedMaxWorkgroups workgroups each: whole matrices per launch, the pointers
-// advanced to the chunk's first matrix) of tile K over every matrix.  Whole-tile or guarded for the whole matrix set
+// advanced to the chunk's first matrix) of tile F::K over every matrix.  Whole-tile or guarded for the whole matrix set
 // (dma5_form with the strides); the tail split of launch_dma5_tile on the residency of the NN twin.
-template <class K, int OP>
+template <class F>
 int launch_batched_tile(mmh_context *ctx, const GemmArgs &g, const BatchArgs &bt) {
-  constexpr int BM = K::BM, BN = K::BN, KB = 32, WTM = K::WTM, WTN = K::WTN, NBUF = K::NBUF, NL = K::NL, D = K::D;
-  using T = Dma5Tile<BM, BN, KB, WTM, WTN, NBUF, NL>;
-  const int form = dma5_form(ctx, BM, BN, g, bt);
+  using K = typename F::K;
+  using T = Dma5Tile<MMH_K2W_ARGS(K), K::NL>;
+  const int form = dma5_form(ctx, K::BM, K::BN, g, bt);
   if (form < 0) return 1;
   const bool edge = form == 1;
-  auto kern = edge ? sgemm_mfma_dma5_batched_kernel<BM, BN, KB, WTM, WTN, NBUF, true, NL, D, OP>
-                   : sgemm_mfma_dma5_batched_kernel<BM, BN, KB, WTM, WTN, NBUF, false, NL, D, OP>;
-  auto twin = edge ? sgemm_mfma_dma5_kernel<BM, BN, KB, WTM, WTN, NBUF, true, NL, D, 1>
-                   : sgemm_mfma_dma5_kernel<BM, BN, KB, WTM, WTN, NBUF, false, NL, D, 1>;
+  auto kern = F::plain(edge);
   const int ok = allow_big_lds(kern, T::LDS_BYTES);
   if (ok != MMH_OK) return ok;
-  const int nbm = (g.m + BM - 1) / BM, nbn = (g.n + BN - 1) / BN;
+  const int nbm = (g.m + K::BM - 1) / K::BM, nbn = (g.n + K::BN - 1) / K::BN;
   const long per = (long)nbm * nbn;   // (<= 2^17: a matrix inside the descriptor window)
   const long mats = std::max(1L, kBatchedMaxWorkgroups / per);   // matrices per launch
   int acc = g.acc;
@@ -52,69 +60,30 @@ int launch_batched_tile(mmh_context *ctx, const GemmArgs &g, const BatchArgs &bt
   long launches = 0;
   bool split = false;
   for (long b0 = 0; b0 < bt.batch; b0 += mats) {
-    const long nb = std::min(mats, bt.batch - b0);
-    const long tiles = nb * per;
+    const long tiles = std::min(mats, bt.batch - b0) * per;
     const float *A = g.A + b0 * bt.sA, *B = g.B + b0 * bt.sB;
     float *C = g.C + b0 * bt.sC;
-    const long first = dma5_split_first(ctx, twin, T::THREADS, T::LDS_BYTES, tiles, g.k);
-    hipLaunchKernelGGL(kern, dim3((unsigned)first), dim3(T::THREADS), T::LDS_BYTES, g.s, g.m, g.n, g.k, A, g.lda, bt.sA, B, g.ldb,
-                       bt.sB, C, g.ldc, bt.sC, acc, nbm, nbn, 0u);
-    ++launches;
-    if (first < tiles) {
-      hipLaunchKernelGGL(kern, dim3((unsigned)(tiles - first)), dim3(T::THREADS), T::LDS_BYTES, g.s, g.m, g.n, g.k, A, g.lda, bt.sA,
-                         B, g.ldb, bt.sB, C, g.ldc, bt.sC, acc, nbm, nbn, (unsigned)first);
+    const long first = dma5_split_first(ctx, NnForm<K>::plain(edge), T::THREADS, T::LDS_BYTES, tiles, g.k);
+    dma5_launch_rounds(first, tiles, [&](long workgroups, long id0) {
+      hipLaunchKernelGGL(kern, dim3((unsigned)workgroups), dim3(T::THREADS), T::LDS_BYTES, g.s, g.m, g.n, g.k, A, g.lda, bt.sA, B, g.ldb,
+                         bt.sB, C, g.ldc, bt.sC, acc, nbm, nbn, (unsigned)id0);
       ++launches;
-      split = true;
-    }
+    });
+    split |= first < tiles;
     HIP_TRY(hipGetLastError());
   }
-  char what[384];
-  char how[64] = "";
-  if (launches > 1) snprintf(how, sizeof how, " as %ld launches", launches);
-  snprintf(what, sizeof what,
-           "sgemm_mfma_dma5_batched_kernel<%d,%d> wave tile %dx%d, K-slice %d x %d ring buffers by %d loader waves' LDS-DMA, "
-           "fragments %d k-steps ahead, %s%ld workgroups of %d threads%s%s, batch %ld%s",
-           BM, BN, 16 * WTM, 16 * WTN, KB, NBUF, NL, D, edge ? "guarded, " : "", bt.batch * per, T::THREADS,
-           split ? " (the last round as a launch of its own)" : "", op_tag(g), bt.batch, how);
+  char what[kTextSize];
+  int at = dma5_plain_text<K>(what, "sgemm_mfma_dma5_batched_kernel", edge, bt.batch * per, split);
+  at = text_add(what, at, "%s, batch %ld", op_tag(g), bt.batch);
+  if (launches > 1) text_add(what, at, " as %ld launches", launches);
   set_last_launch(what);
   return MMH_OK;
-}
-
-template <int OP>
-int launch_batched_family(mmh_context *ctx, int kernel, const GemmArgs &g, const BatchArgs &b) {
-  return k2w_tiles::with(kernel, [&](auto t) {
-    using K = decltype(t);
-    if constexpr (K::OPS) return launch_batched_tile<K, OP>(ctx, g, b);
-    return 1;
-  }, 1);
-}
-
-// the LDS opt-ins of one op pair's batched instantiations, tile by tile
-template <int OP>
-int warm_batched_families() {
-  return k2w_tiles::each([](auto t) {
-    using K = decltype(t);
-    if constexpr (K::OPS) {
-      constexpr int BM = K::BM, BN = K::BN, KB = 32, WTM = K::WTM, WTN = K::WTN, NBUF = K::NBUF, NL = K::NL, D = K::D;
-      constexpr size_t lds = Dma5Tile<BM, BN, KB, WTM, WTN, NBUF, NL>::LDS_BYTES;
-      const int rc = allow_big_lds(sgemm_mfma_dma5_batched_kernel<BM, BN, KB, WTM, WTN, NBUF, false, NL, D, OP>, lds);
-      if (rc != MMH_OK) return rc;
-      return allow_big_lds(sgemm_mfma_dma5_batched_kernel<BM, BN, KB, WTM, WTN, NBUF, true, NL, D, OP>, lds);
-    } else {
-      return (int)MMH_OK;
-    }
-  });
 }
 
 }  // namespace
 
 int launch_dma5_batched(mmh_context *ctx, int kernel, const GemmArgs &g, const BatchArgs &b) {
-  switch (g.ta | (g.tb << 1)) {
-    case 0: return launch_batched_family<0>(ctx, kernel, g, b);
-    case 1: return launch_batched_family<1>(ctx, kernel, g, b);
-    case 2: return launch_batched_family<2>(ctx, kernel, g, b);
-    default: return launch_batched_family<3>(ctx, kernel, g, b);
-  }
+  return launch_form<BatchedForm, 0, 1, 2, 3>(kernel, g, [&](auto f) { return launch_batched_tile<decltype(f)>(ctx, g, b); });
 }
 
 int launch_naive_batched(const GemmArgs &g, const BatchArgs &b) {
@@ -138,13 +107,6 @@ int launch_naive_batched(const GemmArgs &g, const BatchArgs &b) {
 }
 
 // the batched kernels' LDS opt-ins (> 64 KiB), so that a first batched launch can be captured into a graph
-int warm_dma5_batched(mmh_context *ctx) {
-  (void)ctx;
-  int rc;
-  if ((rc = warm_batched_families<0>()) != MMH_OK) return rc;
-  if ((rc = warm_batched_families<1>()) != MMH_OK) return rc;
-  if ((rc = warm_batched_families<2>()) != MMH_OK) return rc;
-  return warm_batched_families<3>();
-}
+int warm_dma5_batched() { return warm_form<BatchedForm, 0, 1, 2, 3>(); }
 
 }  // namespace mmh

@@ -66,7 +66,7 @@ int launch_nn(mmh_context *ctx, const GemmArgs &g) {
     }
   }
 #endif
-  return launch_dma5_tile<K, 0>(ctx, g);
+  return launch_dma5_tile<NnForm<K>>(ctx, g);
 }
 
 #ifdef MMH_AB_BUILD

@@ -1,7 +1,14 @@
-// launch_dma5.hpp -- the one launcher of the K2W tiles (sgemm_dma5.hpp) that launch_dma5.hip (NN), launch_op.hip (op forms)
-// and launch_batched.hip (its tail split and descriptions) instantiate for their own kernels: whole or guarded, plain or
-// chained stream-K, the tail split.  A tile is a K2wTile (internal.hpp).
+// launch_dma5.hpp -- the one launcher of the K2W tiles (sgemm_dma5.hpp): whole or guarded, plain or chained stream-K, the
+// tail split.  A tile is a K2wTile (internal.hpp); the kernels of a call FORM on it -- NN, transposed operands, the fused
+// epilogue -- are a NnForm / OpForm / ExForm below.  launch_dma5.hip instantiates launch_dma5_tile<NnForm<tile>> (and has the
+// NN warm-up, which launches); launch_op.hip, launch_ex.hip and launch_ex_t.hip instantiate it for their own forms through
+// launch_form / warm_form; launch_batched.hip brings its own form and tile launch to those two and takes the tail split and
+// the description from here.
 #pragma once
+#include <stdarg.h>
+
+#include <tuple>
+
 #include "ab_build.hpp"
 #include "launch_common.hpp"
 #include "sgemm_dma5.hpp"
@@ -40,102 +47,199 @@ long dma5_split_first(mmh_context *ctx, K twin, int threads, size_t lds, long ti
   return dma5_tail_split(tiles, w, cus, k) ? w * cus : tiles;
 }
 
-// One launch of tile K: OP == 0 the NN instantiations (and unchained stream-K, and the tools build's A/B option bits), OP = 1 / 2 / 3 (g.ta | g.tb << 1) the op instantiations -- bounded by the NN twins' residency, so that an
-// op launch has the grid and the rounds of the NN launch of its shape (tests/test_op_kernel_resources.py holds the op
-// kernels' registers to at least the NN twins' co-residency).  Returns MMH_OK, an error, or 1: the shape does not qualify.
-// EX: the epilogue kernels (mmh_sgemm_ex, g.alpha .. g.act) of operand form OP, 0 = NN included: the launch an op form of the
-// shape gets -- the same bounds, grid, rounds, tail split and stream-K decision (tests/test_ex_kernel_resources.py holds
-// their registers to the NN twins' co-residency too) -- with the epilogue behind the common arguments.
-template <class K, int OP, bool EX = false>
+// ---- the kernels of a form ----
+// What launch_dma5_tile needs to know of a call form on tile K, operand form OP = g.ta | g.tb << 1: the plain kernel (whole-tile
+// / guarded) and, where K::SK, the stream-K kernel (... x unchained / chained parts), their names in the launch descriptions,
+// the tag a description ends in, what the kernels take behind the common arguments (a tuple) and the value of `accumulate`.
+// The two kernels of a pair have one function type; those of another form have another: this is where that difference lives.
+template <class K_>
+struct NnForm {   // mmh_sgemm: the only form with unchained stream-K and the tools build's A/B option bits
+  using K = K_;
+  static constexpr bool NN = true, SK = K::SK;
+  static constexpr const char *plain_name = "sgemm_mfma_dma5_kernel", *streamk_name = "sgemm_dma5_streamk_kernel";
+  static auto plain(bool edge) {
+    return edge ? sgemm_mfma_dma5_kernel<MMH_K2W_ARGS(K), true, K::NL, K::D, K::RS>
+                : sgemm_mfma_dma5_kernel<MMH_K2W_ARGS(K), false, K::NL, K::D, K::RS>;
+  }
+  // the guarded chained stream-K kernel: its residency bounds the persistent grid of every form (a function of its own, so
+  // that the other forms' units instantiate this kernel alone)
+  static auto streamk_bound() { return sgemm_dma5_streamk_kernel<MMH_K2W_ARGS(K), true, true, K::NL, K::D, K::RS>; }
+  static auto streamk(bool edge, bool chained) {
+    return edge ? (chained ? streamk_bound() : sgemm_dma5_streamk_kernel<MMH_K2W_ARGS(K), true, false, K::NL, K::D, K::RS>)
+                : (chained ? sgemm_dma5_streamk_kernel<MMH_K2W_ARGS(K), false, true, K::NL, K::D, K::RS>
+                           : sgemm_dma5_streamk_kernel<MMH_K2W_ARGS(K), false, false, K::NL, K::D, K::RS>);
+  }
+  static std::string tag(const GemmArgs &) { return {}; }
+  static std::tuple<> extra(const GemmArgs &) { return {}; }
+  static int acc(const mmh_context *ctx, const GemmArgs &g) {   // (tools build: A/B switches ride in the upper bits, sgemm_dma5.hpp)
+    if (kAbBuild && ctx) return g.acc | (ctx->ab_nodefer ? 2 : 0) | (ctx->ab_whole_ranges ? 4 : 0) | ((ctx->ab_group_m & 0xff) << 8);
+    return g.acc;
+  }
+};
+template <class K_, int OP>
+struct OpForm {   // mmh_sgemm_op, OP = 1 / 2 / 3: the chained stream-K kernels alone, which keep the bits
+  using K = K_;
+  static constexpr bool NN = false, SK = K::SK;
+  static constexpr const char *plain_name = "sgemm_mfma_dma5_op_kernel", *streamk_name = "sgemm_dma5_op_streamk_kernel";
+  static auto plain(bool edge) {
+    return edge ? sgemm_mfma_dma5_op_kernel<MMH_K2W_ARGS(K), true, K::NL, K::D, OP>
+                : sgemm_mfma_dma5_op_kernel<MMH_K2W_ARGS(K), false, K::NL, K::D, OP>;
+  }
+  static auto streamk(bool edge, bool) {
+    return edge ? sgemm_dma5_op_streamk_kernel<MMH_K2W_ARGS(K), true, K::NL, K::D, OP>
+                : sgemm_dma5_op_streamk_kernel<MMH_K2W_ARGS(K), false, K::NL, K::D, OP>;
+  }
+  static std::string tag(const GemmArgs &g) { return op_tag(g); }   // (no allocation: the small-string buffer holds it)
+  static std::tuple<> extra(const GemmArgs &) { return {}; }
+  static int acc(const mmh_context *, const GemmArgs &g) { return g.acc; }
+};
+template <class K_, int OP>
+struct ExForm {   // mmh_sgemm_ex (g.alpha .. g.act), OP = 0 .. 3, NN included: the epilogue behind the common arguments
+  using K = K_;
+  static constexpr bool NN = false, SK = K::SK;
+  static constexpr const char *plain_name = "sgemm_mfma_dma5_ex_kernel", *streamk_name = "sgemm_dma5_ex_streamk_kernel";
+  static auto plain(bool edge) {
+    return edge ? sgemm_mfma_dma5_ex_kernel<MMH_K2W_ARGS(K), true, K::NL, K::D, OP>
+                : sgemm_mfma_dma5_ex_kernel<MMH_K2W_ARGS(K), false, K::NL, K::D, OP>;
+  }
+  static auto streamk(bool edge, bool) {
+    return edge ? sgemm_dma5_ex_streamk_kernel<MMH_K2W_ARGS(K), true, K::NL, K::D, OP>
+                : sgemm_dma5_ex_streamk_kernel<MMH_K2W_ARGS(K), false, K::NL, K::D, OP>;
+  }
+  static std::string tag(const GemmArgs &g) { return ex_tag(g); }
+  static std::tuple<Dma5Epilogue> extra(const GemmArgs &g) { return {ex_args(g)}; }
+  static int acc(const mmh_context *, const GemmArgs &) { return 0; }   // (the chain starts at +0: beta C is the epilogue's)
+};
+
+// A launch description is written into a char[kTextSize] (the longest is under 300 characters) piece by piece: text_add
+// appends at `at` and returns where the next piece goes -- never past the buffer: a longer text is cut, as by one snprintf.
+constexpr int kTextSize = 448;
+inline int text_add(char *what, int at, const char *format, ...) __attribute__((format(printf, 3, 4)));
+inline int text_add(char *what, int at, const char *format, ...) {
+  va_list args;
+  va_start(args, format);
+  const int n = vsnprintf(what + at, kTextSize - at, format, args);
+  va_end(args);
+  return std::min(at + std::max(n, 0), kTextSize - 1);
+}
+// How every description of a launch on tile K starts ...
+template <class K>
+int dma5_tile_text(char *what, const char *kernel) {
+  return text_add(what, 0, "%s<%d,%d> wave tile %dx%d, K-slice %d x %d ring buffers by %d loader wave%s' LDS-DMA, fragments %d k-steps ahead",
+                  kernel, K::BM, K::BN, 16 * K::WTM, 16 * K::WTN, 32, K::NBUF, K::NL, K::NL > 1 ? "s" : "", K::D);
+}
+// ... and the description of a plain launch (one workgroup per tile), up to its tag
+template <class K>
+int dma5_plain_text(char *what, const char *kernel, bool edge, long workgroups, bool split) {
+  return text_add(what, dma5_tile_text<K>(what, kernel), ", %s%ld workgroups of %d threads%s", edge ? "guarded, " : "", workgroups,
+                  Dma5Tile<MMH_K2W_ARGS(K), K::NL>::THREADS, split ? " (the last round as a launch of its own)" : "");
+}
+// The first launch, and the last round as a launch of its own (dma5_split_first): launch(workgroups, id of the first one)
+template <class L>
+void dma5_launch_rounds(long first, long tiles, L launch) {
+  launch(first, 0L);
+  if (first < tiles) launch(tiles - first, first);
+}
+
+// One launch of tile F::K in form F -- bounded by the NN twins' residency whatever the form, so that an op or `ex` launch has
+// the grid, the rounds, the tail split and the stream-K decision of the NN launch of its shape (tests/test_op_kernel_resources.py
+// and tests/test_ex_kernel_resources.py hold those kernels' registers to at least the NN twins' co-residency).  Returns MMH_OK,
+// an error, or 1: the shape does not qualify.
+template <class F>
 int launch_dma5_tile(mmh_context *ctx, const GemmArgs &g) {
-  constexpr int BM = K::BM, BN = K::BN, KB = 32, WTM = K::WTM, WTN = K::WTN, NBUF = K::NBUF, NL = K::NL, D = K::D, RS = K::RS;
-  using T = Dma5Tile<BM, BN, KB, WTM, WTN, NBUF, NL>;
+  using K = typename F::K;
+  constexpr int BM = K::BM, BN = K::BN, KB = 32;
+  using T = Dma5Tile<MMH_K2W_ARGS(K), K::NL>;
   const int form = dma5_form(ctx, BM, BN, g);
   if (form < 0) return 1;
   const bool edge = form == 1;
-  char what[320];
-  GemmArgs ga = g;   // (tools build: A/B switches ride in the upper bits of `accumulate`, sgemm_dma5.hpp)
-  if (kAbBuild && OP == 0 && !EX && ctx) ga.acc |= (ctx->ab_nodefer ? 2 : 0) | (ctx->ab_whole_ranges ? 4 : 0) | ((ctx->ab_group_m & 0xff) << 8);
-  if constexpr (K::SK) {
+  GemmArgs ga = g;
+  ga.acc = F::acc(ctx, g);
+  if constexpr (F::SK) {
     if (ctx && ctx->streamk) {
-      // the parts of a range as ONE stream of slices (MMH_OPT_STREAMK_CHAIN, default on), or each with a prologue of its own
-      // (NN only: the op forms have the chained kernels alone, which keep the bits)
-      const bool chained = OP != 0 || EX || ctx->sk_chain != 0;
-      auto occ = sgemm_dma5_streamk_kernel<BM, BN, KB, WTM, WTN, NBUF, true, true, NL, D, RS>;   // (the NN launch's bound)
-      auto kern = occ;
-      if constexpr (EX) {
-        (void)kern;
-        (void)allow_big_lds(occ, T::LDS_BYTES);
-      } else if constexpr (OP == 0) {
-        kern = edge ? (chained ? occ : sgemm_dma5_streamk_kernel<BM, BN, KB, WTM, WTN, NBUF, true, false, NL, D, RS>)
-                    : (chained ? sgemm_dma5_streamk_kernel<BM, BN, KB, WTM, WTN, NBUF, false, true, NL, D, RS>
-                               : sgemm_dma5_streamk_kernel<BM, BN, KB, WTM, WTN, NBUF, false, false, NL, D, RS>);
-        // (tools build, option 103: the residency of the instantiation that is launched -- DESIGN.md section 8, found on the CPU)
+      // the parts of a range as ONE stream of slices (MMH_OPT_STREAMK_CHAIN, default on), or each with a prologue of its own (NN only)
+      const bool chained = !F::NN || ctx->sk_chain != 0;
+      auto occ = NnForm<K>::streamk_bound();
+      auto kern = F::streamk(edge, chained);
+      // (tools build, option 103: the residency of the instantiation that is launched -- DESIGN.md section 8, found on the CPU)
+      if constexpr (F::NN) {
         if (kAbBuild && ctx->ab_own_occ && !edge) occ = kern;
       } else {
-        kern = edge ? sgemm_dma5_op_streamk_kernel<BM, BN, KB, WTM, WTN, NBUF, true, NL, D, OP>
-                    : sgemm_dma5_op_streamk_kernel<BM, BN, KB, WTM, WTN, NBUF, false, NL, D, OP>;
         (void)allow_big_lds(occ, T::LDS_BYTES);
       }
-      snprintf(what, sizeof what,
-               "%s<%d,%d> wave tile %dx%d, K-slice %d x %d ring buffers by %d loader wave%s' LDS-DMA, fragments %d k-steps ahead%s%s",
-               EX ? "sgemm_dma5_ex_streamk_kernel" : OP ? "sgemm_dma5_op_streamk_kernel" : "sgemm_dma5_streamk_kernel", BM, BN, 16 * WTM,
-               16 * WTN, KB, NBUF, NL, NL > 1 ? "s" : "", D, chained ? ", chained parts" : "", edge ? ", guarded" : "");
+      char what[kTextSize];
+      text_add(what, dma5_tile_text<K>(what, F::streamk_name), "%s%s", chained ? ", chained parts" : "", edge ? ", guarded" : "");
       // a thin last tile row / column (dma5_raster dispatches those last, at a fraction of a tile's cost) does not make a
       // tile count ragged: plain or persistent is decided on the whole tiles alone
       const int order_min10 = (BM == 128 && BN == 128) ? 10 : 0;   // (phase-ordered tables from one 128x128 tile per workgroup)
-      int sk;
-      if constexpr (EX) {
-        auto kx = edge ? sgemm_dma5_ex_streamk_kernel<BM, BN, KB, WTM, WTN, NBUF, true, NL, D, OP>
-                       : sgemm_dma5_ex_streamk_kernel<BM, BN, KB, WTM, WTN, NBUF, false, NL, D, OP>;
-        sk = launch_streamk(ctx, kx, occ, BM, BN, KB, T::THREADS, T::LDS_BYTES, what, ga, full_tiles(g.m, g.n, BM, BN), order_min10,
-                            ex_args(g));
-        if (sk == MMH_OK) set_last_launch(last_launch_ref() + ex_tag(g));
-      } else {
-        sk = launch_streamk(ctx, kern, occ, BM, BN, KB, T::THREADS, T::LDS_BYTES, what, ga, full_tiles(g.m, g.n, BM, BN), order_min10);
-        if (OP && sk == MMH_OK) set_last_launch(last_launch_ref() + op_tag(g));
-      }
+      const int sk = std::apply([&](auto... x) {
+        return launch_streamk(ctx, kern, occ, BM, BN, KB, T::THREADS, T::LDS_BYTES, what, ga, full_tiles(g.m, g.n, BM, BN), order_min10, x...);
+      }, F::extra(g));
+      if (!F::NN && sk == MMH_OK) set_last_launch(last_launch_ref() + F::tag(g));
       if (sk <= 0) return sk;
     }
   }
   const int nbm = (g.m + BM - 1) / BM, nbn = (g.n + BN - 1) / BN;
-  auto twin = edge ? sgemm_mfma_dma5_kernel<BM, BN, KB, WTM, WTN, NBUF, true, NL, D, RS>
-                   : sgemm_mfma_dma5_kernel<BM, BN, KB, WTM, WTN, NBUF, false, NL, D, RS>;
   const long tiles = (long)nbm * nbn;
-  const long first = dma5_split_first(ctx, twin, T::THREADS, T::LDS_BYTES, tiles, g.k);
-  const int acc_bits = edge ? g.acc : ga.acc;
-  if constexpr (EX) {
-    auto kx = edge ? sgemm_mfma_dma5_ex_kernel<BM, BN, KB, WTM, WTN, NBUF, true, NL, D, OP>
-                   : sgemm_mfma_dma5_ex_kernel<BM, BN, KB, WTM, WTN, NBUF, false, NL, D, OP>;
-    const int ok = allow_big_lds(kx, T::LDS_BYTES);
-    if (ok != MMH_OK) return ok;
-    hipLaunchKernelGGL(kx, dim3((unsigned)first), dim3(T::THREADS), T::LDS_BYTES, g.s, g.m, g.n, g.k, g.A, g.lda, g.B, g.ldb, g.C,
-                       g.ldc, 0, nbm, nbn, ex_args(g));
-    if (first < tiles)
-      hipLaunchKernelGGL(kx, dim3((unsigned)(tiles - first)), dim3(T::THREADS), T::LDS_BYTES, g.s, g.m, g.n, g.k, g.A, g.lda, g.B,
-                         g.ldb, g.C, g.ldc, (int)((unsigned)(first >> 3) << 16), nbm, nbn, ex_args(g));
-  } else {
-  auto kern = twin;
-  if constexpr (OP != 0)
-    kern = edge ? sgemm_mfma_dma5_op_kernel<BM, BN, KB, WTM, WTN, NBUF, true, NL, D, OP>
-                : sgemm_mfma_dma5_op_kernel<BM, BN, KB, WTM, WTN, NBUF, false, NL, D, OP>;
+  const long first = dma5_split_first(ctx, NnForm<K>::plain(edge), T::THREADS, T::LDS_BYTES, tiles, g.k);
+  const int acc_bits = edge ? F::acc(nullptr, g) : ga.acc;   // (the guarded plain kernels take no A/B bits)
+  auto kern = F::plain(edge);
   const int ok = allow_big_lds(kern, T::LDS_BYTES);
   if (ok != MMH_OK) return ok;
-  hipLaunchKernelGGL(kern, dim3((unsigned)first), dim3(T::THREADS), T::LDS_BYTES, g.s, g.m, g.n, g.k, g.A, g.lda, g.B, g.ldb, g.C,
-                     g.ldc, acc_bits, nbm, nbn);
-  if (first < tiles)
-    hipLaunchKernelGGL(kern, dim3((unsigned)(tiles - first)), dim3(T::THREADS), T::LDS_BYTES, g.s, g.m, g.n, g.k, g.A, g.lda, g.B,
-                       g.ldb, g.C, g.ldc, acc_bits | (int)((unsigned)(first >> 3) << 16), nbm, nbn);
-  }
+  dma5_launch_rounds(first, tiles, [&](long workgroups, long id0) {
+    std::apply([&](auto... x) {
+      hipLaunchKernelGGL(kern, dim3((unsigned)workgroups), dim3(T::THREADS), T::LDS_BYTES, g.s, g.m, g.n, g.k, g.A, g.lda, g.B, g.ldb, g.C,
+                         g.ldc, acc_bits | (int)((unsigned)(id0 >> 3) << 16), nbm, nbn, x...);
+    }, F::extra(g));
+  });
   HIP_TRY(hipGetLastError());
-  snprintf(what, sizeof what,
-           "%s<%d,%d> wave tile %dx%d, K-slice %d x %d ring buffers by %d loader wave%s' LDS-DMA, fragments %d k-steps ahead, "
-           "%s%ld workgroups of %d threads%s%s",
-           EX ? "sgemm_mfma_dma5_ex_kernel" : OP ? "sgemm_mfma_dma5_op_kernel" : "sgemm_mfma_dma5_kernel", BM, BN, 16 * WTM, 16 * WTN, KB,
-           NBUF, NL, NL > 1 ? "s" : "", D, edge ? "guarded, " : "", tiles, T::THREADS,
-           first < tiles ? " (the last round as a launch of its own)" : "", EX ? "" : op_tag(g));
-  set_last_launch(EX ? what + ex_tag(g) : std::string(what));
+  char what[kTextSize];
+  text_add(what, dma5_plain_text<K>(what, F::plain_name, edge, tiles, first < tiles), "%s", F::tag(g).c_str());
+  set_last_launch(what);
   return MMH_OK;
+}
+
+// launch(F<tile of `kernel`, g.ta | g.tb << 1>{}) for the operand forms OPS a translation unit instantiates of form F, on the
+// tiles with op forms; 1 (does not qualify) for every other tile and operand form
+template <template <class, int> class F, int... OPS, class L>
+int launch_form(int kernel, const GemmArgs &g, L launch) {
+  const int op = g.ta | (g.tb << 1);
+  return k2w_tiles::with(kernel, [&](auto t) {
+    using K = decltype(t);
+    int rc = 1;
+    if constexpr (K::OPS) {
+      auto launch_if = [&](auto form, int form_op) {
+        if (op == form_op) rc = launch(form);
+      };
+      (launch_if(F<K, OPS>{}, OPS), ...);
+    }
+    return rc;
+  }, 1);
+}
+// the LDS opt-ins (> 64 KiB) of the same instantiations, operand form by operand form and tile by tile, so that a first launch
+// can be captured into a graph like an NN one (persistent launches may ask for up to 160 KiB: launch_streamk's residency pin)
+template <class F>
+int warm_form_tile() {
+  constexpr size_t lds = Dma5Tile<MMH_K2W_ARGS(F::K), F::K::NL>::LDS_BYTES;
+  int rc;
+  if ((rc = allow_big_lds(F::plain(false), lds)) != MMH_OK || (rc = allow_big_lds(F::plain(true), lds)) != MMH_OK) return rc;
+  if constexpr (F::SK)
+    if ((rc = allow_big_lds(F::streamk(false, true), 160 * 1024)) == MMH_OK) rc = allow_big_lds(F::streamk(true, true), 160 * 1024);
+  return rc;
+}
+template <template <class, int> class F, int... OPS>
+int warm_form() {
+  int rc = MMH_OK;
+  auto warm_op = [&](auto op) {   // one operand form on every tile with op forms, unless an earlier one failed
+    if (rc != MMH_OK) return;
+    rc = k2w_tiles::each([](auto t) {
+      using K = decltype(t);
+      if constexpr (K::OPS) return warm_form_tile<F<K, decltype(op)::value>>();
+      else return (int)MMH_OK;
+    });
+  };
+  (warm_op(std::integral_constant<int, OPS>{}), ...);
+  return rc;
 }
 
 }  // namespace mmh

@@ -1,8 +1,9 @@
 // launch_ex.hip -- launches of the fused-epilogue forms (mmh_sgemm_ex: C = act(alpha op(A) op(B) + beta C + bias), GemmArgs::ex)
 // with A stored m x k (NN, NT) on the K2W tiles with op forms, and the naive kernel with the epilogue written out the same
 // way -- the independent reference on the device, what MMH_KERNEL_NAIVE runs and what an empty contraction (k == 0) runs.
-// launch_ex_t.hip holds the forms with A stored k x m.  Part of libmmult_hip.so (see internal.hpp).
-#include "launch_ex.hpp"
+// launch_ex_t.hip holds the forms with A stored k x m (24 kernels per unit, so that build.py compiles them side by side) and
+// is reached through this unit's two entry points.  Part of libmmult_hip.so (see internal.hpp).
+#include "launch_dma5.hpp"
 
 namespace mmh {
 
@@ -27,7 +28,8 @@ sgemm_naive_ex_kernel(int transa, int transb, int m, int n, int k, const float *
 }
 
 int launch_dma5_ex(mmh_context *ctx, int kernel, const GemmArgs &g) {
-  return g.tb ? launch_ex_family<2>(ctx, kernel, g) : launch_ex_family<0>(ctx, kernel, g);
+  if (g.ta) return launch_dma5_ex_ta(ctx, kernel, g);
+  return launch_form<ExForm, 0, 2>(kernel, g, [&](auto f) { return launch_dma5_tile<decltype(f)>(ctx, g); });
 }
 
 int launch_naive_ex(const GemmArgs &g) {
@@ -40,10 +42,9 @@ int launch_naive_ex(const GemmArgs &g) {
 }
 
 // the ex kernels' LDS opt-ins (> 64 KiB), so that a first ex launch can be captured into a graph like an op one
-int warm_dma5_ex(mmh_context *ctx) {
-  (void)ctx;
-  const int rc = warm_ex_families<0>();
-  return rc != MMH_OK ? rc : warm_ex_families<2>();
+int warm_dma5_ex() {
+  const int rc = warm_form<ExForm, 0, 2>();
+  return rc != MMH_OK ? rc : warm_dma5_ex_ta();
 }
 
 }  // namespace mmh

@@ -1,6 +1,6 @@
 // launch_op.hip -- launches of the transposed-operand forms (mmh_sgemm_op, GemmArgs::ta / tb): the K2W tiles with op forms
-// (k2w_tiles, internal.hpp; sgemm_dma5.hpp, OP) through launch_dma5.hpp's launcher, and the naive kernel with two index
-// swaps.  A translation unit of its own so that build.py compiles the op instantiations beside launch_dma5.hip's NN ones.
+// (k2w_tiles, internal.hpp; sgemm_dma5.hpp, OP) as launch_dma5.hpp's OpForm through its launcher, and the naive kernel with
+// two index swaps.  A translation unit of its own so that build.py compiles the op instantiations beside launch_dma5.hip's NN ones.
 // Part of libmmult_hip.so (see internal.hpp).
 #include "launch_dma5.hpp"
 
@@ -21,47 +21,8 @@ sgemm_naive_op_kernel(int transa, int transb, int m, int n, int k, const float *
   C[(size_t)row * ldc + col] = acc;
 }
 
-namespace {
-
-template <int OP>
-int launch_op_family(mmh_context *ctx, int kernel, const GemmArgs &g) {
-  return k2w_tiles::with(kernel, [&](auto t) {
-    using K = decltype(t);
-    if constexpr (K::OPS) return launch_dma5_tile<K, OP>(ctx, g);
-    return 1;
-  }, 1);
-}
-
-// the LDS opt-ins of one op pair's instantiations, tile by tile
-template <int OP>
-int warm_op_families() {
-  return k2w_tiles::each([](auto t) {
-    using K = decltype(t);
-    if constexpr (K::OPS) {
-      constexpr int BM = K::BM, BN = K::BN, KB = 32, WTM = K::WTM, WTN = K::WTN, NBUF = K::NBUF, NL = K::NL, D = K::D;
-      constexpr size_t lds = Dma5Tile<BM, BN, KB, WTM, WTN, NBUF, NL>::LDS_BYTES;
-      int rc;
-      if ((rc = allow_big_lds(sgemm_mfma_dma5_op_kernel<BM, BN, KB, WTM, WTN, NBUF, false, NL, D, OP>, lds)) != MMH_OK) return rc;
-      if ((rc = allow_big_lds(sgemm_mfma_dma5_op_kernel<BM, BN, KB, WTM, WTN, NBUF, true, NL, D, OP>, lds)) != MMH_OK) return rc;
-      // (persistent launches may ask for up to 160 KiB: launch_streamk's residency pin)
-      if ((rc = allow_big_lds(sgemm_dma5_op_streamk_kernel<BM, BN, KB, WTM, WTN, NBUF, false, NL, D, OP>, 160 * 1024)) != MMH_OK)
-        return rc;
-      return allow_big_lds(sgemm_dma5_op_streamk_kernel<BM, BN, KB, WTM, WTN, NBUF, true, NL, D, OP>, 160 * 1024);
-    } else {
-      return (int)MMH_OK;
-    }
-  });
-}
-
-}  // namespace
-
 int launch_dma5_op(mmh_context *ctx, int kernel, const GemmArgs &g) {
-  switch (g.ta | (g.tb << 1)) {
-    case 1: return launch_op_family<1>(ctx, kernel, g);
-    case 2: return launch_op_family<2>(ctx, kernel, g);
-    case 3: return launch_op_family<3>(ctx, kernel, g);
-    default: return 1;
-  }
+  return launch_form<OpForm, 1, 2, 3>(kernel, g, [&](auto f) { return launch_dma5_tile<decltype(f)>(ctx, g); });
 }
 
 int launch_naive_op(const GemmArgs &g) {
@@ -73,12 +34,6 @@ int launch_naive_op(const GemmArgs &g) {
 }
 
 // the op kernels' LDS opt-ins (> 64 KiB), so that a first op launch can be captured into a graph like an NN one
-int warm_dma5_op(mmh_context *ctx) {
-  (void)ctx;
-  int rc;
-  if ((rc = warm_op_families<1>()) != MMH_OK) return rc;
-  if ((rc = warm_op_families<2>()) != MMH_OK) return rc;
-  return warm_op_families<3>();
-}
+int warm_dma5_op() { return warm_form<OpForm, 1, 2, 3>(); }
 
 }  // namespace mmh

@@ -1,6 +1,7 @@
 // policy.hip -- sgemm_on(): argument checks, the empty contraction, and MMH_KERNEL_AUTO's tile choice (the
-// reference's `NEW := MMult_xxx` makefile switch, cuda/makefile:1-3, as a run-time decision).  Pure host code;
-// the kernels are launched by launch_reg.hip / launch_dma.hip / launch_valu.hip.
+// reference's `NEW := MMult_xxx` makefile switch, cuda/makefile:1-3, as a run-time decision); call_on(): the same for
+// mmh_sgemm_op / _ex / _batched, one front end behind three argument packers; the plan entry points.  Pure host code;
+// the kernels are launched by the launch_*.hip units.
 #include <algorithm>
 
 #include "internal.hpp"
@@ -231,108 +232,7 @@ int sgemm_on(mmh_context *ctx, int kernel, int m, int n, int k, const float *dA,
   return (d <= 0 || row->fallback < 0) ? d : launch_reg(ctx, row->fallback, g);
 }
 
-// mmh_sgemm_op.  NN is mmh_sgemm's own path.  The op forms run on the three K2W tiles that have them (AUTO: the table
-// restricted to those; forced: 29 / 30 / 31) and on the naive kernel; every other kernel, and operands beyond the 2 GiB
-// descriptor window (the register-staged fallback is NN-only), are refused before anything is launched.  Split-K and
-// MMH_OPT_STREAMK_CHAIN = 0 are NN A/B switches: the op forms run the chained stream-K kernels, which keep the bits.
-int sgemm_op_on(mmh_context *ctx, int kernel, int ta, int tb, int m, int n, int k, const float *dA, int lda, const float *dB,
-                int ldb, float *dC, int ldc, int accumulate, hipStream_t s) {
-  if ((ta != MMH_OP_N && ta != MMH_OP_T) || (tb != MMH_OP_N && tb != MMH_OP_T)) {
-    set_last_error("transa / transb must be MMH_OP_N or MMH_OP_T");
-    return MMH_ERR_INVALID_ARG;
-  }
-  if (!ta && !tb) return sgemm_on(ctx, kernel, m, n, k, dA, lda, dB, ldb, dC, ldc, accumulate, s);
-  int rc = check_gemm_args(m, n, k, dA, lda, dB, ldb, dC, ldc, ta, tb);
-  if (rc != MMH_OK) {
-    set_last_error("invalid argument");
-    return rc;
-  }
-  if (m == 0 || n == 0) return MMH_OK;
-  if (kernel != MMH_KERNEL_AUTO && kernel != MMH_KERNEL_NAIVE && !has_op_forms(kernel)) {
-    set_last_error("transposed operands run on MMH_KERNEL_AUTO, the 64x64 / 128x64 / 128x128 LDS-DMA tiles (29 / 30 / 31) and "
-                   "MMH_KERNEL_NAIVE only");
-    return MMH_ERR_UNSUPPORTED;
-  }
-  if (k == 0) {
-    if (!accumulate)
-      HIP_TRY(hipMemset2DAsync(dC, (size_t)ldc * sizeof(float), 0, (size_t)n * sizeof(float), (size_t)m, s));
-    return MMH_OK;
-  }
-  GemmArgs g{m, n, k, dA, lda, dB, ldb, dC, ldc, accumulate ? 1 : 0, s};
-  g.ta = ta;
-  g.tb = tb;
-  if (kernel == MMH_KERNEL_NAIVE) return launch_naive_op(g);
-  if (kernel == MMH_KERNEL_AUTO) {
-    const Plan plan = auto_plan_for(ctx, g);
-    if (plan.kernel >= 0) {
-      g.form = plan.form;
-      g.sk_w = plan.sk_w;
-      kernel = plan.kernel;
-    }
-  }
-  if (has_op_forms(kernel)) {
-    const int d = launch_dma5_op(ctx, kernel, g);
-    if (d <= 0) return d;
-  }
-  set_last_error("transposed operands need the LDS-DMA tiles: an operand lies beyond their 2 GiB descriptor window, or "
-                 "MMH_OPT_DMA_EDGE keeps this shape off them (the register-staged tiles take NN operands only)");
-  return MMH_ERR_UNSUPPORTED;
-}
-
-// mmh_sgemm_ex: C = act(alpha op(A) op(B) + beta C + bias).  Planned like an op call, NN included (auto_plan_for, g.ex): the
-// `ex` kernels exist on the three tiles with op forms; MMH_KERNEL_NAIVE and the empty contraction (s = +0: A and B are not
-// read) run the naive kernel with the same epilogue.  Everything else is refused before anything is launched.
-int sgemm_ex_on(mmh_context *ctx, int kernel, int ta, int tb, int m, int n, int k, float alpha, const float *dA, int lda,
-                const float *dB, int ldb, float beta, float *dC, int ldc, const float *dBias, int bias_mode, int activation,
-                hipStream_t s) {
-  if ((ta != MMH_OP_N && ta != MMH_OP_T) || (tb != MMH_OP_N && tb != MMH_OP_T)) {
-    set_last_error("transa / transb must be MMH_OP_N or MMH_OP_T");
-    return MMH_ERR_INVALID_ARG;
-  }
-  if (bias_mode < MMH_BIAS_NONE || bias_mode > MMH_BIAS_ROW || (activation != MMH_ACT_NONE && activation != MMH_ACT_RELU) ||
-      (bias_mode != MMH_BIAS_NONE && !dBias)) {
-    set_last_error("bias_mode must be MMH_BIAS_NONE / _COL / _ROW (with a bias pointer), activation MMH_ACT_NONE / _RELU");
-    return MMH_ERR_INVALID_ARG;
-  }
-  int rc = check_gemm_args(m, n, k, dA, lda, dB, ldb, dC, ldc, ta, tb);
-  if (rc != MMH_OK) {
-    set_last_error("invalid argument");
-    return rc;
-  }
-  if (m == 0 || n == 0) return MMH_OK;
-  if (kernel != MMH_KERNEL_AUTO && kernel != MMH_KERNEL_NAIVE && !has_op_forms(kernel)) {
-    set_last_error("the fused epilogue runs on MMH_KERNEL_AUTO, the 64x64 / 128x64 / 128x128 LDS-DMA tiles (29 / 30 / 31) and "
-                   "MMH_KERNEL_NAIVE only");
-    return MMH_ERR_UNSUPPORTED;
-  }
-  GemmArgs g{m, n, k, dA, lda, dB, ldb, dC, ldc, 0, s};
-  g.ta = ta;
-  g.tb = tb;
-  g.ex = 1;
-  g.alpha = alpha;
-  g.beta = beta;
-  g.bias = bias_mode != MMH_BIAS_NONE ? dBias : nullptr;
-  g.bias_mode = bias_mode;
-  g.act = activation;
-  if (k == 0 || kernel == MMH_KERNEL_NAIVE) return launch_naive_ex(g);
-  if (kernel == MMH_KERNEL_AUTO) {
-    const Plan plan = auto_plan_for(ctx, g);
-    if (plan.kernel >= 0) {
-      g.form = plan.form;
-      g.sk_w = plan.sk_w;
-      kernel = plan.kernel;
-    }
-  }
-  if (has_op_forms(kernel)) {
-    const int d = ta ? launch_dma5_ex_ta(ctx, kernel, g) : launch_dma5_ex(ctx, kernel, g);
-    if (d <= 0) return d;
-  }
-  set_last_error("the fused epilogue needs the LDS-DMA tiles: an operand lies beyond their 2 GiB descriptor window, or "
-                 "MMH_OPT_DMA_EDGE keeps this shape off them");
-  return MMH_ERR_UNSUPPORTED;
-}
-
-// ---- mmh_sgemm_batched ----
+// ---- mmh_sgemm_batched's plan; argument rules the call and the plan entry points share ----
 namespace {
 struct BatchPlan {
   int form = 0;      // MMH_BATCH_FORM_*
@@ -379,9 +279,11 @@ BatchPlan batched_plan_for(const mmh_context *ctx, const GemmArgs &g, const Batc
   return bp;
 }
 
+bool op_flags_ok(int ta, int tb) { return (ta == MMH_OP_N || ta == MMH_OP_T) && (tb == MMH_OP_N || tb == MMH_OP_T); }
+
 // the argument rules of mmh_sgemm_batched that need no pointer (mmh_auto_plan_batched shares them)
-int check_batch_args(int ta, int tb, int m, int n, int ldc, long long sA, long long sB, long long sC, int batch) {
-  if ((ta != MMH_OP_N && ta != MMH_OP_T) || (tb != MMH_OP_N && tb != MMH_OP_T)) return MMH_ERR_INVALID_ARG;
+int check_batch_args(int ta, int tb, int m, int n, int ldc, long long sA, long long sB, long long sC, long batch) {
+  if (!op_flags_ok(ta, tb)) return MMH_ERR_INVALID_ARG;
   if (batch < 0 || sA < 0 || sB < 0 || sC < 0) return MMH_ERR_INVALID_ARG;
   if (batch > 1 && m > 0 && n > 0 && ldc >= n && sC < (long long)(m - 1) * ldc + n) return MMH_ERR_INVALID_ARG;   // C matrices overlap
   return MMH_OK;
@@ -392,7 +294,7 @@ int check_batch_args(int ta, int tb, int m, int n, int ldc, long long sA, long l
 // for a shape mmh_sgemm_op refuses.
 int plan_inputs(int ta, int tb, int m, int n, int k, int lda, int ldb, int ldc, int base_align, int cu_count, mmh_context *ctx,
                 GemmArgs *g) {
-  if ((ta != MMH_OP_N && ta != MMH_OP_T) || (tb != MMH_OP_N && tb != MMH_OP_T)) return MMH_ERR_INVALID_ARG;
+  if (!op_flags_ok(ta, tb)) return MMH_ERR_INVALID_ARG;
   if (m <= 0 || n <= 0 || k <= 0 || lda < (ta ? m : k) || ldb < (tb ? k : n) || ldc < n) return MMH_ERR_INVALID_ARG;
   ctx->cu_count = cu_count > 0 ? cu_count : 256;
   const uintptr_t base = (uintptr_t)1 << 32, off = base_align >= 16 ? 0 : 4;
@@ -402,58 +304,136 @@ int plan_inputs(int ta, int tb, int m, int n, int k, int lda, int ldb, int ldc, 
   g->tb = tb;
   return MMH_OK;
 }
-}  // namespace
 
-// mmh_sgemm_batched: the argument rules, the empty cases, then the form (AUTO: batched_plan_for; 29 / 30 / 31: one
-// launch on that tile; MMH_KERNEL_NAIVE: the naive batched kernel; anything else is refused before anything is launched)
-int sgemm_batched_on(mmh_context *ctx, int kernel, int ta, int tb, int m, int n, int k, const float *dA, int lda, long long sA,
-                     const float *dB, int ldb, long long sB, float *dC, int ldc, long long sC, int batch, int accumulate,
-                     hipStream_t s) {
-  int rc = check_batch_args(ta, tb, m, n, ldc, sA, sB, sC, batch);
-  if (rc == MMH_OK && batch > 0) rc = check_gemm_args(m, n, k, dA, lda, dB, ldb, dC, ldc, ta, tb);
+// ---- mmh_sgemm_op, mmh_sgemm_ex, mmh_sgemm_batched: the call forms of the three K2W tiles with op forms ----
+// They run on those tiles (AUTO: the table restricted to them; forced: 29 / 30 / 31) and on a naive kernel of their own; every
+// other kernel, and operands beyond the 2 GiB descriptor window (the register-staged fallback is NN-only), are refused before
+// anything is launched.  Split-K and MMH_OPT_STREAMK_CHAIN = 0 are NN A/B switches: these forms run the chained stream-K
+// kernels, which keep the bits.  What differs between them: their own argument rules, the empty contraction, the naive
+// kernel, AUTO's plan, the launcher -- and the subject of the two refusals.
+enum class Call { Op, Ex, Batched };
+struct CallText {
+  const char *run, *need, *what, *why;
+};
+constexpr CallText kCallText[] = {
+    {"transposed operands run", "transposed operands need", "an operand", " (the register-staged tiles take NN operands only)"},
+    {"the fused epilogue runs", "the fused epilogue needs", "an operand", ""},
+    {"batched GEMMs run", "batched GEMMs need", "a matrix", ""}};
+
+int naive_call(Call call, const GemmArgs &g, const BatchArgs &b) {
+  return call == Call::Batched ? launch_naive_batched(g, b) : call == Call::Ex ? launch_naive_ex(g) : launch_naive_op(g);
+}
+// (1: not a tile with op forms -- AUTO found none --, or the shape does not qualify)
+int tile_call(Call call, mmh_context *ctx, int kernel, const GemmArgs &g, const BatchArgs &b) {
+  return call == Call::Batched ? launch_dma5_batched(ctx, kernel, g, b)
+                               : call == Call::Ex ? launch_dma5_ex(ctx, kernel, g) : launch_dma5_op(ctx, kernel, g);
+}
+
+// g: the call's arguments as they came (ta / tb, bias and its mode unchecked; acc 0 / 1); b: a batched call's
+int call_on(mmh_context *ctx, Call call, int kernel, GemmArgs g, const BatchArgs &b = BatchArgs{}) {
+  const CallText &text = kCallText[(int)call];
+  const bool batched = call == Call::Batched, ex = call == Call::Ex;
+  if (!op_flags_ok(g.ta, g.tb)) {
+    set_last_error(batched ? "invalid argument" : "transa / transb must be MMH_OP_N or MMH_OP_T");
+    return MMH_ERR_INVALID_ARG;
+  }
+  // NN is mmh_sgemm's own path -- but for an epilogue call, which is planned like an op call (auto_plan_for, g.ex)
+  if (call == Call::Op && !g.ta && !g.tb) return sgemm_on(ctx, kernel, g.m, g.n, g.k, g.A, g.lda, g.B, g.ldb, g.C, g.ldc, g.acc, g.s);
+  if (ex && (g.bias_mode < MMH_BIAS_NONE || g.bias_mode > MMH_BIAS_ROW || (g.act != MMH_ACT_NONE && g.act != MMH_ACT_RELU) ||
+             (g.bias_mode != MMH_BIAS_NONE && !g.bias))) {
+    set_last_error("bias_mode must be MMH_BIAS_NONE / _COL / _ROW (with a bias pointer), activation MMH_ACT_NONE / _RELU");
+    return MMH_ERR_INVALID_ARG;
+  }
+  if (g.bias_mode == MMH_BIAS_NONE) g.bias = nullptr;
+  int rc = batched ? check_batch_args(g.ta, g.tb, g.m, g.n, g.ldc, b.sA, b.sB, b.sC, b.batch) : MMH_OK;
+  if (rc == MMH_OK && b.batch > 0) rc = check_gemm_args(g.m, g.n, g.k, g.A, g.lda, g.B, g.ldb, g.C, g.ldc, g.ta, g.tb);
   if (rc != MMH_OK) {
     set_last_error("invalid argument");
     return rc;
   }
-  if (batch == 0 || m == 0 || n == 0) return MMH_OK;
+  if (b.batch == 0 || g.m == 0 || g.n == 0) return MMH_OK;
   if (kernel != MMH_KERNEL_AUTO && kernel != MMH_KERNEL_NAIVE && !has_op_forms(kernel)) {
-    set_last_error("batched GEMMs run on MMH_KERNEL_AUTO, the 64x64 / 128x64 / 128x128 LDS-DMA tiles (29 / 30 / 31) and "
+    set_last_error(std::string(text.run) + " on MMH_KERNEL_AUTO, the 64x64 / 128x64 / 128x128 LDS-DMA tiles (29 / 30 / 31) and "
                    "MMH_KERNEL_NAIVE only");
     return MMH_ERR_UNSUPPORTED;
   }
-  GemmArgs g{m, n, k, dA, lda, dB, ldb, dC, ldc, accumulate ? 1 : 0, s};
-  g.ta = ta;
-  g.tb = tb;
-  const BatchArgs b{sA, sB, sC, batch};
-  if (k == 0) {   // C = 0 (overwrite) or C unchanged (accumulate); the zeros go out through the naive kernel, matrix by matrix
-    if (!accumulate) return launch_naive_batched(g, b);
+  if (g.k == 0 && !ex) {
+    // empty contraction: C = 0 (overwrite) or C unchanged (accumulate); a batch's zeros go out through the naive kernel,
+    // matrix by matrix.  (ex: s = +0 through the naive kernel's epilogue, A and B are not read)
+    if (g.acc) return MMH_OK;
+    if (batched) return launch_naive_batched(g, b);
+    HIP_TRY(hipMemset2DAsync(g.C, (size_t)g.ldc * sizeof(float), 0, (size_t)g.n * sizeof(float), (size_t)g.m, g.s));
     return MMH_OK;
   }
-  if (kernel == MMH_KERNEL_NAIVE) return launch_naive_batched(g, b);
-  if (kernel == MMH_KERNEL_AUTO) {
+  if (g.k == 0 || kernel == MMH_KERNEL_NAIVE) return naive_call(call, g, b);
+  if (kernel == MMH_KERNEL_AUTO && batched) {
     const BatchPlan bp = batched_plan_for(ctx, g, b);
+    const int batch = (int)b.batch;
     if (bp.form == MMH_BATCH_FORM_FOLD) {
-      rc = sgemm_op_on(ctx, MMH_KERNEL_AUTO, ta, tb, batch * m, n, k, dA, lda, dB, ldb, dC, ldc, accumulate, s);
+      rc = sgemm_op_on(ctx, MMH_KERNEL_AUTO, g.ta, g.tb, batch * g.m, g.n, g.k, g.A, g.lda, g.B, g.ldb, g.C, g.ldc, g.acc, g.s);
       if (rc == MMH_OK)
-        set_last_launch(last_launch_ref() + ", batch " + std::to_string(batch) + " folded into one " + std::to_string(batch * m) +
+        set_last_launch(last_launch_ref() + ", batch " + std::to_string(batch) + " folded into one " + std::to_string(batch * g.m) +
                         "-row GEMM");
       return rc;
     }
     if (bp.form == MMH_BATCH_FORM_LOOP) {
       for (int i = 0; i < batch && rc == MMH_OK; ++i)
-        rc = sgemm_op_on(ctx, MMH_KERNEL_AUTO, ta, tb, m, n, k, dA + i * sA, lda, dB + i * sB, ldb, dC + i * sC, ldc, accumulate, s);
+        rc = sgemm_op_on(ctx, MMH_KERNEL_AUTO, g.ta, g.tb, g.m, g.n, g.k, g.A + i * b.sA, g.lda, g.B + i * b.sB, g.ldb, g.C + i * b.sC,
+                         g.ldc, g.acc, g.s);
       if (rc == MMH_OK)
         set_last_launch(last_launch_ref() + ", batch " + std::to_string(batch) + " as a loop of " + std::to_string(batch) +
                         " per-matrix launches");
       return rc;
     }
     kernel = bp.kernel;
+  } else if (kernel == MMH_KERNEL_AUTO) {
+    const Plan plan = auto_plan_for(ctx, g);
+    if (plan.kernel >= 0) {
+      g.form = plan.form;
+      g.sk_w = plan.sk_w;
+      kernel = plan.kernel;
+    }
   }
-  const int d = launch_dma5_batched(ctx, kernel, g, b);
+  const int d = tile_call(call, ctx, kernel, g, b);
   if (d <= 0) return d;
-  set_last_error("batched GEMMs need the LDS-DMA tiles: a matrix lies beyond their 2 GiB descriptor window, or "
-                 "MMH_OPT_DMA_EDGE keeps this shape off them");
+  set_last_error(std::string(text.need) + " the LDS-DMA tiles: " + text.what + " lies beyond their 2 GiB descriptor window, or "
+                 "MMH_OPT_DMA_EDGE keeps this shape off them" + text.why);
   return MMH_ERR_UNSUPPORTED;
+}
+}  // namespace
+
+int sgemm_op_on(mmh_context *ctx, int kernel, int ta, int tb, int m, int n, int k, const float *dA, int lda, const float *dB,
+                int ldb, float *dC, int ldc, int accumulate, hipStream_t s) {
+  GemmArgs g{m, n, k, dA, lda, dB, ldb, dC, ldc, accumulate ? 1 : 0, s};
+  g.ta = ta;
+  g.tb = tb;
+  return call_on(ctx, Call::Op, kernel, g);
+}
+
+// mmh_sgemm_ex: C = act(alpha op(A) op(B) + beta C + bias); acc is 0 -- the chain starts at +0, beta C is the epilogue's
+int sgemm_ex_on(mmh_context *ctx, int kernel, int ta, int tb, int m, int n, int k, float alpha, const float *dA, int lda,
+                const float *dB, int ldb, float beta, float *dC, int ldc, const float *dBias, int bias_mode, int activation,
+                hipStream_t s) {
+  GemmArgs g{m, n, k, dA, lda, dB, ldb, dC, ldc, 0, s};
+  g.ta = ta;
+  g.tb = tb;
+  g.ex = 1;
+  g.alpha = alpha;
+  g.beta = beta;
+  g.bias = dBias;
+  g.bias_mode = bias_mode;
+  g.act = activation;
+  return call_on(ctx, Call::Ex, kernel, g);
+}
+
+// mmh_sgemm_batched (AUTO: batched_plan_for; 29 / 30 / 31: one launch on that tile; MMH_KERNEL_NAIVE: the naive batched kernel)
+int sgemm_batched_on(mmh_context *ctx, int kernel, int ta, int tb, int m, int n, int k, const float *dA, int lda, long long sA,
+                     const float *dB, int ldb, long long sB, float *dC, int ldc, long long sC, int batch, int accumulate,
+                     hipStream_t s) {
+  GemmArgs g{m, n, k, dA, lda, dB, ldb, dC, ldc, accumulate ? 1 : 0, s};
+  g.ta = ta;
+  g.tb = tb;
+  return call_on(ctx, Call::Batched, kernel, g, BatchArgs{sA, sB, sC, batch});
 }
 
 // mmh_auto_plan_batched: batched_plan_for on a default handle, as host arithmetic

@@ -388,9 +388,9 @@ int warm_context(mmh_context *h) {
   HIP_TRY(hipMemsetAsync(scratch.p, 0, scratch.bytes, nullptr));
   float *p = static_cast<float *>(scratch.p);
   if ((rc = warm_reg(h, p, nullptr)) == MMH_OK && (rc = warm_dma(h, p, nullptr)) == MMH_OK &&
-      (rc = warm_dma5(h, p, nullptr)) == MMH_OK && (rc = warm_valu(h, p, nullptr)) == MMH_OK && (rc = warm_dma5_op(h)) == MMH_OK &&
-      (rc = warm_dma5_ex(h)) == MMH_OK && (rc = warm_dma5_ex_ta(h)) == MMH_OK)
-    rc = warm_dma5_batched(h);
+      (rc = warm_dma5(h, p, nullptr)) == MMH_OK && (rc = warm_valu(h, p, nullptr)) == MMH_OK && (rc = warm_dma5_op()) == MMH_OK &&
+      (rc = warm_dma5_ex()) == MMH_OK)
+    rc = warm_dma5_batched();
 #ifdef MMH_AB_BUILD
   if (rc == MMH_OK) rc = warm_dma32(h, p, nullptr);   // (K2M: tools/ab/)
 #endif
