@@ -4,7 +4,11 @@ C = act(alpha op(A) op(B) + beta C + bias) in one launch, every rounding defined
 The expectation is built HERE from the pinned oracle and numpy alone, never from the library: s = the oracle's fused chain,
 then float32 numpy operations one at a time -- each rounds once, which is the contract.  32-bit patterns are compared
 wherever the expectation is not NaN (and there the result must be NaN too); with the inputs below the expectation has no
-NaN except in the one case that feeds NaN through beta != 0 on purpose."""
+NaN except in the one case that feeds NaN through beta != 0 on purpose.
+
+tests/test_gpu_ex_parity.py::EX_INSTANTIATIONS pins each of the 48 `ex` instantiations by name and runs the special values
+of the contract (inf, -0, NaN through ReLU, alpha == 0).  sgemm_naive_ex_kernel shares dma5_epilogue_apply with the tiles:
+for the epilogue the numpy expectation is the only independent reference."""
 import os
 
 import numpy as np
