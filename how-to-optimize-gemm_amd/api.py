@@ -67,6 +67,7 @@ EXPORTS = [
     "mmh_sgemm_op", "mmh_time_sgemm_op", "mmh_auto_plan_op",
     "mmh_sgemm_batched", "mmh_time_sgemm_batched", "mmh_auto_plan_batched",
     "mmh_sgemm_ex", "mmh_time_sgemm_ex", "mmh_auto_plan_ex",
+    "mmh_sgemm_batched_ex", "mmh_time_sgemm_batched_ex", "mmh_auto_plan_batched_ex",
 ]
 
 
@@ -153,6 +154,22 @@ def auto_plan_batched(transa: int, transb: int, m: int, n: int, k: int, lda: int
     return _SHORT_NAMES.get(kern.value, str(kern.value)), BATCH_FORMS.get(form.value, str(form.value)), wgs.value
 
 
+def auto_plan_batched_ex(transa: int, transb: int, m: int, n: int, k: int, lda: int = 0, ldb: int = 0, ldc: int = 0,
+                         stride_a: int = -1, stride_b: int = -1, stride_c: int = -1, stride_bias: int = 0,
+                         bias_mode: int = BIAS_NONE, batch: int = 1, base_align: int = 16, cu_count: int = 256):
+    """auto_plan_batched for mmh_sgemm_batched_ex: the fold form only where the biases fold too (no bias, a column bias with
+    stride_bias == 0, a row bias with stride_bias == m), the loop form at batch x auto_plan_ex's per-matrix plan."""
+    lda, ldb, ldc = _dense_ld(transa, transb, m, n, k, lda, ldb, ldc)
+    sa = (k if transa else m) * lda if stride_a < 0 else stride_a
+    sb = (n if transb else k) * ldb if stride_b < 0 else stride_b
+    sc = m * ldc if stride_c < 0 else stride_c
+    kern, form, wgs = C.c_int(), C.c_int(), C.c_long()
+    _check(lib().mmh_auto_plan_batched_ex(transa, transb, m, n, k, lda, ldb, ldc, sa, sb, sc, stride_bias, int(bias_mode), batch,
+                                          base_align, cu_count, C.byref(kern), C.byref(form), C.byref(wgs)),
+           "mmh_auto_plan_batched_ex")
+    return _SHORT_NAMES.get(kern.value, str(kern.value)), BATCH_FORMS.get(form.value, str(form.value)), wgs.value
+
+
 def use_timeline_library() -> str:
     """tools/dma_timeline.py only: the A/B library built with per-workgroup timeline stamps."""
     global _lib_path
@@ -233,6 +250,11 @@ def lib() -> C.CDLL:
     L.mmh_sgemm_batched.argtypes = batched + [C.c_int, vp]
     L.mmh_time_sgemm_batched.argtypes = batched + [C.c_int, C.c_int, vp, fp]
     L.mmh_auto_plan_batched.argtypes = [C.c_int] * 8 + [ll] * 3 + [C.c_int] * 3 + [ip, ip, C.POINTER(C.c_long)]
+    # (handle, transa, transb, m, n, k, alpha, A, lda, strideA, B, ldb, strideB, beta, C, ldc, strideC, bias, strideBias, bias_mode, activation, batch)
+    batched_ex = [vp] + [C.c_int] * 5 + [C.c_float, vp, C.c_int, ll, vp, C.c_int, ll, C.c_float, vp, C.c_int, ll, vp, ll] + [C.c_int] * 3
+    L.mmh_sgemm_batched_ex.argtypes = batched_ex + [vp]
+    L.mmh_time_sgemm_batched_ex.argtypes = batched_ex + [C.c_int, C.c_int, vp, fp]
+    L.mmh_auto_plan_batched_ex.argtypes = [C.c_int] * 8 + [ll] * 4 + [C.c_int] * 4 + [ip, ip, C.POINTER(C.c_long)]
     L.mmh_sgemm_host.argtypes = gemm + [C.c_int]
     L.mmh_sgemm_host_timed.argtypes = gemm + [C.c_int, C.POINTER(C.c_float)]
     L.mmh_igemm_s8.argtypes = gemm + [C.c_int, vp]
@@ -451,6 +473,16 @@ class MMult:
         _check(lib().mmh_sgemm_batched(self._h, int(transa), int(transb), m, n, k, dA, lda, stride_a, dB, ldb, stride_b, dC, ldc,
                                        stride_c, batch, int(bool(accumulate)), stream), "mmh_sgemm_batched")
 
+    def sgemm_batched_ex(self, transa, transb, m, n, k, alpha, dA: int, lda, stride_a, dB: int, ldb, stride_b, beta, dC: int, ldc,
+                         stride_c, batch, dBias: int = 0, stride_bias: int = 0, bias_mode: int = BIAS_NONE,
+                         activation: int = ACT_NONE, stream: int = 0) -> None:
+        """C_i = act(alpha op(A_i) op(B_i) + beta C_i + bias_i) for i < batch in one call (include/mmult_hip.h,
+        mmh_sgemm_batched_ex): per matrix what sgemm_ex computes on it alone.  stride_bias: elements between two matrices'
+        biases, 0 = one bias for the whole batch."""
+        _check(lib().mmh_sgemm_batched_ex(self._h, int(transa), int(transb), m, n, k, float(alpha), dA, lda, stride_a, dB, ldb,
+                                          stride_b, float(beta), dC, ldc, stride_c, dBias or None, stride_bias, int(bias_mode),
+                                          int(activation), batch, stream), "mmh_sgemm_batched_ex")
+
     def MY_MMult_device(self, m, n, k, d_A: int, lda, d_B: int, ldb, d_C: int, ldc, stream: int = 0):
         """cuda/test_MMult.cpp:102 -- MY_MMult(handle, m, n, k, d_A, k, d_B, n, d_C, n):
         C = A*B on device pointers, asynchronous."""
@@ -658,6 +690,94 @@ class MMult:
         self.sgemm_batched(ta, tb, m, n, k, pa, lda, sa, pb, ldb, sb, pc, ldc, sc, batch, accumulate, stream)
         return out
 
+    def _batched_ex(self, what, a, b, out, alpha, beta, bias, stride_bias, activation):
+        """out[i] = act(alpha a[i] @ b[i] + beta out[i] + bias_i) through mmh_sgemm_batched_ex on torch's current stream; a / b /
+        out as bmm takes them; bias: None, or a column bias -- a tensor whose n floats per matrix are dense, matrix i's
+        stride_bias elements behind matrix i - 1's."""
+        import torch
+        if a.dtype != torch.float32 or b.dtype != torch.float32:
+            raise MMultError(ERR_INVALID_ARG, what, "fp32 only")
+        if a.dim() != 3 or b.dim() != 3 or a.shape[0] != b.shape[0] or a.shape[2] != b.shape[1]:
+            raise MMultError(ERR_INVALID_ARG, what, "need 3-D operands whose batch and inner dimensions agree")
+        (batch, m, k), n = a.shape, b.shape[2]
+        pa, lda, ta, sa = self._batched_args(a, batch, m, k, what + "(A)", True)
+        pb, ldb, tb, sb = self._batched_args(b, batch, k, n, what + "(B)", True)
+        pc, ldc, _, sc = self._batched_args(out, batch, m, n, what + "(C)", False)
+        pbias = 0
+        if bias is not None:
+            if not bias.is_cuda or bias.device.index != self.device or bias.dtype != torch.float32 or stride_bias < 0 or \
+                    (n > 1 and bias.stride(-1) != 1):
+                raise MMultError(ERR_INVALID_ARG, what, "the bias is an fp32 tensor on the handle's device, one dense run of floats per "
+                                 "matrix, one float per output column")
+            pbias = bias.data_ptr()
+        if batch == 0:
+            return out
+        stream = torch.cuda.current_stream(a.device).cuda_stream
+        self.sgemm_batched_ex(ta, tb, m, n, k, alpha, pa, lda, sa, pb, ldb, sb, beta, pc, ldc, sc, batch, pbias, stride_bias,
+                              BIAS_COL if bias is not None else BIAS_NONE, activation, stream)
+        return out
+
+    def baddbmm(self, input, a, b, *, beta=1.0, alpha=1.0, out=None):
+        """torch.baddbmm: out[i] = beta input[i] + alpha a[i] @ b[i] in ONE call (mmh_sgemm_batched_ex), addmm's rules per matrix.
+        `input` (batch, m, n): in place when `out is input`, otherwise copied into `out` first (not when beta == 0; out.copy_
+        broadcasts any shape torch broadcasts); `input` (n,) or (batch, 1, n) with beta == 1: the kernel's column bias, shared
+        or per matrix (no copy).  a, b as bmm takes them: transposed views, expand()ed batches."""
+        import torch
+        if a.dim() != 3 or b.dim() != 3:
+            raise MMultError(ERR_INVALID_ARG, "baddbmm", "need 3-D operands")
+        batch, m, n = a.shape[0], a.shape[1], b.shape[2]
+        if float(beta) == 1.0 and out is not input and n >= 1 and (
+                (input.dim() == 1 and input.shape[0] == n) or
+                (input.dim() == 3 and tuple(input.shape) == (batch, 1, n))):
+            if out is None:
+                out = torch.empty((batch, m, n), dtype=torch.float32, device=a.device)
+            stride_bias = input.stride(0) if input.dim() == 3 and batch > 1 else 0
+            return self._batched_ex("baddbmm", a, b, out, alpha, 0.0, input, stride_bias, ACT_NONE)
+        if out is None:
+            out = torch.empty((batch, m, n), dtype=torch.float32, device=a.device)
+        if out is not input:
+            try:
+                fits = tuple(torch.broadcast_shapes(tuple(input.shape), (batch, m, n))) == (batch, m, n)
+            except RuntimeError:
+                fits = False
+            if not fits:
+                raise MMultError(ERR_INVALID_ARG, "baddbmm", f"input must broadcast to ({batch},{m},{n})")
+            if float(beta) != 0.0:
+                # (nothing is copied into an `out` the call will refuse: a CPU tensor, matrices that overlap)
+                _, ldc, _, sc = self._batched_args(out, batch, m, n, "baddbmm(C)", False)
+                if batch > 1 and sc < (m - 1) * ldc + n:
+                    raise MMultError(ERR_INVALID_ARG, "baddbmm(C)", "the matrices of out overlap")
+                if input.device != out.device:
+                    raise MMultError(ERR_INVALID_ARG, "baddbmm", "input and out live on different devices")
+                out.copy_(input)
+        return self._batched_ex("baddbmm", a, b, out, alpha, beta, None, 0, ACT_NONE)
+
+    def batched_linear(self, x, w, bias=None, activation=None, out=None):
+        """A batch of equally shaped linear layers (+ ReLU) in ONE call: y[i] = act(x[i] @ w[i].t() + bias[i]).  x (batch, rows,
+        in); w (batch, out, in), or (out, in) shared by the whole batch -- read in place (NT); bias (batch, out) or (out,);
+        activation None or "relu"."""
+        import torch
+        if activation not in (None, "relu"):
+            raise MMultError(ERR_INVALID_ARG, "batched_linear", "activation is None or 'relu'")
+        if x.dim() != 3 or w.dim() not in (2, 3):
+            raise MMultError(ERR_INVALID_ARG, "batched_linear", "need a 3-D x (batch, rows, in) and a w (batch, out, in) or (out, in)")
+        batch = x.shape[0]
+        if w.dim() == 2:
+            w = w.unsqueeze(0).expand(batch, -1, -1)
+        if w.shape[0] != batch:
+            raise MMultError(ERR_INVALID_ARG, "batched_linear", "x and w differ in their batch")
+        n = w.shape[1]
+        stride_bias = 0
+        if bias is not None:
+            if bias.dim() == 2 and tuple(bias.shape) == (batch, n):
+                stride_bias = bias.stride(0) if batch > 1 else 0
+            elif not (bias.dim() == 1 and bias.shape[0] == n):
+                raise MMultError(ERR_INVALID_ARG, "batched_linear", f"bias must be ({batch},{n}) or ({n},)")
+        if out is None:
+            out = torch.empty((batch, x.shape[1], n), dtype=torch.float32, device=x.device)
+        return self._batched_ex("batched_linear", x, w.transpose(1, 2), out, 1.0, 0.0, bias, stride_bias,
+                                ACT_RELU if activation == "relu" else ACT_NONE)
+
     def igemm_s8(self, a, b, out=None, accumulate: bool = False):
         """int8 x int8 -> int32 for CUDA tensors (any int8; every sum must fit in int32)."""
         import torch
@@ -767,6 +887,17 @@ class MMult:
                                        dBias or None, int(bias_mode), int(activation), warmup, reps, stream, C.byref(ms)),
                "mmh_time_sgemm_ex")
         return ms.value
+
+    def time_sgemm_batched_ex(self, transa, transb, m, n, k, alpha, dA, lda, stride_a, dB, ldb, stride_b, beta, dC, ldc, stride_c,
+                              batch, dBias=0, stride_bias=0, bias_mode=BIAS_NONE, activation=ACT_NONE, warmup=1, reps=20,
+                              stream: int = 0) -> float:
+        """time_sgemm for mmh_sgemm_batched_ex: ms per batched call."""
+        ms = C.c_float(0.0)
+        _check(lib().mmh_time_sgemm_batched_ex(self._h, int(transa), int(transb), m, n, k, float(alpha), dA, lda, stride_a, dB, ldb,
+                                               stride_b, float(beta), dC, ldc, stride_c, dBias or None, stride_bias, int(bias_mode),
+                                               int(activation), batch, warmup, reps, stream, C.byref(ms)),
+               "mmh_time_sgemm_batched_ex")
+        return float(ms.value)
 
     def time_sgemm_batched(self, transa, transb, m, n, k, dA, lda, stride_a, dB, ldb, stride_b, dC, ldc, stride_c, batch,
                            warmup=1, reps=20, stream: int = 0) -> float:
@@ -917,7 +1048,7 @@ def sgemm_sharded(ngpus: int, a: np.ndarray, b: np.ndarray, kernel="mfma"):
 
 
 __all__ = ["MMult", "ShardedMMult", "MMultError", "lib", "use_ab_library", "device_count", "rccl_version", "shard_rows", "shard_chunks",
-           "kernel_name", "last_launch", "use_timeline_library", "streamk_plan", "auto_plan", "auto_plan_op", "auto_plan_ex", "auto_plan_batched", "BIAS_NONE", "BIAS_COL", "BIAS_ROW", "ACT_NONE", "ACT_RELU", "BATCH_FORMS", "BATCHED_MAX_WORKGROUPS", "OP_N", "OP_T", "sgemm_sharded", "KERNELS", "CHAIN_KERNELS", "AB_LIB_PATH",
+           "kernel_name", "last_launch", "use_timeline_library", "streamk_plan", "auto_plan", "auto_plan_op", "auto_plan_ex", "auto_plan_batched", "auto_plan_batched_ex", "BIAS_NONE", "BIAS_COL", "BIAS_ROW", "ACT_NONE", "ACT_RELU", "BATCH_FORMS", "BATCHED_MAX_WORKGROUPS", "OP_N", "OP_T", "sgemm_sharded", "KERNELS", "CHAIN_KERNELS", "AB_LIB_PATH",
            "OPT_SPLITK", "OPT_HOST_PANELS", "OPT_STREAMK_SPIN_LIMIT", "OPT_FAULT_INJECT", "OPT_STREAMK_ORDER", "OPT_DMA_EDGE", "OPT_STREAMK_DELEGATIONS", "OPT_RIM", "OPT_STREAMK_CHAIN", "OPT_PERSIST", "OPT_RIM5", "KERNEL_AUTO", "KERNEL_VALU", "KERNEL_MFMA", "KERNEL_MFMA_256", "KERNEL_NAIVE", "KERNEL_MFMA_SIMPLE", "KERNEL_MFMA_PIPE",
            "EXPORTS", "LIB_PATH", "OPT_STREAMK", "OPT_STREAMK_TIMEOUTS", "OPT_IGEMM_MODE", "OK", "ERR_INVALID_ARG", "ERR_HIP", "ERR_NO_DEVICE",
            "ERR_UNSUPPORTED", "ERR_ALLOC", "ERR_COMM"]

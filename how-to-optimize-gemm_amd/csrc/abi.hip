@@ -122,7 +122,7 @@ const char *mmh_last_error(void) { return last_error_ref().c_str(); }
 
 const char *mmh_last_launch(void) { return last_launch_ref().c_str(); }
 
-int mmh_version(void) { return 301; }
+int mmh_version(void) { return 302; }
 
 int mmh_is_ab_build(void) {
 #ifdef MMH_AB_BUILD
@@ -389,6 +389,15 @@ int mmh_sgemm_batched(mmh_handle_t h, int transa, int transb, int m, int n, int 
   return sgemm_batched_on(h, h->kernel, transa, transb, m, n, k, dA, lda, strideA, dB, ldb, strideB, dC, ldc, strideC, batch,
                           accumulate, static_cast<hipStream_t>(stream));
 }
+int mmh_sgemm_batched_ex(mmh_handle_t h, int transa, int transb, int m, int n, int k, float alpha, const float *dA, int lda,
+                         long long strideA, const float *dB, int ldb, long long strideB, float beta, float *dC, int ldc,
+                         long long strideC, const float *dBias, long long strideBias, int bias_mode, int activation, int batch,
+                         void *stream) {
+  if (!h) return MMH_ERR_INVALID_ARG;
+  ENTER(h);
+  return sgemm_batched_ex_on(h, h->kernel, transa, transb, m, n, k, alpha, dA, lda, strideA, dB, ldb, strideB, beta, dC, ldc, strideC,
+                             dBias, strideBias, bias_mode, activation, batch, static_cast<hipStream_t>(stream));
+}
 int mmh_time_sgemm(mmh_handle_t h, int m, int n, int k, const float *dA, int lda, const float *dB,
                    int ldb, float *dC, int ldc, int warmup, int reps, void *stream,
                    float *ms_per_call) {
@@ -412,6 +421,15 @@ int mmh_time_sgemm_batched(mmh_handle_t h, int transa, int transb, int m, int n,
                            int batch, int warmup, int reps, void *stream, float *ms_per_call) {
   return time_calls(h, stream, warmup, reps, ms_per_call, "mmh_time_sgemm_batched", [&](hipStream_t s) {
     return sgemm_batched_on(h, h->kernel, transa, transb, m, n, k, dA, lda, strideA, dB, ldb, strideB, dC, ldc, strideC, batch, 0, s);
+  });
+}
+int mmh_time_sgemm_batched_ex(mmh_handle_t h, int transa, int transb, int m, int n, int k, float alpha, const float *dA, int lda,
+                              long long strideA, const float *dB, int ldb, long long strideB, float beta, float *dC, int ldc,
+                              long long strideC, const float *dBias, long long strideBias, int bias_mode, int activation,
+                              int batch, int warmup, int reps, void *stream, float *ms_per_call) {
+  return time_calls(h, stream, warmup, reps, ms_per_call, "mmh_time_sgemm_batched_ex", [&](hipStream_t s) {
+    return sgemm_batched_ex_on(h, h->kernel, transa, transb, m, n, k, alpha, dA, lda, strideA, dB, ldb, strideB, beta, dC, ldc, strideC,
+                               dBias, strideBias, bias_mode, activation, batch, s);
   });
 }
 
@@ -462,6 +480,12 @@ int mmh_auto_plan_batched(int transa, int transb, int m, int n, int k, int lda, 
                           int *form, long *workgroups) {
   return mmh::auto_plan_batched(transa, transb, m, n, k, lda, ldb, ldc, strideA, strideB, strideC, batch, base_align, cu_count,
                                 kernel, form, workgroups);
+}
+int mmh_auto_plan_batched_ex(int transa, int transb, int m, int n, int k, int lda, int ldb, int ldc, long long strideA,
+                             long long strideB, long long strideC, long long strideBias, int bias_mode, int batch, int base_align,
+                             int cu_count, int *kernel, int *form, long *workgroups) {
+  return mmh::auto_plan_batched_ex(transa, transb, m, n, k, lda, ldb, ldc, strideA, strideB, strideC, strideBias, bias_mode, batch,
+                                   base_align, cu_count, kernel, form, workgroups);
 }
 
 }  // extern "C"

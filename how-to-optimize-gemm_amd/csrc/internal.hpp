@@ -10,8 +10,9 @@
 //   launch_dma.hip   LDS-DMA tiles (sgemm_dma.hpp): plain, stream-K; whole and guarded shapes
 //   launch_dma5.hip  LDS-DMA tiles with loader waves (K2W, sgemm_dma5.hpp): plain, chained stream-K -- the NN forms;
 //   launch_op.hip    ... their transposed-operand forms, launch_batched.hip their strided batched form, launch_ex.hip /
-//                    launch_ex_t.hip their fused-epilogue forms (mmh_sgemm_ex): each TU instantiates launch_dma5.hpp's one
-//                    launcher for the kernels of its own form (NnForm / OpForm / ExForm / BatchedForm; built in parallel)
+//                    launch_ex_t.hip their fused-epilogue forms (mmh_sgemm_ex), launch_batched_ex.hip the batched form with the
+//                    epilogue: each TU instantiates launch_dma5.hpp's one launcher for the kernels of its own form (NnForm /
+//                    OpForm / ExForm / BatchedForm / BatchedExForm; built in parallel)
 //   launch_valu.hip  K1 / K0 (sgemm_valu.hpp)
 //   host_flavour.hip mmh_sgemm_host(_timed): the host-pointer MY_MMult, row-panel pipeline
 //   shard.hip        mmh_shard_*: single-process row-panel shard over RCCL
@@ -372,6 +373,7 @@ using k2w_tiles = TileTable<
 struct BatchArgs {
   long long sA = 0, sB = 0, sC = 0;
   long batch = 1;
+  long long sBias = 0;   // mmh_sgemm_batched_ex: matrix i's bias at g.bias + i sBias (0: one bias for the whole batch)
 };
 // one launch never holds more workgroups than this; a larger batch goes out as several launches of the same kernel
 constexpr long kBatchedMaxWorkgroups = MMH_BATCHED_MAX_WORKGROUPS;
@@ -411,12 +413,24 @@ int warm_dma5_ex_ta();
 int launch_dma5_batched(mmh_context *ctx, int kernel, const GemmArgs &g, const BatchArgs &b);
 int launch_naive_batched(const GemmArgs &g, const BatchArgs &b);
 int warm_dma5_batched();   // LDS opt-ins only (nothing is launched)
+// launch_batched_ex.hip: the same two with the fused epilogue (g.ex, b.sBias) -- mmh_sgemm_batched_ex's one-launch form and its
+// naive kernel (k == 0 included: s = +0 through the epilogue, A and B are not read)
+int launch_dma5_batched_ex(mmh_context *ctx, int kernel, const GemmArgs &g, const BatchArgs &b);   // 1: the matrices do not qualify
+int launch_naive_batched_ex(const GemmArgs &g, const BatchArgs &b);
+int warm_dma5_batched_ex();   // LDS opt-ins only
 // policy.hip: mmh_sgemm_batched / mmh_auto_plan_batched
 int sgemm_batched_on(mmh_context *ctx, int kernel, int ta, int tb, int m, int n, int k, const float *dA, int lda, long long sA,
                      const float *dB, int ldb, long long sB, float *dC, int ldc, long long sC, int batch, int accumulate,
                      hipStream_t s);
 int auto_plan_batched(int ta, int tb, int m, int n, int k, int lda, int ldb, int ldc, long long sA, long long sB, long long sC,
                       int batch, int base_align, int cu_count, int *kernel, int *form, long *workgroups);
+// policy.hip: mmh_sgemm_batched_ex / mmh_auto_plan_batched_ex
+int sgemm_batched_ex_on(mmh_context *ctx, int kernel, int ta, int tb, int m, int n, int k, float alpha, const float *dA, int lda,
+                        long long sA, const float *dB, int ldb, long long sB, float beta, float *dC, int ldc, long long sC,
+                        const float *dBias, long long sBias, int bias_mode, int activation, int batch, hipStream_t s);
+int auto_plan_batched_ex(int ta, int tb, int m, int n, int k, int lda, int ldb, int ldc, long long sA, long long sB, long long sC,
+                         long long sBias, int bias_mode, int batch, int base_align, int cu_count, int *kernel, int *form,
+                         long *workgroups);
 // launch_valu.hip
 int launch_valu(mmh_context *ctx, int kernel, const GemmArgs &g);
 int warm_valu(mmh_context *ctx, float *scratch, hipStream_t s);

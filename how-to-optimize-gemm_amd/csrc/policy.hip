@@ -1,6 +1,6 @@
 // policy.hip -- sgemm_on(): argument checks, the empty contraction, and MMH_KERNEL_AUTO's tile choice (the
 // reference's `NEW := MMult_xxx` makefile switch, cuda/makefile:1-3, as a run-time decision); call_on(): the same for
-// mmh_sgemm_op / _ex / _batched, one front end behind three argument packers; the plan entry points.  Pure host code;
+// mmh_sgemm_op / _ex / _batched / _batched_ex, one front end behind four argument packers; the plan entry points.  Pure host code;
 // the kernels are launched by the launch_*.hip units.
 #include <algorithm>
 
@@ -240,15 +240,19 @@ struct BatchPlan {
   Plan per;          // fold / loop: the plan of the one GEMM mmh_sgemm_op runs (the folded one, or one matrix's)
 };
 
+// (mmh_sgemm_batched_ex: ... and the biases are ONE bias of the folded GEMM -- none, a column bias the whole batch shares, or
+// row biases packed m apart: a row bias of batch x m floats)
 bool fold_ok(const GemmArgs &g, const BatchArgs &b) {
+  const bool bias_folds = g.bias_mode == MMH_BIAS_NONE || (g.bias_mode == MMH_BIAS_COL && b.sBias == 0) ||
+                          (g.bias_mode == MMH_BIAS_ROW && b.sBias == g.m);
   return !g.ta && b.sB == 0 && b.sA == (long long)g.m * g.lda && b.sC == (long long)g.m * g.ldc &&
-         (long long)b.batch * g.m <= 0x7fffffff;
+         (long long)b.batch * g.m <= 0x7fffffff && bias_folds;
 }
 
 // MMH_KERNEL_AUTO for a batch: fold where the matrices ARE one GEMM (B shared, A and C packed); else the cheaper of one
 // batched launch on one of the three tiles -- the plain price of auto_plan_for with batch x tiles per matrix, thin edge
 // tiles and ragged last round included -- and a loop of the per-matrix plan at batch x its price.  A batch of one is the
-// per-matrix plan.
+// per-matrix plan.  (g.ex, mmh_sgemm_batched_ex: the per-matrix plan is the `ex` call's, the tiles' plain price the same.)
 BatchPlan batched_plan_for(const mmh_context *ctx, const GemmArgs &g, const BatchArgs &b) {
   BatchPlan bp;
   if (fold_ok(g, b)) {
@@ -305,34 +309,49 @@ int plan_inputs(int ta, int tb, int m, int n, int k, int lda, int ldb, int ldc, 
   return MMH_OK;
 }
 
-// ---- mmh_sgemm_op, mmh_sgemm_ex, mmh_sgemm_batched: the call forms of the three K2W tiles with op forms ----
+// ---- mmh_sgemm_op, mmh_sgemm_ex, mmh_sgemm_batched, mmh_sgemm_batched_ex: the call forms of the three K2W tiles with op forms ----
 // They run on those tiles (AUTO: the table restricted to them; forced: 29 / 30 / 31) and on a naive kernel of their own; every
 // other kernel, and operands beyond the 2 GiB descriptor window (the register-staged fallback is NN-only), are refused before
 // anything is launched.  Split-K and MMH_OPT_STREAMK_CHAIN = 0 are NN A/B switches: these forms run the chained stream-K
 // kernels, which keep the bits.  What differs between them: their own argument rules, the empty contraction, the naive
 // kernel, AUTO's plan, the launcher -- and the subject of the two refusals.
-enum class Call { Op, Ex, Batched };
+enum class Call { Op, Ex, Batched, BatchedEx };
 struct CallText {
   const char *run, *need, *what, *why;
 };
 constexpr CallText kCallText[] = {
     {"transposed operands run", "transposed operands need", "an operand", " (the register-staged tiles take NN operands only)"},
     {"the fused epilogue runs", "the fused epilogue needs", "an operand", ""},
-    {"batched GEMMs run", "batched GEMMs need", "a matrix", ""}};
+    {"batched GEMMs run", "batched GEMMs need", "a matrix", ""},
+    {"batched GEMMs with the fused epilogue run", "batched GEMMs with the fused epilogue need", "a matrix", ""}};
 
 int naive_call(Call call, const GemmArgs &g, const BatchArgs &b) {
-  return call == Call::Batched ? launch_naive_batched(g, b) : call == Call::Ex ? launch_naive_ex(g) : launch_naive_op(g);
+  switch (call) {
+    case Call::BatchedEx: return launch_naive_batched_ex(g, b);
+    case Call::Batched: return launch_naive_batched(g, b);
+    case Call::Ex: return launch_naive_ex(g);
+    default: return launch_naive_op(g);
+  }
 }
 // (1: not a tile with op forms -- AUTO found none --, or the shape does not qualify)
 int tile_call(Call call, mmh_context *ctx, int kernel, const GemmArgs &g, const BatchArgs &b) {
-  return call == Call::Batched ? launch_dma5_batched(ctx, kernel, g, b)
-                               : call == Call::Ex ? launch_dma5_ex(ctx, kernel, g) : launch_dma5_op(ctx, kernel, g);
+  switch (call) {
+    case Call::BatchedEx: return launch_dma5_batched_ex(ctx, kernel, g, b);
+    case Call::Batched: return launch_dma5_batched(ctx, kernel, g, b);
+    case Call::Ex: return launch_dma5_ex(ctx, kernel, g);
+    default: return launch_dma5_op(ctx, kernel, g);
+  }
+}
+// one GEMM of a batched call's fold or loop form: m rows at A, C (and bias), as the unbatched call of the same kind runs it
+int one_gemm(mmh_context *ctx, const GemmArgs &g, int m, const float *A, const float *B, float *C, const float *bias) {
+  if (g.ex) return sgemm_ex_on(ctx, MMH_KERNEL_AUTO, g.ta, g.tb, m, g.n, g.k, g.alpha, A, g.lda, B, g.ldb, g.beta, C, g.ldc, bias, g.bias_mode, g.act, g.s);
+  return sgemm_op_on(ctx, MMH_KERNEL_AUTO, g.ta, g.tb, m, g.n, g.k, A, g.lda, B, g.ldb, C, g.ldc, g.acc, g.s);
 }
 
 // g: the call's arguments as they came (ta / tb, bias and its mode unchecked; acc 0 / 1); b: a batched call's
 int call_on(mmh_context *ctx, Call call, int kernel, GemmArgs g, const BatchArgs &b = BatchArgs{}) {
   const CallText &text = kCallText[(int)call];
-  const bool batched = call == Call::Batched, ex = call == Call::Ex;
+  const bool batched = call == Call::Batched || call == Call::BatchedEx, ex = call == Call::Ex || call == Call::BatchedEx;
   if (!op_flags_ok(g.ta, g.tb)) {
     set_last_error(batched ? "invalid argument" : "transa / transb must be MMH_OP_N or MMH_OP_T");
     return MMH_ERR_INVALID_ARG;
@@ -342,6 +361,10 @@ int call_on(mmh_context *ctx, Call call, int kernel, GemmArgs g, const BatchArgs
   if (ex && (g.bias_mode < MMH_BIAS_NONE || g.bias_mode > MMH_BIAS_ROW || (g.act != MMH_ACT_NONE && g.act != MMH_ACT_RELU) ||
              (g.bias_mode != MMH_BIAS_NONE && !g.bias))) {
     set_last_error("bias_mode must be MMH_BIAS_NONE / _COL / _ROW (with a bias pointer), activation MMH_ACT_NONE / _RELU");
+    return MMH_ERR_INVALID_ARG;
+  }
+  if (batched && g.bias_mode != MMH_BIAS_NONE && b.sBias < 0) {
+    set_last_error("strideBias must not be negative");
     return MMH_ERR_INVALID_ARG;
   }
   if (g.bias_mode == MMH_BIAS_NONE) g.bias = nullptr;
@@ -370,7 +393,7 @@ int call_on(mmh_context *ctx, Call call, int kernel, GemmArgs g, const BatchArgs
     const BatchPlan bp = batched_plan_for(ctx, g, b);
     const int batch = (int)b.batch;
     if (bp.form == MMH_BATCH_FORM_FOLD) {
-      rc = sgemm_op_on(ctx, MMH_KERNEL_AUTO, g.ta, g.tb, batch * g.m, g.n, g.k, g.A, g.lda, g.B, g.ldb, g.C, g.ldc, g.acc, g.s);
+      rc = one_gemm(ctx, g, batch * g.m, g.A, g.B, g.C, g.bias);
       if (rc == MMH_OK)
         set_last_launch(last_launch_ref() + ", batch " + std::to_string(batch) + " folded into one " + std::to_string(batch * g.m) +
                         "-row GEMM");
@@ -378,8 +401,7 @@ int call_on(mmh_context *ctx, Call call, int kernel, GemmArgs g, const BatchArgs
     }
     if (bp.form == MMH_BATCH_FORM_LOOP) {
       for (int i = 0; i < batch && rc == MMH_OK; ++i)
-        rc = sgemm_op_on(ctx, MMH_KERNEL_AUTO, g.ta, g.tb, g.m, g.n, g.k, g.A + i * b.sA, g.lda, g.B + i * b.sB, g.ldb, g.C + i * b.sC,
-                         g.ldc, g.acc, g.s);
+        rc = one_gemm(ctx, g, g.m, g.A + i * b.sA, g.B + i * b.sB, g.C + i * b.sC, g.bias ? g.bias + i * b.sBias : nullptr);
       if (rc == MMH_OK)
         set_last_launch(last_launch_ref() + ", batch " + std::to_string(batch) + " as a loop of " + std::to_string(batch) +
                         " per-matrix launches");
@@ -436,14 +458,35 @@ int sgemm_batched_on(mmh_context *ctx, int kernel, int ta, int tb, int m, int n,
   return call_on(ctx, Call::Batched, kernel, g, BatchArgs{sA, sB, sC, batch});
 }
 
-// mmh_auto_plan_batched: batched_plan_for on a default handle, as host arithmetic
-int auto_plan_batched(int ta, int tb, int m, int n, int k, int lda, int ldb, int ldc, long long sA, long long sB, long long sC,
-                      int batch, int base_align, int cu_count, int *kernel, int *form, long *workgroups) {
+// mmh_sgemm_batched_ex: C_i = act(alpha op(A_i) op(B_i) + beta C_i + bias_i); acc is 0, as in sgemm_ex_on
+int sgemm_batched_ex_on(mmh_context *ctx, int kernel, int ta, int tb, int m, int n, int k, float alpha, const float *dA, int lda,
+                        long long sA, const float *dB, int ldb, long long sB, float beta, float *dC, int ldc, long long sC,
+                        const float *dBias, long long sBias, int bias_mode, int activation, int batch, hipStream_t s) {
+  GemmArgs g{m, n, k, dA, lda, dB, ldb, dC, ldc, 0, s};
+  g.ta = ta;
+  g.tb = tb;
+  g.ex = 1;
+  g.alpha = alpha;
+  g.beta = beta;
+  g.bias = dBias;
+  g.bias_mode = bias_mode;
+  g.act = activation;
+  return call_on(ctx, Call::BatchedEx, kernel, g, BatchArgs{sA, sB, sC, batch, sBias});
+}
+
+namespace {
+// mmh_auto_plan_batched (ex = 0) and mmh_auto_plan_batched_ex: batched_plan_for on a default handle, as host arithmetic
+int plan_batched(int ta, int tb, int m, int n, int k, int lda, int ldb, int ldc, long long sA, long long sB, long long sC,
+                 long long sBias, int bias_mode, int ex, int batch, int base_align, int cu_count, int *kernel, int *form,
+                 long *workgroups) {
   mmh_context ctx;
   GemmArgs g;
+  if (bias_mode < MMH_BIAS_NONE || bias_mode > MMH_BIAS_ROW || (bias_mode != MMH_BIAS_NONE && sBias < 0)) return MMH_ERR_INVALID_ARG;
   if (check_batch_args(ta, tb, m, n, ldc, sA, sB, sC, batch) != MMH_OK || batch < 1) return MMH_ERR_INVALID_ARG;
   if (plan_inputs(ta, tb, m, n, k, lda, ldb, ldc, base_align, cu_count, &ctx, &g) != MMH_OK) return MMH_ERR_INVALID_ARG;
-  const BatchArgs b{sA, sB, sC, batch};
+  g.ex = ex;
+  g.bias_mode = bias_mode;
+  const BatchArgs b{sA, sB, sC, batch, sBias};
   const BatchPlan bp = batched_plan_for(&ctx, g, b);
   if (form) *form = bp.form;
   if (bp.form == MMH_BATCH_FORM_ONE_LAUNCH) {
@@ -456,10 +499,23 @@ int auto_plan_batched(int ta, int tb, int m, int n, int k, int lda, int ldb, int
   const bool fold = bp.form == MMH_BATCH_FORM_FOLD;
   long tiles = 0;
   int grid = 0;
-  const int rc = auto_plan_op(ta, tb, fold ? batch * m : m, n, k, lda, ldb, ldc, base_align, cu_count, kernel, &tiles, &grid);
+  const int rc = auto_plan_op(ta, tb, fold ? batch * m : m, n, k, lda, ldb, ldc, base_align, cu_count, kernel, &tiles, &grid, ex);
   if (rc != MMH_OK) return rc;
   if (workgroups) *workgroups = (fold ? 1L : (long)batch) * (grid > 0 ? grid : tiles);
   return MMH_OK;
+}
+}  // namespace
+
+int auto_plan_batched(int ta, int tb, int m, int n, int k, int lda, int ldb, int ldc, long long sA, long long sB, long long sC,
+                      int batch, int base_align, int cu_count, int *kernel, int *form, long *workgroups) {
+  return plan_batched(ta, tb, m, n, k, lda, ldb, ldc, sA, sB, sC, 0, MMH_BIAS_NONE, 0, batch, base_align, cu_count, kernel, form,
+                      workgroups);
+}
+int auto_plan_batched_ex(int ta, int tb, int m, int n, int k, int lda, int ldb, int ldc, long long sA, long long sB, long long sC,
+                         long long sBias, int bias_mode, int batch, int base_align, int cu_count, int *kernel, int *form,
+                         long *workgroups) {
+  return plan_batched(ta, tb, m, n, k, lda, ldb, ldc, sA, sB, sC, sBias, bias_mode, 1, batch, base_align, cu_count, kernel, form,
+                      workgroups);
 }
 
 // What MMH_KERNEL_AUTO would do with a shape, as host arithmetic (mmh_auto_plan: no device, no launch): the tile it

@@ -1328,4 +1328,53 @@ sgemm_dma5_ex_streamk_kernel(int m, int n, int k, const float *__restrict__ A, i
                                                                                       flags, parts, order, place, stats, ep);
 }
 
+// The strided batched form WITH the epilogue (mmh_sgemm_batched_ex, launch_batched_ex.hip): sgemm_mfma_dma5_batched_kernel's
+// block id -> (matrix, tile) map -- the XCD-contiguous remap, `first`, dma5_raster written out -- over the `ex` segment.
+// Matrix b's bias is at ep.bias + b sBias (elements; 0 shares one bias over the batch), advanced next to A, B and C.  No
+// `accumulate`: the chain starts at +0 and beta C is the epilogue's.  A kernel of its own, so that the batched and the `ex`
+// instantiations keep their names and their code.
+template <int BM, int BN, int KB, int WTM, int WTN, int NBUF, bool EDGE, int NL, int D, int OP>
+__global__ void __launch_bounds__(64 * (4 + NL))
+sgemm_mfma_dma5_batched_ex_kernel(int m, int n, int k, const float *__restrict__ A, int lda, long long sA,
+                                  const float *__restrict__ B, int ldb, long long sB, float *__restrict__ C, int ldc,
+                                  long long sC, int nbm, int nbn, unsigned first, const Dma5Epilogue ep0, long long sBias) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  using S = Dma5Segment<BM, BN, KB, WTM, WTN, NBUF, false, EDGE, false, NL, D, false, false, 1, OP, Dma5Epilogue>;
+  constexpr int GM = Dma5Tile<BM, BN, KB, WTM, WTN, NBUF, NL>::GM;
+  asm volatile("" ::"s"(A), "s"(B), "s"(C), "s"(lda), "s"(ldb), "s"(ldc), "s"(k));
+  const unsigned G = gridDim.x, x = blockIdx.x;
+  // (block_to_tile_g's remap, a bijection of [0, G) for any G)
+  const unsigned xcd = x % NXCD, local = x / NXCD, q = G / NXCD, rr = G % NXCD;
+  const unsigned id = (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + local + first;
+  const unsigned per = (unsigned)nbm * (unsigned)nbn;
+  const unsigned b = id / per;
+  const int bid = (int)(id - b * per);
+  A += (long long)b * sA;
+  B += (long long)b * sB;
+  C += (long long)b * sC;
+  Dma5Epilogue ep = ep0;
+  ep.bias += (long long)b * sBias;   // (no bias: the launcher passes a stride of 0 and the pointer is never read)
+  int tm, tn;
+  const int thin_row = (EDGE && nbm > 1 && m - (nbm - 1) * BM <= 16) ? 1 : 0, thin_col = (EDGE && nbn > 1 && n - (nbn - 1) * BN <= 16) ? 1 : 0;
+  const int n_full = (nbm - thin_row) * (nbn - thin_col);
+  int r = bid - n_full;
+  if (r < 0) {
+    block_to_tile_g(bid, n_full, nbm - thin_row, nbn - thin_col, GM, tm, tn);
+  } else if (thin_col && r < nbm) {
+    tm = r;
+    tn = nbn - 1;
+  } else {
+    if (thin_col) r -= nbm;
+    tm = nbm - 1;
+    tn = r;
+  }
+  typename S::Lane L;
+  L.init(lda, ldb);
+  typename S::Frags fr;
+  Dma5Link link;
+  int no_reply = 0;
+  S::run(lds, L, m, n, k, A, lda, B, ldb, C, ldc, tm, tn, 0, (k + KB - 1) / KB, false, nullptr, nullptr, fr, link, Dma5Next{},
+         nullptr, no_reply, Dma5Rim{}, ep);
+}
+
 }  // namespace mmh

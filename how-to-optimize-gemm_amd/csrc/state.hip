@@ -389,8 +389,8 @@ int warm_context(mmh_context *h) {
   float *p = static_cast<float *>(scratch.p);
   if ((rc = warm_reg(h, p, nullptr)) == MMH_OK && (rc = warm_dma(h, p, nullptr)) == MMH_OK &&
       (rc = warm_dma5(h, p, nullptr)) == MMH_OK && (rc = warm_valu(h, p, nullptr)) == MMH_OK && (rc = warm_dma5_op()) == MMH_OK &&
-      (rc = warm_dma5_ex()) == MMH_OK)
-    rc = warm_dma5_batched();
+      (rc = warm_dma5_ex()) == MMH_OK && (rc = warm_dma5_batched()) == MMH_OK)
+    rc = warm_dma5_batched_ex();
 #ifdef MMH_AB_BUILD
   if (rc == MMH_OK) rc = warm_dma32(h, p, nullptr);   // (K2M: tools/ab/)
 #endif

@@ -319,6 +319,12 @@ int mmh_auto_plan_batched(int transa, int transb, int m, int n, int k, int lda, 
  * not priced).  Host arithmetic only. */
 int mmh_auto_plan_ex(int transa, int transb, int m, int n, int k, int lda, int ldb, int ldc, int base_align, int cu_count,
                      int *kernel, long *tiles, int *streamk_grid);
+/* The same for mmh_sgemm_batched_ex: mmh_auto_plan_batched's three forms, the fold form only where the biases fold too
+ * (bias_mode, strideBias: see mmh_sgemm_batched_ex), the loop form at batch x mmh_auto_plan_ex's per-matrix plan.  A bad
+ * bias_mode, or a negative strideBias with a bias mode: MMH_ERR_INVALID_ARG.  Host arithmetic only. */
+int mmh_auto_plan_batched_ex(int transa, int transb, int m, int n, int k, int lda, int ldb, int ldc, long long strideA,
+                             long long strideB, long long strideC, long long strideBias, int bias_mode, int batch,
+                             int base_align, int cu_count, int *kernel, int *form, long *workgroups);
 int mmh_get_option(mmh_handle_t handle, int option, int *value);
 
 /* The hot path ------------------------------------------------------------ */
@@ -422,6 +428,39 @@ int mmh_sgemm_ex(mmh_handle_t handle, int transa, int transb, int m, int n, int 
 int mmh_sgemm_batched(mmh_handle_t handle, int transa, int transb, int m, int n, int k, const float *dA, int lda,
                       long long strideA, const float *dB, int ldb, long long strideB, float *dC, int ldc, long long strideC,
                       int batch, int accumulate, void *stream);
+
+/* Strided batched with the fused epilogue: C_i = act(alpha * op(A_i) * op(B_i) + beta * C_i + bias_i) for i in [0, batch), in
+ * ONE launch, everything ROW-MAJOR (cublasSgemmStridedBatched / rocblas_sgemm_strided_batched with their `&alpha` and
+ * `&beta`; torch.baddbmm; a batch of equally shaped linear layers relu(x_i W_i^T + b_i)).
+ *   Matrix i is at dA + i * strideA, dB + i * strideB, dC + i * strideC, its bias at dBias + i * strideBias (elements, 64-bit).
+ *   MMH_BIAS_COL: n floats per matrix, MMH_BIAS_ROW: m floats per matrix; strideBias >= 0, 0 shares ONE bias over the whole
+ *   batch; any 4-byte aligned pointer.  MMH_BIAS_NONE: dBias and strideBias are ignored.
+ * For every matrix the result is what mmh_sgemm_ex computes on that matrix alone, bit for bit: the fp32 fma chain from +0 over
+ * ascending k, then the epilogue of mmh_sgemm_ex -- one rounding per operation, nothing contracted; beta == 0 never reads C;
+ * ReLU maps -0 to +0 and keeps NaN.  There is no `accumulate`: beta is the only way C enters.
+ * Operand and batch rules are mmh_sgemm_batched's (op flags, strides >= 0, the C-overlap rule, batch == 0, m == 0 or n == 0:
+ * MMH_OK with nothing launched), epilogue rules mmh_sgemm_ex's (bias_mode / activation outside their sets, a bias mode with a
+ * NULL dBias: MMH_ERR_INVALID_ARG); a negative strideBias with a bias mode: MMH_ERR_INVALID_ARG.  k == 0: the formula with
+ * s = +0 through the naive kernel (A and B are not read; the gaps between matrices are never written).
+ * MMH_KERNEL_AUTO picks one of mmh_sgemm_batched's three forms (mmh_auto_plan_batched_ex):
+ *   MMH_BATCH_FORM_FOLD        the operands fold (see mmh_sgemm_batched) AND the biases are one bias of the folded GEMM: no
+ *                              bias, MMH_BIAS_COL with strideBias == 0, or MMH_BIAS_ROW with strideBias == m (a row bias of
+ *                              batch * m floats): ONE mmh_sgemm_ex of batch * m rows
+ *   MMH_BATCH_FORM_ONE_LAUNCH  one launch of the batched `ex` kernel (csrc/sgemm_dma5.hpp) over batch x tiles on the 64x64,
+ *                              128x64 or 128x128 LDS-DMA tile, whichever the cost table prices cheapest
+ *   MMH_BATCH_FORM_LOOP        batch calls of mmh_sgemm_ex's per-matrix plan (which may be its chained stream-K kernels: call
+ *                              mmh_reserve_stream before capturing this form into a graph), the bias advanced per matrix
+ * A batch of one is the per-matrix plan.  Forced kernels: 29 / 30 / 31 run the one-launch form on that tile,
+ * MMH_KERNEL_NAIVE a naive batched kernel with the epilogue written out; every other kernel, and matrices beyond the tiles'
+ * 2 GiB buffer-descriptor window, give MMH_ERR_UNSUPPORTED with nothing launched and C untouched.  One launch holds at most
+ * MMH_BATCHED_MAX_WORKGROUPS workgroups.  mmh_last_launch ends in the operand pair, the epilogue tag and the batch:
+ * "..., operands NT, epilogue alpha beta bias(col) relu, batch 64" ("... folded into one 8192-row GEMM", "... as a loop of 2
+ * per-matrix launches").  A column-major caller swaps the operands, m / n and the strides, and its per-column bias becomes
+ * MMH_BIAS_ROW. */
+int mmh_sgemm_batched_ex(mmh_handle_t handle, int transa, int transb, int m, int n, int k, float alpha, const float *dA,
+                         int lda, long long strideA, const float *dB, int ldb, long long strideB, float beta, float *dC,
+                         int ldc, long long strideC, const float *dBias, long long strideBias, int bias_mode, int activation,
+                         int batch, void *stream);
 
 /* Host-pointer flavour: stages A, B (and C when accumulating) to the device,
  * runs mmh_sgemm, copies C back, synchronises.  Staging buffers are cached in
@@ -548,6 +587,11 @@ int mmh_time_sgemm_ex(mmh_handle_t handle, int transa, int transb, int m, int n,
 int mmh_time_sgemm_batched(mmh_handle_t handle, int transa, int transb, int m, int n, int k, const float *dA, int lda,
                            long long strideA, const float *dB, int ldb, long long strideB, float *dC, int ldc,
                            long long strideC, int batch, int warmup, int reps, void *stream, float *ms_per_call);
+/* mmh_time_sgemm for mmh_sgemm_batched_ex (with beta != 0 every call reads what the call before it wrote). */
+int mmh_time_sgemm_batched_ex(mmh_handle_t handle, int transa, int transb, int m, int n, int k, float alpha, const float *dA,
+                              int lda, long long strideA, const float *dB, int ldb, long long strideB, float beta, float *dC,
+                              int ldc, long long strideC, const float *dBias, long long strideBias, int bias_mode,
+                              int activation, int batch, int warmup, int reps, void *stream, float *ms_per_call);
 
 /* The same measurement for a vendor comparator (the calls are issued from C, like mmh_time_sgemm's, so that
  * a 20 us kernel is not timed through an interpreter's call overhead). */
