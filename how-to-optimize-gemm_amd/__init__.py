@@ -4,6 +4,7 @@ Layout (only what the hot path needs):
   csrc/      hand-written gfx950 HIP kernels + the C-ABI shim (libmmult_hip.so)
   harness/   C++ host side: MY_MMult forwarder and the test_MMult sweep driver
   api.py     ctypes mirror of include/mmult_hip.h (+ torch device-pointer glue)
+  autograd.py torch.autograd glue: a linear layer (+ ReLU) that trains through MMult.linear / linear_backward
   shard.py   one-process-per-GPU row-panel shard over torch.distributed (RCCL)
   build.py   hipcc recipe
 """

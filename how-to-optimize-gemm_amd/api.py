@@ -37,6 +37,7 @@ BIAS_NONE, BIAS_COL, BIAS_ROW = 0, 1, 2   # mmh_sgemm_ex's MMH_BIAS_*: no bias, 
 ACT_NONE, ACT_RELU = 0, 1                 # ... and MMH_ACT_*
 BATCH_FORMS = {1: "fold", 2: "one_launch", 3: "loop"}   # mmh_sgemm_batched's MMH_BATCH_FORM_*
 BATCHED_MAX_WORKGROUPS = 1 << 22   # MMH_BATCHED_MAX_WORKGROUPS: one batched launch holds at most this many workgroups
+COLSUM_BLOCK_ROWS = 128            # MMH_COLSUM_BLOCK_ROWS: the row blocks of mmh_relu_grad_colsum's column sum (part of its numerics)
 KERNELS = {"auto": KERNEL_AUTO, "valu": KERNEL_VALU, "mfma": KERNEL_MFMA,
            "mfma256": KERNEL_MFMA_256, "naive": KERNEL_NAIVE, "mfma_simple": KERNEL_MFMA_SIMPLE,
            "mfma_pipe": KERNEL_MFMA_PIPE, "mfma_tiles": 10, "mfma_128x64": 8, "mfma_64x64": 11, "mfma_256x256": 12,
@@ -68,6 +69,7 @@ EXPORTS = [
     "mmh_sgemm_batched", "mmh_time_sgemm_batched", "mmh_auto_plan_batched",
     "mmh_sgemm_ex", "mmh_time_sgemm_ex", "mmh_auto_plan_ex",
     "mmh_sgemm_batched_ex", "mmh_time_sgemm_batched_ex", "mmh_auto_plan_batched_ex",
+    "mmh_relu_grad_colsum", "mmh_time_relu_grad_colsum", "mmh_kernel_has_op_forms",
 ]
 
 
@@ -230,6 +232,7 @@ def lib() -> C.CDLL:
     L.mmh_warm.argtypes = [vp]
     L.mmh_reserve_stream.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int]
     L.mmh_kernel_id.argtypes = [C.c_char_p]
+    L.mmh_kernel_has_op_forms.argtypes = [C.c_int]
     L.mmh_set_kernel.argtypes = [vp, C.c_int]
     L.mmh_get_kernel.argtypes = [vp, ip]
     L.mmh_set_option.argtypes = [vp, C.c_int, C.c_int]
@@ -255,6 +258,10 @@ def lib() -> C.CDLL:
     L.mmh_sgemm_batched_ex.argtypes = batched_ex + [vp]
     L.mmh_time_sgemm_batched_ex.argtypes = batched_ex + [C.c_int, C.c_int, vp, fp]
     L.mmh_auto_plan_batched_ex.argtypes = [C.c_int] * 8 + [ll] * 4 + [C.c_int] * 4 + [ip, ip, C.POINTER(C.c_long)]
+    # (handle, rows, cols, G, ldg, Y, ldy, Z, ldz, colsum, accumulate)
+    relu_grad = [vp, C.c_int, C.c_int, vp, C.c_int, vp, C.c_int, vp, C.c_int, vp, C.c_int]
+    L.mmh_relu_grad_colsum.argtypes = relu_grad + [vp]
+    L.mmh_time_relu_grad_colsum.argtypes = relu_grad + [C.c_int, C.c_int, vp, fp]
     L.mmh_sgemm_host.argtypes = gemm + [C.c_int]
     L.mmh_sgemm_host_timed.argtypes = gemm + [C.c_int, C.POINTER(C.c_float)]
     L.mmh_igemm_s8.argtypes = gemm + [C.c_int, vp]
@@ -648,6 +655,113 @@ class MMult:
         if out is None:
             out = torch.empty((x.shape[0], w.shape[0]), dtype=torch.float32, device=x.device)
         return self._ex("linear", x, w.t(), out, 1.0, 0.0, bias, BIAS_COL, ACT_RELU if activation == "relu" else ACT_NONE)
+
+    # -- the linear layer's backward (mmh_relu_grad_colsum + the GEMMs that are already there) --------------------------
+    def _relu_grad_args(self, what, g, y, dz, want_dz, bias_grad, want_colsum, accumulate):
+        """The C call's arguments for relu_grad_colsum / time_relu_grad_colsum, outputs allocated: (rows, cols, pg, ldg, py, ldy,
+        pz, ldz, pcolsum, accumulate), dz, colsum."""
+        import torch
+        if g.dim() != 2:
+            raise MMultError(ERR_INVALID_ARG, what, "need a 2-D gradient (rows, cols)")
+        rows, cols = g.shape
+        pg, ldg = self._tensor_args(g, rows, cols, what + "(g)", torch.float32)
+        py, ldy = (0, max(cols, 1)) if y is None else self._tensor_args(y, rows, cols, what + "(y)", torch.float32)
+        if dz is None and want_dz:
+            dz = torch.empty((rows, cols), dtype=torch.float32, device=g.device)
+        pz, ldz = (0, max(cols, 1)) if dz is None else self._tensor_args(dz, rows, cols, what + "(dz)", torch.float32)
+        colsum = bias_grad
+        if colsum is None and want_colsum:
+            if accumulate:
+                raise MMultError(ERR_INVALID_ARG, what, "accumulate needs bias_grad=")
+            colsum = torch.empty((cols,), dtype=torch.float32, device=g.device)
+        if colsum is not None and (not colsum.is_cuda or colsum.device.index != self.device or colsum.dtype != torch.float32 or
+                                   colsum.dim() != 1 or colsum.shape[0] != cols or (cols > 1 and colsum.stride(0) != 1)):
+            raise MMultError(ERR_INVALID_ARG, what, f"bias_grad is a dense 1-D fp32 tensor of {cols} floats on the handle's device")
+        if dz is None and colsum is None:
+            raise MMultError(ERR_INVALID_ARG, what, "nothing to compute: neither dz nor the column sum is wanted")
+        args = (rows, cols, pg, ldg, py or None, ldy, pz or None, ldz, colsum.data_ptr() if colsum is not None else None,
+                int(bool(accumulate)))
+        return args, dz, colsum
+
+    def relu_grad_colsum(self, g, y=None, *, dz=None, want_dz=True, bias_grad=None, want_colsum=True, accumulate=False):
+        """The memory-bound pass of a linear layer's backward, ONE launch (mmh_relu_grad_colsum; every rounding is defined in
+        include/mmult_hip.h) on torch's current stream: dz = g where y > 0 (dz = g without y) and colsum = the column sums of
+        dz in blocks of COLSUM_BLOCK_ROWS rows.  g, y (the forward OUTPUT), dz: (rows, cols) row-major windows; dz=g works in
+        place; want_dz=False / want_colsum=False skip an output; bias_grad= receives the sums (accumulate=True: adds them).
+        Returns (dz or None, colsum or None)."""
+        import torch
+        args, dz, colsum = self._relu_grad_args("relu_grad_colsum", g, y, dz, want_dz, bias_grad, want_colsum, accumulate)
+        rows, cols = args[0], args[1]
+        if cols == 0:
+            return dz, colsum
+        if rows == 0:   # (an empty tensor has no pointer to pass: the empty sum is +0)
+            if colsum is not None and not accumulate:
+                colsum.zero_()
+            return dz, colsum
+        stream = torch.cuda.current_stream(g.device).cuda_stream
+        _check(lib().mmh_relu_grad_colsum(self._h, *args, stream), "mmh_relu_grad_colsum")
+        return dz, colsum
+
+    def time_relu_grad_colsum(self, g, y=None, *, dz=None, want_dz=True, bias_grad=None, want_colsum=True, accumulate=False,
+                              warmup=1, reps=20) -> float:
+        """time_sgemm for relu_grad_colsum (same arguments): mean ms per call, one event pair on torch's current stream."""
+        import torch
+        args, _, _ = self._relu_grad_args("time_relu_grad_colsum", g, y, dz, want_dz, bias_grad, want_colsum, accumulate)
+        if args[0] == 0 or args[1] == 0:   # (an empty tensor has no pointer to pass; relu_grad_colsum launches nothing either)
+            raise MMultError(ERR_INVALID_ARG, "time_relu_grad_colsum", "nothing to time: the gradient is empty")
+        ms = C.c_float(0.0)
+        stream = torch.cuda.current_stream(g.device).cuda_stream
+        _check(lib().mmh_time_relu_grad_colsum(self._h, *args, warmup, reps, stream, C.byref(ms)), "mmh_time_relu_grad_colsum")
+        return float(ms.value)
+
+    def linear_backward(self, grad_out, x, w, y=None, *, need=(True, True, True), grad_w=None, grad_b=None):
+        """The backward of linear(x, w, b) (+ ReLU when `y`, the forward output, is given): (dx, dw, db) for the incoming
+        gradient grad_out (rows, out), x (rows, in), w (out, in).  One relu_grad_colsum call -- it gates when y is given, sums
+        the columns when need[2], and writes dz only when a GEMM needs it and y is given (without y, dz IS grad_out) -- then
+        dx = dz @ w (sgemm) and dw = dz.t() @ x (sgemm_op, TN).  grad_w= / grad_b= accumulate in place: fl(grad_w + s) with s
+        the whole TN chain (sgemm_ex, beta = 1: torch's `+=`, not the chain started at grad_w), fl(grad_b + colsum).  Entries
+        of `need` that are False give None and cost no launch.  Every launch is on torch's current stream."""
+        import torch
+        need_x, need_w, need_b = (bool(v) for v in need)
+        if grad_out.dim() != 2 or x.dim() != 2 or w.dim() != 2 or grad_out.shape[0] != x.shape[0] or \
+                tuple(w.shape) != (grad_out.shape[1], x.shape[1]):
+            raise MMultError(ERR_INVALID_ARG, "linear_backward", "need grad_out (rows, out), x (rows, in) and w (out, in)")
+        rows, n_out, n_in = grad_out.shape[0], grad_out.shape[1], x.shape[1]
+        pg, ldg = self._tensor_args(grad_out, rows, n_out, "linear_backward(grad_out)", torch.float32)
+        px, ldx = self._tensor_args(x, rows, n_in, "linear_backward(x)", torch.float32)
+        pw, ldw = self._tensor_args(w, n_out, n_in, "linear_backward(w)", torch.float32)
+        if y is not None:
+            self._tensor_args(y, rows, n_out, "linear_backward(y)", torch.float32)
+        if grad_w is not None:
+            pgw, ldgw = self._tensor_args(grad_w, n_out, n_in, "linear_backward(grad_w)", torch.float32)
+        if need_w:
+            # a selected kernel without op / ex forms refuses before anything is launched (the plan is host arithmetic)
+            kern = self.get_kernel()
+            if lib().mmh_kernel_has_op_forms(kern) != 1:
+                raise MMultError(ERR_UNSUPPORTED, "linear_backward",
+                                 f"the selected kernel {kernel_name(kern)} has no transposed-operand form for dw = dz.t() @ x")
+        dev = grad_out.device
+        gemm = need_x or need_w
+        dz, db = grad_out, None
+        if need_b or (gemm and y is not None):
+            dz_, db = self.relu_grad_colsum(grad_out, y, want_dz=gemm and y is not None, bias_grad=grad_b if need_b else None,
+                                            want_colsum=need_b, accumulate=need_b and grad_b is not None)
+            if dz_ is not None:
+                dz = dz_
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        dx = dw = None
+        pz, ldz = (dz.data_ptr(), max(dz.stride(0) if rows > 1 else n_out, 1)) if dz is not grad_out else (pg, ldg)
+        if need_x:
+            dx = torch.empty((rows, n_in), dtype=torch.float32, device=dev)
+            self.sgemm(rows, n_in, n_out, pz, ldz, pw, ldw, dx.data_ptr(), max(n_in, 1), False, stream)
+        if need_w:
+            if grad_w is None:
+                dw = torch.empty((n_out, n_in), dtype=torch.float32, device=dev)
+                self.sgemm_op(OP_T, OP_N, n_out, n_in, rows, pz, ldz, px, ldx, dw.data_ptr(), max(n_in, 1), False, stream)
+            else:
+                dw = grad_w
+                self.sgemm_ex(OP_T, OP_N, n_out, n_in, rows, 1.0, pz, ldz, px, ldx, 1.0, pgw, ldgw, stream=stream)
+        return dx, dw, db
 
     def _batched_args(self, t, batch, rows, cols, what, operand):
         """(data_ptr, leading dimension, op, batch stride) of a 3-D (batch, rows, cols) tensor: each matrix a row-major
@@ -1048,7 +1162,7 @@ def sgemm_sharded(ngpus: int, a: np.ndarray, b: np.ndarray, kernel="mfma"):
 
 
 __all__ = ["MMult", "ShardedMMult", "MMultError", "lib", "use_ab_library", "device_count", "rccl_version", "shard_rows", "shard_chunks",
-           "kernel_name", "last_launch", "use_timeline_library", "streamk_plan", "auto_plan", "auto_plan_op", "auto_plan_ex", "auto_plan_batched", "auto_plan_batched_ex", "BIAS_NONE", "BIAS_COL", "BIAS_ROW", "ACT_NONE", "ACT_RELU", "BATCH_FORMS", "BATCHED_MAX_WORKGROUPS", "OP_N", "OP_T", "sgemm_sharded", "KERNELS", "CHAIN_KERNELS", "AB_LIB_PATH",
+           "kernel_name", "last_launch", "use_timeline_library", "streamk_plan", "auto_plan", "auto_plan_op", "auto_plan_ex", "auto_plan_batched", "auto_plan_batched_ex", "BIAS_NONE", "BIAS_COL", "BIAS_ROW", "ACT_NONE", "ACT_RELU", "BATCH_FORMS", "BATCHED_MAX_WORKGROUPS", "COLSUM_BLOCK_ROWS", "OP_N", "OP_T", "sgemm_sharded", "KERNELS", "CHAIN_KERNELS", "AB_LIB_PATH",
            "OPT_SPLITK", "OPT_HOST_PANELS", "OPT_STREAMK_SPIN_LIMIT", "OPT_FAULT_INJECT", "OPT_STREAMK_ORDER", "OPT_DMA_EDGE", "OPT_STREAMK_DELEGATIONS", "OPT_RIM", "OPT_STREAMK_CHAIN", "OPT_PERSIST", "OPT_RIM5", "KERNEL_AUTO", "KERNEL_VALU", "KERNEL_MFMA", "KERNEL_MFMA_256", "KERNEL_NAIVE", "KERNEL_MFMA_SIMPLE", "KERNEL_MFMA_PIPE",
            "EXPORTS", "LIB_PATH", "OPT_STREAMK", "OPT_STREAMK_TIMEOUTS", "OPT_IGEMM_MODE", "OK", "ERR_INVALID_ARG", "ERR_HIP", "ERR_NO_DEVICE",
            "ERR_UNSUPPORTED", "ERR_ALLOC", "ERR_COMM"]

@@ -122,7 +122,7 @@ const char *mmh_last_error(void) { return last_error_ref().c_str(); }
 
 const char *mmh_last_launch(void) { return last_launch_ref().c_str(); }
 
-int mmh_version(void) { return 302; }
+int mmh_version(void) { return 303; }
 
 int mmh_is_ab_build(void) {
 #ifdef MMH_AB_BUILD
@@ -416,6 +416,12 @@ int mmh_time_sgemm_ex(mmh_handle_t h, int transa, int transb, int m, int n, int 
     return sgemm_ex_on(h, h->kernel, transa, transb, m, n, k, alpha, dA, lda, dB, ldb, beta, dC, ldc, dBias, bias_mode, activation, s);
   });
 }
+int mmh_time_relu_grad_colsum(mmh_handle_t h, int rows, int cols, const float *dG, int ldg, const float *dY, int ldy, float *dZ, int ldz,
+                              float *dColsum, int accumulate, int warmup, int reps, void *stream, float *ms_per_call) {
+  return time_calls(h, stream, warmup, reps, ms_per_call, "mmh_time_relu_grad_colsum", [&](hipStream_t s) {
+    return relu_grad_colsum_on(h, rows, cols, dG, ldg, dY, ldy, dZ, ldz, dColsum, accumulate, s);
+  });
+}
 int mmh_time_sgemm_batched(mmh_handle_t h, int transa, int transb, int m, int n, int k, const float *dA, int lda,
                            long long strideA, const float *dB, int ldb, long long strideB, float *dC, int ldc, long long strideC,
                            int batch, int warmup, int reps, void *stream, float *ms_per_call) {
@@ -467,6 +473,10 @@ int mmh_auto_plan(int m, int n, int k, int lda, int ldb, int ldc, int base_align
   return mmh::auto_plan(m, n, k, lda, ldb, ldc, base_align, cu_count, kernel, tiles, streamk_grid);
 }
 
+int mmh_kernel_has_op_forms(int kernel) {
+  if (!known_kernel(kernel)) return MMH_ERR_INVALID_ARG;
+  return kernel == MMH_KERNEL_AUTO || kernel == MMH_KERNEL_NAIVE || k2w_tiles::with(kernel, [](auto t) { return (int)t.OPS; }, 0);
+}
 int mmh_auto_plan_op(int transa, int transb, int m, int n, int k, int lda, int ldb, int ldc, int base_align, int cu_count,
                      int *kernel, long *tiles, int *streamk_grid) {
   return mmh::auto_plan_op(transa, transb, m, n, k, lda, ldb, ldc, base_align, cu_count, kernel, tiles, streamk_grid);

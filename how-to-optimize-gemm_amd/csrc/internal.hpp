@@ -17,6 +17,7 @@
 //   host_flavour.hip mmh_sgemm_host(_timed): the host-pointer MY_MMult, row-panel pipeline
 //   shard.hip        mmh_shard_*: single-process row-panel shard over RCCL
 //   igemm.hip        int8 GEMM, quantisation passes
+//   relu_grad.hip    mmh_relu_grad_colsum: the linear layer's backward beside its GEMMs (ReLU gate, bias gradient)
 //   vendor.hip       rocBLAS / hipBLASLt comparators, RCCL loader
 //   probes.hip       peak probes
 //   abi.hip          the remaining extern "C" entry points
@@ -109,6 +110,7 @@ struct mmh_context {
   int igemm_mode = 0;      // 0 auto, see MMH_OPT_IGEMM_MODE
   int i8_grid_cap = 0;     // test hook (environment MMH_I8_GRID_CAP, read at mmh_create): K3p's persistent grid, so that small shapes walk several tiles per workgroup
   mmh::DevBuf qa, qb, qc, qs;   // quantised GEMM workspace: int8 A, int8 B, int32 C, {amax bits, scales}
+  mmh::DevBuf colsum_parts;     // mmh_relu_grad_colsum: the row blocks' partial column sums (ceil(rows / R) x cols floats)
   // stream-K / split-K workspaces, one set PER STREAM the handle has launched on: launches on different streams
   // never share hand-off words or partial tiles, so nothing has to order one stream behind another and the handle
   // never touches a stream again after the call that used it returns (the caller may destroy it).
@@ -431,6 +433,9 @@ int sgemm_batched_ex_on(mmh_context *ctx, int kernel, int ta, int tb, int m, int
 int auto_plan_batched_ex(int ta, int tb, int m, int n, int k, int lda, int ldb, int ldc, long long sA, long long sB, long long sC,
                          long long sBias, int bias_mode, int batch, int base_align, int cu_count, int *kernel, int *form,
                          long *workgroups);
+// relu_grad.hip: mmh_relu_grad_colsum behind its handle checks (argument checks included)
+int relu_grad_colsum_on(mmh_context *ctx, int rows, int cols, const float *dG, int ldg, const float *dY, int ldy, float *dZ, int ldz,
+                        float *dColsum, int accumulate, hipStream_t s);
 // launch_valu.hip
 int launch_valu(mmh_context *ctx, int kernel, const GemmArgs &g);
 int warm_valu(mmh_context *ctx, float *scratch, hipStream_t s);

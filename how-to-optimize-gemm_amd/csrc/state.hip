@@ -437,6 +437,7 @@ void destroy_context(mmh_context *h) {
   h->qb.release();
   h->qc.release();
   h->qs.release();
+  h->colsum_parts.release();
   for (void *p : h->retired) (void)hipFree(p);
   for (auto *t : h->sk_tables) {
     t->buf.release();

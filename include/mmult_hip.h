@@ -307,6 +307,11 @@ int mmh_auto_plan(int m, int n, int k, int lda, int ldb, int ldc, int base_align
  * descriptor window. */
 int mmh_auto_plan_op(int transa, int transb, int m, int n, int k, int lda, int ldb, int ldc, int base_align, int cu_count,
                      int *kernel, long *tiles, int *streamk_grid);
+/* 1 when mmh_sgemm_op's transposed forms, mmh_sgemm_ex and the batched calls run with `kernel` selected (MMH_KERNEL_AUTO,
+ * MMH_KERNEL_NAIVE and the LDS-DMA tiles with op forms), 0 when they answer MMH_ERR_UNSUPPORTED; MMH_ERR_INVALID_ARG for an
+ * id this build does not know.  Host arithmetic only: for callers that compose several calls and want to refuse before the
+ * first launch (MMult.linear_backward). */
+int mmh_kernel_has_op_forms(int kernel);
 /* The same for mmh_sgemm_batched (batch >= 1, m, n, k >= 1): *kernel = the tile (or the per-matrix plan's kernel for
  * the fold and loop forms), *form = MMH_BATCH_FORM_*, *workgroups = what all its launches hold together (fold: the folded
  * GEMM's tiles or stream-K grid; one launch: batch x tiles; loop: batch x the per-matrix plan's).  The argument rules
@@ -495,6 +500,41 @@ int mmh_quantize_sym_s8(mmh_handle_t handle, int rows, int cols, const float *dX
 int mmh_qgemm_f32(mmh_handle_t handle, int m, int n, int k, const float *dA, int lda,
                   const float *dB, int ldb, float *dC, int ldc, void *stream);
 
+/* The linear layer's backward beside its two GEMMs: the ReLU gate on the incoming gradient and the bias gradient, in ONE
+ * memory-bound pass over rows x cols floats (cuBLASLt / hipBLASLt know the pair as the DRELU and BGRAD epilogues).  With
+ * y = relu(x W^T + b) and g = dL/dy:  dz = g where y > 0,  db = column sums of dz,  and then  dx = dz W  (mmh_sgemm),
+ * dW = dz^T x  (mmh_sgemm_op, TN)  or  dW += dz^T x  (mmh_sgemm_ex, beta = 1).
+ *
+ * Row-major fp32; dG, dY, dZ are rows x cols windows with any leading dimension >= cols, any 4-byte aligned pointer.
+ * Every rounding is defined, the result is bitwise reproducible, and there is no atomic on a float.  For every (i, j):
+ *   gate:   z = g                  when dY == NULL;
+ *           z = y <= 0 ? +0 : g    otherwise -- a SELECT, never a multiply: a closed gate gives +0 for g = NaN / Inf too;
+ *                                  y = NaN leaves the gate open (!(y <= 0): the forward ReLU's own predicate, and torch's
+ *                                  threshold_backward); y = +-0, negatives and -Inf close it; g's bits pass unchanged
+ *                                  (-0 and subnormals are kept).  dY is the forward OUTPUT (what mmh_sgemm_ex wrote).
+ *   dZ:     if non-NULL it receives z.  dZ == dG with ldz == ldg (in place) is allowed; any other overlap of the outputs
+ *           with the inputs or with each other is the caller's error.
+ *   column sum, if dColsum is non-NULL, with R = MMH_COLSUM_BLOCK_ROWS: row block b covers rows [bR, min(bR + R, rows));
+ *           p_b = z(bR, j), then p_b = fl(p_b + z(r, j)) for r ascending;  s = p_0, then s = fl(s + p_b) for b ascending;
+ *           dColsum[j] = s, or fl(dColsum[j] + s) when accumulate != 0.  The order depends on rows and R only -- never on
+ *           the device, the grid or the path taken.  R is part of this contract (provisional until its sweep is on file).
+ *   rows == 0: dColsum gets +0 (left alone when accumulating), dZ nothing.  cols == 0: MMH_OK, nothing launched.
+ * MMH_ERR_INVALID_ARG: a NULL handle, a NULL dG, both dZ and dColsum NULL, a leading dimension below cols (ldy / ldz are
+ * looked at only with a non-NULL dY / dZ), negative sizes -- nothing is launched and no output is touched.
+ *
+ * With more than R rows the blocks' partial sums go to a handle-owned workspace of ceil(rows / R) x cols floats that grows on
+ * demand and a small finish kernel sums them per column in block order.  The workspace is per handle, NOT per stream: one
+ * mmh_relu_grad_colsum at a time per handle, as for mmh_qgemm_f32 (one handle per stream for calls that should overlap).
+ * Nothing can be allocated while a stream is capturing: a caller who captures graphs makes one uncaptured call at the largest
+ * size first (a captured call that would have to grow the workspace is MMH_ERR_UNSUPPORTED).  16-byte loads and stores when
+ * every operand's base and leading dimension allow it, a scalar path otherwise -- same bits; mmh_last_launch names the path and
+ * what was done: "relu_grad_colsum_kernel (vector path), gate on, dz written, colsum 33 blocks of 128 rows + finish"
+ * ("... (scalar path), gate off, dz not written, colsum 1 block of 128 rows, written by the pass, accumulated";
+ * "..., no colsum"). */
+#define MMH_COLSUM_BLOCK_ROWS 128
+int mmh_relu_grad_colsum(mmh_handle_t handle, int rows, int cols, const float *dG, int ldg, const float *dY, int ldy,
+                         float *dZ, int ldz, float *dColsum, int accumulate, void *stream);
+
 /* Vendor comparator (rocBLAS sgemm, row-major via the swapped-operand trick
  * of cuda/MMult_cuBLAS_1.cpp:17-18).  MMH_ERR_UNSUPPORTED if librocblas
  * cannot be loaded. */
@@ -592,6 +632,11 @@ int mmh_time_sgemm_batched_ex(mmh_handle_t handle, int transa, int transb, int m
                               int lda, long long strideA, const float *dB, int ldb, long long strideB, float beta, float *dC,
                               int ldc, long long strideC, const float *dBias, long long strideBias, int bias_mode,
                               int activation, int batch, int warmup, int reps, void *stream, float *ms_per_call);
+
+/* mmh_time_sgemm for mmh_relu_grad_colsum (in place, or with accumulate, every call reads what the call before it wrote). */
+int mmh_time_relu_grad_colsum(mmh_handle_t handle, int rows, int cols, const float *dG, int ldg, const float *dY, int ldy,
+                              float *dZ, int ldz, float *dColsum, int accumulate, int warmup, int reps, void *stream,
+                              float *ms_per_call);
 
 /* The same measurement for a vendor comparator (the calls are issued from C, like mmh_time_sgemm's, so that
  * a 20 us kernel is not timed through an interpreter's call overhead). */
