@@ -597,7 +597,9 @@ def test_nonfinite_padding_does_not_leak_through_the_k_tail(mm, oracle, kernel):
 
 def test_huge_leading_dimension_uses_64bit_addressing(mm, oracle):
     """Offsets beyond the 2 GiB buffer-descriptor window must fall back to
-    64-bit global addressing, not wrap."""
+    64-bit global addressing, not wrap.  (One tile, whole, B only: tests/test_gpu_reg_parity.py runs the 64-bit
+    instantiations of every register-staged tile, whole and guarded, with A and with B beyond the window, and proves
+    from window_ok which instantiation each shape reaches.)"""
     import torch
     mm.set_kernel("mfma")
     k, n, ldb = 544, 128, 1 << 20                     # (k-1)*ldb*4 B > 2 GiB
