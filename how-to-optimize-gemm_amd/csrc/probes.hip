@@ -64,14 +64,22 @@ __global__ void __launch_bounds__(1024) probe_valu_kernel(float *out, int iters,
 #pragma unroll
   for (int i = 0; i < 32; ++i) acc[i] = f32x2{seed * (float)(i + 1), seed * (float)(threadIdx.x + i)};
   f32x2 a = {1.0f + seed * (float)threadIdx.x, 1.0f - seed * (float)threadIdx.x}, b = {seed, -seed};
+  float b0 = b[0], b1 = b[1];
+  if constexpr (!PACKED) asm volatile("" : "+v"(b0), "+v"(b1));   // (in vector registers before the loop, not moved there every iteration)
   for (int it = 0; it < iters; ++it) {
 #pragma unroll
     for (int i = 0; i < 32; ++i) {
       if constexpr (PACKED) {
         acc[i] = __builtin_elementwise_fma(a, b, acc[i]);
       } else {
-        acc[i][0] = __builtin_fmaf(a[0], b[0], acc[i][0]);
-        acc[i][1] = __builtin_fmaf(a[1], b[1], acc[i][1]);
+        // spelled in inline asm: hipcc's vectoriser pairs two __builtin_fmaf on the halves of acc[i] into one v_pk_fma_f32,
+        // and the "unpacked" probe was a second packed one.  (Both loops read the same rate -- 77 / 104 TFLOP/s at one / two
+        // waves per SIMD: the SIMD is 32 lanes wide, a wave64 v_fma_f32 issues in two cycles and a v_pk_fma_f32 in four.)
+        float x = acc[i][0], y = acc[i][1];
+        asm volatile("v_fma_f32 %0, %2, %3, %0\n\tv_fma_f32 %1, %4, %5, %1"
+                     : "+v"(x), "+v"(y)
+                     : "v"(a[0]), "v"(b0), "v"(a[1]), "v"(b1));
+        acc[i] = f32x2{x, y};
       }
     }
 #pragma unroll
