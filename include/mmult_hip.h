@@ -135,7 +135,14 @@ typedef struct mmh_context *mmh_handle_t;
  * partial tiles are summed in part order.  Deterministic, inside the reference harness's tolerance,
  * but NOT the one-chain-per-element bits every other variant returns; never chosen unless asked for
  * (these ids, or MMH_OPT_SPLITK with MMH_KERNEL_AUTO).  Whole-tile, 16-byte-aligned shapes only,
- * anything else runs the chain kernels. */
+ * anything else runs the chain kernels.
+ * The bits are a contract of their own.  With nk = k / 32, part s of S is the ascending-k fp32 fma chain
+ * over K-slices [nk*s/S, nk*(s+1)/S) (integer division).  Parts 1..S-1 start from zero; part 0 starts
+ * from C when accumulating, else from zero.  The tile is ((P0 + P1) + P2) + ... in plain fp32 adds.
+ * S is the count asked for (none stated: min(2 * CUs / tiles, k / 256, 8)), at most nk, then lowered
+ * until tiles * S workgroups are resident at once; mmh_last_launch reports it ("T tiles x S concurrent
+ * K parts").  tests/splitk_ref.py restates the contract from the oracle's chains and
+ * tests/test_gpu_splitk_parity.py::SPLITK_INSTANTIATIONS holds both ids to it bit for bit. */
 #define MMH_KERNEL_MFMA_SPLITK 15        /* 128x128 tiles, MMH_OPT_SPLITK parts (<= 1: as many as fill the chip) */
 #define MMH_KERNEL_MFMA_SPLITK_128X64 20 /* the same on 128x64 tiles                                            */
 /* The product library accepts exactly the ids above: every one of them returns correct results.

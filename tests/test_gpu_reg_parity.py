@@ -2,11 +2,12 @@
 the oracle's fused chain, bit for bit -- and the addressing beyond, at the edge of and far past the 2 GiB buffer-descriptor
 window.
 
-REG_INSTANTIATIONS has one row per instantiation of sgemm_mfma_kernel, sgemm_mfma_streamk_kernel, sgemm_mfma_simple_kernel
-and sgemm_mfma_splitk_kernel, in the style of tests/test_gpu_lds_dma_parity.py::INSTANTIATIONS (whose helpers run the rows
-here).  A row says how a caller reaches its instantiation through the C ABI -- forced kernel, MMH_OPT_STREAMK, MMH_OPT_PERSIST,
-whole or guarded operands, each operand inside or beyond the descriptor window --, which words of mmh_last_launch prove that
-its family and form ran, and the shapes it runs.  The launch string does not say whether the descriptor (BUFLD) or the 64-bit
+REG_INSTANTIATIONS has one row per instantiation of sgemm_mfma_kernel, sgemm_mfma_streamk_kernel and sgemm_mfma_simple_kernel,
+in the style of tests/test_gpu_lds_dma_parity.py::INSTANTIATIONS (whose helpers run the rows here); the opt-in split-K
+instantiations, which are not chain kernels, have a table and a bit contract of their own (tests/test_gpu_splitk_parity.py).
+A row says how a caller reaches its instantiation through the C ABI -- forced kernel, MMH_OPT_STREAMK, MMH_OPT_PERSIST, whole
+or guarded operands, each operand inside or beyond the descriptor window --, which words of mmh_last_launch prove that its
+family and form ran, and the shapes it runs.  The launch string does not say whether the descriptor (BUFLD) or the 64-bit
 instantiation ran: that is a pure function of (BM, BN, k, lda, ldb), window_ok below (csrc/internal.hpp restated), asserted
 for every shape a row runs.  tests/test_reg_coverage.py holds the table to the symbols of the built library on the CPU.
 
@@ -81,8 +82,6 @@ REG_TILES = {"mfma": (128, 128, 4, 4, 32), "mfma_256x256": (256, 256, 4, 8, 32),
 SK_TILES = ("mfma", "mfma_256x256", "mfma_128x64", "mfma_64x64")     # reg_tiles: the ones with a stream-K form
 BEYOND_KERNELS = ("mfma", "mfma256", "mfma_256x256", "mfma_128x64", "mfma_64x64", "mfma_pipe")
 BOOL = ("false", "true")
-SPLITK_TEST = "tests/test_gpu_parity.py::test_opt_in_split_k_meets_the_harness_tolerance"
-SPLITK_IDS = {"sgemm_mfma_splitk_kernel<128,128,4,4,32>": "mfma_splitk", "sgemm_mfma_splitk_kernel<128,64,2,4,32>": "mfma_splitk_128x64"}
 UNREACHABLE = {"sgemm_mfma_kernel<128,128,true,0,0,true,4,4,32,false>":
                "csrc/launch_reg.hip:34 -- launch_mfma<128,128,false,0,0,false> (mfma_pipe) instantiates it in the guarded branch's "
                "`BUFLD && win ? ... : ...`, whose condition folds to false with the template argument BUFLD = false"}
@@ -102,7 +101,6 @@ def _symbols():
             yield f"sgemm_mfma_streamk_kernel<{bm},{bn},{e},{wtn},{wtm},{kb}>"
     for e in BOOL:
         yield f"sgemm_mfma_simple_kernel<128,128,{e}>"
-    yield from SPLITK_IDS
 
 
 # family -> the template arguments after <BM,BN,
@@ -110,7 +108,6 @@ FAMILIES = {
     "sgemm_mfma_kernel": r"(?P<edge>true|false),(?P<sched>\d+),0,(?P<bufld>true|false),(?P<wtn>\d+),(?P<wtm>\d+),(?P<kb>\d+),false",
     "sgemm_mfma_streamk_kernel": r"(?P<edge>true|false),(?P<wtn>\d+),(?P<wtm>\d+),(?P<kb>\d+)",
     "sgemm_mfma_simple_kernel": r"(?P<edge>true|false)",
-    "sgemm_mfma_splitk_kernel": r"(?P<wtn>\d+),(?P<wtm>\d+),(?P<kb>\d+)",
 }
 FAMILY_RE = re.compile(r"^(?P<family>" + "|".join(FAMILIES) + r")<(?P<bm>\d+),(?P<bn>\d+),(?P<rest>.*)>$")
 
@@ -136,7 +133,6 @@ class Reg:
     absent: tuple = ()                # ... and must not
     cases: Optional[Callable] = None  # cus -> [Case]
     bufld: Optional[bool] = None      # what window_ok must say of every case (None: the instantiation is not chosen by it)
-    covered_by: Optional[str] = None  # the test that runs the instantiation instead (nothing runs here)
     unreachable: Optional[str] = None  # file:line and the constant that folds: no call reaches the instantiation
 
     @property
@@ -225,8 +221,6 @@ def _row(symbol):
     g = g.groupdict()
     if symbol in UNREACHABLE:
         return Reg(symbol=symbol, unreachable=UNREACHABLE[symbol])
-    if fam == "sgemm_mfma_splitk_kernel":   # not a chain kernel: its own tolerance test, with launch-string checks
-        return Reg(symbol=symbol, covered_by=SPLITK_TEST)
     edge = g["edge"] == "true"
     kb = int(g.get("kb", 32))
     head = f"{fam}<{bm},{bn}>"
@@ -325,7 +319,7 @@ def _reach(mm, kernel, streamk=0, persist=0):
 
 @pytest.mark.parametrize("row", REG_INSTANTIATIONS, ids=lambda r: r.symbol)
 def test_every_register_staged_instantiation_returns_the_oracle_bits(mm, cus, big, row):
-    if row.covered_by is not None or row.unreachable is not None:
+    if row.unreachable is not None:
         return   # nothing to run here: tests/test_reg_coverage.py checks the row's claim
     bm, bn, _ = row.tile
     for kernel in row.kernels:

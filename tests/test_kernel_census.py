@@ -1,5 +1,5 @@
 """A census of libmmult_hip.so: every kernel in its code objects (tools/kernel_resources.py) is claimed by exactly one entry of
-CENSUS -- one of the seven per-instantiation tables, which must then hold a row for it, or the GPU test that runs a kernel that
+CENSUS -- one of the eight per-instantiation tables, which must then hold a row for it, or the GPU test that runs a kernel that
 has no table (the naive kernels, the ReLU-gate / column-sum pair, the peak probes).  A new kernel family that ships without an
 entry fails here by name, on the CPU; so does an entry that matches no kernel of the library any more."""
 import importlib
@@ -52,15 +52,16 @@ def single(pattern, test, mentions):
 
 
 CENSUS = [
-    # ---- the seven tables: one row per instantiation, the row's shapes proved to reach it, bit for bit against the oracle
+    # ---- the eight tables: one row per instantiation, the row's shapes proved to reach it, bit for bit against the oracle
+    # (split-K: against the restatement of its own contract, tests/splitk_ref.py, which is built from the oracle's chains)
     table(r"^(sgemm_mfma_dma_kernel|sgemm_dma_streamk_kernel|sgemm_mfma_dma5_kernel|sgemm_dma5_streamk_kernel|sgemm_valu_dma5_kernel|"
           r"sgemm_valu_dma5_streamk_kernel|sgemm_mfma_dma5_op_kernel|sgemm_dma5_op_streamk_kernel)<", "test_gpu_lds_dma_parity", "INSTANTIATIONS"),
     table(r"^(igemm_s8_simple_kernel|igemm_s8_dma_kernel|igemm_s8_pp_kernel)<|^(absmax_kernel|quantize_kernel|dequantize_kernel)$",
           "test_gpu_int8_parity", "INSTANTIATIONS"),
     table(r"^sgemm_(mfma_dma5_ex|dma5_ex_streamk)_kernel<", "test_gpu_ex_parity", "EX_INSTANTIATIONS"),
     table(r"^sgemm_mfma_dma5_batched_ex_kernel<", "test_gpu_batched_ex", "BATCHED_EX_INSTANTIATIONS"),
-    table(r"^(sgemm_mfma_kernel|sgemm_mfma_streamk_kernel|sgemm_mfma_simple_kernel|sgemm_mfma_splitk_kernel)<", "test_gpu_reg_parity",
-          "REG_INSTANTIATIONS"),
+    table(r"^(sgemm_mfma_kernel|sgemm_mfma_streamk_kernel|sgemm_mfma_simple_kernel)<", "test_gpu_reg_parity", "REG_INSTANTIATIONS"),
+    table(r"^sgemm_mfma_splitk_kernel<", "test_gpu_splitk_parity", "SPLITK_INSTANTIATIONS"),
     table(r"^sgemm_mfma_dma5_batched_kernel<", "test_gpu_batched_parity", "BATCHED_INSTANTIATIONS"),
     table(r"^sgemm_valu_kernel<", "test_gpu_k1_parity", "K1_INSTANTIATIONS"),
     # ---- the naive kernels: the bottom rung, and the independent on-device reference of the fuzzers
@@ -120,17 +121,18 @@ def test_a_kernel_without_an_entry_fails_by_name():
 
 def test_a_table_entry_holds_a_row_for_each_of_its_kernels():
     _, _, _, entry_of = census(_symbols())
-    seven = [e for e in CENSUS if "table" in e]
-    assert len(seven) == 7 and len({e["table"] for e in seven}) == 7
+    eight = [e for e in CENSUS if "table" in e]
+    assert len(eight) == 8 and len({e["table"] for e in eight}) == 8
     rows = {}
-    for e in seven:
+    for e in eight:
         module, name = e["table"]
         assert os.path.exists(os.path.join(REPO, "tests", module + ".py")), module
         rows[e["table"]] = {r.symbol for r in getattr(importlib.import_module(module), name)}
     missing = sorted(s for s, i in entry_of.items() if "table" in CENSUS[i] and s not in rows[CENSUS[i]["table"]])
     assert not missing, f"kernels whose table holds no row for them: {missing}"
-    # ... and the tables hold nothing of another entry's: 28 rows in the two newest
+    # ... and the tables hold nothing of another entry's: 30 rows in the three newest
     assert len(rows[("test_gpu_batched_parity", "BATCHED_INSTANTIATIONS")]) == 24 and len(rows[("test_gpu_k1_parity", "K1_INSTANTIATIONS")]) == 4
+    assert len(rows[("test_gpu_splitk_parity", "SPLITK_INSTANTIATIONS")]) == 2
 
 
 def test_a_single_entry_names_a_gpu_test_that_runs_its_kernel():
