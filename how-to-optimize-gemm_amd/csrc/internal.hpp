@@ -111,6 +111,7 @@ struct mmh_context {
   int i8_grid_cap = 0;     // test hook (environment MMH_I8_GRID_CAP, read at mmh_create): K3p's persistent grid, so that small shapes walk several tiles per workgroup
   mmh::DevBuf qa, qb, qc, qs;   // quantised GEMM workspace: int8 A, int8 B, int32 C, {amax bits, scales}
   mmh::DevBuf colsum_parts;     // mmh_relu_grad_colsum: the row blocks' partial column sums (ceil(rows / R) x cols floats)
+  bool colsum_parts_captured = false;   // a captured launch points at colsum_parts: retire on growth, never free under the graph
   // stream-K / split-K workspaces, one set PER STREAM the handle has launched on: launches on different streams
   // never share hand-off words or partial tiles, so nothing has to order one stream behind another and the handle
   // never touches a stream again after the call that used it returns (the caller may destroy it).

@@ -533,7 +533,11 @@ int mmh_qgemm_f32(mmh_handle_t handle, int m, int n, int k, const float *dA, int
  * demand and a small finish kernel sums them per column in block order.  The workspace is per handle, NOT per stream: one
  * mmh_relu_grad_colsum at a time per handle, as for mmh_qgemm_f32 (one handle per stream for calls that should overlap).
  * Nothing can be allocated while a stream is capturing: a caller who captures graphs makes one uncaptured call at the largest
- * size first (a captured call that would have to grow the workspace is MMH_ERR_UNSUPPORTED).  16-byte loads and stores when
+ * size first (a captured call that would have to grow the workspace is MMH_ERR_UNSUPPORTED, nothing launched, no output
+ * touched).  A graph points at the workspace of its capture: once a captured call has used the workspace, a later call that
+ * has to grow it RETIRES the old buffer -- it is freed with the handle, never under the graph, as the stream-K sets are --
+ * so a graph stays replayable whatever sizes are run eagerly afterwards (a handle that never captures frees on growth as
+ * before).  Replays share the workspace with every other call of the handle: order them on one stream.  16-byte loads and stores when
  * every operand's base and leading dimension allow it, a scalar path otherwise -- same bits; mmh_last_launch names the path and
  * what was done: "relu_grad_colsum_kernel (vector path), gate on, dz written, colsum 33 blocks of 128 rows + finish"
  * ("... (scalar path), gate off, dz not written, colsum 1 block of 128 rows, written by the pass, accumulated";

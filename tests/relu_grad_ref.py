@@ -40,6 +40,49 @@ def blocked_colsum(z, R, old=None):
         return s if old is None else (np.asarray(old, dtype=np.float32) + s)
 
 
+def case_inputs(rows, cols):
+    """(g, y, old) of the GPU table's case (rows, cols), tests/test_gpu_relu_grad.py: normal variates with -0 and subnormals
+    sprinkled into g and +-0 into y; `old` is what an accumulating call finds in the sums."""
+    rng = np.random.default_rng(rows * 4099 + cols)
+    g = rng.standard_normal((rows, cols)).astype(np.float32)
+    y = rng.standard_normal((rows, cols)).astype(np.float32)
+    pick = rng.random((rows, cols))
+    g[pick < 0.03] = np.float32(-0.0)
+    g[(pick >= 0.03) & (pick < 0.06)] = np.float32(3e-42)
+    y[(pick >= 0.5) & (pick < 0.55)] = np.float32(0.0)
+    y[(pick >= 0.55) & (pick < 0.6)] = np.float32(-0.0)
+    old = rng.standard_normal(cols).astype(np.float32)
+    return g, y, old
+
+
+def block_partials(z, R):
+    """p_b of the contract for every row block: (nblocks, cols)."""
+    z = np.asarray(z, dtype=np.float32)
+    parts = []
+    with np.errstate(invalid="ignore", over="ignore"):
+        for r0 in range(0, z.shape[0], R):
+            p = z[r0].copy()
+            for r in range(r0 + 1, min(r0 + R, z.shape[0])):
+                p = p + z[r]
+            parts.append(p)
+    return np.array(parts, dtype=np.float32).reshape(len(parts), z.shape[1])
+
+
+def chain(parts):
+    """parts[0], then fl(s + parts[b]) for b ascending."""
+    s = parts[0].copy()
+    with np.errstate(invalid="ignore", over="ignore"):
+        for p in parts[1:]:
+            s = s + p
+    return s
+
+
+def agreeing_share(a, b):
+    """The share of elements whose bits are equal."""
+    a, b = np.asarray(a, dtype=np.float32), np.asarray(b, dtype=np.float32)
+    return float(np.mean(a.view(np.uint32) == b.view(np.uint32)))
+
+
 def relu_grad_colsum(g, y, R, old=None):
     """(dz, colsum) of the contract."""
     z = gate(g, y)

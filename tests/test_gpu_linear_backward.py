@@ -1,7 +1,8 @@
 """MMult.linear_backward and the autograd glue on the device: db against tests/relu_grad_ref.py, dx / dw against the library's own
 GEMMs on the contract's dz (bit for bit: the backward is a composition of entry points that already have their bit contract),
 everything against float64 within the chains' bounds, the `need` masks, accumulation into grad_w / grad_b, and a two-layer
-MLP through autograd.Linear whose gradients are the hand-written sequence's bits."""
+MLP through autograd.Linear whose gradients are the hand-written sequence's bits -- and, within a bound computed from the data,
+torch's own autograd of the same function in float64."""
 import os
 import sys
 
@@ -15,7 +16,9 @@ pytestmark = pytest.mark.gpu
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 R = ref.header_block_rows(REPO)
-SHAPES = [(37, 45, 70), (129, 64, 200), (1, 5, 3)]   # (rows, in, out)
+# (rows, in, out); the last two leave the single tile: dw = dz.t() @ x runs 65 - 71 K-slices, dx spans dozens of tiles, db goes
+# through 18 and 17 row blocks (one batch of the finish kernel's 16 partial rows plus one; exactly one batch)
+SHAPES = [(37, 45, 70), (129, 64, 200), (1, 5, 3), (17 * R + 77, 130, 200), (16 * R + 1, 64, 260)]
 
 
 @pytest.fixture(scope="module")
@@ -211,3 +214,99 @@ def test_a_two_layer_mlp_through_autograd_is_the_hand_written_sequence(amm):
     l3(x).sum().backward()
     _, dw3, db3 = amm.linear_backward(torch.ones((rows, 8), device="cuda"), x, l3.weight.detach(), None, need=(False, True, False))
     assert db3 is None and ref.same_bits(l3.weight.grad.cpu().numpy(), dw3.cpu().numpy())
+
+
+def test_the_autograd_glue_against_torchs_own_autograd_in_float64(amm):
+    """130 -> 200 (relu) -> 72 at 300 rows, loss = (out * t).sum() with a random t: .grad of w1, b1, w2, b2 (and of x when it
+    requires grad) against torch's autograd of the same function on the CPU in float64 -- the device's fp32 parameters and x,
+    layer 1's gate imposed as the constant 0 / 1 mask of the device's own forward output (y1 > 0), so that nothing hinges on
+    the sign of a pre-activation next to zero.  What is saved, the `need` mask, the order of the returned gradients and the
+    bias flag all show here; nothing on the reference's side comes from the library.
+
+    No fitted tolerance.  Each bound is the first-order running error of the device's chains, on the float64 magnitudes, with
+    u = 2^-24 and gamma_n = n u / (1 - n u), composed through the layers:
+      e_y1  = gamma(in + 1) M (|x| |w1|^T + |b1|)       the forward output feeding dw2 (M: the mask)
+      e_dz1 = M gamma(out) (|t| |w2|)                    dx2 feeding dz1
+      db2: gamma(R + nblocks) sum|t|                     dw2: gamma(rows) |t|^T |y1| + |t|^T e_y1
+      db1: gamma(R + nblocks) sum|dz1| + sum e_dz1       dw1: gamma(rows) |dz1|^T |x| + e_dz1^T |x|
+      dx:  gamma(hidden) |dz1| |w1| + e_dz1 |w1|
+    No factor for second-order terms is taken (the issue allows up to 2).  Largest error / bound ratio observed on an
+    MI355X: 0.0064 (dx; dw1 0.0048, db1 0.0018, dw2 0.0022, db2 0.0049) -- worst-case bounds on random data.  On the same inputs three wrong answers exceed the bound in numpy: an ungated dz (db1 and dx),
+    dw1 taken from the incoming gradient instead of dz, and db1 with one row block dropped."""
+    import torch
+    from how_to_optimize_gemm_amd import autograd
+    torch.manual_seed(29)
+    rows, n_in, hidden, n_out = 300, 130, 200, 72
+    l1 = autograd.Linear(amm, n_in, hidden, activation="relu").cuda()
+    l2 = autograd.Linear(amm, hidden, n_out).cuda()
+    names = ("w1", "b1", "w2", "b2")
+    params = dict(zip(names, (l1.weight, l1.bias, l2.weight, l2.bias)))
+    x = torch.randn((rows, n_in), device="cuda")
+    t = torch.randn((rows, n_out), device="cuda")
+    y1 = amm.linear(x, l1.weight.detach(), l1.bias.detach(), "relu")
+    mask = (y1 > 0).cpu().numpy().astype(np.float64)
+    assert 0.2 < mask.mean() < 0.8
+
+    # the reference: torch's autograd on the CPU, float64
+    c = {k: p.detach().cpu().double().requires_grad_(True) for k, p in params.items()}
+    cx, ct, cm = x.cpu().double().requires_grad_(True), t.cpu().double(), torch.from_numpy(mask)
+    h = (cx @ c["w1"].t() + c["b1"]) * cm
+    ((h @ c["w2"].t() + c["b2"]) * ct).sum().backward()
+    want = {k: v.grad.numpy() for k, v in c.items()}
+    want["x"] = cx.grad.numpy()
+
+    # the bounds, float64, from the data alone
+    gam = ref.gamma
+    X, W1, B1, W2, T = (np.abs(a.detach().cpu().numpy().astype(np.float64)) for a in (x, l1.weight, l1.bias, l2.weight, t))
+    Y1 = np.abs(h.detach().numpy())
+    dz1 = (ct @ c["w2"].detach()).numpy() * mask            # float64 dz1, signed
+    DZ1 = np.abs(dz1)
+    nblocks = (rows + R - 1) // R
+    e_y1 = gam(n_in + 1) * mask * (X @ W1.T + B1)
+    e_dz1 = mask * gam(n_out) * (T @ W2)
+    bound = {
+        "b2": gam(R + nblocks) * T.sum(axis=0),
+        "w2": gam(rows) * (T.T @ Y1) + T.T @ e_y1,
+        "b1": gam(R + nblocks) * DZ1.sum(axis=0) + e_dz1.sum(axis=0),
+        "w1": gam(rows) * (DZ1.T @ X) + e_dz1.T @ X,
+        "x": gam(hidden) * (DZ1 @ W1) + e_dz1 @ W1,
+    }
+    ratios = {}
+
+    def check(tag, got):
+        for k, g_ in got.items():
+            assert g_ is not None, (tag, k)
+            g_ = g_.cpu().numpy().astype(np.float64)
+            assert g_.shape == want[k].shape, (tag, k)
+            err = np.abs(g_ - want[k])
+            ratios[(tag, k)] = float(np.max(err / np.maximum(bound[k], 1e-300)))
+            print("autograd vs float64 [%s] %s: largest error / bound %.4f" % (tag, k, ratios[(tag, k)]))
+        for (tg, k), r in ratios.items():
+            assert r <= 1.0, (tg, k, r)
+
+    (l2(l1(x)) * t).sum().backward()                     # x does not require grad: need = (False, True, True) in layer 1
+    check("x constant", {k: p.grad for k, p in params.items()})
+    for p in params.values():
+        p.grad = None
+    xr = x.clone().requires_grad_(True)
+    (l2(l1(xr)) * t).sum().backward()
+    check("x requires grad", dict({k: p.grad for k, p in params.items()}, x=xr.grad))
+    # no bias: the bias flag gives no gradient slot and the others are unchanged
+    l3 = autograd.Linear(amm, hidden, n_out, bias=False).cuda()
+    with torch.no_grad():
+        l3.weight.copy_(l2.weight)
+    for p in params.values():
+        p.grad = None
+    ((l3(l1(x)) + l2.bias.detach()) * t).sum().backward()
+    check("no bias", {"w1": l1.weight.grad, "b1": l1.bias.grad, "w2": l3.weight.grad})
+    assert l2.bias.grad is None and l2.weight.grad is None
+
+    # three wrong answers, in float64 numpy, are outside the bound on these inputs
+    x64, t64 = x.cpu().numpy().astype(np.float64), t.cpu().numpy().astype(np.float64)
+    w1_64, w2_64 = (p.detach().cpu().numpy().astype(np.float64) for p in (l1.weight, l2.weight))
+    dx2 = t64 @ w2_64                                       # the incoming gradient of layer 1, ungated
+    assert np.allclose(dx2 * mask, dz1, rtol=1e-12, atol=0)
+    outside = lambda wrong, k: float(np.mean(np.abs(wrong - want[k]) > bound[k]))
+    assert outside(dx2.sum(axis=0), "b1") > 0.9 and outside(dx2 @ w1_64, "x") > 0.9            # an ungated dz
+    assert outside(dx2.T @ x64, "w1") > 0.9                                                     # dw from g instead of dz
+    assert outside(np.delete(dz1, np.s_[R:2 * R], axis=0).sum(axis=0), "b1") > 0.9             # one row block dropped

@@ -20,6 +20,11 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 R = ref.header_block_rows(REPO)
 ROWS = [1, R - 1, R, R + 1, 2 * R + 44]
 COLS = [1, 3, 4, 255, 256, 257, 1028]
+# the finish kernel adds the partial rows RG_FU = 16 at a time, behind p_0: one full batch with a one-row last block, a batch plus
+# one block, two full batches, two batches plus one block (tests/test_relu_grad_ref.py: at these very inputs other orders,
+# other block heights and dropped blocks give other bits)
+MANY_BLOCK_ROWS = [16 * R + 1, 17 * R + 77, 32 * R + 1, 33 * R + 77]
+MANY_BLOCK_COLS = [5, 260]      # one quad and a leftover column; more than one chunk of 256 scalar items, 65 quads
 CANARY = np.float32(-777.25)
 FRONT = 8   # canary floats in front of a window (a multiple of 4: the window's base stays 16-byte aligned)
 
@@ -40,15 +45,7 @@ def _case(rows, cols):
     """Inputs and the contract's results for a shape, computed once: g with -0 and subnormals sprinkled in, y with +-0."""
     key = (rows, cols)
     if key not in _CASES:
-        rng = np.random.default_rng(rows * 4099 + cols)
-        g = rng.standard_normal((rows, cols)).astype(np.float32)
-        y = rng.standard_normal((rows, cols)).astype(np.float32)
-        pick = rng.random((rows, cols))
-        g[pick < 0.03] = np.float32(-0.0)
-        g[(pick >= 0.03) & (pick < 0.06)] = np.float32(3e-42)
-        y[(pick >= 0.5) & (pick < 0.55)] = np.float32(0.0)
-        y[(pick >= 0.55) & (pick < 0.6)] = np.float32(-0.0)
-        old = rng.standard_normal(cols).astype(np.float32)
+        g, y, old = ref.case_inputs(rows, cols)
         z_on, s_on = ref.relu_grad_colsum(g, y, R)
         z_off, s_off = ref.relu_grad_colsum(g, None, R)
         _CASES[key] = dict(g=g, y=y, old=old, z_on=z_on, s_on=s_on, z_off=z_off, s_off=s_off,
@@ -94,7 +91,7 @@ class Window:
 
 def _run(torch, H, amm, c, layout, gate, dz, colsum, accumulate, inplace):
     rows, cols = c["g"].shape
-    ld_of, off = LAYOUTS[layout]
+    ld_of, off = LAYOUTS[layout] if isinstance(layout, str) else layout
     ld = ld_of(cols)
     vector = off == 0 and (ld if rows > 1 else cols) % 4 == 0    # (a one-row tensor's leading dimension is its length)
     g = Window(torch, rows, cols, ld, off, c["g"])
@@ -155,6 +152,96 @@ def test_every_mode_and_layout_is_bit_equal_to_the_contract(amm, rows, cols):
     for layout in LAYOUTS:
         for mode in MODES:
             _run(torch, H, amm, c, layout, *mode)
+
+
+@pytest.mark.parametrize("cols", MANY_BLOCK_COLS)
+@pytest.mark.parametrize("rows", MANY_BLOCK_ROWS)
+def test_every_mode_and_layout_at_the_finish_kernels_batch_boundaries(amm, rows, cols):
+    import torch
+    import how_to_optimize_gemm_amd as H
+    c = _case(rows, cols)
+    for layout in LAYOUTS:
+        for mode in MODES:
+            _run(torch, H, amm, c, layout, *mode)
+
+
+def _wide_case(rows, cols):
+    """_case for a two-vector-operation reference: at most R rows, so every sum is one chain."""
+    assert rows <= R
+    g, y, old = ref.case_inputs(rows, cols)
+    z_on = ref.gate(g, y)
+    s_on, s_off = ref.chain(z_on), ref.chain(g)
+    return dict(g=g, y=y, old=old, z_on=z_on, z_off=g, s_on=s_on, s_off=s_off, s_on_acc=old + s_on, s_off_acc=old + s_off)
+
+
+def test_the_strided_column_loop_of_the_scalar_path(amm):
+    """65535 * 256 + 256 + 3 columns on the scalar path: more than 65535 chunks of 256 items, so grid.y stops at 65535 and the
+    blockIdx.y loop takes a second step -- a whole chunk and a ragged one."""
+    import torch
+    import how_to_optimize_gemm_amd as H
+    rows, cols = 2, 65535 * 256 + 256 + 3
+    assert (cols + 255) // 256 == 65535 + 2
+    c = _wide_case(rows, cols)
+    for layout in (LAYOUTS["padded_odd"], (lambda n: n, 1)):         # an odd leading dimension; dense, the base one float off
+        _run(torch, H, amm, c, layout, True, True, True, False, False)
+        _run(torch, H, amm, c, layout, False, False, True, True, False)
+
+
+def test_the_strided_column_loop_of_the_vector_path(amm):
+    """4 (65535 * 256 + 256) + 3 columns in one 16-byte aligned row: 65535 + 2 chunks of quads, the three columns past them on
+    the last chunk's scalar walk.  Through the C entry point, which takes a one-row window's leading dimension as given (the
+    torch glue passes the row's length, which is odd here)."""
+    import torch
+    import how_to_optimize_gemm_amd as H
+    cols = 4 * 65535 * 256 + 4 * 256 + 3
+    assert (cols // 4 + cols % 4 + 255) // 256 == 65535 + 2
+    rng = np.random.default_rng(cols)
+    g, y = rng.standard_normal(cols, dtype=np.float32), rng.standard_normal(cols, dtype=np.float32)
+    y[::7] = np.float32(-0.0)
+    want = ref.gate(g, y)
+    pad = np.full(FRONT, CANARY, dtype=np.float32)
+    dg, dy = (torch.from_numpy(np.concatenate([pad, a, pad])).cuda() for a in (g, y))
+    dz, ds = torch.full_like(dg, float(CANARY)), torch.full_like(dg, float(CANARY))
+    ptr = lambda t: C.c_void_p(t.data_ptr() + 4 * FRONT)
+    assert H.lib().mmh_relu_grad_colsum(amm._h, 1, cols, ptr(dg), cols + 1, ptr(dy), cols + 1, ptr(dz), cols + 1, ptr(ds), 0, None) == H.OK
+    text = H.last_launch()
+    torch.cuda.synchronize()
+    assert text == "relu_grad_colsum_kernel (vector path), gate on, dz written, colsum 1 block of %d rows, written by the pass" % R, text
+    for got in (dz, ds):                      # one row: the sums are the row
+        got = got.cpu().numpy()
+        assert ref.same_bits(got[FRONT:FRONT + cols], want)
+        assert np.all(got[:FRONT] == CANARY) and np.all(got[FRONT + cols:] == CANARY)
+    assert ref.same_bits(dg.cpu().numpy()[FRONT:FRONT + cols], g) and ref.same_bits(dy.cpu().numpy()[FRONT:FRONT + cols], y)
+
+
+def test_the_workspace_across_calls_of_changing_size():
+    """One handle of its own (the workspace starts empty), one stream, no synchronisation between the calls: the partial-row
+    workspace grows twice, its row length changes from call to call, and a larger buffer serves a smaller call.  Every call
+    once more accumulating, without a gate."""
+    import torch
+    import how_to_optimize_gemm_amd as H
+    shapes = [(2 * R + 1, 64), (17 * R + 77, 260), (2 * R + 1, 1028), (33 * R + 77, 5), (2 * R + 1, 64)]
+    steps = []
+    for rows, cols in shapes:
+        c = _case(rows, cols)
+        steps.append((c, torch.from_numpy(c["g"].copy()).cuda(), torch.from_numpy(c["y"].copy()).cuda(), torch.full((rows, cols), float(CANARY), device="cuda"),
+                      torch.full((cols,), float(CANARY), device="cuda"), torch.from_numpy(c["old"].copy()).cuda()))
+    texts = []
+    with H.MMult(0, "auto") as own:
+        torch.cuda.synchronize()
+        for c, g, y, dz, s, s_acc in steps:
+            own.relu_grad_colsum(g, y, dz=dz, bias_grad=s)
+            texts.append(H.last_launch())
+            own.relu_grad_colsum(g, None, want_dz=False, bias_grad=s_acc, accumulate=True)
+            texts.append(H.last_launch())
+        torch.cuda.synchronize()
+        for i, (c, g, y, dz, s, s_acc) in enumerate(steps):
+            rows = c["g"].shape[0]
+            assert f"colsum {(rows + R - 1) // R} blocks of {R} rows + finish" in texts[2 * i], (i, texts[2 * i])
+            assert texts[2 * i + 1].endswith("+ finish, accumulated") and "gate off, dz not written" in texts[2 * i + 1], (i, texts[2 * i + 1])
+            assert ref.same_bits(dz.cpu().numpy(), c["z_on"]), i
+            assert ref.same_bits(s.cpu().numpy(), c["s_on"]), i
+            assert ref.same_bits(s_acc.cpu().numpy(), c["s_off_acc"]), i
 
 
 def test_mixed_alignment_takes_the_scalar_path(amm):

@@ -28,3 +28,5 @@ def test_the_kernels_as_host_functions_under_the_sanitizers(tmp_path):
     run = subprocess.run([exe], capture_output=True, text=True, timeout=300)
     assert run.returncode == 0, run.stdout[-2000:] + run.stderr[-4000:]
     assert "all equal" in run.stdout, run.stdout
+    # 8 x 9 shapes and the 4 x 2 at the finish kernel's batch boundaries, x 3 layouts x 7 modes
+    assert "emulated %d cases" % ((8 * 9 + 4 * 2) * 3 * 7) in run.stdout, run.stdout

@@ -2,7 +2,8 @@
 // buffers, against a plain scalar loop: built with -fsanitize=address,undefined it shows on the CPU every access outside a
 // window's last row, every misaligned vector access and every use of an index the grid does not cover, for shapes x layouts
 // x modes (gate on / off, dz written / not / in place, column sum on / off / accumulated; 16-byte and scalar paths; the strided
-// column loop).  No GPU, no HIP runtime: hip/hip_runtime.h next to this file stands in for the few constructs the header uses.
+// column loop; the finish kernel's batches), and -- the inputs' sums round, the scalar loop is the contract's order, and
+// -ffp-contract=off keeps its adds adds -- every column sum's order.  No GPU, no HIP runtime: hip/hip_runtime.h next to this file stands in for the few constructs the header uses.
 //
 //   clang++ -std=c++17 -O1 -g -ffp-contract=off -fsanitize=address,undefined -fno-sanitize-recover=undefined \
 //           -Itools/host_check tools/host_check/relu_grad_host_check.cpp -o /tmp/relu_grad_host_check && /tmp/relu_grad_host_check
@@ -14,6 +15,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <utility>
 #include <vector>
 thread_local dim3 blockIdx, threadIdx, gridDim, blockDim;
 using namespace mmh;
@@ -37,10 +39,17 @@ static unsigned bits(float f) { unsigned u; memcpy(&u, &f, 4); return u; }
 static bool same(float a, float b) { return (std::isnan(a) && std::isnan(b)) || bits(a) == bits(b); }
 
 int main() {
+  setvbuf(stdout, nullptr, _IONBF, 0);   // a mismatch returns with its buffers still allocated: the message must be out before the leak report ends the process
   const int R = MMH_COLSUM_BLOCK_ROWS;
   const int rowsv[] = {1, 7, 8, 9, R - 1, R, R + 1, 2 * R + 44}, colsv[] = {1, 3, 4, 5, 255, 256, 257, 1023, 1028};
+  // the finish kernel's batches of RG_FU partial rows behind p_0: one full batch (the last block one row), a batch plus one
+  // block, two batches, two batches plus one block -- at two column counts only (thread by thread, the full list would take minutes)
+  const int manyv[] = {RG_FU * R + 1, (RG_FU + 1) * R + 77, 2 * RG_FU * R + 1, (2 * RG_FU + 1) * R + 77}, manycolsv[] = {5, 260};
+  std::vector<std::pair<int, int>> shapes;
+  for (int rows : rowsv) for (int cols : colsv) shapes.push_back({rows, cols});
+  for (int rows : manyv) for (int cols : manycolsv) shapes.push_back({rows, cols});
   long checked = 0;
-  for (int rows : rowsv) for (int cols : colsv) for (int layout = 0; layout < 3; ++layout)
+  for (auto [rows, cols] : shapes) for (int layout = 0; layout < 3; ++layout)
   for (int mode = 0; mode < 7; ++mode) {
     const bool gate = mode == 0 || mode == 2 || mode == 3 || mode == 4, dz = mode != 2 && mode != 5, sum = mode != 3 && mode != 6;
     const bool inplace = mode == 4 || mode == 6, acc = mode == 1 || mode == 4;
@@ -52,14 +61,15 @@ int main() {
     float *g = (float *)aligned_alloc(16, (n * 4 + 15) / 16 * 16), *y = (float *)aligned_alloc(16, (n * 4 + 15) / 16 * 16);
     float *z = inplace ? g : (float *)aligned_alloc(16, (n * 4 + 15) / 16 * 16);
     std::vector<float> hg(n), hy(n);
-    for (size_t i = 0; i < n; ++i) { hg[i] = (float)(rand() % 2001 - 1000) / 64.0f; hy[i] = (float)(rand() % 7 - 3); if (rand() % 17 == 0) hg[i] = -0.0f; }
+    // (sevenths: the sums ROUND, so the order of the additions shows in the bits, not only the addressing)
+    for (size_t i = 0; i < n; ++i) { hg[i] = (float)(rand() % 2001 - 1000) / 7.0f; hy[i] = (float)(rand() % 7 - 3); if (rand() % 17 == 0) hg[i] = -0.0f; }
     memcpy(g, hg.data(), n * 4); memcpy(y, hy.data(), n * 4);
     if (!inplace) for (size_t i = 0; i < n; ++i) z[i] = -777.25f;
     const int nblocks = (rows + R - 1) / R;
     const long long ldo = ((long long)cols + 3) & ~3ll;
     float *parts = (float *)malloc((size_t)nblocks * ldo * 4), *out = (float *)malloc((size_t)cols * 4);
     std::vector<float> old(cols);
-    for (int j = 0; j < cols; ++j) out[j] = old[j] = (float)(rand() % 100) / 8.0f;
+    for (int j = 0; j < cols; ++j) out[j] = old[j] = (float)(rand() % 100) / 7.0f;
     ReluGradArgs a{g, gate ? y : nullptr, dz ? z : nullptr, nblocks > 1 ? parts : out, ld, ld, ld, nblocks > 1 ? ldo : 0, rows, cols, R, nblocks > 1 ? 0 : (acc ? 2 : 1)};
     const int W = vec ? 4 : 1;
     const long long items = cols / W + cols % W, chunks = (items + RG_THREADS - 1) / RG_THREADS;
