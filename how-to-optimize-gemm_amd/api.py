@@ -122,23 +122,38 @@ def auto_plan(m: int, n: int, k: int, lda: int = 0, ldb: int = 0, ldc: int = 0, 
     return _SHORT_NAMES.get(kern.value, str(kern.value)), tiles.value, grid.value
 
 
+def _plan_op(name, transa, transb, m, n, k, lda, ldb, ldc, base_align, cu_count):
+    """auto_plan_op / auto_plan_ex: mmh_auto_plan_op's arguments and result triple."""
+    kern, grid, tiles = C.c_int(), C.c_int(), C.c_long()
+    _check(getattr(lib(), name)(transa, transb, m, n, k, *_dense_ld(transa, transb, m, n, k, lda, ldb, ldc), base_align, cu_count,
+                                C.byref(kern), C.byref(tiles), C.byref(grid)), name)
+    return _SHORT_NAMES.get(kern.value, str(kern.value)), tiles.value, grid.value
+
+
 def auto_plan_op(transa: int, transb: int, m: int, n: int, k: int, lda: int = 0, ldb: int = 0, ldc: int = 0, base_align: int = 16,
                  cu_count: int = 256):
     """auto_plan for mmh_sgemm_op (OP_N / OP_T per operand; lda / ldb default to the dense stored rows: k or m, n or k)."""
-    kern, grid, tiles = C.c_int(), C.c_int(), C.c_long()
-    _check(lib().mmh_auto_plan_op(transa, transb, m, n, k, *_dense_ld(transa, transb, m, n, k, lda, ldb, ldc), base_align, cu_count,
-                                  C.byref(kern), C.byref(tiles), C.byref(grid)), "mmh_auto_plan_op")
-    return _SHORT_NAMES.get(kern.value, str(kern.value)), tiles.value, grid.value
+    return _plan_op("mmh_auto_plan_op", transa, transb, m, n, k, lda, ldb, ldc, base_align, cu_count)
 
 
 def auto_plan_ex(transa: int, transb: int, m: int, n: int, k: int, lda: int = 0, ldb: int = 0, ldc: int = 0, base_align: int = 16,
                  cu_count: int = 256):
     """auto_plan for mmh_sgemm_ex: planned like an op form -- one of the 64x64 / 128x64 / 128x128 LDS-DMA tiles -- for
     (OP_N, OP_N) too."""
-    kern, tiles, grid = C.c_int(), C.c_long(), C.c_int()
-    _check(lib().mmh_auto_plan_ex(transa, transb, m, n, k, *_dense_ld(transa, transb, m, n, k, lda, ldb, ldc), base_align, cu_count,
-                                  C.byref(kern), C.byref(tiles), C.byref(grid)), "mmh_auto_plan_ex")
-    return _SHORT_NAMES.get(kern.value, str(kern.value)), tiles.value, grid.value
+    return _plan_op("mmh_auto_plan_ex", transa, transb, m, n, k, lda, ldb, ldc, base_align, cu_count)
+
+
+def _plan_batched(name, transa, transb, m, n, k, lda, ldb, ldc, stride_a, stride_b, stride_c, *rest):
+    """auto_plan_batched / auto_plan_batched_ex: the dense leading dimensions, the packed matrices a negative stride stands for,
+    `rest` -- what the C function takes between strideC and its results -- and the result triple."""
+    lda, ldb, ldc = _dense_ld(transa, transb, m, n, k, lda, ldb, ldc)
+    sa = (k if transa else m) * lda if stride_a < 0 else stride_a
+    sb = (n if transb else k) * ldb if stride_b < 0 else stride_b
+    sc = m * ldc if stride_c < 0 else stride_c
+    kern, form, wgs = C.c_int(), C.c_int(), C.c_long()
+    _check(getattr(lib(), name)(transa, transb, m, n, k, lda, ldb, ldc, sa, sb, sc, *rest, C.byref(kern), C.byref(form),
+                                C.byref(wgs)), name)
+    return _SHORT_NAMES.get(kern.value, str(kern.value)), BATCH_FORMS.get(form.value, str(form.value)), wgs.value
 
 
 def auto_plan_batched(transa: int, transb: int, m: int, n: int, k: int, lda: int = 0, ldb: int = 0, ldc: int = 0,
@@ -146,14 +161,8 @@ def auto_plan_batched(transa: int, transb: int, m: int, n: int, k: int, lda: int
                       cu_count: int = 256):
     """What MMH_KERNEL_AUTO would run for mmh_sgemm_batched (host arithmetic only): (short kernel name, form name --
     "fold", "one_launch" or "loop" --, workgroups of all its launches).  Strides default to the packed matrices."""
-    lda, ldb, ldc = _dense_ld(transa, transb, m, n, k, lda, ldb, ldc)
-    sa = (k if transa else m) * lda if stride_a < 0 else stride_a
-    sb = (n if transb else k) * ldb if stride_b < 0 else stride_b
-    sc = m * ldc if stride_c < 0 else stride_c
-    kern, form, wgs = C.c_int(), C.c_int(), C.c_long()
-    _check(lib().mmh_auto_plan_batched(transa, transb, m, n, k, lda, ldb, ldc, sa, sb, sc, batch, base_align, cu_count,
-                                       C.byref(kern), C.byref(form), C.byref(wgs)), "mmh_auto_plan_batched")
-    return _SHORT_NAMES.get(kern.value, str(kern.value)), BATCH_FORMS.get(form.value, str(form.value)), wgs.value
+    return _plan_batched("mmh_auto_plan_batched", transa, transb, m, n, k, lda, ldb, ldc, stride_a, stride_b, stride_c, batch,
+                         base_align, cu_count)
 
 
 def auto_plan_batched_ex(transa: int, transb: int, m: int, n: int, k: int, lda: int = 0, ldb: int = 0, ldc: int = 0,
@@ -161,15 +170,8 @@ def auto_plan_batched_ex(transa: int, transb: int, m: int, n: int, k: int, lda: 
                          bias_mode: int = BIAS_NONE, batch: int = 1, base_align: int = 16, cu_count: int = 256):
     """auto_plan_batched for mmh_sgemm_batched_ex: the fold form only where the biases fold too (no bias, a column bias with
     stride_bias == 0, a row bias with stride_bias == m), the loop form at batch x auto_plan_ex's per-matrix plan."""
-    lda, ldb, ldc = _dense_ld(transa, transb, m, n, k, lda, ldb, ldc)
-    sa = (k if transa else m) * lda if stride_a < 0 else stride_a
-    sb = (n if transb else k) * ldb if stride_b < 0 else stride_b
-    sc = m * ldc if stride_c < 0 else stride_c
-    kern, form, wgs = C.c_int(), C.c_int(), C.c_long()
-    _check(lib().mmh_auto_plan_batched_ex(transa, transb, m, n, k, lda, ldb, ldc, sa, sb, sc, stride_bias, int(bias_mode), batch,
-                                          base_align, cu_count, C.byref(kern), C.byref(form), C.byref(wgs)),
-           "mmh_auto_plan_batched_ex")
-    return _SHORT_NAMES.get(kern.value, str(kern.value)), BATCH_FORMS.get(form.value, str(form.value)), wgs.value
+    return _plan_batched("mmh_auto_plan_batched_ex", transa, transb, m, n, k, lda, ldb, ldc, stride_a, stride_b, stride_c,
+                         stride_bias, int(bias_mode), batch, base_align, cu_count)
 
 
 def use_timeline_library() -> str:
@@ -575,20 +577,37 @@ class MMult:
                 raise
         return self._tensor_args(t.t(), cols, rows, what, torch.float32) + (OP_T,)
 
+    def _shapes_and_out(self, what, a, b, out, out_dtype, accumulate=False):
+        """(m, n, k) of a 2-D a @ b after the inner-dimension check, and `out`: the caller's, or a new (m, n) tensor beside a."""
+        import torch
+        m, k = a.shape
+        k2, n = b.shape
+        if k != k2:
+            raise MMultError(ERR_INVALID_ARG, what, "inner dimensions differ")
+        if out is None:
+            if accumulate:
+                raise MMultError(ERR_INVALID_ARG, what, "accumulate needs out=")
+            out = torch.empty((m, n), dtype=out_dtype, device=a.device)
+        return m, n, k, out
+
+    def _gemm_2d(self, what, label, a, b, out, in_dtype, out_dtype, accumulate=False):
+        """The front end of the 2-D calls on row-major windows: _shapes_and_out, then A, B and C through _tensor_args -- errors
+        name them label(A), label(B), label(C) -- and torch's current stream.  Returns the C functions' (m, n, k, A, lda, B, ldb,
+        C, ldc), the stream, and out."""
+        import torch
+        m, n, k, out = self._shapes_and_out(what, a, b, out, out_dtype, accumulate)
+        pa, lda = self._tensor_args(a, m, k, label + "(A)", in_dtype)
+        pb, ldb = self._tensor_args(b, k, n, label + "(B)", in_dtype)
+        pc, ldc = self._tensor_args(out, m, n, label + "(C)", out_dtype)
+        return (m, n, k, pa, lda, pb, ldb, pc, ldc), torch.cuda.current_stream(a.device).cuda_stream, out
+
     def matmul(self, a, b, out=None, accumulate: bool = False):
         """C = A @ B (+ C) for fp32 CUDA tensors, on torch's current stream.  A and B may be transposed views (x @ w.t(),
         a.t() @ b): they are read in place through mmh_sgemm_op; `out` is row-major."""
         import torch
         if a.dtype != torch.float32 or b.dtype != torch.float32:
             raise MMultError(ERR_INVALID_ARG, "matmul", "fp32 only")
-        m, k = a.shape
-        k2, n = b.shape
-        if k != k2:
-            raise MMultError(ERR_INVALID_ARG, "matmul", "inner dimensions differ")
-        if out is None:
-            if accumulate:
-                raise MMultError(ERR_INVALID_ARG, "matmul", "accumulate needs out=")
-            out = torch.empty((m, n), dtype=torch.float32, device=a.device)
+        m, n, k, out = self._shapes_and_out("matmul", a, b, out, torch.float32, accumulate)
         pa, lda, ta = self._operand_args(a, m, k, "matmul(A)")
         pb, ldb, tb = self._operand_args(b, k, n, "matmul(B)")
         pc, ldc = self._tensor_args(out, m, n, "matmul(C)", torch.float32)
@@ -709,10 +728,7 @@ class MMult:
         args, _, _ = self._relu_grad_args("time_relu_grad_colsum", g, y, dz, want_dz, bias_grad, want_colsum, accumulate)
         if args[0] == 0 or args[1] == 0:   # (an empty tensor has no pointer to pass; relu_grad_colsum launches nothing either)
             raise MMultError(ERR_INVALID_ARG, "time_relu_grad_colsum", "nothing to time: the gradient is empty")
-        ms = C.c_float(0.0)
-        stream = torch.cuda.current_stream(g.device).cuda_stream
-        _check(lib().mmh_time_relu_grad_colsum(self._h, *args, warmup, reps, stream, C.byref(ms)), "mmh_time_relu_grad_colsum")
-        return float(ms.value)
+        return self._time("mmh_time_relu_grad_colsum", *args, warmup, reps, torch.cuda.current_stream(g.device).cuda_stream)
 
     def linear_backward(self, grad_out, x, w, y=None, *, need=(True, True, True), grad_w=None, grad_b=None):
         """The backward of linear(x, w, b) (+ ReLU when `y`, the forward output, is given): (dx, dw, db) for the incoming
@@ -897,20 +913,8 @@ class MMult:
         import torch
         if a.dtype != torch.int8 or b.dtype != torch.int8:
             raise MMultError(ERR_INVALID_ARG, "igemm_s8", "int8 inputs only")
-        m, k = a.shape
-        k2, n = b.shape
-        if k != k2:
-            raise MMultError(ERR_INVALID_ARG, "igemm_s8", "inner dimensions differ")
-        if out is None:
-            if accumulate:
-                raise MMultError(ERR_INVALID_ARG, "igemm_s8", "accumulate needs out=")
-            out = torch.empty((m, n), dtype=torch.int32, device=a.device)
-        pa, lda = self._tensor_args(a, m, k, "igemm_s8(A)", torch.int8)
-        pb, ldb = self._tensor_args(b, k, n, "igemm_s8(B)", torch.int8)
-        pc, ldc = self._tensor_args(out, m, n, "igemm_s8(C)", torch.int32)
-        stream = torch.cuda.current_stream(a.device).cuda_stream
-        _check(lib().mmh_igemm_s8(self._h, m, n, k, pa, lda, pb, ldb, pc, ldc, int(accumulate), stream),
-               "mmh_igemm_s8")
+        args, stream, out = self._gemm_2d("igemm_s8", "igemm_s8", a, b, out, torch.int8, torch.int32, accumulate)
+        _check(lib().mmh_igemm_s8(self._h, *args, int(accumulate), stream), "mmh_igemm_s8")
         return out
 
     def quantize_sym_s8(self, x):
@@ -930,103 +934,64 @@ class MMult:
     def qgemm(self, a, b, out=None):
         """C_f32 = dequantise(quantise(A) @ quantise(B)): chgemm-style symmetric int8 GEMM."""
         import torch
-        m, k = a.shape
-        k2, n = b.shape
-        if k != k2:
-            raise MMultError(ERR_INVALID_ARG, "qgemm", "inner dimensions differ")
-        if out is None:
-            out = torch.empty((m, n), dtype=torch.float32, device=a.device)
-        pa, lda = self._tensor_args(a, m, k, "qgemm(A)", torch.float32)
-        pb, ldb = self._tensor_args(b, k, n, "qgemm(B)", torch.float32)
-        pc, ldc = self._tensor_args(out, m, n, "qgemm(C)", torch.float32)
-        stream = torch.cuda.current_stream(a.device).cuda_stream
-        _check(lib().mmh_qgemm_f32(self._h, m, n, k, pa, lda, pb, ldb, pc, ldc, stream), "mmh_qgemm_f32")
+        args, stream, out = self._gemm_2d("qgemm", "qgemm", a, b, out, torch.float32, torch.float32)
+        _check(lib().mmh_qgemm_f32(self._h, *args, stream), "mmh_qgemm_f32")
         return out
 
     def matmul_rocblas(self, a, b, out=None):
         """Vendor comparator (cuda/MMult_cuBLAS_1.cpp:11-19)."""
         import torch
-        m, k = a.shape
-        k2, n = b.shape
-        if k != k2:
-            raise MMultError(ERR_INVALID_ARG, "matmul_rocblas", "inner dimensions differ")
-        if out is None:
-            out = torch.empty((m, n), dtype=torch.float32, device=a.device)
-        pa, lda = self._tensor_args(a, m, k, "rocblas(A)", torch.float32)
-        pb, ldb = self._tensor_args(b, k, n, "rocblas(B)", torch.float32)
-        pc, ldc = self._tensor_args(out, m, n, "rocblas(C)", torch.float32)
-        stream = torch.cuda.current_stream(a.device).cuda_stream
-        _check(lib().mmh_sgemm_rocblas(self._h, m, n, k, pa, lda, pb, ldb, pc, ldc, stream),
-               "mmh_sgemm_rocblas")
+        args, stream, out = self._gemm_2d("matmul_rocblas", "rocblas", a, b, out, torch.float32, torch.float32)
+        _check(lib().mmh_sgemm_rocblas(self._h, *args, stream), "mmh_sgemm_rocblas")
         return out
 
     def matmul_hipblaslt(self, a, b, out=None):
         """The second vendor comparator (cuda/MMult_cuBLAS_2.cpp:11-26): hipBLASLt, fp32 compute."""
         import torch
-        m, k = a.shape
-        k2, n = b.shape
-        if k != k2:
-            raise MMultError(ERR_INVALID_ARG, "matmul_hipblaslt", "inner dimensions differ")
-        if out is None:
-            out = torch.empty((m, n), dtype=torch.float32, device=a.device)
-        pa, lda = self._tensor_args(a, m, k, "hipblaslt(A)", torch.float32)
-        pb, ldb = self._tensor_args(b, k, n, "hipblaslt(B)", torch.float32)
-        pc, ldc = self._tensor_args(out, m, n, "hipblaslt(C)", torch.float32)
-        stream = torch.cuda.current_stream(a.device).cuda_stream
-        _check(lib().mmh_sgemm_hipblaslt(self._h, m, n, k, pa, lda, pb, ldb, pc, ldc, stream),
-               "mmh_sgemm_hipblaslt")
+        args, stream, out = self._gemm_2d("matmul_hipblaslt", "hipblaslt", a, b, out, torch.float32, torch.float32)
+        _check(lib().mmh_sgemm_hipblaslt(self._h, *args, stream), "mmh_sgemm_hipblaslt")
         return out
 
     # -- measurement -------------------------------------------------------------
+    def _time(self, name, *args) -> float:
+        """The mmh_time_* function `name` on this handle: its arguments up to the result, which is returned (ms per call)."""
+        ms = C.c_float(0.0)
+        _check(getattr(lib(), name)(self._h, *args, C.byref(ms)), name)
+        return float(ms.value)
+
     def time_sgemm(self, m, n, k, dA, lda, dB, ldb, dC, ldc, warmup=1, reps=20, stream: int = 0) -> float:
         """Mean ms per call: one hipEvent pair around `reps` back-to-back launches on
         `stream` (the reference's convention, cuda/test_MMult.cpp:98-114)."""
-        ms = C.c_float(0)
-        _check(lib().mmh_time_sgemm(self._h, m, n, k, dA, lda, dB, ldb, dC, ldc, warmup, reps, stream,
-                                    C.byref(ms)), "mmh_time_sgemm")
-        return ms.value
+        return self._time("mmh_time_sgemm", m, n, k, dA, lda, dB, ldb, dC, ldc, warmup, reps, stream)
 
     def time_sgemm_op(self, transa, transb, m, n, k, dA, lda, dB, ldb, dC, ldc, warmup=1, reps=20, stream: int = 0) -> float:
         """time_sgemm for mmh_sgemm_op (every op pair, (OP_N, OP_N) included)."""
-        ms = C.c_float(0)
-        _check(lib().mmh_time_sgemm_op(self._h, int(transa), int(transb), m, n, k, dA, lda, dB, ldb, dC, ldc, warmup, reps, stream,
-                                       C.byref(ms)), "mmh_time_sgemm_op")
-        return ms.value
+        return self._time("mmh_time_sgemm_op", int(transa), int(transb), m, n, k, dA, lda, dB, ldb, dC, ldc, warmup, reps, stream)
 
     def time_sgemm_ex(self, transa, transb, m, n, k, alpha, dA, lda, dB, ldb, beta, dC, ldc, dBias=0, bias_mode=BIAS_NONE,
                       activation=ACT_NONE, warmup=1, reps=20, stream: int = 0) -> float:
         """time_sgemm for mmh_sgemm_ex."""
-        ms = C.c_float()
-        _check(lib().mmh_time_sgemm_ex(self._h, int(transa), int(transb), m, n, k, float(alpha), dA, lda, dB, ldb, float(beta), dC, ldc,
-                                       dBias or None, int(bias_mode), int(activation), warmup, reps, stream, C.byref(ms)),
-               "mmh_time_sgemm_ex")
-        return ms.value
+        return self._time("mmh_time_sgemm_ex", int(transa), int(transb), m, n, k, float(alpha), dA, lda, dB, ldb, float(beta), dC, ldc,
+                          dBias or None, int(bias_mode), int(activation), warmup, reps, stream)
 
     def time_sgemm_batched_ex(self, transa, transb, m, n, k, alpha, dA, lda, stride_a, dB, ldb, stride_b, beta, dC, ldc, stride_c,
                               batch, dBias=0, stride_bias=0, bias_mode=BIAS_NONE, activation=ACT_NONE, warmup=1, reps=20,
                               stream: int = 0) -> float:
         """time_sgemm for mmh_sgemm_batched_ex: ms per batched call."""
-        ms = C.c_float(0.0)
-        _check(lib().mmh_time_sgemm_batched_ex(self._h, int(transa), int(transb), m, n, k, float(alpha), dA, lda, stride_a, dB, ldb,
-                                               stride_b, float(beta), dC, ldc, stride_c, dBias or None, stride_bias, int(bias_mode),
-                                               int(activation), batch, warmup, reps, stream, C.byref(ms)),
-               "mmh_time_sgemm_batched_ex")
-        return float(ms.value)
+        return self._time("mmh_time_sgemm_batched_ex", int(transa), int(transb), m, n, k, float(alpha), dA, lda, stride_a, dB, ldb,
+                          stride_b, float(beta), dC, ldc, stride_c, dBias or None, stride_bias, int(bias_mode), int(activation), batch,
+                          warmup, reps, stream)
 
     def time_sgemm_batched(self, transa, transb, m, n, k, dA, lda, stride_a, dB, ldb, stride_b, dC, ldc, stride_c, batch,
                            warmup=1, reps=20, stream: int = 0) -> float:
         """time_sgemm for mmh_sgemm_batched: ms per batched call."""
-        ms = C.c_float(0)
-        _check(lib().mmh_time_sgemm_batched(self._h, int(transa), int(transb), m, n, k, dA, lda, stride_a, dB, ldb, stride_b, dC,
-                                            ldc, stride_c, batch, warmup, reps, stream, C.byref(ms)), "mmh_time_sgemm_batched")
-        return ms.value
+        return self._time("mmh_time_sgemm_batched", int(transa), int(transb), m, n, k, dA, lda, stride_a, dB, ldb, stride_b, dC, ldc,
+                          stride_c, batch, warmup, reps, stream)
 
     def time_comparator(self, which: str, m, n, k, dA, lda, dB, ldb, dC, ldc, warmup=1, reps=20, stream: int = 0) -> float:
         """time_sgemm for a vendor comparator ("rocblas" / "hipblaslt"): calls issued from C, one event pair."""
-        ms = C.c_float(0)
-        _check(lib().mmh_time_comparator(self._h, {"rocblas": 1, "hipblaslt": 2}[which], m, n, k, dA, lda, dB, ldb, dC, ldc,
-                                         warmup, reps, stream, C.byref(ms)), "mmh_time_comparator")
-        return ms.value
+        return self._time("mmh_time_comparator", {"rocblas": 1, "hipblaslt": 2}[which], m, n, k, dA, lda, dB, ldb, dC, ldc, warmup, reps,
+                          stream)
 
     def trace_sgemm(self, m, n, k, dA, lda, dB, ldb, dC, ldc, count=400, stream: int = 0):
         """Per-launch ms of `count` back-to-back launches (one hipEvent pair each): the clock ramp."""

@@ -96,6 +96,55 @@ constexpr KernelIndex kernel_index() {
 }
 constexpr KernelIndex kKernelIndex = kernel_index();
 static_assert(kKernelIndex.ok, "kKernels: an id twice or out of range, or a fall-back that is no register-staged id");
+
+// The handle options that are ONE int of the handle, read by mmh_set_option and mmh_get_option alike: the id, the field, and
+// what set accepts -- lo .. hi, stored as it came, or (squash) any value, stored as 0 / 1.  get returns the field.  The options
+// that are more than that -- a counter on the device, a value in other units, a side effect, two fields -- are the explicit
+// cases of the two functions.
+struct OptionRow {
+  int id;
+  int mmh_context::*field;
+  int lo, hi;
+  bool squash;
+};
+constexpr OptionRow kOptions[] = {
+    {MMH_OPT_STREAMK, &mmh_context::streamk, 0, 2, false},
+    {MMH_OPT_SPLITK, &mmh_context::splitk, 0, 16, false},
+    {MMH_OPT_HOST_PANELS, &mmh_context::host_panels, -1, kMaxHostPanels, false},
+    {MMH_OPT_STREAMK_ORDER, &mmh_context::sk_order, 0, 1, true},
+    {MMH_OPT_STREAMK_CHAIN, &mmh_context::sk_chain, 0, 1, true},
+    {MMH_OPT_PERSIST, &mmh_context::persist, 0, 1, false},
+    // the rim lives in the tools build (measured: it does not pay); the product accepts "off" only
+    {MMH_OPT_RIM, &mmh_context::rim, 0, kAbBuild ? 16 : 0, false},
+    {MMH_OPT_RIM5, &mmh_context::rim5, 0, 0, kAbBuild},   // (tools build: the fused rim, on / off)
+#ifdef MMH_AB_BUILD
+    // A/B: pin the residency of persistent launches by their LDS request (default on)
+    {100, &mmh_context::pin, 0, 1, true},
+    // A/B: raster group height of the plain K2W launch (0 = the product's GROUP_M)
+    {101, &mmh_context::ab_group_m, 0, 1024, false},
+    // A/B: chained stream-K heads publish on the spot instead of on the next part's first slice
+    {102, &mmh_context::ab_nodefer, 0, 1, true},
+    // A/B (prepared at the end of round 4, not yet measured): whole-tile stream-K launches of the K2W tiles bounded by their own
+    // instantiation's residency (77 / 117 registers: three / two workgroups per CU) instead of the guarded one's
+    {103, &mmh_context::ab_own_occ, 0, 1, true},
+    // A/B: phase-ordered stream-K tables from this many tiles per workgroup, in tenths (product: 18)
+    {104, &mmh_context::sk_order_min10, 10, 1000, false},
+    // A/B: the vector-ALU rung as it was before round 5 (register-staged K1) instead of K1W
+    {105, &mmh_context::ab_valu_old, 0, 1, true},
+    // A/B (round 6): persistent launches of ragged counts with WHOLE-tile ranges -- no partial tiles, no hand-over, a
+    // deterministic share per CU where a plain launch's last round is placed greedily (profiles/r06_notes.md section 6)
+    {106, &mmh_context::ab_whole_ranges, 0, 1, true},
+    // A/B (round 6): the tail split of plain K2W launches (launch_dma5.hpp) on (product) / off
+    {107, &mmh_context::split_tail, 0, 1, true},
+    // A/B: the batched K2W launch in plain batch-major order instead of XCD-contiguous runs (profiles/batched_sweep.md)
+    {108, &mmh_context::ab_batch_major, 0, 1, true},
+#endif
+};
+const OptionRow *option_row(int option) {
+  for (const OptionRow &r : kOptions)
+    if (r.id == option) return &r;
+  return nullptr;
+}
 }  // namespace
 
 const KernelRow *mmh::kernel_row(int kernel) {
@@ -172,11 +221,12 @@ int mmh_set_kernel(mmh_handle_t h, int kernel) {
 
 int mmh_set_option(mmh_handle_t h, int option, int value) {
   if (!h) return MMH_ERR_INVALID_ARG;
+  if (const OptionRow *r = option_row(option)) {
+    if (!r->squash && (value < r->lo || value > r->hi)) return MMH_ERR_INVALID_ARG;
+    h->*(r->field) = r->squash ? (value ? 1 : 0) : value;
+    return MMH_OK;
+  }
   switch (option) {
-    case MMH_OPT_STREAMK:
-      if (value < 0 || value > 2) return MMH_ERR_INVALID_ARG;
-      h->streamk = value;
-      return MMH_OK;
     case MMH_OPT_STREAMK_TIMEOUTS:   // writing 0 clears the sticky error
       if (value != 0) return MMH_ERR_INVALID_ARG;
       {
@@ -187,23 +237,9 @@ int mmh_set_option(mmh_handle_t h, int option, int value) {
       if (h->sticky) *reinterpret_cast<volatile int *>(h->sticky) = 0;
       workspaces_suspect(h);   // a launch that timed out may have left hand-off counters behind
       return MMH_OK;
-    case MMH_OPT_IGEMM_MODE:
-      if ((value >= 0 && value <= 9 && value != 1 && value != 3 && value != 4)
-#ifdef MMH_AB_BUILD
-          || value == 1 || value == 3 || value == 4 || (value >= 10 && value <= 13)   // tools/ab/igemm_s8_k3.hpp
-#endif
-      ) {
-        h->igemm_mode = value;
-        return MMH_OK;
-      }
-      return MMH_ERR_INVALID_ARG;
-    case MMH_OPT_SPLITK:
-      if (value < 0 || value > 16) return MMH_ERR_INVALID_ARG;
-      h->splitk = value;
-      return MMH_OK;
-    case MMH_OPT_HOST_PANELS:
-      if (value < -1 || value > kMaxHostPanels) return MMH_ERR_INVALID_ARG;
-      h->host_panels = value;
+    case MMH_OPT_IGEMM_MODE:   // (1, 3, 4 and the timing-only 10 .. 13: the tools build's, tools/ab/igemm_s8_k3.hpp)
+      if (value < 0 || (kAbBuild ? value > 13 : value > 9 || value == 1 || value == 3 || value == 4)) return MMH_ERR_INVALID_ARG;
+      h->igemm_mode = value;
       return MMH_OK;
     case MMH_OPT_STREAMK_SPIN_LIMIT:   // in units of 1024 polls
       if (value < 1) return MMH_ERR_INVALID_ARG;
@@ -212,9 +248,6 @@ int mmh_set_option(mmh_handle_t h, int option, int value) {
     case MMH_OPT_FAULT_INJECT:
       h->fault = value ? 1 : 0;
       workspaces_suspect(h);
-      return MMH_OK;
-    case MMH_OPT_STREAMK_ORDER:
-      h->sk_order = value ? 1 : 0;
       return MMH_OK;
     case MMH_OPT_STREAMK_DELEGATIONS:   // writing 0 resets the counter
       if (value != 0) return MMH_ERR_INVALID_ARG;
@@ -229,60 +262,6 @@ int mmh_set_option(mmh_handle_t h, int option, int value) {
       h->dma_edge = value ? 1 : 0;     //    for rows that are 16-byte aligned; 2 (default): for any 4-byte aligned rows
       h->dma_dword_rows = value >= 2 ? 1 : 0;
       return MMH_OK;
-    case MMH_OPT_RIM:   // the rim lives in the tools build (measured: it does not pay); the product accepts "off" only
-#ifdef MMH_AB_BUILD
-      if (value < 0 || value > 16) return MMH_ERR_INVALID_ARG;
-#else
-      if (value != 0) return MMH_ERR_INVALID_ARG;
-#endif
-      h->rim = value;
-      return MMH_OK;
-    case MMH_OPT_STREAMK_CHAIN:
-      h->sk_chain = value ? 1 : 0;
-      return MMH_OK;
-    case MMH_OPT_PERSIST:
-      if (value < 0 || value > 1) return MMH_ERR_INVALID_ARG;
-      h->persist = value;
-      return MMH_OK;
-    case MMH_OPT_RIM5:   // (tools build: the fused rim; the product accepts "off" only)
-#ifndef MMH_AB_BUILD
-      if (value != 0) return MMH_ERR_INVALID_ARG;
-#endif
-      h->rim5 = value ? 1 : 0;
-      return MMH_OK;
-#ifdef MMH_AB_BUILD
-    case 100:   // A/B: pin the residency of persistent launches by their LDS request (default on)
-      h->pin = value ? 1 : 0;
-      return MMH_OK;
-    case 101:   // A/B: raster group height of the plain K2W launch (0 = the product's GROUP_M)
-      if (value < 0 || value > 1024) return MMH_ERR_INVALID_ARG;
-      h->ab_group_m = value;
-      return MMH_OK;
-    case 102:   // A/B: chained stream-K heads publish on the spot instead of on the next part's first slice
-      h->ab_nodefer = value ? 1 : 0;
-      return MMH_OK;
-    case 103:   // A/B (prepared at the end of round 4, not yet measured): whole-tile stream-K launches of the K2W tiles bounded by
-                // their own instantiation's residency (77 / 117 registers: three / two workgroups per CU) instead of the guarded one's
-      h->ab_own_occ = value ? 1 : 0;
-      return MMH_OK;
-    case 106:   // A/B (round 6): persistent launches of ragged counts with WHOLE-tile ranges -- no partial tiles, no hand-over, a
-                // deterministic share per CU where a plain launch's last round is placed greedily (profiles/r06_notes.md section 6)
-      h->ab_whole_ranges = value ? 1 : 0;
-      return MMH_OK;
-    case 107:   // A/B (round 6): the tail split of plain K2W launches (launch_dma5.hip) on (product) / off
-      h->split_tail = value ? 1 : 0;
-      return MMH_OK;
-    case 108:   // A/B: the batched K2W launch in plain batch-major order instead of XCD-contiguous runs (profiles/batched_sweep.md)
-      h->ab_batch_major = value ? 1 : 0;
-      return MMH_OK;
-    case 105:   // A/B: the vector-ALU rung as it was before round 5 (register-staged K1) instead of K1W
-      h->ab_valu_old = value ? 1 : 0;
-      return MMH_OK;
-    case 104:   // A/B: phase-ordered stream-K tables from this many tiles per workgroup, in tenths (product: 18)
-      if (value < 10 || value > 1000) return MMH_ERR_INVALID_ARG;
-      h->sk_order_min10 = value;
-      return MMH_OK;
-#endif
     default:
       return MMH_ERR_INVALID_ARG;
   }
@@ -290,28 +269,11 @@ int mmh_set_option(mmh_handle_t h, int option, int value) {
 
 int mmh_get_option(mmh_handle_t h, int option, int *value) {
   if (!h || !value) return MMH_ERR_INVALID_ARG;
+  if (const OptionRow *r = option_row(option)) {
+    *value = h->*(r->field);
+    return MMH_OK;
+  }
   switch (option) {
-    case MMH_OPT_STREAMK: *value = h->streamk; return MMH_OK;
-    case MMH_OPT_IGEMM_MODE: *value = h->igemm_mode; return MMH_OK;
-    case MMH_OPT_SPLITK: *value = h->splitk; return MMH_OK;
-    case MMH_OPT_HOST_PANELS: *value = h->host_panels; return MMH_OK;
-    case MMH_OPT_STREAMK_SPIN_LIMIT: *value = (int)(h->spin_limit >> 10); return MMH_OK;
-    case MMH_OPT_FAULT_INJECT: *value = h->fault; return MMH_OK;
-    case MMH_OPT_STREAMK_ORDER: *value = h->sk_order; return MMH_OK;
-    case MMH_OPT_STREAMK_DELEGATIONS: {
-      *value = 0;
-      if (!h->sk_stats) return MMH_OK;
-      DeviceGuard guard;
-      HIP_TRY(guard.enter(h->device));
-      HIP_TRY(hipDeviceSynchronize());
-      HIP_TRY(hipMemcpy(value, h->sk_stats, sizeof(int), hipMemcpyDeviceToHost));
-      return MMH_OK;
-    }
-    case MMH_OPT_DMA_EDGE: *value = h->dma_edge ? (h->dma_dword_rows ? 2 : 1) : 0; return MMH_OK;
-    case MMH_OPT_RIM: *value = h->rim; return MMH_OK;
-    case MMH_OPT_STREAMK_CHAIN: *value = h->sk_chain; return MMH_OK;
-    case MMH_OPT_PERSIST: *value = h->persist; return MMH_OK;
-    case MMH_OPT_RIM5: *value = h->rim5; return MMH_OK;
     case MMH_OPT_STREAMK_TIMEOUTS: {
       // synchronises, then reads the sticky word: how many hand-off waits have timed out on this
       // handle since it was last cleared
@@ -322,6 +284,19 @@ int mmh_get_option(mmh_handle_t h, int option, int *value) {
       if (h->sticky) *value = *reinterpret_cast<volatile int *>(h->sticky);
       return MMH_OK;
     }
+    case MMH_OPT_IGEMM_MODE: *value = h->igemm_mode; return MMH_OK;
+    case MMH_OPT_STREAMK_SPIN_LIMIT: *value = (int)(h->spin_limit >> 10); return MMH_OK;
+    case MMH_OPT_FAULT_INJECT: *value = h->fault; return MMH_OK;
+    case MMH_OPT_STREAMK_DELEGATIONS: {
+      *value = 0;
+      if (!h->sk_stats) return MMH_OK;
+      DeviceGuard guard;
+      HIP_TRY(guard.enter(h->device));
+      HIP_TRY(hipDeviceSynchronize());
+      HIP_TRY(hipMemcpy(value, h->sk_stats, sizeof(int), hipMemcpyDeviceToHost));
+      return MMH_OK;
+    }
+    case MMH_OPT_DMA_EDGE: *value = h->dma_edge ? (h->dma_dword_rows ? 2 : 1) : 0; return MMH_OK;
     default:
       return MMH_ERR_INVALID_ARG;
   }
@@ -488,14 +463,14 @@ int mmh_auto_plan_ex(int transa, int transb, int m, int n, int k, int lda, int l
 int mmh_auto_plan_batched(int transa, int transb, int m, int n, int k, int lda, int ldb, int ldc, long long strideA,
                           long long strideB, long long strideC, int batch, int base_align, int cu_count, int *kernel,
                           int *form, long *workgroups) {
-  return mmh::auto_plan_batched(transa, transb, m, n, k, lda, ldb, ldc, strideA, strideB, strideC, batch, base_align, cu_count,
-                                kernel, form, workgroups);
+  return plan_batched(transa, transb, m, n, k, lda, ldb, ldc, strideA, strideB, strideC, 0, MMH_BIAS_NONE, 0, batch, base_align,
+                      cu_count, kernel, form, workgroups);
 }
 int mmh_auto_plan_batched_ex(int transa, int transb, int m, int n, int k, int lda, int ldb, int ldc, long long strideA,
                              long long strideB, long long strideC, long long strideBias, int bias_mode, int batch, int base_align,
                              int cu_count, int *kernel, int *form, long *workgroups) {
-  return mmh::auto_plan_batched_ex(transa, transb, m, n, k, lda, ldb, ldc, strideA, strideB, strideC, strideBias, bias_mode, batch,
-                                   base_align, cu_count, kernel, form, workgroups);
+  return plan_batched(transa, transb, m, n, k, lda, ldb, ldc, strideA, strideB, strideC, strideBias, bias_mode, 1, batch, base_align,
+                      cu_count, kernel, form, workgroups);
 }
 
 }  // extern "C"

@@ -5,14 +5,16 @@
 // kernels of this directory.  Translation units (build.py compiles them in parallel):
 //   state.hip        handle life cycle, sticky error, stream-K workspaces and phase tables, mmh_warm
 //   policy.hip       sgemm_on(): MMH_KERNEL_AUTO's tile choice -- the reference's `NEW := MMult_xxx`
-//                    makefile switch (cuda/makefile:1-3) made a run-time choice.  Pure host code.
+//                    makefile switch (cuda/makefile:1-3) made a run-time choice; the op / ex / batched calls' one front end;
+//                    the plans behind mmh_auto_plan* (plan_batched: both batched ones).  Pure host code.
 //   launch_reg.hip   register-staged MFMA tiles (sgemm_mfma.hpp): plain, stream-K, split-K
 //   launch_dma.hip   LDS-DMA tiles (sgemm_dma.hpp): plain, stream-K; whole and guarded shapes
 //   launch_dma5.hip  LDS-DMA tiles with loader waves (K2W, sgemm_dma5.hpp): plain, chained stream-K -- the NN forms;
-//   launch_op.hip    ... their transposed-operand forms, launch_batched.hip their strided batched form, launch_ex.hip /
-//                    launch_ex_t.hip their fused-epilogue forms (mmh_sgemm_ex), launch_batched_ex.hip the batched form with the
-//                    epilogue: each TU instantiates launch_dma5.hpp's one launcher for the kernels of its own form (NnForm /
-//                    OpForm / ExForm / BatchedForm / BatchedExForm; built in parallel)
+//   launch_op.hip    ... their transposed-operand forms, launch_ex.hip / launch_ex_t.hip their fused-epilogue forms
+//                    (mmh_sgemm_ex): each TU instantiates launch_dma5.hpp's launch_dma5_tile for the kernels of its own form
+//                    (NnForm / OpForm / ExForm); launch_batched.hip their strided batched form and launch_batched_ex.hip the
+//                    batched form with the epilogue: launch_dma5.hpp's launch_batched_tile for a BatchedForm / BatchedExForm,
+//                    and the two naive batched kernels behind its one chunk loop (built in parallel)
 //   launch_valu.hip  K1 / K0 (sgemm_valu.hpp)
 //   host_flavour.hip mmh_sgemm_host(_timed): the host-pointer MY_MMult, row-panel pipeline
 //   shard.hip        mmh_shard_*: single-process row-panel shard over RCCL
@@ -20,7 +22,7 @@
 //   relu_grad.hip    mmh_relu_grad_colsum: the linear layer's backward beside its GEMMs (ReLU gate, bias gradient)
 //   vendor.hip       rocBLAS / hipBLASLt comparators, RCCL loader
 //   probes.hip       peak probes
-//   abi.hip          the remaining extern "C" entry points
+//   abi.hip          the remaining extern "C" entry points; the catalogue of kernel ids; the table of handle options
 // No torch, no CPU fallback: without a gfx950 device every compute entry point returns
 // MMH_ERR_NO_DEVICE / MMH_ERR_HIP.
 #pragma once
@@ -359,7 +361,7 @@ struct K2wTile {
   static constexpr bool SK = SK_, OPS = OPS_;
 };
 // the template arguments every kernel of sgemm_dma5.hpp starts with, for a K2wTile K (KB = 32): `kernel<MMH_K2W_ARGS(K), ...>` in
-// launch_dma5.hpp's forms and launch_batched.hip's (the kernels are function templates over bare numbers: no alias can name them)
+// launch_dma5.hpp's forms (the kernels are function templates over bare numbers: no alias can name them)
 #define MMH_K2W_ARGS(K) K::BM, K::BN, 32, K::WTM, K::WTN, K::NBUF
 using k2w_tiles = TileTable<
     //      id                            BM   BN WTM WTN NBUF NL D  SK     OPS
@@ -421,19 +423,17 @@ int warm_dma5_batched();   // LDS opt-ins only (nothing is launched)
 int launch_dma5_batched_ex(mmh_context *ctx, int kernel, const GemmArgs &g, const BatchArgs &b);   // 1: the matrices do not qualify
 int launch_naive_batched_ex(const GemmArgs &g, const BatchArgs &b);
 int warm_dma5_batched_ex();   // LDS opt-ins only
-// policy.hip: mmh_sgemm_batched / mmh_auto_plan_batched
+// policy.hip: mmh_sgemm_batched and mmh_sgemm_batched_ex (the same with the fused epilogue: g.ex, b.sBias) ...
 int sgemm_batched_on(mmh_context *ctx, int kernel, int ta, int tb, int m, int n, int k, const float *dA, int lda, long long sA,
                      const float *dB, int ldb, long long sB, float *dC, int ldc, long long sC, int batch, int accumulate,
                      hipStream_t s);
-int auto_plan_batched(int ta, int tb, int m, int n, int k, int lda, int ldb, int ldc, long long sA, long long sB, long long sC,
-                      int batch, int base_align, int cu_count, int *kernel, int *form, long *workgroups);
-// policy.hip: mmh_sgemm_batched_ex / mmh_auto_plan_batched_ex
 int sgemm_batched_ex_on(mmh_context *ctx, int kernel, int ta, int tb, int m, int n, int k, float alpha, const float *dA, int lda,
                         long long sA, const float *dB, int ldb, long long sB, float beta, float *dC, int ldc, long long sC,
                         const float *dBias, long long sBias, int bias_mode, int activation, int batch, hipStream_t s);
-int auto_plan_batched_ex(int ta, int tb, int m, int n, int k, int lda, int ldb, int ldc, long long sA, long long sB, long long sC,
-                         long long sBias, int bias_mode, int batch, int base_align, int cu_count, int *kernel, int *form,
-                         long *workgroups);
+// ... and the plan of both: mmh_auto_plan_batched (ex = 0, MMH_BIAS_NONE, sBias = 0) and mmh_auto_plan_batched_ex (ex = 1)
+int plan_batched(int ta, int tb, int m, int n, int k, int lda, int ldb, int ldc, long long sA, long long sB, long long sC,
+                 long long sBias, int bias_mode, int ex, int batch, int base_align, int cu_count, int *kernel, int *form,
+                 long *workgroups);
 // relu_grad.hip: mmh_relu_grad_colsum behind its handle checks (argument checks included)
 int relu_grad_colsum_on(mmh_context *ctx, int rows, int cols, const float *dG, int ldg, const float *dY, int ldy, float *dZ, int ldz,
                         float *dColsum, int accumulate, hipStream_t s);

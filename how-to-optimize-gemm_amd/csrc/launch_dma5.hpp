@@ -1,9 +1,10 @@
 // launch_dma5.hpp -- the one launcher of the K2W tiles (sgemm_dma5.hpp): whole or guarded, plain or chained stream-K, the
 // tail split.  A tile is a K2wTile (internal.hpp); the kernels of a call FORM on it -- NN, transposed operands, the fused
-// epilogue -- are a NnForm / OpForm / ExForm below.  launch_dma5.hip instantiates launch_dma5_tile<NnForm<tile>> (and has the
-// NN warm-up, which launches); launch_op.hip, launch_ex.hip and launch_ex_t.hip instantiate it for their own forms through
-// launch_form / warm_form; launch_batched.hip brings its own form and tile launch to those two and takes the tail split and
-// the description from here.
+// epilogue, and the two strided batched forms -- are a NnForm / OpForm / ExForm / BatchedForm / BatchedExForm below.
+// launch_dma5.hip instantiates launch_dma5_tile<NnForm<tile>> (and has the NN warm-up, which launches); launch_op.hip,
+// launch_ex.hip and launch_ex_t.hip instantiate it for their own forms through launch_form / warm_form; launch_batched.hip and
+// launch_batched_ex.hip instantiate launch_batched_tile -- the batch in chunks, each with the tail split -- the same way, and
+// run their naive kernels through launch_naive_chunks.
 #pragma once
 #include <stdarg.h>
 
@@ -111,6 +112,48 @@ struct ExForm {   // mmh_sgemm_ex (g.alpha .. g.act), OP = 0 .. 3, NN included: 
   static int acc(const mmh_context *, const GemmArgs &) { return 0; }   // (the chain starts at +0: beta C is the epilogue's)
 };
 
+// ---- the kernels of a batched form ----
+// The strided batched kernels of tile K, operand form OP (0 = NN included): plain launches only, and `first` -- the id of a
+// launch's first workgroup -- an argument of its own.  What launch_batched_tile needs to know of the two: the kernel pair, its
+// name and the tag of the description, and what differs in the arguments -- front(): what the kernels take in front of `nbm,
+// nbn, first`; back(): what they take behind it, for the launches of the chunk that starts at matrix b0.
+template <class K_, int OP>
+struct BatchedForm {   // mmh_sgemm_batched: `accumulate` in front (tools build: option 108 rides in its bit 1), nothing behind
+  using K = K_;
+  static constexpr bool SK = false;
+  static constexpr const char *plain_name = "sgemm_mfma_dma5_batched_kernel";
+  static auto plain(bool edge) {
+    return edge ? sgemm_mfma_dma5_batched_kernel<MMH_K2W_ARGS(K), true, K::NL, K::D, OP>
+                : sgemm_mfma_dma5_batched_kernel<MMH_K2W_ARGS(K), false, K::NL, K::D, OP>;
+  }
+  static std::string tag(const GemmArgs &g) { return op_tag(g); }
+  static std::tuple<int> front(const mmh_context *ctx, const GemmArgs &g) {
+    return {g.acc | ((kAbBuild && ctx && ctx->ab_batch_major) ? 2 : 0)};
+  }
+  static std::tuple<> back(const GemmArgs &, const BatchArgs &, long) { return {}; }
+};
+// the epilogue of the matrices from b0 on, and the stride of their biases: the bias pointer advanced to matrix b0's (no bias:
+// NULL and stride 0, whatever came) -- what the batched `ex` kernels, the naive one included, take behind their other arguments
+inline std::tuple<Dma5Epilogue, long long> ex_chunk_args(const GemmArgs &g, const BatchArgs &bt, long b0) {
+  const bool none = g.bias_mode == MMH_BIAS_NONE;
+  Dma5Epilogue ep = ex_args(g);
+  ep.bias = none ? nullptr : g.bias + b0 * bt.sBias;
+  return {ep, none ? 0 : bt.sBias};
+}
+template <class K_, int OP>
+struct BatchedExForm {   // mmh_sgemm_batched_ex: no `accumulate` (the chain starts at +0); the epilogue and the bias stride behind
+  using K = K_;
+  static constexpr bool SK = false;
+  static constexpr const char *plain_name = "sgemm_mfma_dma5_batched_ex_kernel";
+  static auto plain(bool edge) {
+    return edge ? sgemm_mfma_dma5_batched_ex_kernel<MMH_K2W_ARGS(K), true, K::NL, K::D, OP>
+                : sgemm_mfma_dma5_batched_ex_kernel<MMH_K2W_ARGS(K), false, K::NL, K::D, OP>;
+  }
+  static std::string tag(const GemmArgs &g) { return ex_tag(g); }
+  static std::tuple<> front(const mmh_context *, const GemmArgs &) { return {}; }
+  static std::tuple<Dma5Epilogue, long long> back(const GemmArgs &g, const BatchArgs &bt, long b0) { return ex_chunk_args(g, bt, b0); }
+};
+
 // A launch description is written into a char[kTextSize] (the longest is under 300 characters) piece by piece: text_add
 // appends at `at` and returns where the next piece goes -- never past the buffer: a longer text is cut, as by one snprintf.
 constexpr int kTextSize = 448;
@@ -195,6 +238,68 @@ int launch_dma5_tile(mmh_context *ctx, const GemmArgs &g) {
   HIP_TRY(hipGetLastError());
   char what[kTextSize];
   text_add(what, dma5_plain_text<K>(what, F::plain_name, edge, tiles, first < tiles), "%s", F::tag(g).c_str());
+  set_last_launch(what);
+  return MMH_OK;
+}
+
+// One launch (or several of at most kBatchedMaxWorkgroups workgroups each: whole matrices per launch, the pointers
+// advanced to the chunk's first matrix) of tile F::K in batched form F over every matrix.  Whole-tile or guarded for the whole
+// matrix set (dma5_form with the strides); the tail split of launch_dma5_tile on the residency of the NN twin, chunk by chunk.
+// Returns MMH_OK, an error, or 1: the matrices do not qualify.
+template <class F>
+int launch_batched_tile(mmh_context *ctx, const GemmArgs &g, const BatchArgs &bt) {
+  using K = typename F::K;
+  using T = Dma5Tile<MMH_K2W_ARGS(K), K::NL>;
+  const int form = dma5_form(ctx, K::BM, K::BN, g, bt);
+  if (form < 0) return 1;
+  const bool edge = form == 1;
+  auto kern = F::plain(edge);
+  const int ok = allow_big_lds(kern, T::LDS_BYTES);
+  if (ok != MMH_OK) return ok;
+  const int nbm = (g.m + K::BM - 1) / K::BM, nbn = (g.n + K::BN - 1) / K::BN;
+  const long per = (long)nbm * nbn;   // (<= 2^17: a matrix inside the descriptor window)
+  const long mats = std::max(1L, kBatchedMaxWorkgroups / per);   // matrices per launch
+  long launches = 0;
+  bool split = false;
+  for (long b0 = 0; b0 < bt.batch; b0 += mats) {
+    const long tiles = std::min(mats, bt.batch - b0) * per;
+    const float *A = g.A + b0 * bt.sA, *B = g.B + b0 * bt.sB;
+    float *C = g.C + b0 * bt.sC;
+    const long first = dma5_split_first(ctx, NnForm<K>::plain(edge), T::THREADS, T::LDS_BYTES, tiles, g.k);
+    dma5_launch_rounds(first, tiles, [&](long workgroups, long id0) {
+      std::apply([&](auto... x) {
+        hipLaunchKernelGGL(kern, dim3((unsigned)workgroups), dim3(T::THREADS), T::LDS_BYTES, g.s, g.m, g.n, g.k, A, g.lda, bt.sA, B, g.ldb,
+                           bt.sB, C, g.ldc, bt.sC, x...);
+      }, std::tuple_cat(F::front(ctx, g), std::make_tuple(nbm, nbn, (unsigned)id0), F::back(g, bt, b0)));
+      ++launches;
+    });
+    split |= first < tiles;
+    HIP_TRY(hipGetLastError());
+  }
+  char what[kTextSize];
+  int at = dma5_plain_text<K>(what, F::plain_name, edge, bt.batch * per, split);
+  at = text_add(what, at, "%s, batch %ld", F::tag(g).c_str(), bt.batch);
+  if (launches > 1) text_add(what, at, " as %ld launches", launches);
+  set_last_launch(what);
+  return MMH_OK;
+}
+
+// The chunk loop of the two naive batched kernels (the matrix in blockIdx.z): at most 65535 matrices and kBatchedMaxWorkgroups
+// workgroups per launch, launch(grid, A, B, C, b0) with the pointers advanced to the chunk's first matrix b0 (A and B may be
+// NULL: an empty contraction reads neither), and the description: `what`, the batch and, for more than one, the launches.
+template <class L>
+int launch_naive_chunks(const GemmArgs &g, const BatchArgs &b, std::string what, L launch) {
+  const long gx = (g.n + 63) / 64, gy = (g.m + 3) / 4;
+  const long mats = std::max(1L, std::min(65535L, kBatchedMaxWorkgroups / (gx * gy)));   // matrices per launch
+  long launches = 0;
+  for (long b0 = 0; b0 < b.batch; b0 += mats) {
+    launch(dim3((unsigned)gx, (unsigned)gy, (unsigned)std::min(mats, b.batch - b0)), g.A ? g.A + b0 * b.sA : nullptr,
+           g.B ? g.B + b0 * b.sB : nullptr, g.C + b0 * b.sC, b0);
+    ++launches;
+    HIP_TRY(hipGetLastError());
+  }
+  what += ", batch " + std::to_string(b.batch);
+  if (launches > 1) what += " as " + std::to_string(launches) + " launches";
   set_last_launch(what);
   return MMH_OK;
 }

@@ -293,6 +293,35 @@ def test_a_batch_whose_last_round_is_one_tile_per_cu_goes_out_split(h, oracle, c
         h.set_kernel("auto")
 
 
+# ---- the workgroup cap ------------------------------------------------------------------------------------------------
+def test_a_batch_beyond_the_workgroup_cap_advances_the_per_matrix_biases(h):
+    """tests/test_gpu_batched.py's cap test with an epilogue: 1x1x1 matrices, one float of bias each (stride_bias = 1), ReLU.  A
+    launch of a later chunk that did not advance its bias pointer would give the matrices behind the cap the first ones' biases.
+    The expectation is float32 numpy, one rounding per operation: r = fl(fl(a b) + bias), r where r > 0, else +0."""
+    import torch
+    import how_to_optimize_gemm_amd as H
+    batch = H.BATCHED_MAX_WORKGROUPS + 4097
+    g = torch.Generator(device="cuda").manual_seed(6)
+    a, b, bias = (torch.rand(batch, device="cuda", generator=g) * 2 - 1 for _ in range(3))
+    r = a.cpu().numpy() * b.cpu().numpy() + bias.cpu().numpy()
+    assert r.dtype == np.float32
+    want = np.where(r > 0, r, np.float32(0.0)).astype(np.float32)
+    naive_launches = -(-batch // 65535)
+    try:
+        for kern, head, tail in (("auto", TILE_HEAD, "as 2 launches"), ("naive", NAIVE_HEAD, f"as {naive_launches} launches")):
+            h.set_kernel(kern)
+            c = torch.full((batch,), float("nan"), device="cuda")
+            h.sgemm_batched_ex(0, 0, 1, 1, 1, 1.0, a.data_ptr(), 1, 1, b.data_ptr(), 1, 1, 0.0, c.data_ptr(), 1, 1, batch,
+                               bias.data_ptr(), 1, COL, RELU, torch.cuda.current_stream().cuda_stream)
+            torch.cuda.synchronize()
+            launch = H.last_launch()
+            assert head in launch and launch.endswith(f", batch {batch} {tail}"), (kern, launch)
+            got = c.cpu().numpy()
+            assert same_bits(got, want), (kern, first_difference(got.reshape(1, -1), want.reshape(1, -1)))
+    finally:
+        h.set_kernel("auto")
+
+
 # ---- AUTO's forms -----------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("op", ["NN", "NT"])
 def test_auto_folds_a_shared_b_with_foldable_biases(h, oracle, op):
