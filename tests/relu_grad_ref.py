@@ -4,6 +4,8 @@ a sequential fp32 chain started at block 0.  Vectorised over the columns: every 
 correctly rounded fp32 add per column, the operation the kernels perform.  A helper, not a test module."""
 import numpy as np
 
+from bitcmp import same_bits  # noqa: F401 (bit equality with every NaN equal to every NaN: ref.same_bits)
+
 
 def header_block_rows(repo):
     """MMH_COLSUM_BLOCK_ROWS as include/mmult_hip.h defines it."""
@@ -93,12 +95,3 @@ def gamma(n):
     """Higham's gamma_n for fp32: n u / (1 - n u), u = 2^-24."""
     u = 2.0 ** -24
     return n * u / (1.0 - n * u)
-
-
-def same_bits(a, b):
-    """Bit equality with every NaN equal to every NaN."""
-    a, b = np.asarray(a, dtype=np.float32), np.asarray(b, dtype=np.float32)
-    if a.shape != b.shape:
-        return False
-    na, nb = np.isnan(a), np.isnan(b)
-    return bool(np.array_equal(na, nb) and np.array_equal(a.view(np.uint32)[~na], b.view(np.uint32)[~nb]))

@@ -1,20 +1,16 @@
 """Every plain batched instantiation in the built product library has a row in
 tests/test_gpu_batched_parity.py::BATCHED_INSTANTIATIONS, and every row names an instantiation that is there -- read on the CPU
 from the library's code objects (tools/kernel_resources.py).  The rows' shapes are checked here too, on the host arithmetic the
-launcher uses (dma5_form, csrc/internal.hpp, as tests/test_batched_ex_coverage.py restates it): that each one reaches its row's
+launcher uses (dma5_form, csrc/internal.hpp, as tests/kernel_tables.py restates it): that each one reaches its row's
 instantiation, whole or guarded, and the classes the table claims; and the shapes of the tail-split, per == 3 and special-value
 tests of that module."""
 import math
-import os
 import re
-import sys
 
-import pytest
+import built_lib
+from kernel_tables import TILES, _special_shapes, _whole, tail_split, tail_split_case
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(REPO, "tools"))
-LIB = os.path.join(REPO, "how-to-optimize-gemm_amd", "libmmult_hip.so")
-pytestmark = pytest.mark.skipif(not os.path.exists(LIB), reason="libmmult_hip.so has not been built")
+pytestmark = built_lib.needs_library
 
 FAMILY = re.compile(r"^sgemm_mfma_dma5_batched_kernel<")
 CUS = 256   # the MI355X's compute units (the GPU test derives its tail-split batch from the device's count)
@@ -25,15 +21,10 @@ def _T():
     return T
 
 
-def _built():
-    import kernel_resources as K
-    return {r["kernel"] for r in K.resources(LIB) if FAMILY.match(r["kernel"])}
-
-
 def test_the_table_names_every_batched_instantiation_of_the_library():
     symbols = [r.symbol for r in _T().BATCHED_INSTANTIATIONS]
     assert len(symbols) == len(set(symbols)), "a symbol has two rows"
-    built = _built()
+    built = built_lib.built(FAMILY)
     missing = sorted(built - set(symbols))
     stale = sorted(set(symbols) - built)
     assert not missing, f"instantiations in libmmult_hip.so without a row in BATCHED_INSTANTIATIONS: {missing}"
@@ -59,7 +50,6 @@ def _thin(x, tile):
 
 def test_every_row_is_reached_the_way_it_says():
     import how_to_optimize_gemm_amd as H
-    from test_batched_ex_coverage import _whole
     T = _T()
     for r in T.BATCHED_INSTANTIATIONS:
         g = T.FAMILY_RE.match(r.symbol)
@@ -107,7 +97,6 @@ def test_the_planner_names_a_kernel_for_every_rows_shapes():
 
 def test_the_tail_split_case_splits_on_the_launchers_rule():
     """dma5_split_first gives the first launch 3 CUs workgroups; the second one's ids start there: the last quarter of the batch."""
-    from test_gpu_batched_ex import tail_split, tail_split_case
     T = _T()
     for cus in (CUS, 304, 64):
         m, n, k, batch = tail_split_case(cus)
@@ -140,8 +129,6 @@ def test_the_per_3_case_leaves_a_first_launch_that_is_no_multiple_of_8():
 
 
 def test_the_special_shapes_are_whole_and_guarded_on_every_tile(oracle):
-    from test_gpu_batched_ex import TILES
-    from test_gpu_lds_dma_parity import _special_shapes
     T = _T()
     assert [t for t, _ in T.SPECIAL_CASES[::4]] == TILES and len(T.SPECIAL_CASES) == 12
     for kernel in TILES:

@@ -6,17 +6,9 @@ import ctypes as C
 
 import pytest
 
+from built_lib import needs_loadable_library
 
-def _library_loads():
-    try:
-        import how_to_optimize_gemm_amd as H
-        H.lib()
-        return True
-    except Exception:
-        return False
-
-
-pytestmark = pytest.mark.skipif(not _library_loads(), reason="libmmult_hip.so (or the HIP runtime it links) is not loadable here")
+pytestmark = needs_loadable_library()
 
 NONE, COL, ROW = 0, 1, 2
 FOLD, ONE_LAUNCH, LOOP = 1, 2, 3

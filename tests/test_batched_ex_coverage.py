@@ -4,16 +4,12 @@ from the library's code objects (tools/kernel_resources.py).  The rows' shapes a
 launcher uses (dma5_form, csrc/internal.hpp): that each one reaches its row's instantiation, whole or guarded, and what the
 guarded ones cover; and the shapes of the tail-split, loop and special-value tests."""
 import math
-import os
 import re
-import sys
 
-import pytest
+import built_lib
+from kernel_tables import _special_shapes, _whole
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(REPO, "tools"))
-LIB = os.path.join(REPO, "how-to-optimize-gemm_amd", "libmmult_hip.so")
-pytestmark = pytest.mark.skipif(not os.path.exists(LIB), reason="libmmult_hip.so has not been built")
+pytestmark = built_lib.needs_library
 
 FAMILY = re.compile(r"^sgemm_mfma_dma5_batched_ex_kernel<")
 CUS = 256   # the MI355X's compute units (the GPU test derives its tail-split batch from the device's count)
@@ -24,15 +20,10 @@ def _rows():
     return BATCHED_EX_INSTANTIATIONS
 
 
-def _built():
-    import kernel_resources as K
-    return {r["kernel"] for r in K.resources(LIB) if FAMILY.match(r["kernel"])}
-
-
 def test_the_table_names_every_batched_ex_instantiation_of_the_library():
     symbols = [r.symbol for r in _rows()]
     assert len(symbols) == len(set(symbols)), "a symbol has two rows"
-    built = _built()
+    built = built_lib.built(FAMILY)
     missing = sorted(built - set(symbols))
     stale = sorted(set(symbols) - built)
     assert not missing, f"instantiations in libmmult_hip.so without a row in BATCHED_EX_INSTANTIATIONS: {missing}"
@@ -43,18 +34,6 @@ def test_the_table_names_every_batched_ex_instantiation_of_the_library():
 def test_the_rows_spell_their_symbols_as_the_resource_test_does():
     from test_batched_ex_kernel_resources import _twins
     assert {r.symbol for r in _rows()} == {b for b, _, _ in _twins()}
-
-
-def _whole(bm, bn, ta, tb, m, n, k, batch, extra):
-    """dma5_form == 0 for the batch as tests/test_gpu_batched.py `Batch` lays it out (device allocations are 256-byte aligned):
-    whole tiles, leading dimensions, strides and bases multiples of 4 floats."""
-    ra, ca = (k, m) if ta else (m, k)
-    rb, cb = (n, k) if tb else (k, n)
-    lda, ldb, ldc = extra.get("lda") or ca, extra.get("ldb") or cb, extra.get("ldc") or n
-    sa, sb, sc = extra.get("sa", ra * lda), extra.get("sb", rb * ldb), extra.get("sc", m * ldc)
-    offs = extra.get("offs", (0, 0, 0))
-    tiles = m % bm == 0 and n % bn == 0 and k % 32 == 0
-    return tiles and all(x % 4 == 0 for x in (lda, ldb, ldc) + tuple(offs)) and (batch == 1 or all(s % 4 == 0 for s in (sa, sb, sc)))
 
 
 def test_every_row_is_reached_the_way_it_says():
@@ -106,7 +85,6 @@ def test_the_tail_split_case_splits_on_the_launchers_rule():
 
 def test_the_special_shapes_are_whole_and_guarded_on_every_tile():
     from test_gpu_batched_ex import TILES
-    from test_gpu_lds_dma_parity import _special_shapes
     for kernel in TILES:
         bm, bn = (int(x) for x in re.search(r"_(\d+)x(\d+)", kernel).groups())
         (wm, wn, wk, wg), (gm, gn, gk, gg) = _special_shapes(kernel)

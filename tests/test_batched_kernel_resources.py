@@ -2,28 +2,10 @@
 product library, read on the CPU (tools/kernel_resources.py): all 24 exist with the naive batched kernel, none spills,
 and each one's registers allow at least the workgroups per CU of its NN twin -- the launcher takes the tail split from
 the twin's residency."""
-import os
-import re
-import sys
+import built_lib
+from built_lib import K2W_RING as TILES   # NL,D; ring KiB
 
-import pytest
-
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(REPO, "tools"))
-LIB = os.path.join(REPO, "how-to-optimize-gemm_amd", "libmmult_hip.so")
-pytestmark = pytest.mark.skipif(not os.path.exists(LIB), reason="libmmult_hip.so has not been built")
-
-TILES = {"64,64,32,2,2,3": ("2,2", 48), "128,64,32,4,2,3": ("4,2", 72), "128,128,32,4,4,3": ("4,2", 96)}   # NL,D; ring KiB
-
-
-def _rows():
-    import kernel_resources as K
-    return {r["kernel"]: r for r in K.resources(LIB)}
-
-
-def _wgs(r):
-    alloc = (r["vgpr"] + r["agpr"] + 7) // 8 * 8
-    return (4 * min(8, 512 // max(alloc, 1))) // (r["threads"] // 64)
+pytestmark = built_lib.needs_library
 
 
 def _twins():
@@ -34,25 +16,12 @@ def _twins():
 
 
 def test_the_24_batched_instantiations_exist():
-    rows = _rows()
-    pairs = list(_twins())
-    assert len(pairs) == 24
-    missing = [b for b, _, _ in pairs if b not in rows]
-    assert missing == [], missing
-    assert sum(1 for k in rows if re.match(r"sgemm_mfma_dma5_batched_kernel<", k)) == 24
-    assert "sgemm_naive_batched_kernel" in rows
+    built_lib.check_twins_exist(_twins, 24, r"sgemm_mfma_dma5_batched_kernel<", "sgemm_naive_batched_kernel")
 
 
 def test_no_batched_instantiation_spills():
-    rows = _rows()
-    for name in [b for b, _, _ in _twins()] + ["sgemm_naive_batched_kernel"]:
-        r = rows[name]
-        assert r["vgpr_spill"] == 0 and r["scratch"] == 0 and r["sgpr_spill"] == 0, r
+    built_lib.check_no_spill([b for b, _, _ in _twins()] + ["sgemm_naive_batched_kernel"])
 
 
 def test_batched_instantiations_fit_their_nn_twins_co_residency():
-    rows = _rows()
-    for b, twin, tile in _twins():
-        lds_wgs = 160 // TILES[tile][1]
-        want = min(_wgs(rows[twin]), lds_wgs)
-        assert min(_wgs(rows[b]), lds_wgs) >= want, (b, rows[b]["vgpr"], twin, rows[twin]["vgpr"])
+    built_lib.check_twins_co_residency(_twins)

@@ -6,19 +6,9 @@ import os
 
 import pytest
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from built_lib import REPO, needs_loadable_library
 
-
-def _library_loads():
-    try:
-        import how_to_optimize_gemm_amd as H
-        H.lib()
-        return True
-    except Exception:
-        return False
-
-
-pytestmark = pytest.mark.skipif(not _library_loads(), reason="libmmult_hip.so (or the HIP runtime it links) is not loadable here")
+pytestmark = needs_loadable_library()
 
 OK, INVALID, UNSUPPORTED = 0, -1, -4
 FOLD, ONE_LAUNCH, LOOP = 1, 2, 3

@@ -7,7 +7,8 @@ import os
 
 import pytest
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from built_lib import REPO
+
 CONTRACT = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
             "dtype", "data", "config", "roofline")
 SHARDED = ("rccl_ranks", "backend", "bcast_ms", "bcast_gbps", "gemm_ms_per_rank", "gemm_ms", "value_incl_bcast", "streamed_equals_plain",

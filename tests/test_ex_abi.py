@@ -6,28 +6,15 @@ import ctypes as C
 
 import pytest
 
+from built_lib import needs_loadable_library
+from built_lib import plan as _plan
 
-def _library_loads():
-    try:
-        import how_to_optimize_gemm_amd as H
-        H.lib()
-        return True
-    except Exception:
-        return False
-
-
-pytestmark = pytest.mark.skipif(not _library_loads(), reason="libmmult_hip.so (or the HIP runtime it links) is not loadable here")
+pytestmark = needs_loadable_library()
 
 EX_FAMILIES = {29, 30, 31}   # MMH_KERNEL_MFMA_{64X64,128X64,128X128}_DMA5
 SWEEP = [(n, n, n) for n in range(1024, 4097, 128)]   # the reference sweep
 RAGGED = [(1000, 1030, 999), (1025, 1025, 1025), (33, 17, 5), (1, 1, 1), (7, 300, 1), (4096, 4096, 512), (2304, 2176, 320),
           (4822, 1268, 2551), (100, 5000, 64)]
-
-
-def _plan(fn, *args):
-    kern, tiles, grid = C.c_int(-9), C.c_long(-9), C.c_int(-9)
-    rc = fn(*args, C.byref(kern), C.byref(tiles), C.byref(grid))
-    return rc, (kern.value, tiles.value, grid.value)
 
 
 def test_the_three_symbols_are_exported_and_the_version_moved():

@@ -6,16 +6,11 @@ instantiation (whole or guarded, ragged or whole-round tile counts) and that mmh
 blocks of that file are built here as well, and each one's expectation is held to contain the class of values it is there
 for (the oracle's CPU library is all this needs)."""
 import math
-import os
 import re
-import sys
 
-import pytest
+import built_lib
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(REPO, "tools"))
-LIB = os.path.join(REPO, "how-to-optimize-gemm_amd", "libmmult_hip.so")
-pytestmark = pytest.mark.skipif(not os.path.exists(LIB), reason="libmmult_hip.so has not been built")
+pytestmark = built_lib.needs_library
 
 FAMILY = re.compile(r"^sgemm_(mfma_dma5_ex|dma5_ex_streamk)_kernel<")
 CUS = 256   # the MI355X's compute units (the GPU test derives its shapes from the device's count)
@@ -26,15 +21,10 @@ def _rows():
     return EX_INSTANTIATIONS
 
 
-def _built():
-    import kernel_resources as K
-    return {r["kernel"] for r in K.resources(LIB) if FAMILY.match(r["kernel"])}
-
-
 def test_the_table_names_every_ex_instantiation_of_the_library():
     symbols = [r.symbol for r in _rows()]
     assert len(symbols) == len(set(symbols)), "a symbol has two rows"
-    built = _built()
+    built = built_lib.built(FAMILY)
     missing = sorted(built - set(symbols))
     stale = sorted(set(symbols) - built)
     assert not missing, f"instantiations in libmmult_hip.so without a row in EX_INSTANTIATIONS: {missing}"

@@ -3,30 +3,12 @@ library, read on the CPU (tools/kernel_resources.py): all 48 exist, none spills 
 plain ones spill no scalar register and the persistent ones at most 64, and each one's registers allow at least the
 workgroups per CU of its NN twin -- the launcher takes grids, rounds and the tail split from the twins' residency
 (launch_dma5.hpp), so an `ex` kernel that needed more registers than its twin would be launched on a grid it cannot hold."""
-import os
-import re
-import sys
+import built_lib
+from built_lib import K2W_RING as TILES   # NL,D; ring KiB
 
-import pytest
-
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(REPO, "tools"))
-LIB = os.path.join(REPO, "how-to-optimize-gemm_amd", "libmmult_hip.so")
-pytestmark = pytest.mark.skipif(not os.path.exists(LIB), reason="libmmult_hip.so has not been built")
-
-TILES = {"64,64,32,2,2,3": ("2,2", 48), "128,64,32,4,2,3": ("4,2", 72), "128,128,32,4,4,3": ("4,2", 96)}   # NL,D; ring KiB
+pytestmark = built_lib.needs_library
 # stream-K instantiations launched on their OWN residency instead of the NN twin's (a smaller persistent grid): none needed
 OWN_RESIDENCY = {}
-
-
-def _rows():
-    import kernel_resources as K
-    return {r["kernel"]: r for r in K.resources(LIB)}
-
-
-def _wgs(r):
-    alloc = (r["vgpr"] + r["agpr"] + 7) // 8 * 8
-    return (4 * min(8, 512 // max(alloc, 1))) // (r["threads"] // 64)
 
 
 def _twins():
@@ -38,33 +20,12 @@ def _twins():
 
 
 def test_the_48_ex_instantiations_exist():
-    rows = _rows()
-    pairs = list(_twins())
-    assert len(pairs) == 48
-    missing = [ex for ex, _, _ in pairs if ex not in rows]
-    assert missing == [], missing
-    n = sum(1 for k in rows if re.match(r"sgemm_(mfma_dma5_ex|dma5_ex_streamk)_kernel<", k))
-    assert n == 48, n
-    assert "sgemm_naive_ex_kernel" in rows
+    built_lib.check_twins_exist(_twins, 48, r"sgemm_(mfma_dma5_ex|dma5_ex_streamk)_kernel<", "sgemm_naive_ex_kernel")
 
 
 def test_no_ex_instantiation_spills():
-    rows = _rows()
-    for ex, _, _ in _twins():
-        r = rows[ex]
-        assert r["vgpr_spill"] == 0 and r["scratch"] == 0, r
-        assert r["sgpr_spill"] <= (64 if "streamk" in ex else 0), r
-    r = rows["sgemm_naive_ex_kernel"]
-    assert r["vgpr_spill"] == 0 and r["scratch"] == 0 and r["sgpr_spill"] == 0, r
+    built_lib.check_no_spill([ex for ex, _, _ in _twins()] + ["sgemm_naive_ex_kernel"], lambda ex: 64 if "streamk" in ex else 0)
 
 
 def test_ex_instantiations_fit_their_nn_twins_co_residency():
-    rows = _rows()
-    for ex, twin, tile in _twins():
-        lds_wgs = 160 // TILES[tile][1]
-        want = min(_wgs(rows[twin]), lds_wgs)
-        have = min(_wgs(rows[ex]), lds_wgs)
-        if ex in OWN_RESIDENCY:
-            assert "streamk" in ex and rows[ex]["vgpr"] == OWN_RESIDENCY[ex] and have >= 1, (ex, rows[ex]["vgpr"])
-            continue
-        assert have >= want, (ex, rows[ex]["vgpr"], twin, rows[twin]["vgpr"])
+    built_lib.check_twins_co_residency(_twins, OWN_RESIDENCY)

@@ -7,95 +7,14 @@ import os
 import numpy as np
 import pytest
 
+from bitcmp import same_bits
+from gpu_operands import Batch, handle_fixture
+from kernel_tables import FAMILY, OPS
+
 pytestmark = pytest.mark.gpu
+h = handle_fixture(reset_kernel=True)
 
-OPS = {"NN": (0, 0), "NT": (0, 1), "TN": (1, 0), "TT": (1, 1)}
 KERNELS = ["auto", "mfma_64x64_dma5", "mfma_128x64_dma5", "mfma_128x128_dma5", "naive"]
-FAMILY = {"mfma_64x64_dma5": "<64,64>", "mfma_128x64_dma5": "<128,64>", "mfma_128x128_dma5": "<128,128>"}
-
-
-def same_bits(got, want) -> bool:
-    got, want = np.asarray(got, dtype=np.float32), np.asarray(want, dtype=np.float32)
-    if got.shape != want.shape:
-        return False
-    nan_g, nan_w = np.isnan(got), np.isnan(want)
-    if not np.array_equal(nan_g, nan_w):
-        return False
-    return np.array_equal(np.where(nan_g, 0, got.view(np.uint32)), np.where(nan_w, 0, want.view(np.uint32)))
-
-
-@pytest.fixture(scope="module")
-def h():
-    import how_to_optimize_gemm_amd as H
-    x = H.MMult(0, "auto")
-    yield x
-    x.set_kernel("auto")
-    x.close()
-
-
-class Batch:
-    """One batched problem laid out in flat host buffers: each operand's matrices at off + i * stride with leading dimension
-    ld (stride 0: one matrix for the whole batch), NaN everywhere else -- ld padding, gaps between matrices, in front of
-    the base.  Logical matrices are kept for the oracle."""
-
-    def __init__(self, ta, tb, m, n, k, batch, seed, lda=0, ldb=0, ldc=0, sa=None, sb=None, sc=None, offs=(0, 0, 0),
-                 a_val=None, b_val=None, c_val=None):
-        rng = np.random.default_rng(seed)
-        self.ta, self.tb, self.m, self.n, self.k, self.batch = ta, tb, m, n, k, batch
-        ra, ca = (k, m) if ta else (m, k)
-        rb, cb = (n, k) if tb else (k, n)
-        self.lda, self.ldb, self.ldc = lda or ca, ldb or cb, ldc or n
-        self.sa = ra * self.lda if sa is None else sa
-        self.sb = rb * self.ldb if sb is None else sb
-        self.sc = m * self.ldc if sc is None else sc
-        self.offs = offs
-
-        def lay(rows, cols, ld, s, off, fill):
-            count = batch if s else 1
-            flat = np.full(off + (count - 1) * s + rows * ld + 5, np.nan, np.float32)
-            mats = []
-            for i in range(count):
-                x = fill(rows, cols)
-                flat[off + i * s:off + i * s + rows * ld].reshape(rows, ld)[:, :cols] = x
-                mats.append(x)
-            return flat, mats
-
-        uni = lambda r, c: rng.uniform(-1, 1, (r, c)).astype(np.float32)
-        self.a, am = lay(ra, ca, self.lda, self.sa, offs[0], a_val or uni)
-        self.b, bm = lay(rb, cb, self.ldb, self.sb, offs[1], b_val or uni)
-        self.c0, self.cm = lay(m, n, self.ldc, self.sc, offs[2], c_val or uni)
-        self.A = [(x.T if ta else x) for x in am]
-        self.B = [(x.T if tb else x) for x in bm]
-
-    def logical(self, i):
-        return (np.ascontiguousarray(self.A[i if self.sa else 0]), np.ascontiguousarray(self.B[i if self.sb else 0]))
-
-    def c_window(self, flat, i):
-        o = self.offs[2] + i * self.sc
-        return flat[o:o + self.m * self.ldc].reshape(self.m, self.ldc)[:, :self.n]
-
-    def want(self, oracle, i, accumulate):
-        a, b = self.logical(i)
-        c = self.cm[i].copy() if accumulate else None
-        return oracle.ref_mmult(a, b, c, fma=True)
-
-    def run(self, h, accumulate=False, stream=None):
-        import torch
-        da, db, dc = (torch.from_numpy(x).cuda() for x in (self.a, self.b, self.c0))
-        s = stream if stream is not None else torch.cuda.current_stream().cuda_stream
-        h.sgemm_batched(self.ta, self.tb, self.m, self.n, self.k, da.data_ptr() + 4 * self.offs[0], self.lda, self.sa,
-                        db.data_ptr() + 4 * self.offs[1], self.ldb, self.sb, dc.data_ptr() + 4 * self.offs[2], self.ldc, self.sc,
-                        self.batch, accumulate, s)
-        torch.cuda.synchronize()
-        return dc.cpu().numpy()
-
-    def check(self, oracle, got, accumulate, what):
-        inside = np.zeros(got.shape, dtype=bool)
-        for i in range(self.batch):
-            assert same_bits(self.c_window(got, i), self.want(oracle, i, accumulate)), (what, "matrix", i)
-            o = self.offs[2] + i * self.sc
-            inside[o:o + self.m * self.ldc].reshape(self.m, self.ldc)[:, :self.n] = True
-        assert same_bits(got[~inside], self.c0[~inside]), (what, "wrote outside the C matrices")
 
 
 # name: (m, n, k, batch, extra Batch arguments, AUTO's expected form marker or None)

@@ -4,8 +4,8 @@ C_i = act(alpha op(A_i) op(B_i) + beta C_i + bias_i) for every matrix of a batch
 dBias + i * strideBias.  The contract is mmh_sgemm_ex's, matrix by matrix.
 
 The expectation is built HERE from the pinned oracle's fused chain and float32 numpy, one operation at a time
-(tests/test_gpu_ex.py `expected`), never from the library; results are compared as 32-bit patterns.  Operand buffers hold NaN
-in all padding, in the gaps between matrices and in front of the bases (tests/test_gpu_batched.py `Batch`), and nothing
+(tests/ex_ref.py `expected`), never from the library; results are compared as 32-bit patterns.  Operand buffers hold NaN
+in all padding, in the gaps between matrices and in front of the bases (tests/gpu_operands.py `Batch`), and nothing
 outside the C windows may change.
 
 BATCHED_EX_INSTANTIATIONS has one row per instantiation: three tiles x whole / guarded x four operand pairs = 24;
@@ -17,20 +17,19 @@ import re
 import numpy as np
 import pytest
 
-from test_gpu_batched import Batch, same_bits
-from test_gpu_ex import COL, NONE, RELU, ROW, expected
-from test_gpu_ex_parity import ex_tag, pair_name, special_blocks
-from test_gpu_lds_dma_parity import K2W_SK, K2W_TILES, _special_shapes, first_difference
+from bitcmp import first_difference, same_bits
+from ex_ref import COL, NONE, RELU, ROW, expected
+from gpu_operands import Batch, cus_fixture, handle_fixture
+from kernel_tables import (FAMILY, K2W_SK, K2W_TILES, OPS, SPLIT_MARKER, TILES, _special_shapes, ex_tag, pair_name, special_blocks,
+                           tail_split, tail_split_case)   # noqa: F401 (tail_split: tests/test_batched_ex_coverage.py reads it here)
 
 pytestmark = pytest.mark.gpu
+h = handle_fixture(check_timeouts=True)
+cus = cus_fixture("h")
 
-OPS = {"NN": (0, 0), "NT": (0, 1), "TN": (1, 0), "TT": (1, 1)}
-TILES = ["mfma_64x64_dma5", "mfma_128x64_dma5", "mfma_128x128_dma5"]
 KERNELS = ["auto"] + TILES + ["naive"]
-FAMILY = {"mfma_64x64_dma5": "<64,64>", "mfma_128x64_dma5": "<128,64>", "mfma_128x128_dma5": "<128,128>"}
 TILE_HEAD = "sgemm_mfma_dma5_batched_ex_kernel"
 NAIVE_HEAD = "sgemm_naive_batched_ex_kernel"
-SPLIT_MARKER = "(the last round as a launch of its own)"
 # name: alpha, beta, bias mode, activation.  beta == 0 runs over C buffers that are NaN throughout: C must not be read.
 EPILOGUES = {"identity": (1.0, 0.0, NONE, 0), "all": (-1.3, 0.5, COL, RELU), "row_bias": (1.0, 0.0, ROW, 0)}
 # The smallest cube on the 128 grid, from 2176 upwards, whose batch of 2 (NT) mmh_auto_plan_batched_ex plans as a loop of the
@@ -136,21 +135,6 @@ def batch_tag(ops, epilogue, batch):
     return ex_tag(ops, *epilogue) + f", batch {batch}"
 
 
-@pytest.fixture(scope="module")
-def h():
-    import how_to_optimize_gemm_amd as H
-    x = H.MMult(0, "auto")
-    yield x
-    timeouts = x.streamk_timeouts()
-    x.close()
-    assert timeouts == 0
-
-
-@pytest.fixture(scope="module")
-def cus(h):
-    return h.device_info()["cu_count"]
-
-
 # ---- the table --------------------------------------------------------------------------------------------------------
 FAMILY_RE = re.compile(r"^sgemm_mfma_dma5_batched_ex_kernel<(?P<bm>\d+),(?P<bn>\d+),32,\d+,\d+,3,(?P<edge>true|false),\d+,2,(?P<op>[0-3])>$")
 
@@ -174,7 +158,7 @@ class BatchedExInst:
         return [(m, n, 64, 3, {"ldc": n + 4, "sc": m * (n + 4) + 8, "offs": (4, 0, 8)})]
 
 
-def _rows():
+def _table_rows():
     for t in K2W_SK:
         bm, bn = (int(x) for x in t.split(",")[:2])
         for edge in ("false", "true"):
@@ -183,7 +167,7 @@ def _rows():
                                     ops=(op & 1, op >> 1), guarded=edge == "true", bm=bm, bn=bn)
 
 
-BATCHED_EX_INSTANTIATIONS = list(_rows())
+BATCHED_EX_INSTANTIATIONS = list(_table_rows())
 
 
 @functools.lru_cache(maxsize=8)
@@ -262,21 +246,6 @@ def test_many_small_matrices_cross_the_xcd_runs(h, oracle, op):
 
 
 # ---- the tail split ---------------------------------------------------------------------------------------------------
-def tail_split(tiles, w, cus, k):
-    """dma5_tail_split (csrc/internal.hpp)."""
-    rem = tiles - w * cus
-    return w >= 2 and k >= 512 and 100 * rem > 85 * cus and rem <= cus and (w * cus) % 8 == 0
-
-
-def tail_split_case(cus):
-    """(m, n, k, batch) on the 64x64 tile whose batch x tiles takes the tail split: three workgroups per CU (the 48 KiB ring) and a
-    last round of one tile per CU -- batch = CUs matrices of 2 x 2 tiles.  k = 512: the rule's floor (a second launch has to be
-    small beside a tile), the shallowest contraction that splits."""
-    m, n, k, batch = 128, 128, 512, cus
-    assert tail_split(batch * 4, 3, cus, k) and not tail_split(batch * 4, 3, cus, k - 32)
-    return m, n, k, batch
-
-
 def test_a_batch_whose_last_round_is_one_tile_per_cu_goes_out_split(h, oracle, cus):
     """A and B are shared (stride 0): one oracle chain serves every matrix, and the per-matrix biases and C matrices tell the
     matrices -- and with them the ids of the second launch -- apart."""

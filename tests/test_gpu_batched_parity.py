@@ -7,7 +7,7 @@ BATCHED_INSTANTIATIONS has one row per instantiation: three tiles x whole / guar
 tests/test_batched_kernel_resources.py::_twins spells them; tests/test_batched_coverage.py holds the table to the symbols
 of the built library on the CPU.  Every matrix of every case has an A, a B and a C of its own (no stride 0 in the table),
 so a wrong matrix index shows in the bits.  Operand buffers hold NaN in all padding, in the gaps between matrices and in
-front of the bases (tests/test_gpu_batched.py `Batch`), and nothing outside the C windows may change.
+front of the bases (tests/gpu_operands.py `Batch`), and nothing outside the C windows may change.
 
 Behind the table: the tail split (a second launch with first != 0), launches of whole matrices where the tiles per matrix do
 not divide MMH_BATCHED_MAX_WORKGROUPS (per == 3: a first grid that is no multiple of 8), special values matrix next to
@@ -18,12 +18,13 @@ import re
 import numpy as np
 import pytest
 
-from test_gpu_batched import Batch, same_bits
-from test_gpu_batched_ex import FAMILY, OPS, SPLIT_MARKER, TILES, tail_split_case
-from test_gpu_ex_parity import pair_name
-from test_gpu_lds_dma_parity import K2W_SK, K2W_TILES, _signed_zero_inputs, _special_shapes, first_difference
+from bitcmp import first_difference, same_bits
+from gpu_operands import Batch, cus_fixture, handle_fixture
+from kernel_tables import FAMILY, K2W_SK, K2W_TILES, OPS, SPLIT_MARKER, TILES, _signed_zero_inputs, _special_shapes, pair_name, tail_split_case
 
 pytestmark = pytest.mark.gpu
+h = handle_fixture(check_timeouts=True, reset_kernel=True)
+cus = cus_fixture("h")
 
 TILE_HEAD = "sgemm_mfma_dma5_batched_kernel"
 FAMILY_RE = re.compile(r"^sgemm_mfma_dma5_batched_kernel<(?P<bm>\d+),(?P<bn>\d+),32,\d+,\d+,3,(?P<edge>true|false),\d+,2,(?P<op>[0-3])>$")
@@ -33,22 +34,6 @@ OP_TAGS = {(0, 0): "", (1, 0): ", operands TN", (0, 1): ", operands NT", (1, 1):
 def batch_tag(ops, batch):
     """What the description of a one-launch batched call ends in (before " as N launches")."""
     return OP_TAGS[tuple(ops)] + f", batch {batch}"
-
-
-@pytest.fixture(scope="module")
-def h():
-    import how_to_optimize_gemm_amd as H
-    x = H.MMult(0, "auto")
-    yield x
-    timeouts = x.streamk_timeouts()
-    x.set_kernel("auto")
-    x.close()
-    assert timeouts == 0
-
-
-@pytest.fixture(scope="module")
-def cus(h):
-    return h.device_info()["cu_count"]
 
 
 # ---- the table --------------------------------------------------------------------------------------------------------
@@ -93,7 +78,7 @@ class BatchedInst:
         return [(m, n, k, 3, {"ldc": n + 4, "sa": ra * ca + 4, "sb": rb * cb + 8, "sc": m * (n + 4) + 8, "offs": (4, 0, 8)})]
 
 
-def _rows():
+def _table_rows():
     for t in K2W_SK:
         bm, bn = (int(x) for x in t.split(",")[:2])
         for edge in ("false", "true"):
@@ -102,7 +87,7 @@ def _rows():
                                   ops=(op & 1, op >> 1), guarded=edge == "true", bm=bm, bn=bn)
 
 
-BATCHED_INSTANTIATIONS = list(_rows())
+BATCHED_INSTANTIATIONS = list(_table_rows())
 
 
 class Expected(Batch):

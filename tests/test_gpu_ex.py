@@ -1,7 +1,7 @@
 """The fused epilogue on the GPU (mmh_sgemm_ex, csrc/launch_ex.hip, csrc/sgemm_dma5.hpp EP):
 C = act(alpha op(A) op(B) + beta C + bias) in one launch, every rounding defined (include/mmult_hip.h).
 
-The expectation is built HERE from the pinned oracle and numpy alone, never from the library: s = the oracle's fused chain,
+The expectation (tests/ex_ref.py) is built from the pinned oracle and numpy alone, never from the library: s = the oracle's fused chain,
 then float32 numpy operations one at a time -- each rounds once, which is the contract.  32-bit patterns are compared
 wherever the expectation is not NaN (and there the result must be NaN too); with the inputs below the expectation has no
 NaN except in the one case that feeds NaN through beta != 0 on purpose.
@@ -14,16 +14,16 @@ import os
 import numpy as np
 import pytest
 
-from test_gpu_lds_dma_parity import first_difference, same_bits
-from test_gpu_op import SHAPES
+from bitcmp import bits_equal_on_device, first_difference, same_bits
+from ex_ref import COL, NONE, RELU, ROW, expected
+from gpu_operands import _nan_stored, dev, handle_fixture, stored
+from kernel_tables import FAMILY, OPS
+from kernel_tables import OP_SHAPES as SHAPES
 
 pytestmark = pytest.mark.gpu
+h = handle_fixture(check_timeouts=True)
 
-OPS = {"NN": (0, 0), "NT": (0, 1), "TN": (1, 0), "TT": (1, 1)}
 KERNELS = ["auto", "mfma_64x64_dma5", "mfma_128x64_dma5", "mfma_128x128_dma5"]
-FAMILY = {"mfma_64x64_dma5": "<64,64>", "mfma_128x64_dma5": "<128,64>", "mfma_128x128_dma5": "<128,128>"}
-NONE, COL, ROW = 0, 1, 2
-RELU = 1
 # name: alpha, beta, bias mode, activation, C pre-filled with NaN (beta == 0 must not read it)
 EPILOGUES = {
     "identity": (1.0, 0.0, NONE, 0, False),
@@ -41,49 +41,9 @@ def tol(k):
     return 2e-7 * k + 1e-6
 
 
-def dev(x):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(x)).cuda()
-
-
-def stored(x, t):
-    return np.ascontiguousarray(x.T if t else x)
-
-
-def expected(s, alpha, beta, c, bias, bias_mode, act):
-    """The contract, restated: float32 arrays throughout, one rounding per numpy operation."""
-    assert s.dtype == np.float32
-    r = np.float32(alpha) * s
-    if beta != 0:
-        r = r + np.float32(beta) * c.astype(np.float32)
-    if bias_mode == COL:
-        r = r + bias.astype(np.float32)[None, :]
-    elif bias_mode == ROW:
-        r = r + bias.astype(np.float32)[:, None]
-    if act == RELU:
-        r = np.where((r > 0) | np.isnan(r), r, np.float32(0))
-    assert r.dtype == np.float32
-    return r
-
-
-def bits_equal_on_device(got, want):
-    import torch
-    return torch.equal(got.view(torch.int32), want.view(torch.int32))
-
-
 def is_ex_launch(launched, name):
     return launched.startswith(("sgemm_mfma_dma5_ex_kernel<", "sgemm_dma5_ex_streamk_kernel<")) and \
         (", operands " + name + ", epilogue") in launched
-
-
-@pytest.fixture(scope="module")
-def h():
-    import how_to_optimize_gemm_amd as H
-    x = H.MMult(0, "auto")
-    yield x
-    timeouts = x.streamk_timeouts()
-    x.close()
-    assert timeouts == 0
 
 
 def _inputs(oracle, m, n, k, seed, scale=1.0):
@@ -212,14 +172,6 @@ def test_stream_k_ex_launches_happen(h, oracle):
     finally:
         h.set_streamk(1)
         h.set_kernel("auto")
-
-
-def _nan_stored(rows, cols, ld, off):
-    """A device buffer of `rows` x `cols` values at row stride `ld`, `off` floats into the allocation: NaN in the padding
-    of every row, in front of the first row and behind the last one."""
-    import torch
-    flat = torch.full((off + rows * ld + 64,), float("nan"), device="cuda")
-    return flat, flat[off:off + rows * ld].view(rows, ld)
 
 
 @pytest.mark.parametrize("kernel", KERNELS + ["naive"])

@@ -7,37 +7,29 @@ pairs = 48.  A row says how a caller reaches it (forced kernel, MMH_OPT_STREAMK,
 of mmh_last_launch prove that it ran, and the shapes it runs -- the ones the NN and op rows of the same tile and edge run in
 tests/test_gpu_lds_dma_parity.py.  tests/test_ex_coverage.py holds the table to the symbols of the built library on the CPU.
 
-The expectation is tests/test_gpu_ex.py's `expected` on the oracle's fused chain: numpy alone.  sgemm_naive_ex_kernel calls
+The expectation is tests/ex_ref.py's `expected` on the oracle's fused chain: numpy alone.  sgemm_naive_ex_kernel calls
 the tiles' dma5_epilogue_apply, so for the epilogue it is no independent reference; numpy is the only one."""
 import dataclasses
 import functools
 import re
-from typing import Callable, Optional
+from typing import Callable
 
 import numpy as np
 import pytest
 
-from test_gpu_ex import COL, NONE, RELU, ROW, dev, expected
-from test_gpu_lds_dma_parity import (K2W_SK, K2W_TILES, OP_LAYOUTS, _case, _ld, _padded, _plain_shapes, _special_shapes,
-                                     _streamk_shapes, first_difference, same_bits)
+from bitcmp import first_difference, same_bits, same_bits_on_device
+from ex_ref import COL, NONE, RELU, ROW, expected
+from gpu_operands import _case, _ld, _padded, cus_fixture, dev
+from kernel_tables import (K2W_SK, K2W_TILES, OP_LAYOUTS, _plain_shapes, _special_shapes, _streamk_shapes, ex_tag, pair_name,
+                           special_blocks)
 
 pytestmark = pytest.mark.gpu
+cus = cus_fixture("mm")
 
 # ---- the table --------------------------------------------------------------------------------------------------------
 EX_OPS = {0: (0, 0), **OP_LAYOUTS}   # the OP template argument = transa | transb << 1 -> (transa, transb)
 EX_FAMILY_RE = re.compile(r"^(?P<family>sgemm_mfma_dma5_ex_kernel|sgemm_dma5_ex_streamk_kernel)<(?P<bm>\d+),(?P<bn>\d+),32,\d+,\d+,3,"
                           r"(?P<edge>true|false),\d+,2,(?P<op>[0-3])>$")
-
-
-def pair_name(ops):
-    return "NT"[ops[0]] + "NT"[ops[1]]
-
-
-def ex_tag(ops, alpha, beta, mode, act):
-    """What the description of an `ex` launch ends in (ex_tag, csrc/launch_dma5.hpp)."""
-    words = [w for on, w in ((np.float32(alpha) != 1, "alpha"), (np.float32(beta) != 0, "beta"), (mode == COL, "bias(col)"),
-                             (mode == ROW, "bias(row)"), (act == RELU, "relu")) if on]
-    return f", operands {pair_name(ops)}, epilogue " + (" ".join(words) or "identity")
 
 
 def _ex_symbols():
@@ -108,14 +100,6 @@ def _ex_case(m, n, k):
     return a, b, dev(c0), bias, want, {name: dev(w) for name, w in want.items()}
 
 
-def same_bits_on_device(got, want):
-    """same_bits on device tensors."""
-    import torch
-    nan = torch.isnan(want)
-    return torch.equal(torch.isnan(got), nan) and \
-        torch.equal(got.view(torch.int32).masked_fill(nan, 0), want.view(torch.int32).masked_fill(nan, 0))
-
-
 def run_ex(mm, ops, a, b, alpha, beta, c_init, bias, mode, act, guarded):
     """C = act(alpha op(A) op(B) + beta C + bias) through mmh_sgemm_ex on NaN-padded operands laid out as
     test_gpu_lds_dma_parity.run_gemm lays them: guarded -- odd leading dimensions, bases and the bias 4 bytes past 16-byte
@@ -177,11 +161,6 @@ class _ExOptions:
         self.mm.set_kernel("mfma")
 
 
-@pytest.fixture(scope="module")
-def cus(mm):
-    return mm.device_info()["cu_count"]
-
-
 @pytest.mark.parametrize("inst", EX_INSTANTIATIONS, ids=lambda i: i.symbol)
 def test_every_ex_instantiation_returns_the_contract_bits(mm, cus, inst):
     bm, bn = inst.bm_bn
@@ -207,198 +186,7 @@ def test_every_ex_instantiation_returns_the_contract_bits(mm, cus, inst):
 
 
 # ---- special values of the epilogue -----------------------------------------------------------------------------------
-TINY = np.finfo(np.float32).tiny
-
-
-def _is_subnormal(x):
-    return (x != 0) & (np.abs(x) < TINY)
-
-
-def _neg_zero(x):
-    return (x == 0) & np.signbit(x)
-
-
-def _pos_zero(x):
-    return (x == 0) & ~np.signbit(x)
-
-
-@dataclasses.dataclass
-class Block:
-    name: str
-    a: np.ndarray
-    b: np.ndarray
-    alpha: float
-    beta: float
-    c: Optional[np.ndarray]      # None: C's window is NaN (beta == 0 must not read it)
-    bias: Optional[np.ndarray]
-    mode: int
-    act: int
-    want: np.ndarray = None
-    reaches: Callable = None     # reaches(want) asserts on the expectation alone that the block's class of values is really there
-
-    def check_expectation(self):
-        self.reaches(self.want)
-
-
-@functools.lru_cache(maxsize=4)
-def special_blocks(oracle, m, n, k):
-    """The special-value blocks of one shape (m > 70, n > 100, k > 20), each with its expectation and a check of it.  The GPU
-    test below runs them; tests/test_ex_coverage.py checks every expectation on a machine without a GPU."""
-    f32 = np.float32
-    a, b = oracle.harness_inputs(m, n, k, seed=1234 + m + n + k)
-    rng = np.random.default_rng(m * n + k)
-    c0 = rng.uniform(-1, 1, (m, n)).astype(f32)
-    bias_n, bias_m = rng.uniform(-1, 1, n).astype(f32), rng.uniform(-1, 1, m).astype(f32)
-
-    def chain(x, y):
-        with np.errstate(over="ignore", invalid="ignore"):
-            return oracle.ref_mmult(x, y, fma=True)
-
-    def block(name, x, y, s, alpha, beta=0.0, c=None, bias=None, mode=NONE, act=0):
-        blk = Block(name, x, y, alpha, beta, c, bias, mode, act)
-        with np.errstate(over="ignore", invalid="ignore", under="ignore"):
-            blk.want = expected(s, alpha, beta, c, bias, mode, act)
-        return blk
-
-    s = chain(a, b)
-    assert np.isfinite(s).all()
-    blocks = []
-
-    # alpha == 0 is not special: 0 * s -- NaN where s is not finite, a zero of s's sign elsewhere
-    a_p, b_p = a.copy(), b.copy()
-    a_p[3, 5], a_p[70, 10], b_p[5, 7], b_p[20, 100] = np.inf, -np.inf, 0.0, np.nan
-    s_p = chain(a_p, b_p)
-    blk = block("alpha == 0", a_p, b_p, s_p, 0.0)
-
-    def reaches(w):
-        wild = ~np.isfinite(s_p)
-        assert np.isnan(s_p[3, 7]) and np.isnan(s_p[:, 100]).all() and np.isinf(s_p[3]).any() and np.isinf(s_p[70]).any()
-        assert np.isnan(w[wild]).all() and np.isnan(w).sum() == wild.sum() >= m + n - 1
-        assert (w[~wild] == 0).all() and np.array_equal(np.signbit(w[~wild]), np.signbit(s_p[~wild]))
-        assert _neg_zero(w).sum() > n and _pos_zero(w).sum() > n
-    blk.reaches = reaches
-    blocks.append(blk)
-
-    # signed zero through skipped operations: rows of A all +0 give s = +0 and, with alpha = -1, r1 = -0
-    zero_rows = np.arange(1, m, 4)
-    a_z = a.copy()
-    a_z[zero_rows] = 0.0
-    s_z = chain(a_z, b)
-    assert _pos_zero(s_z[zero_rows]).all()
-    zero_cols = np.arange(n) % 3 == 0
-    bias_neg = bias_m.copy()
-    bias_neg[zero_rows] = -0.0
-    bias_pos = bias_n.copy()
-    bias_pos[zero_cols] = 0.0
-    blk = block("signed zero, nothing switched on", a_z, b, s_z, -1.0)
-    blk.reaches = lambda w: _assert(_neg_zero(w[zero_rows]).all())
-    blocks.append(blk)
-    blk = block("signed zero, bias -0", a_z, b, s_z, -1.0, bias=bias_neg, mode=ROW)
-    blk.reaches = lambda w: _assert(_neg_zero(w[zero_rows]).all())
-    blocks.append(blk)
-    blk = block("signed zero, bias +0", a_z, b, s_z, -1.0, bias=bias_pos, mode=COL)
-    blk.reaches = lambda w: _assert(_pos_zero(w[zero_rows][:, zero_cols]).all() and zero_cols.sum() * len(zero_rows) > 0
-                                             and (w[zero_rows][:, ~zero_cols] != 0).all())
-    blocks.append(blk)
-    blk = block("signed zero, relu", a_z, b, s_z, -1.0, act=RELU)
-    blk.reaches = lambda w: _assert(_pos_zero(w[zero_rows]).all())
-    blocks.append(blk)
-
-    # beta = -0.0 is zero: C (all NaN) is not read
-    blk = block("beta == -0", a, b, s, 0.7, beta=-0.0)
-    blk.reaches = lambda w: _assert(not np.isnan(w).any() and (w != 0).any())
-    blocks.append(blk)
-
-    # ReLU's classes, from C and the bias: alpha = -1 on the +0 rows gives r1 = -0, beta = 1 adds C's planted value, the bias -0
-    # keeps it -- r3 is NaN, -inf, +inf, a negative subnormal, a positive subnormal, -0 by column
-    planted = np.array([np.nan, -np.inf, np.inf, -2.0 ** -140, 3 * 2.0 ** -149, -0.0], dtype=f32)
-    c_r = c0.copy()
-    c_r[zero_rows] = planted[np.arange(n) % 6][None, :]
-    blk = block("relu classes from C", a_z, b, s_z, -1.0, beta=1.0, c=c_r, bias=np.full(n, -0.0, f32), mode=COL, act=RELU)
-    with np.errstate(invalid="ignore"):
-        pre = expected(s_z, -1.0, 1.0, c_r, np.full(n, -0.0, f32), COL, 0)
-    blk.reaches = lambda w: _relu_classes(pre, w)
-    blocks.append(blk)
-
-    # ... and from the product, ReLU alone switched on: r3 = -s with s = +0 (rows of +0), subnormals of both signs (a row whose
-    # one nonzero element is 2^-100 against a row of B scaled by 2^-35), +inf, -inf and NaN (inf in A against a zero in B)
-    a_q, b_q = a_z.copy(), b.copy()
-    i_sub, i_inf, p_sub, p_inf = 2, 6, 4, 9
-    a_q[i_sub] = 0.0
-    a_q[i_sub, p_sub] = 2.0 ** -100
-    b_q[p_sub] = b[p_sub] * f32(2.0 ** -35)
-    a_q[i_inf, p_inf] = np.inf
-    b_q[p_inf, 11] = 0.0
-    s_q = chain(a_q, b_q)
-    blk = block("relu classes from the product", a_q, b_q, s_q, -1.0, act=RELU)
-    blk.reaches = lambda w: _relu_classes(-s_q, w)
-    blocks.append(blk)
-
-    # overflow inside the epilogue: fl(alpha s) = +-inf where s is finite; C (beta = 1) holds the opposite infinity on every 7th of
-    # those elements, the bias holds +inf on every 5th column and -inf on every 5th + 1: NaN exactly where opposite infinities meet
-    big = 3e38
-    with np.errstate(over="ignore"):
-        r1 = f32(big) * s
-    over = np.isinf(r1)
-    c_o = c0.copy()
-    pick = np.zeros(m * n, bool)
-    pick[np.flatnonzero(over.ravel())[::7]] = True
-    pick = pick.reshape(m, n)
-    c_o[pick] = -r1[pick]
-    bias_o = bias_n.copy()
-    bias_o[0::5], bias_o[1::5] = np.inf, -np.inf
-    blk = block("overflow in the epilogue", a, b, s, big, beta=1.0, c=c_o, bias=bias_o, mode=COL)
-
-    def reaches(w):
-        assert over.sum() > s.size // 2 and (r1[over] > 0).any() and (r1[over] < 0).any()
-        r2_inf = np.isinf(r1) | np.isinf(bias_o)[None, :]
-        nan = pick | (over & np.isinf(bias_o)[None, :] & (np.sign(r1) != np.sign(bias_o)[None, :]))
-        assert pick.sum() > 0 and (nan & ~pick).sum() > 0
-        assert np.array_equal(np.isnan(w), nan)
-        assert np.isinf(w[r2_inf & ~nan]).all() and np.isinf(w[over & ~nan]).sum() > 0
-    blk.reaches = reaches
-    blocks.append(blk)
-
-    # subnormal beta c beside alpha s of its size: fl(beta c) rounds (a subnormal keeps fewer bits than c has), then the sum
-    # rounds -- not the one rounding of fma(beta, c, r1)
-    alpha_t, beta_t = 2.0 ** -126, 2.0 ** -10
-    c_t = (c0 * f32(2.0 ** -120)).astype(f32)
-    blk = block("subnormal beta c", a, b, s, alpha_t, beta=beta_t, c=c_t)
-
-    def reaches(w):
-        bc = f32(beta_t) * c_t
-        r1_t = f32(alpha_t) * s
-        assert _is_subnormal(bc).sum() > s.size // 2 and _is_subnormal(r1_t).sum() > 0 and (np.abs(r1_t) >= TINY).sum() > 0
-        assert (bc.astype(np.float64) != np.float64(beta_t) * c_t.astype(np.float64)).sum() > s.size // 4   # the product rounded
-        assert (r1_t.astype(np.float64) != np.float64(alpha_t) * s.astype(np.float64)).sum() > 0
-        # fma(beta, c, r1): exact in fp64, rounded once.  It differs from the two roundings only where the sum is normal (subnormals
-        # add exactly) and fl(beta c) lands on a tie of the sum's coarser grid: one to three bits coarser here, so 1/4 .. 1/16 of
-        # the elements with a normal sum -- a few percent of all
-        fused = (np.float64(beta_t) * c_t.astype(np.float64) + r1_t.astype(np.float64)).astype(f32)
-        assert (fused != w).sum() > s.size // 64
-        assert _is_subnormal(w).sum() > 0
-    blk.reaches = reaches
-    blocks.append(blk)
-    return blocks
-
-
-def _assert(ok):
-    assert ok
-
-
-def _relu_classes(pre, want):
-    """`pre`, the value in front of ReLU, takes every class, and `want` is what the contract makes of each."""
-    nan, ninf, pinf = np.isnan(pre), np.isneginf(pre), np.isposinf(pre)
-    with np.errstate(invalid="ignore"):
-        nsub, psub, nz = _is_subnormal(pre) & (pre < 0), _is_subnormal(pre) & (pre > 0), _neg_zero(pre)
-    for name, cls in (("NaN", nan), ("-inf", ninf), ("+inf", pinf), ("negative subnormal", nsub), ("positive subnormal", psub), ("-0", nz)):
-        assert cls.sum() > 0, f"no {name} in front of ReLU"
-    assert np.array_equal(np.isnan(want), nan)
-    assert _pos_zero(want[ninf | nsub | nz]).all()
-    assert np.isposinf(want[pinf]).all()
-    assert np.array_equal(want[psub].view(np.uint32), pre[psub].view(np.uint32)) and _is_subnormal(want[psub]).all()
-
-
+# (the blocks: special_blocks, tests/kernel_tables.py)
 SPECIAL_TILES = ("mfma_64x64_dma5", "mfma_128x64_dma5", "mfma_128x128_dma5")
 
 

@@ -22,9 +22,10 @@ from typing import Callable, Optional
 import numpy as np
 import pytest
 
+from built_lib import REPO
+
 pytestmark = pytest.mark.gpu
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NXCD = 8                       # XCDs: a persistent K3p grid is a multiple of it
 GUARD_I32 = -2139062144        # 0x80808080: never a sum here
 GUARD_I8 = 77

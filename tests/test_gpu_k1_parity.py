@@ -4,7 +4,7 @@ csrc/launch_valu.hip) against the oracle's fused chain, bit for bit, overwrite a
 Since K1W (sgemm_valu_dma5_*) took the whole-tile shapes, the two whole-tile instantiations of K1 run only where K1W does
 not: beyond the buffer-descriptor window (launch_valu_w returns 1 and launch_valu_tile picks `fast` by the tile's own K-slice
 depth), and, for the 128x128 tile, from four tiles per CU.  K1_INSTANTIATIONS has one row per instantiation, in the style of
-tests/test_gpu_reg_parity.py::REG_INSTANTIATIONS, whose helpers run the rows here: a row says which forced kernels reach its
+tests/test_gpu_reg_parity.py::REG_INSTANTIATIONS (tests/gpu_operands.py runs the rows of both): a row says which forced kernels reach its
 instantiation, which words of mmh_last_launch prove it, and the shapes it runs.  tests/test_k1_coverage.py holds the table to
 the symbols of the built library on the CPU and proves every case's route on launch_valu.hip's host arithmetic, restated in
 `k1_route` below.
@@ -17,10 +17,12 @@ import re
 
 import pytest
 
-from test_gpu_lds_dma_parity import _case, _ld, first_difference, same_bits
-from test_gpu_reg_parity import _edge_cases, _reach, big, run_strided, smallest_beyond, window_ok   # noqa: F401 (big: a fixture)
+from bitcmp import first_difference, same_bits
+from gpu_operands import BIG_FLOATS, _case, _ld, _reach, big, cus_fixture, run_strided   # noqa: F401 (big: a fixture)
+from kernel_tables import _edge_cases, smallest_beyond, window_ok
 
 pytestmark = pytest.mark.gpu
+cus = cus_fixture("mm")
 
 K1_HEAD = "sgemm_valu_kernel"
 K1W_HEAD = "sgemm_valu_dma5"
@@ -88,14 +90,14 @@ class K1:
         return case.lda or _ld(case.k, guarded), case.ldb or _ld(case.n, guarded), _ld(case.n, guarded)
 
 
-def _rows():
+def _table_rows():
     for (bm, bn), (kb, p) in K1_TILES.items():
         for edge in ("false", "true"):
             yield K1(symbol=f"{K1_HEAD}<{bm},{bn},{kb},{edge},1,{p}>", bm=bm, bn=bn, kb=kb, guarded=edge == "true",
                      kernels=K1_KERNELS[(bm, bn)] if edge == "true" else K1_KERNELS[(bm, bn)][:1])
 
 
-K1_INSTANTIATIONS = list(_rows())
+K1_INSTANTIATIONS = list(_table_rows())
 
 
 def k1_route(kernel, case, lds, cus, streamk=0):
@@ -125,11 +127,6 @@ def k1_route(kernel, case, lds, cus, streamk=0):
         return (K1W_HEAD, 128, 64, False) if w(128, 64) else k1_128()
     assert kernel == "valu_128x128", kernel
     return k1_128()
-
-
-@pytest.fixture(scope="module")
-def cus(mm):
-    return mm.device_info()["cu_count"]
 
 
 @pytest.mark.parametrize("row", K1_INSTANTIATIONS, ids=lambda r: r.symbol)

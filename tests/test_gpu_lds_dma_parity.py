@@ -7,10 +7,9 @@ kernel, MMH_OPT_STREAMK, MMH_OPT_STREAMK_CHAIN, MMH_OPT_PERSIST, operand layouts
 that it ran, and the shapes it runs.  tests/test_lds_dma_coverage.py holds the table to the symbols of the built library on
 the CPU, so a new instantiation cannot ship without a row.
 
-"Bit for bit" is same_bits: the uint32 patterns are equal wherever the oracle's value is not NaN (so -0.0 is not +0.0),
-and NaN stands where the oracle has NaN (payloads are not compared)."""
+"Bit for bit" is same_bits (tests/bitcmp.py): the uint32 patterns are equal wherever the oracle's value is not NaN (so -0.0 is
+not +0.0), and NaN stands where the oracle has NaN (payloads are not compared)."""
 import dataclasses
-import functools
 import math
 import re
 from typing import Callable, Optional
@@ -18,37 +17,18 @@ from typing import Callable, Optional
 import numpy as np
 import pytest
 
+from bitcmp import first_difference, same_bits
+from gpu_operands import _Options, _case, cus_fixture, run_gemm
+from kernel_tables import (K2L_TILES, K2W_SK, K2W_TILES, OP_LAYOUTS, _plain_shapes, _signed_zero_inputs, _special_shapes,
+                           _streamk_shapes)
+
 pytestmark = pytest.mark.gpu
-
-
-def same_bits(got, want) -> bool:
-    got, want = np.asarray(got, dtype=np.float32), np.asarray(want, dtype=np.float32)
-    if got.shape != want.shape:
-        return False
-    nan_g, nan_w = np.isnan(got), np.isnan(want)
-    if not np.array_equal(nan_g, nan_w):
-        return False
-    return np.array_equal(np.where(nan_g, 0, got.view(np.uint32)), np.where(nan_w, 0, want.view(np.uint32)))
-
-
-def first_difference(got, want) -> str:
-    got, want = np.asarray(got, dtype=np.float32), np.asarray(want, dtype=np.float32)
-    bad = (np.isnan(got) != np.isnan(want)) | (~np.isnan(want) & (got.view(np.uint32) != want.view(np.uint32)))
-    idx = np.argwhere(bad)
-    if len(idx) == 0:
-        return "no difference"
-    i, j = idx[0]
-    return f"{len(idx)} elements differ, first C[{i},{j}] = {got[i, j]!r} ({got.view(np.uint32)[i, j]:#010x}), " \
-           f"oracle {want[i, j]!r} ({want.view(np.uint32)[i, j]:#010x})"
+cus = cus_fixture("mm")
 
 
 # ---- the table --------------------------------------------------------------------------------------------------------
-# The tile configurations the launchers instantiate (launch_dma.hip, launch_dma5.hip, launch_op.hip, launch_valu.hip);
-# the symbols are spelled as tools/kernel_resources.py demangles them.
-K2L_TILES = ("64,64,32,2,2,3", "128,64,32,4,2,3", "128,128,32,4,4,3")
-K2W_TILES = {"64,64,32,2,2,3": "2,2", "128,64,32,4,2,3": "4,2", "128,128,32,4,4,3": "4,2",        # NL,D; with a stream-K form
-             "96,96,32,3,3,3": "1,2", "96,64,32,3,2,3": "4,2", "160,160,32,5,5,3": "4,2"}        # one workgroup per tile only
-K2W_SK = ("64,64,32,2,2,3", "128,64,32,4,2,3", "128,128,32,4,4,3")
+# The K1W tile configurations (launch_valu.hip), spelled as tools/kernel_resources.py demangles them; the K2L and K2W ones:
+# tests/kernel_tables.py.
 K1W = ("128,128,2,2,2,2,3", "128,64,3,2,2,2,3", "64,64,3,2,2,2,5", "64,64,3,2,2,4,5")
 K1W_SK = ("128,128,2,2,2,2", "128,64,3,2,2,3", "64,64,3,2,2,5")
 BOOL = ("false", "true")
@@ -86,7 +66,6 @@ FAMILIES = {
     "sgemm_valu_dma5_streamk_kernel": r"\d+,\d+,\d+,\d+",
 }
 FAMILY_RE = re.compile(r"^(?P<family>" + "|".join(FAMILIES) + r")<(?P<bm>\d+),(?P<bn>\d+),(?P<rest>.*)>$")
-OP_LAYOUTS = {1: (1, 0), 2: (0, 1), 3: (1, 1)}   # the OP template argument = transa | transb << 1
 
 
 @dataclasses.dataclass(frozen=True)
@@ -106,43 +85,6 @@ class Inst:
     def bm_bn(self):
         m = FAMILY_RE.match(self.symbol)
         return int(m["bm"]), int(m["bn"])
-
-
-def _whole_shapes(bm, bn):
-    return [(bm, bn, 32), (2 * bm, 3 * bn, 224), (8 * bm, 5 * bn, 512)]
-
-
-def _edge_shapes(bm, bn):
-    """Ragged m / n / k on every K-tail class, and a last tile row / column of 1, 15, 16 and 17 (K2W's thin edge tiles)."""
-    return [(1, 1, 1), (bm - 1, bn + 1, 31), (bm + 1, 2 * bn - 1, 33)] + \
-           [(2 * bm + r, 3 * bn + c, k) for r, c, k in ((1, 17, 64), (15, 16, 95), (16, 15, 130), (17, 1, 257))]
-
-
-# the shapes the reference sweep sends to the two odd-blocked K2W tiles (mmh_auto_plan picks them there)
-EXTRA = {(160, 160, False): [(2560, 2560, 2560)], (160, 160, True): [(161, 159, 33), (2561, 2559, 777)],
-         (96, 64, False): [(1152, 1152, 1152)], (96, 64, True): [(97, 65, 31), (1153, 1151, 1000)]}
-
-
-def _plain_shapes(bm, bn, edge):
-    def shapes(cus):
-        base = _edge_shapes(bm, bn) + [(bm, bn, 32)] if edge else _whole_shapes(bm, bn)
-        return [(m, n, k, False) for m, n, k in base + EXTRA.get((bm, bn, edge), [])]
-    return shapes
-
-
-def _streamk_shapes(bm, bn, edge, persist):
-    """Ragged tile counts above one per CU (forced stream-K hands tiles over between workgroups) and, with MMH_OPT_PERSIST,
-    6 tiles per CU: a whole number (>= 2) of rounds of every grid the launcher can pick (1, 2 or 3 workgroups per CU)."""
-    def shapes(cus):
-        r = math.isqrt(cus) + 1                                  # r * r tiles: more than one per CU, fewer than two
-        if edge:
-            out = [((r - 1) * bm + 7, r * bn - 3, 100), (2 * r * bm + 1, (r + 1) * bn + 17, 257)]
-            rounds = (6 * bm - 3, cus * bn - 1, 97)
-        else:
-            out = [(r * bm, r * bn, 160), ((2 * r + 1) * bm, (r + 2) * bn, 96)]
-            rounds = (6 * bm, cus * bn, 96)
-        return [(m, n, k, False) for m, n, k in out] + ([rounds + (True,)] if persist else [])
-    return shapes
 
 
 def _k1w_shapes(bm, bn, ak):
@@ -209,83 +151,6 @@ INSTANTIATIONS = sorted((_row(s) for s in _symbols()), key=_order)
 
 
 # ---- running a row ----------------------------------------------------------------------------------------------------
-@functools.lru_cache(maxsize=16)
-def _case(m, n, k):
-    """Inputs and the oracle's overwrite / accumulate results of one shape (every row that runs it reuses them)."""
-    from oracle import oracle as O
-    a, b = O.harness_inputs(m, n, k, seed=(31 * m + 7 * n + k) % (1 << 31))
-    c0 = np.random.default_rng(m + n + k).uniform(-1, 1, (m, n)).astype(np.float32)
-    return a, b, c0, O.ref_mmult(a, b, fma=True), O.ref_mmult(a, b, c0.copy(), fma=True)
-
-
-def _padded(rows, cols, ld, off, fill=None):
-    """A NaN buffer, and the rows x ld view at `off` floats into it with `fill` in its first `cols` columns."""
-    import torch
-    flat = torch.full((rows * ld + off + 8,), float("nan"), device="cuda")
-    view = flat[off:off + rows * ld].view(rows, ld)
-    if fill is not None:
-        view[:, :cols] = torch.from_numpy(np.ascontiguousarray(fill)).cuda()
-    return flat, view
-
-
-def _ld(cols, guarded):
-    return cols + (1 if cols % 2 == 0 else 2) if guarded else cols + 4   # odd, or a multiple of 4 floats past the row
-
-
-def run_gemm(mm, a, b, c_init, accumulate, guarded, ops=None):
-    """C = op(A) op(B) (+ C) through mmh_sgemm / mmh_sgemm_op on NaN-padded operands: guarded -- odd leading dimensions and
-    bases 4 bytes past 16-byte alignment; otherwise leading dimensions that are multiples of 4 and 16-byte aligned bases.
-    Returns (C's window, whether anything outside it was written, the launch string)."""
-    import torch
-    import how_to_optimize_gemm_amd as H
-    m, k = a.shape
-    n = b.shape[1]
-    off = 1 if guarded else 4
-    ta, tb = ops or (0, 0)
-    sa = np.ascontiguousarray(a.T) if ta else a
-    sb = np.ascontiguousarray(b.T) if tb else b
-    lda, ldb, ldc = _ld(sa.shape[1], guarded), _ld(sb.shape[1], guarded), _ld(n, guarded)
-    _, av = _padded(*sa.shape, lda, off, sa)
-    _, bv = _padded(*sb.shape, ldb, off, sb)
-    cflat, cv = _padded(m, n, ldc, off, c_init)
-    s = torch.cuda.current_stream().cuda_stream
-    if ops is None:
-        mm.sgemm(m, n, k, av.data_ptr(), lda, bv.data_ptr(), ldb, cv.data_ptr(), ldc, accumulate, s)
-    else:
-        mm.sgemm_op(ta, tb, m, n, k, av.data_ptr(), lda, bv.data_ptr(), ldb, cv.data_ptr(), ldc, accumulate, s)
-    launched = H.last_launch()
-    torch.cuda.synchronize()
-    untouched = bool(torch.isnan(cv[:, n:]).all()) and bool(torch.isnan(cflat[:off]).all()) and \
-        bool(torch.isnan(cflat[off + m * ldc:]).all())
-    return cv[:, :n].cpu().numpy(), untouched, launched
-
-
-class _Options:
-    """A row's reach on the session handle, and the defaults back afterwards."""
-
-    def __init__(self, mm, inst):
-        self.mm, self.inst = mm, inst
-
-    def __enter__(self):
-        import how_to_optimize_gemm_amd as H
-        self.mm.set_kernel(self.inst.kernel)
-        self.mm.set_streamk(self.inst.streamk)
-        self.mm.set_option(H.OPT_STREAMK_CHAIN, self.inst.chain)
-        self.mm.set_option(H.OPT_PERSIST, self.inst.persist)
-
-    def __exit__(self, *exc):
-        import how_to_optimize_gemm_amd as H
-        self.mm.set_option(H.OPT_PERSIST, 0)
-        self.mm.set_option(H.OPT_STREAMK_CHAIN, 1)
-        self.mm.set_streamk(1)
-        self.mm.set_kernel("mfma")
-
-
-@pytest.fixture(scope="module")
-def cus(mm):
-    return mm.device_info()["cu_count"]
-
-
 @pytest.mark.parametrize("inst", INSTANTIATIONS, ids=lambda i: i.symbol)
 def test_every_lds_dma_instantiation_returns_the_oracle_bits(mm, cus, inst):
     guarded = "guarded" in inst.markers
@@ -319,33 +184,6 @@ SPECIAL_KERNELS = [(f"mfma_{t}_dma", None) for t in ("64x64", "128x64", "128x128
     [(f"valu_{t}", None) for t in ("64x64", "128x64", "128x128")] + [("naive", None), ("auto", None)] + \
     [(k, None) for k in ("mfma", "mfma_64x64", "mfma_128x64", "mfma_256x256")] + \
     [(f"mfma_{t}_dma5", ops) for t in ("64x64", "128x64", "128x128") for ops in ((0, 1), (1, 0), (1, 1))]
-
-
-def _special_shapes(kernel):
-    """One whole-tile shape and one guarded one whose k leaves a K tail (k % 32 != 0); both reach C[70, 100]."""
-    t = re.search(r"_(\d+)x(\d+)", kernel)
-    bm, bn = (int(t[1]), int(t[2])) if t else (64, 64)
-    wm, wn = bm * (-(-128 // bm)), bn * (-(-192 // bn))
-    return [(wm, wn, 96, False), (wm + 3, wn - 5, 77, True)]
-
-
-def _signed_zero_inputs(a, b):
-    """Rows of A that are +0 and -0 against columns of B that are all negative and all positive: every product of
-    C[+0 row, negative column] and of C[-0 row, positive column] is -0.  C0 is -0 there; the chain keeps it."""
-    a, b = a.copy(), b.copy()
-    m, n = a.shape[0], b.shape[1]
-    rows_p, rows_n = np.arange(0, m, 5), np.arange(2, m, 5)
-    cols_neg = np.arange(n) % 3 == 0
-    a[rows_p] = 0.0
-    a[rows_n] = -0.0
-    b[:, cols_neg] = -np.abs(b[:, cols_neg]) - 0.25
-    b[:, ~cols_neg] = np.abs(b[:, ~cols_neg]) + 0.25
-    neg_zero = np.zeros((m, n), dtype=bool)
-    neg_zero[np.ix_(rows_p, np.flatnonzero(cols_neg))] = True
-    neg_zero[np.ix_(rows_n, np.flatnonzero(~cols_neg))] = True
-    c0 = np.random.default_rng(5).uniform(-1, 1, (m, n)).astype(np.float32)
-    c0[neg_zero] = -0.0
-    return a, b, c0, neg_zero
 
 
 @pytest.mark.parametrize("kernel,ops", SPECIAL_KERNELS,

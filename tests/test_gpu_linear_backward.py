@@ -3,31 +3,23 @@ GEMMs on the contract's dz (bit for bit: the backward is a composition of entry 
 everything against float64 within the chains' bounds, the `need` masks, accumulation into grad_w / grad_b, and a two-layer
 MLP through autograd.Linear whose gradients are the hand-written sequence's bits -- and, within a bound computed from the data,
 torch's own autograd of the same function in float64."""
-import os
-import sys
 
 import numpy as np
 import pytest
 
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-import relu_grad_ref as ref  # noqa: E402
+import relu_grad_ref as ref
+from built_lib import REPO
+from gpu_operands import handle_fixture
 
 pytestmark = pytest.mark.gpu
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 R = ref.header_block_rows(REPO)
 # (rows, in, out); the last two leave the single tile: dw = dz.t() @ x runs 65 - 71 K-slices, dx spans dozens of tiles, db goes
 # through 18 and 17 row blocks (one batch of the finish kernel's 16 partial rows plus one; exactly one batch)
 SHAPES = [(37, 45, 70), (129, 64, 200), (1, 5, 3), (17 * R + 77, 130, 200), (16 * R + 1, 64, 260)]
 
 
-@pytest.fixture(scope="module")
-def amm():
-    """The module's own handle on MMH_KERNEL_AUTO (the session fixture's `mfma` kernel has no transposed-operand forms)."""
-    import how_to_optimize_gemm_amd as H
-    h = H.MMult(0, "auto")
-    yield h
-    h.close()
+amm = handle_fixture()   # the module's own handle on MMH_KERNEL_AUTO (the session fixture's `mfma` kernel has no op forms)
 
 
 _CASES = {}

@@ -3,30 +3,22 @@ inputs; a captured call that would have to grow the partial-row workspace is ref
 later eager call that grows the workspace (the buffer it points at is retired, not freed); MMult.linear_backward and a training
 step of autograd.Linear captured whole replay the eager bits.  Everything is captured on one side stream: no graph here has
 parallel branches."""
-import os
-import sys
 
 import numpy as np
 import pytest
 
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-import relu_grad_ref as ref  # noqa: E402
+import relu_grad_ref as ref
+from built_lib import REPO
+from gpu_operands import handle_fixture
 
 pytestmark = pytest.mark.gpu
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 R = ref.header_block_rows(REPO)
 SMALL, LARGE = (2 * R + 1, 64), (17 * R + 77, 260)     # 3 blocks; 18 blocks (a batch of 16 partial rows plus one)
 FILL = -777.25
 
 
-@pytest.fixture(scope="module")
-def amm():
-    """The module's own handle on MMH_KERNEL_AUTO."""
-    import how_to_optimize_gemm_amd as H
-    h = H.MMult(0, "auto")
-    yield h
-    h.close()
+amm = handle_fixture()   # the module's own handle on MMH_KERNEL_AUTO (the session fixture's `mfma` kernel has no op forms)
 
 
 def _inputs(shape, seed):

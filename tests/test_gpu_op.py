@@ -7,25 +7,19 @@ import os
 import numpy as np
 import pytest
 
+from gpu_operands import _nan_stored, dev, handle_fixture, stored
+from kernel_tables import FAMILY
+from kernel_tables import OP_SHAPES as SHAPES
+
 pytestmark = pytest.mark.gpu
+h = handle_fixture()
 
 OPS = {"NT": (0, 1), "TN": (1, 0), "TT": (1, 1)}
 KERNELS = ["auto", "mfma_64x64_dma5", "mfma_128x64_dma5", "mfma_128x128_dma5"]
-FAMILY = {"mfma_64x64_dma5": "<64,64>", "mfma_128x64_dma5": "<128,64>", "mfma_128x128_dma5": "<128,128>"}
 
 
 def tol(k):
     return 2e-7 * k + 1e-6
-
-
-def dev(x):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(x)).cuda()
-
-
-def stored(x, t):
-    """The operand as mmh_sgemm_op reads it: x itself (op N) or its transpose, materialised (op T)."""
-    return np.ascontiguousarray(x.T if t else x)
 
 
 def run_op(h, ta, tb, a, b, c=None, accumulate=False):
@@ -38,18 +32,6 @@ def run_op(h, ta, tb, a, b, c=None, accumulate=False):
     h.sgemm_op(ta, tb, m, n, k, sa.data_ptr(), m if ta else k, sb.data_ptr(), k if tb else n, out.data_ptr(), n, accumulate,
                torch.cuda.current_stream().cuda_stream)
     return out.cpu().numpy()
-
-
-@pytest.fixture(scope="module")
-def h():
-    import how_to_optimize_gemm_amd as H
-    x = H.MMult(0, "auto")
-    yield x
-    x.close()
-
-
-SHAPES = [(256, 256, 256), (512, 384, 1024), (1024, 1024, 1024), (2176, 2176, 2176), (4096, 4096, 4096), (1000, 1030, 999),
-          (1025, 1025, 1025), (33, 17, 5), (1, 1, 1), (7, 300, 1)]
 
 
 @pytest.mark.parametrize("m,n,k", SHAPES)
@@ -102,14 +84,6 @@ def test_stream_k_op_launches_happen(h, oracle):
     finally:
         h.set_streamk(1)
         h.set_kernel("auto")
-
-
-def _nan_stored(rows, cols, ld, off):
-    """A device buffer of `rows` x `cols` values at row stride `ld`, `off` floats into the allocation: NaN in the padding
-    of every row, in front of the first row and behind the last one."""
-    import torch
-    flat = torch.full((off + rows * ld + 64,), float("nan"), device="cuda")
-    return flat, flat[off:off + rows * ld].view(rows, ld)
 
 
 @pytest.mark.parametrize("kernel", KERNELS)

@@ -15,6 +15,8 @@ Bars:
 import numpy as np
 import pytest
 
+from gpu_operands import dev
+
 from conftest import golden_cases, load_golden
 
 pytestmark = pytest.mark.gpu
@@ -26,11 +28,6 @@ KERNELS = ["mfma", "mfma256", "mfma_256x256", "mfma_128x64", "mfma_64x64", "auto
 
 def tol(k):
     return 2e-7 * k + 1e-6
-
-
-def dev(x):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(x)).cuda()
 
 
 def run_strided(mm, a_buf, b_buf, c_buf, m, n, k, accumulate):

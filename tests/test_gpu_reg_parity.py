@@ -3,7 +3,7 @@ the oracle's fused chain, bit for bit -- and the addressing beyond, at the edge 
 window.
 
 REG_INSTANTIATIONS has one row per instantiation of sgemm_mfma_kernel, sgemm_mfma_streamk_kernel and sgemm_mfma_simple_kernel,
-in the style of tests/test_gpu_lds_dma_parity.py::INSTANTIATIONS (whose helpers run the rows here); the opt-in split-K
+in the style of tests/test_gpu_lds_dma_parity.py::INSTANTIATIONS (tests/gpu_operands.py runs the rows of both); the opt-in split-K
 instantiations, which are not chain kernels, have a table and a bit contract of their own (tests/test_gpu_splitk_parity.py).
 A row says how a caller reaches its instantiation through the C ABI -- forced kernel, MMH_OPT_STREAMK, MMH_OPT_PERSIST, whole
 or guarded operands, each operand inside or beyond the descriptor window --, which words of mmh_last_launch prove that its
@@ -16,28 +16,19 @@ is a strided view into one module-wide NaN buffer, and NaN goes back over what w
 import dataclasses
 import math
 import re
-import types
 from typing import Callable, Optional
 
 import numpy as np
 import pytest
 
-from test_gpu_lds_dma_parity import _Options, _case, _ld, _padded, first_difference, run_gemm, same_bits
+from bitcmp import first_difference, same_bits
+from gpu_operands import BIG_FLOATS, _case, _ld, _reach, _strided, big, cus_fixture, run_strided   # noqa: F401 (big: a fixture)
+from kernel_tables import LIM, REG_TILES, Case, _edge_cases, _parity, per_cu_by_lds, smallest_beyond, window_ok
 
 pytestmark = pytest.mark.gpu
+cus = cus_fixture("mm")
 
-LIM = (1 << 31) - 4096          # csrc/internal.hpp window_ok: every byte offset of a tile below this
-BIG_FLOATS = LIM // 4 + (1 << 21)   # the NaN buffer an operand beyond the window is a view of
 FAR_LD = 1 << 20                # lda = ldc of the operands past 4 GiB
-
-
-def window_ok(bm, bn, k, lda, ldb) -> bool:
-    """csrc/internal.hpp window_ok: the buffer-descriptor path needs every byte offset of a tile inside the 2 GiB window."""
-    return (bm * lda + k) * 4 < LIM and (k * ldb + bn) * 4 < LIM
-
-
-def _parity(ld, guarded) -> bool:
-    return ld % 2 == 1 if guarded else ld % 4 == 0
 
 
 def largest_inside(side, bm, bn, k, guarded) -> int:
@@ -46,14 +37,6 @@ def largest_inside(side, bm, bn, k, guarded) -> int:
     ld = (q - k) // bm if side == "a" else (q - bn) // k
     while not _parity(ld, guarded):
         ld -= 1
-    return ld
-
-
-def smallest_beyond(side, bm, bn, k, guarded) -> int:
-    q = LIM // 4 - 1
-    ld = ((q - k) // bm if side == "a" else (q - bn) // k) + 1
-    while not _parity(ld, guarded):
-        ld += 1
     return ld
 
 
@@ -76,9 +59,7 @@ def fallback_tile(m, n, cus):
 
 
 # ---- the table --------------------------------------------------------------------------------------------------------
-# forced kernel -> BM, BN, WTN, WTM, KB (csrc/internal.hpp reg_tiles; mfma256 is launch_reg's launch_mfma<256, 128>)
-REG_TILES = {"mfma": (128, 128, 4, 4, 32), "mfma_256x256": (256, 256, 4, 8, 32), "mfma_128x64": (128, 64, 2, 4, 32),
-             "mfma_64x64": (64, 64, 2, 2, 128), "mfma256": (256, 128, 4, 4, 32)}
+# (REG_TILES, tests/kernel_tables.py: forced kernel -> BM, BN, WTN, WTM, KB)
 SK_TILES = ("mfma", "mfma_256x256", "mfma_128x64", "mfma_64x64")     # reg_tiles: the ones with a stream-K form
 BEYOND_KERNELS = ("mfma", "mfma256", "mfma_256x256", "mfma_128x64", "mfma_64x64", "mfma_pipe")
 BOOL = ("false", "true")
@@ -110,16 +91,6 @@ FAMILIES = {
     "sgemm_mfma_simple_kernel": r"(?P<edge>true|false)",
 }
 FAMILY_RE = re.compile(r"^(?P<family>" + "|".join(FAMILIES) + r")<(?P<bm>\d+),(?P<bn>\d+),(?P<rest>.*)>$")
-
-
-@dataclasses.dataclass(frozen=True)
-class Case:
-    m: int
-    n: int
-    k: int
-    lda: int = 0                      # 0: run_gemm's small padded leading dimension; else A is a view of the NaN buffer
-    ldb: int = 0                      # likewise B
-    whole_rounds: bool = False        # stream-K rows: a whole number (>= 2) of rounds of the persistent grid (MMH_OPT_PERSIST)
 
 
 @dataclasses.dataclass(frozen=True)
@@ -155,21 +126,8 @@ class Reg:
         return self.bufld is None or window_ok(bm, bn, case.k, *self.leading_dimensions(case)) == self.bufld
 
 
-def _k_tails(kb):
-    """k of the four ragged shapes: a whole number of K-slices, tails of KB - 1, 1 and 2 behind two and more slices."""
-    return (2 * kb, 3 * kb - 1, 2 * kb + 1, 4 * kb + 2)
-
-
 def _whole_cases(bm, bn, kb):
     return [Case(bm, bn, kb), Case(2 * bm, 3 * bn, 7 * kb)]
-
-
-def _edge_cases(bm, bn, kb):
-    """tests/test_gpu_lds_dma_parity.py _edge_shapes with K tails for the tile's own KB (the 64x64 tile's slices are 128 deep:
-    k % 128 of 1, 127, 1, 0, 127, 1, 2), and one whole-tile shape that only its operands' alignment makes guarded."""
-    return [Case(1, 1, 1), Case(bm - 1, bn + 1, kb - 1), Case(bm + 1, 2 * bn - 1, kb + 1)] + \
-           [Case(2 * bm + r, 3 * bn + c, k) for (r, c), k in zip(((1, 17), (15, 16), (16, 15), (17, 1)), _k_tails(kb))] + \
-           [Case(bm, bn, kb)]
 
 
 def _beyond_cases(bm, bn, kb, guarded):
@@ -184,11 +142,6 @@ def _beyond_cases(bm, bn, kb, guarded):
         # descriptor (extent 0x7fffffff) returns zeros -- the cases that tell the two loaders apart by their results.
         out += [Case(m, n, k, ldb=past_2_31(k)), Case(m, n, k, lda=past_2_31(m))]
     return out
-
-
-def per_cu_by_lds(bm, bn, kb):
-    """launch_common.hpp resident_per_cu's upper bound: persistent workgroups per CU the 160 KiB of LDS allow."""
-    return (160 * 1024) // (2 * kb * (bm + bn) * 4)
 
 
 def whole_round_tiles_per_cu(w):
@@ -256,67 +209,6 @@ REG_INSTANTIATIONS = sorted((_row(s) for s in _symbols()), key=_order)
 
 
 # ---- running a row ----------------------------------------------------------------------------------------------------
-@pytest.fixture(scope="module")
-def cus(mm):
-    return mm.device_info()["cu_count"]
-
-
-@pytest.fixture(scope="module")
-def big():
-    """The flat NaN buffer an operand beyond (or at the edge of) the window is a strided view of."""
-    import torch
-    buf = torch.full((BIG_FLOATS,), float("nan"), device="cuda")
-    yield buf
-    del buf
-    torch.cuda.empty_cache()
-
-
-def _strided(flat, rows, cols, ld, off):
-    import torch
-    assert off + (rows - 1) * ld + cols <= flat.numel(), "the operand does not fit its buffer"
-    return torch.as_strided(flat, (rows, cols), (ld, 1), off)
-
-
-def run_strided(mm, big, a, b, c_init, accumulate, guarded, lda=0, ldb=0):
-    """run_gemm with A (lda given) or B (ldb given) as a view of `big` with that leading dimension; NaN goes back over the
-    view afterwards.  Returns (C's window, whether anything outside it was written, the launch string)."""
-    import torch
-    import how_to_optimize_gemm_amd as H
-    if not lda and not ldb:
-        return run_gemm(mm, a, b, c_init, accumulate, guarded)
-    assert not (lda and ldb), "one buffer, one large operand"
-    m, k = a.shape
-    n = b.shape[1]
-    off = 1 if guarded else 4
-    ldc = _ld(n, guarded)
-    if lda:
-        av = _strided(big, m, k, lda, off)
-        av.copy_(torch.from_numpy(a))
-        ldb = _ld(n, guarded)
-        _, bv = _padded(k, n, ldb, off, b)
-        view = av
-    else:
-        bv = _strided(big, k, n, ldb, off)
-        bv.copy_(torch.from_numpy(b))
-        lda = _ld(k, guarded)
-        _, av = _padded(m, k, lda, off, a)
-        view = bv
-    try:
-        cflat, cv = _padded(m, n, ldc, off, c_init)
-        mm.sgemm(m, n, k, av.data_ptr(), lda, bv.data_ptr(), ldb, cv.data_ptr(), ldc, accumulate, torch.cuda.current_stream().cuda_stream)
-        launched = H.last_launch()
-        torch.cuda.synchronize()
-        untouched = bool(torch.isnan(cv[:, n:]).all()) and bool(torch.isnan(cflat[:off]).all()) and \
-            bool(torch.isnan(cflat[off + m * ldc:]).all())
-        return cv[:, :n].cpu().numpy(), untouched, launched
-    finally:
-        view.fill_(float("nan"))
-
-
-def _reach(mm, kernel, streamk=0, persist=0):
-    return _Options(mm, types.SimpleNamespace(kernel=kernel, streamk=streamk, chain=1, persist=persist))
-
-
 @pytest.mark.parametrize("row", REG_INSTANTIATIONS, ids=lambda r: r.symbol)
 def test_every_register_staged_instantiation_returns_the_oracle_bits(mm, cus, big, row):
     if row.unreachable is not None:

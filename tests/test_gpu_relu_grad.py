@@ -4,19 +4,17 @@ four: the vector path, ragged column counts included; odd: the scalar path) and 
 path asserted from mmh_last_launch; the floats between the rows and around the windows are canaries that must survive; the
 special values of the gate; the argument checks; and one rate floor against torch's where + sum(0)."""
 import ctypes as C
-import os
 import statistics
-import sys
 
 import numpy as np
 import pytest
 
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-import relu_grad_ref as ref  # noqa: E402
+import relu_grad_ref as ref
+from built_lib import REPO
+from gpu_operands import handle_fixture
 
 pytestmark = pytest.mark.gpu
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 R = ref.header_block_rows(REPO)
 ROWS = [1, R - 1, R, R + 1, 2 * R + 44]
 COLS = [1, 3, 4, 255, 256, 257, 1028]
@@ -29,13 +27,7 @@ CANARY = np.float32(-777.25)
 FRONT = 8   # canary floats in front of a window (a multiple of 4: the window's base stays 16-byte aligned)
 
 
-@pytest.fixture(scope="module")
-def amm():
-    """The module's own handle on MMH_KERNEL_AUTO."""
-    import how_to_optimize_gemm_amd as H
-    h = H.MMult(0, "auto")
-    yield h
-    h.close()
+amm = handle_fixture()   # the module's own handle on MMH_KERNEL_AUTO (the session fixture's `mfma` kernel has no op forms)
 
 
 _CASES = {}

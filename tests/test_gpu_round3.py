@@ -2,7 +2,6 @@
 residency, handles and streams, hipGraph capture with phase tables, the second vendor comparator, the
 warmed first launch, and the off-grid performance guard.  All call through the C ABI (api.py is ctypes)."""
 import ctypes
-import os
 import subprocess
 import sys
 import time
@@ -10,14 +9,11 @@ import time
 import numpy as np
 import pytest
 
+from built_lib import REPO
+from gpu_operands import dev
+
 pytestmark = pytest.mark.gpu
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def dev(x):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(x)).cuda()
 
 
 DMA_KERNELS = ["mfma_64x64_dma", "mfma_128x64_dma", "mfma_128x128_dma",

@@ -5,14 +5,11 @@ import os
 import numpy as np
 import pytest
 
+from built_lib import REPO
+from gpu_operands import dev
+
 pytestmark = pytest.mark.gpu
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def dev(x):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(x)).cuda()
 
 
 def test_auto_without_the_guarded_lds_dma_tiles_picks_a_register_staged_tile_by_tile_count(mm, oracle):

@@ -2,19 +2,14 @@
 policy that picks its tile AND launch form.  (The int8 tests of the round -- the persistent ping-pong kernel, the
 config-named 16x16x32 instruction, the coalesced C stores -- sit with the other int8 tests in test_gpu_parity.py.)
 All call through the C ABI (api.py is ctypes)."""
-import os
 
 import numpy as np
 import pytest
 
+from gpu_operands import dev
+
 pytestmark = pytest.mark.gpu
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def dev(x):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(x)).cuda()
 
 
 @pytest.mark.parametrize("kernel,bm,bn", [("valu_128x128", 128, 128), ("valu_128x64", 128, 64), ("valu_64x64", 64, 64)])

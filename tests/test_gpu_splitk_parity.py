@@ -13,18 +13,17 @@ partial-tile slots), a split-K launch beside a stream-K launch of another stream
 test makes a handle of its own: the session handle is on `mfma`."""
 import dataclasses
 import math
-import os
 import re
-import sys
+import types
 from typing import Callable
 
 import numpy as np
 import pytest
 
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-import splitk_ref as ref  # noqa: E402
-from test_gpu_lds_dma_parity import _Options, _case, _ld, _padded, first_difference, run_gemm, same_bits  # noqa: E402
-from test_gpu_reg_parity import per_cu_by_lds  # noqa: E402
+import splitk_ref as ref
+from bitcmp import first_difference, same_bits
+from gpu_operands import _Options, _case, _ld, _padded, cus_fixture, handle_fixture, run_gemm
+from kernel_tables import _streamk_shapes, per_cu_by_lds
 
 pytestmark = pytest.mark.gpu
 
@@ -130,17 +129,8 @@ def launch_words(launched):
 
 
 # ---- the table ------------------------------------------------------------------------------------------------------
-@pytest.fixture(scope="module")
-def handle():
-    import how_to_optimize_gemm_amd as H
-    h = H.MMult(0, "mfma")
-    yield h
-    h.close()
-
-
-@pytest.fixture(scope="module")
-def cus(handle):
-    return handle.device_info()["cu_count"]
+handle = handle_fixture("mfma")
+cus = cus_fixture("handle")
 
 
 class _SplitK:
@@ -243,21 +233,20 @@ def test_special_values_follow_the_parts(handle, oracle, row):
 
 # ---- the shared workspace --------------------------------------------------------------------------------------------
 def _streamk_rows():
-    """The register-staged and the K2W stream-K row of the existing tables (128x128 tiles, whole shapes): (row, reach)."""
-    import types
-    from test_gpu_lds_dma_parity import INSTANTIATIONS
-    from test_gpu_reg_parity import REG_INSTANTIATIONS
-    reg = next(r for r in REG_INSTANTIATIONS if r.symbol == "sgemm_mfma_streamk_kernel<128,128,false,4,4,32>")
-    k2w = next(r for r in INSTANTIATIONS if r.symbol == "sgemm_dma5_streamk_kernel<128,128,32,4,4,3,false,true,4,2,1>")
-    reach = types.SimpleNamespace(kernel=reg.kernels[0], streamk=reg.streamk, chain=1, persist=reg.persist)
-    return (reg, reach), (k2w, k2w)
+    """The register-staged and the K2W stream-K launch the split-K steps are interleaved with (128x128 tiles, whole shapes), as
+    their rows of REG_INSTANTIATIONS and INSTANTIATIONS reach and prove them (tests/test_splitk_coverage.py holds these two to
+    those rows): (row, reach)."""
+    reg = types.SimpleNamespace(symbol="sgemm_mfma_streamk_kernel<128,128,false,4,4,32>", kernel="mfma", streamk=2, chain=1, persist=1,
+                                markers=("sgemm_mfma_streamk_kernel<128,128>", "persistent"))
+    k2w = types.SimpleNamespace(symbol="sgemm_dma5_streamk_kernel<128,128,32,4,4,3,false,true,4,2,1>", kernel="mfma_128x128_dma5", streamk=2,
+                                chain=1, persist=1, markers=("sgemm_dma5_streamk_kernel<128,128>", "persistent", "chained parts"))
+    return (reg, reg), (k2w, k2w)
 
 
 def streamk_shapes(cus):
-    """The first (ragged tile count) shape of the two stream-K rows."""
-    (reg, _), (k2w, _) = _streamk_rows()
-    c = reg.cases(cus)[0]
-    return (c.m, c.n, c.k), k2w.shapes(cus)[0][:3]
+    """The first (ragged tile count) shape of the two stream-K rows: r x r whole tiles of five K-slices on both."""
+    shape = _streamk_shapes(128, 128, False, False)(cus)[0][:3]
+    return shape, shape
 
 
 def test_split_k_and_stream_k_share_one_streams_workspace(handle, cus):

@@ -4,17 +4,13 @@ the library's code objects (tools/kernel_resources.py).  Every case of every row
 host arithmetic restated in that module (c_fast, igemm_s8_big_tile at 256 CUs, igemm_s8_inplace_ok, quant_vec_ok and
 K3p's grid): it must reach its row's instantiation, and the table must cover the classes the rows promise."""
 import math
-import os
 import re
-import sys
 
 import pytest
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(REPO, "tools"))
-sys.path.insert(0, os.path.join(REPO, "tests"))
-LIB = os.path.join(REPO, "how-to-optimize-gemm_amd", "libmmult_hip.so")
-pytestmark = pytest.mark.skipif(not os.path.exists(LIB), reason="libmmult_hip.so has not been built")
+import built_lib
+
+pytestmark = built_lib.needs_library
 
 FAMILY = re.compile(r"^(igemm_s8_simple_kernel|igemm_s8_dma_kernel|igemm_s8_pp_kernel)<|^(absmax_kernel|quantize_kernel|"
                     r"dequantize_kernel)$")
@@ -26,16 +22,11 @@ def _table():
     return T
 
 
-def _built():
-    import kernel_resources as K
-    return {r["kernel"] for r in K.resources(LIB) if FAMILY.match(r["kernel"])}
-
-
 def test_the_table_names_every_int8_instantiation_of_the_library():
     T = _table()
     symbols = [r.symbol for r in T.INSTANTIATIONS]
     assert len(symbols) == len(set(symbols)), "a symbol has two rows"
-    built = _built()
+    built = built_lib.built(FAMILY)
     missing = sorted(built - set(symbols))
     stale = sorted(set(symbols) - built)
     assert not missing, f"int8 instantiations in libmmult_hip.so without a row in INSTANTIATIONS: {missing}"

@@ -12,17 +12,15 @@ import re
 import shutil
 import struct
 import subprocess
-import sys
 import tempfile
 
 import pytest
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(REPO, "tools"))
-LIB = os.path.join(REPO, "how-to-optimize-gemm_amd", "libmmult_hip.so")
+from built_lib import LIB, REPO, needs_library
+
 SRC = os.path.join(REPO, "how-to-optimize-gemm_amd", "csrc", "igemm_s8_pp.hpp")
 OBJDUMP = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "llvm", "bin", "llvm-objdump")
-pytestmark = [pytest.mark.skipif(not os.path.exists(LIB), reason="libmmult_hip.so has not been built"),
+pytestmark = [needs_library,
               pytest.mark.skipif(not (os.path.exists(OBJDUMP) or shutil.which("llvm-objdump")), reason="no llvm-objdump")]
 
 INSTRUCTION = re.compile(r"^\s+(?P<text>\S.*?)\s*//\s*(?P<addr>[0-9A-Fa-f]+):(?P<rest>.*)$")

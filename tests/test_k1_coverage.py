@@ -7,14 +7,13 @@ each tile's own slice depth, m and n below the tile, one, two and three or more 
 import math
 import os
 import re
-import sys
 
 import pytest
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(REPO, "tools"))
-LIB = os.path.join(REPO, "how-to-optimize-gemm_amd", "libmmult_hip.so")
-pytestmark = pytest.mark.skipif(not os.path.exists(LIB), reason="libmmult_hip.so has not been built")
+import built_lib
+from built_lib import REPO
+
+pytestmark = built_lib.needs_library
 
 FAMILY = re.compile(r"^sgemm_valu_kernel<")
 CUS = 256   # the MI355X's compute units (the GPU test derives its shapes from the device's count)
@@ -26,16 +25,11 @@ def _T():
     return T
 
 
-def _built():
-    import kernel_resources as K
-    return {r["kernel"] for r in K.resources(LIB) if FAMILY.match(r["kernel"])}
-
-
 def test_the_table_names_every_k1_instantiation_of_the_library():
     rows = _T().K1_INSTANTIATIONS
     symbols = [r.symbol for r in rows]
     assert len(symbols) == len(set(symbols)), "a symbol has two rows"
-    built = _built()
+    built = built_lib.built(FAMILY)
     missing = sorted(built - set(symbols))
     stale = sorted(set(symbols) - built)
     assert not missing, f"instantiations in libmmult_hip.so without a row in K1_INSTANTIATIONS: {missing}"
@@ -86,7 +80,6 @@ def test_window_ok_is_the_librarys():
 @pytest.mark.parametrize("cus", ALL_CUS)
 def test_every_case_reaches_its_row(cus):
     T = _T()
-    import test_gpu_reg_parity as R
     for r in T.K1_INSTANTIATIONS:
         for kernel in r.kernels:
             ran = 0
@@ -107,9 +100,9 @@ def test_every_case_reaches_its_row(cus):
                 off = 4 if c.aligned else 1
                 assert not (c.lda and c.ldb), (r.symbol, c)
                 if c.lda:
-                    assert off + (c.m - 1) * c.lda + c.k <= R.BIG_FLOATS, (r.symbol, c)
+                    assert off + (c.m - 1) * c.lda + c.k <= T.BIG_FLOATS, (r.symbol, c)
                 if c.ldb:
-                    assert off + (c.k - 1) * c.ldb + c.n <= R.BIG_FLOATS, (r.symbol, c)
+                    assert off + (c.k - 1) * c.ldb + c.n <= T.BIG_FLOATS, (r.symbol, c)
                 # the oracle's work per case: under 1 GFLOP; the production route's: the smallest square of four tiles per CU, two K-slices
                 if c.production:
                     assert tiles < (math.isqrt(4 * cus) + 2) ** 2 and c.k == 2 * r.kb, (r.symbol, c)

@@ -6,14 +6,11 @@ import importlib
 import inspect
 import os
 import re
-import sys
 
-import pytest
+import built_lib
+from built_lib import LIB, REPO
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(REPO, "tools"))
-LIB = os.path.join(REPO, "how-to-optimize-gemm_amd", "libmmult_hip.so")
-pytestmark = pytest.mark.skipif(not os.path.exists(LIB), reason="libmmult_hip.so has not been built")
+pytestmark = built_lib.needs_library
 
 ANONYMOUS = "_ZN3mmh12_GLOBAL__N_1"   # a kernel of an unnamed namespace inside mmh: kernel_resources reads no further than this
 
@@ -88,8 +85,7 @@ CENSUS = [
 
 
 def _symbols(lib=LIB):
-    import kernel_resources as K
-    return sorted({symbol_of(r) for r in K.resources(lib)})
+    return sorted({symbol_of(r) for r in built_lib.resources(lib)})
 
 
 def census(symbols):

@@ -4,19 +4,12 @@ needs, is a slow number on the GPU box and nothing else -- round 4's VALU rung w
 ones on the way to its final form.  (The reference has no analogue: nvcc's -Xptxas -v output is not checked anywhere.)"""
 import os
 import re
-import sys
 
-import pytest
+import built_lib
+from built_lib import REPO
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(REPO, "tools"))
-LIB = os.path.join(REPO, "how-to-optimize-gemm_amd", "libmmult_hip.so")
-pytestmark = pytest.mark.skipif(not os.path.exists(LIB), reason="libmmult_hip.so has not been built")
-
-
-def _rows():
-    import kernel_resources as K
-    return K.resources(LIB)
+pytestmark = built_lib.needs_library
+_rows = built_lib.resources
 
 
 def _alloc(vgpr):

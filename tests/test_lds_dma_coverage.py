@@ -4,16 +4,11 @@ from the library's code objects (tools/kernel_resources.py).  A tile family that
 before anything runs on a GPU.  The rows' shapes are checked here too, on the host arithmetic the launchers use: that
 each one reaches its row's instantiation (whole or guarded, ragged or whole-round tile counts)."""
 import math
-import os
 import re
-import sys
 
-import pytest
+import built_lib
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(REPO, "tools"))
-LIB = os.path.join(REPO, "how-to-optimize-gemm_amd", "libmmult_hip.so")
-pytestmark = pytest.mark.skipif(not os.path.exists(LIB), reason="libmmult_hip.so has not been built")
+pytestmark = built_lib.needs_library
 
 FAMILIES = ("sgemm_mfma_dma_kernel", "sgemm_dma_streamk_kernel", "sgemm_mfma_dma5_kernel", "sgemm_dma5_streamk_kernel",   # K2L, K2W
             "sgemm_valu_dma5_kernel", "sgemm_valu_dma5_streamk_kernel",                                                 # K1W
@@ -27,16 +22,11 @@ def _table():
     return FAMILY_RE, INSTANTIATIONS
 
 
-def _built():
-    import kernel_resources as K
-    return {r["kernel"] for r in K.resources(LIB) if FAMILY.match(r["kernel"])}
-
-
 def test_the_table_names_every_lds_dma_instantiation_of_the_library():
     _, rows = _table()
     symbols = [r.symbol for r in rows]
     assert len(symbols) == len(set(symbols)), "a symbol has two rows"
-    built = _built()
+    built = built_lib.built(FAMILY)
     missing = sorted(built - set(symbols))
     stale = sorted(set(symbols) - built)
     assert not missing, f"instantiations in libmmult_hip.so without a row in INSTANTIATIONS: {missing}"

@@ -1,24 +1,14 @@
 """mmh_auto_plan_op (include/mmult_hip.h): MMH_KERNEL_AUTO's choice for transposed operands, as host arithmetic.  The op
 forms run on the 64x64, 128x64 and 128x128 K2W tiles only (csrc/launch_op.hip): the plan is the fitted table restricted to
 those three -- where the NN plan of a shape is one of them, the op plan is that very plan (tile, form, grid).  No device."""
-import ctypes as C
 import os
 
 import pytest
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from built_lib import REPO, needs_loadable_library
+from built_lib import plan as _plan
 
-
-def _library_loads():
-    try:
-        import how_to_optimize_gemm_amd as H
-        H.lib()
-        return True
-    except Exception:
-        return False
-
-
-pytestmark = pytest.mark.skipif(not _library_loads(), reason="libmmult_hip.so (or the HIP runtime it links) is not loadable here")
+pytestmark = needs_loadable_library()
 
 OP_FAMILIES = {29, 30, 31}   # MMH_KERNEL_MFMA_{64X64,128X64,128X128}_DMA5
 
@@ -31,12 +21,6 @@ def _shapes():
             if line and not line.startswith("#"):
                 out.append(tuple(int(x) for x in line.split(",")[:3]))
     return out
-
-
-def _plan(fn, *args):
-    kern, tiles, grid = C.c_int(-9), C.c_long(-9), C.c_int(-9)
-    rc = fn(*args, C.byref(kern), C.byref(tiles), C.byref(grid))
-    return rc, (kern.value, tiles.value, grid.value)
 
 
 def test_the_three_symbols_are_exported():

@@ -7,14 +7,11 @@ beyond the descriptor window), and the Python restatement of window_ok against t
 import math
 import os
 import re
-import sys
 
-import pytest
+import built_lib
+from built_lib import REPO
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(REPO, "tools"))
-LIB = os.path.join(REPO, "how-to-optimize-gemm_amd", "libmmult_hip.so")
-pytestmark = pytest.mark.skipif(not os.path.exists(LIB), reason="libmmult_hip.so has not been built")
+pytestmark = built_lib.needs_library
 
 FAMILIES = ("sgemm_mfma_kernel", "sgemm_mfma_streamk_kernel", "sgemm_mfma_simple_kernel")   # (split-K: tests/test_splitk_coverage.py)
 FAMILY = re.compile(r"^(" + "|".join(FAMILIES) + r")<")
@@ -26,16 +23,11 @@ def _T():
     return T
 
 
-def _built():
-    import kernel_resources as K
-    return {r["kernel"] for r in K.resources(LIB) if FAMILY.match(r["kernel"])}
-
-
 def test_the_table_names_every_register_staged_instantiation_of_the_library():
     rows = _T().REG_INSTANTIATIONS
     symbols = [r.symbol for r in rows]
     assert len(symbols) == len(set(symbols)), "a symbol has two rows"
-    built = _built()
+    built = built_lib.built(FAMILY)
     missing = sorted(built - set(symbols))
     stale = sorted(set(symbols) - built)
     assert not missing, f"instantiations in libmmult_hip.so without a row in REG_INSTANTIATIONS: {missing}"

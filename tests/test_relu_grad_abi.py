@@ -2,11 +2,8 @@
 symbols, the version, the block size the header, the library's Python mirror and the contract agree on, the NULL-handle
 answer, the argument checks that come before the device is touched, and the Python names."""
 import ctypes as C
-import os
-import sys
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from built_lib import REPO
 
 
 def test_the_symbols_are_exported_and_the_version_moved():

@@ -7,7 +7,8 @@ import subprocess
 
 import pytest
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from built_lib import REPO
+
 
 
 def _clangxx():

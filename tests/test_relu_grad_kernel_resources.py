@@ -1,23 +1,14 @@
 """The kernels of mmh_relu_grad_colsum (csrc/relu_grad.hpp) in the built product library, read on the CPU
 (tools/kernel_resources.py): the twelve instantiations of the pass -- {vector, scalar} x {gate, no gate} x {dz + colsum, dz,
 colsum} -- and the finish kernel exist under their own names, and none uses scratch or spills a vector or scalar register."""
-import os
 import re
-import sys
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(REPO, "tools"))
-LIB = os.path.join(REPO, "how-to-optimize-gemm_amd", "libmmult_hip.so")
+from built_lib import rows as _rows
 
 PASS = [f"relu_grad_colsum_kernel<{w},{g},{z},{s}>" for w in (4, 1) for g in ("true", "false")
         for z, s in (("true", "true"), ("true", "false"), ("false", "true"))]
 # the family patterns the existing coverage and resource tests count
 OTHER_FAMILIES = r"sgemm_|igemm_s8_|absmax_kernel|quantize_kernel|dequantize_kernel"
-
-
-def _rows():
-    import kernel_resources as K
-    return {r["kernel"]: r for r in K.resources(LIB)}
 
 
 def test_the_kernels_exist_under_their_own_names():

@@ -9,15 +9,13 @@ first, 17R + 77 rows, no gate: a margin of 0.065 under the 0.5), the next 0.381 
 blocks); descending order 0.131 - 0.304; R = 64 / 256 at most 0.154; one chain at most 0.077; every dropped block at the + 77
 row counts 0.0."""
 import os
-import sys
 
 import numpy as np
 import pytest
 
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-import relu_grad_ref as ref  # noqa: E402
+import relu_grad_ref as ref
+from built_lib import REPO
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 R = ref.header_block_rows(REPO)
 
 

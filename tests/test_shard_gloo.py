@@ -8,11 +8,12 @@ import sys
 
 import numpy as np
 import pytest
+
+from built_lib import REPO
 import torch
 import torch.distributed as dist
 import torch.multiprocessing as mp
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def _free_port():

@@ -6,15 +6,14 @@ proved here, on the launcher's host arithmetic, to split: whole tiles, at least 
 every part resident on any device, so that the part count is the restated one."""
 import os
 import re
-import sys
 
 import pytest
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(REPO, "tools"))
-LIB = os.path.join(REPO, "how-to-optimize-gemm_amd", "libmmult_hip.so")
-CSRC = os.path.join(REPO, "how-to-optimize-gemm_amd", "csrc")
-pytestmark = pytest.mark.skipif(not os.path.exists(LIB), reason="libmmult_hip.so has not been built")
+import built_lib
+import kernel_tables as R
+
+CSRC = os.path.join(built_lib.REPO, "how-to-optimize-gemm_amd", "csrc")
+pytestmark = built_lib.needs_library
 
 FAMILY = re.compile(r"^sgemm_mfma_splitk_kernel<")
 CUS = 256   # the MI355X's compute units (the GPU test derives its shapes from the device's count)
@@ -26,16 +25,11 @@ def _T():
     return T
 
 
-def _built():
-    import kernel_resources as K
-    return {r["kernel"] for r in K.resources(LIB) if FAMILY.match(r["kernel"])}
-
-
 def test_the_table_names_every_split_k_instantiation_of_the_library():
     rows = _T().SPLITK_INSTANTIATIONS
     symbols = [r.symbol for r in rows]
     assert len(symbols) == len(set(symbols)), "a symbol has two rows"
-    built = _built()
+    built = built_lib.built(FAMILY)
     missing = sorted(built - set(symbols))
     stale = sorted(set(symbols) - built)
     assert not missing, f"instantiations in libmmult_hip.so without a row in SPLITK_INSTANTIATIONS: {missing}"
@@ -45,7 +39,6 @@ def test_the_table_names_every_split_k_instantiation_of_the_library():
 
 def test_the_rows_are_the_catalogues_split_k_ids_on_their_tiles():
     import how_to_optimize_gemm_amd as H
-    import test_gpu_reg_parity as R
     T = _T()
     abi = open(os.path.join(CSRC, "abi.hip")).read()
     catalogue = re.findall(r'\{MMH_KERNEL_(\w+), "MMult_hip_(\w+)", Launcher::SplitK, MMH_KERNEL_(\w+)\}', abi)
@@ -64,7 +57,6 @@ def test_the_rows_are_the_catalogues_split_k_ids_on_their_tiles():
 
 @pytest.mark.parametrize("cus", ALL_CUS)
 def test_every_case_splits_the_way_it_says(cus):
-    import test_gpu_reg_parity as R
     T = _T()
     for r in T.SPLITK_INSTANTIATIONS:
         bm, bn, kb = r.tile
@@ -112,6 +104,17 @@ def test_the_shared_shape_and_the_stream_k_rows_it_is_interleaved_with():
     assert (m // 128) * (n // 128) == 6 and k // T.KB == 7 and m % 128 == 0 and n % 128 == 0
     (reg, reach), (k2w, _) = T._streamk_rows()
     assert reg.streamk == 2 and reach.kernel == "mfma" and k2w.streamk == 2 and k2w.kernel == "mfma_128x128_dma5"
+    # ... as the two tables have them: the same reach, the same proof, the same first shape
+    from test_gpu_lds_dma_parity import INSTANTIATIONS
+    from test_gpu_reg_parity import REG_INSTANTIATIONS
+    reg_row = next(r for r in REG_INSTANTIATIONS if r.symbol == reg.symbol)
+    k2w_row = next(r for r in INSTANTIATIONS if r.symbol == k2w.symbol)
+    assert (reg_row.kernels[0], reg_row.streamk, reg_row.persist, reg_row.markers) == (reg.kernel, reg.streamk, reg.persist, reg.markers)
+    assert (k2w_row.kernel, k2w_row.streamk, k2w_row.chain, k2w_row.persist) == (k2w.kernel, k2w.streamk, k2w.chain, k2w.persist)
+    assert k2w_row.markers == k2w.markers and k2w_row.ops is None and not reg_row.guarded, (k2w_row, reg_row)
+    for cus in ALL_CUS:
+        c = reg_row.cases(cus)[0]
+        assert ((c.m, c.n, c.k), k2w_row.shapes(cus)[0][:3]) == T.streamk_shapes(cus) and not c.lda and not c.ldb, cus
     for cus in ALL_CUS:
         for shape in T.streamk_shapes(cus):
             tiles = (shape[0] // 128) * (shape[1] // 128)

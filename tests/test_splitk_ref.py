@@ -5,14 +5,12 @@ chain's, from those of S - 1 and S + 1 parts and from "C added behind the fold" 
 are conditions on the reference; nothing here has seen a kernel's output."""
 import functools
 import os
-import sys
 
 import numpy as np
 import pytest
 
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-import splitk_ref as ref  # noqa: E402
-import test_gpu_splitk_parity as T  # noqa: E402
+import splitk_ref as ref
+import test_gpu_splitk_parity as T
 
 CUS = 256   # the MI355X's compute units (the GPU test derives its part counts from the device's count)
 KB = T.KB

@@ -9,19 +9,10 @@ import numpy as np
 import pytest
 
 import how_to_optimize_gemm_amd as H
+from built_lib import needs_loadable_library
 
 
-def _library_loads():
-    """mmh_streamk_plan is host arithmetic, but it lives in libmmult_hip.so (a hipcc build that needs the HIP
-    runtime to LOAD): on a machine without the library or without libamdhip64 these tests skip, not error."""
-    try:
-        H.lib()
-        return True
-    except (OSError, H.MMultError):
-        return False
-
-
-pytestmark = pytest.mark.skipif(not _library_loads(), reason="libmmult_hip.so (or the HIP runtime it links) is not loadable here")
+pytestmark = needs_loadable_library()
 
 
 def ranges(tiles, nk, grid):

@@ -11,7 +11,8 @@ import sys
 
 import pytest
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from built_lib import REPO
+
 AB_LIB = os.path.join(REPO, "how-to-optimize-gemm_amd", "libmmult_hip_ab.so")
 needs_ab = pytest.mark.usefixtures("ab_library")
 
