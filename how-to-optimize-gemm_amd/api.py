@@ -32,6 +32,7 @@ OPT_RIM = 11
 OPT_STREAMK_CHAIN = 12
 OPT_PERSIST = 13
 OPT_RIM5 = 14
+OPT_RETIRED_BUFFERS = 15   # read-only: allocations retired because a captured graph may point at them
 OP_N, OP_T = 0, 1   # mmh_sgemm_op's operand layouts (include/mmult_hip.h)
 BIAS_NONE, BIAS_COL, BIAS_ROW = 0, 1, 2   # mmh_sgemm_ex's MMH_BIAS_*: no bias, bias[j] (n floats), bias[i] (m floats)
 ACT_NONE, ACT_RELU = 0, 1                 # ... and MMH_ACT_*
@@ -1128,6 +1129,6 @@ def sgemm_sharded(ngpus: int, a: np.ndarray, b: np.ndarray, kernel="mfma"):
 
 __all__ = ["MMult", "ShardedMMult", "MMultError", "lib", "use_ab_library", "device_count", "rccl_version", "shard_rows", "shard_chunks",
            "kernel_name", "last_launch", "use_timeline_library", "streamk_plan", "auto_plan", "auto_plan_op", "auto_plan_ex", "auto_plan_batched", "auto_plan_batched_ex", "BIAS_NONE", "BIAS_COL", "BIAS_ROW", "ACT_NONE", "ACT_RELU", "BATCH_FORMS", "BATCHED_MAX_WORKGROUPS", "COLSUM_BLOCK_ROWS", "OP_N", "OP_T", "sgemm_sharded", "KERNELS", "CHAIN_KERNELS", "AB_LIB_PATH",
-           "OPT_SPLITK", "OPT_HOST_PANELS", "OPT_STREAMK_SPIN_LIMIT", "OPT_FAULT_INJECT", "OPT_STREAMK_ORDER", "OPT_DMA_EDGE", "OPT_STREAMK_DELEGATIONS", "OPT_RIM", "OPT_STREAMK_CHAIN", "OPT_PERSIST", "OPT_RIM5", "KERNEL_AUTO", "KERNEL_VALU", "KERNEL_MFMA", "KERNEL_MFMA_256", "KERNEL_NAIVE", "KERNEL_MFMA_SIMPLE", "KERNEL_MFMA_PIPE",
+           "OPT_SPLITK", "OPT_HOST_PANELS", "OPT_STREAMK_SPIN_LIMIT", "OPT_FAULT_INJECT", "OPT_STREAMK_ORDER", "OPT_DMA_EDGE", "OPT_STREAMK_DELEGATIONS", "OPT_RIM", "OPT_STREAMK_CHAIN", "OPT_PERSIST", "OPT_RIM5", "OPT_RETIRED_BUFFERS", "KERNEL_AUTO", "KERNEL_VALU", "KERNEL_MFMA", "KERNEL_MFMA_256", "KERNEL_NAIVE", "KERNEL_MFMA_SIMPLE", "KERNEL_MFMA_PIPE",
            "EXPORTS", "LIB_PATH", "OPT_STREAMK", "OPT_STREAMK_TIMEOUTS", "OPT_IGEMM_MODE", "OK", "ERR_INVALID_ARG", "ERR_HIP", "ERR_NO_DEVICE",
            "ERR_UNSUPPORTED", "ERR_ALLOC", "ERR_COMM"]

@@ -99,7 +99,7 @@ static_assert(kKernelIndex.ok, "kKernels: an id twice or out of range, or a fall
 
 // The handle options that are ONE int of the handle, read by mmh_set_option and mmh_get_option alike: the id, the field, and
 // what set accepts -- lo .. hi, stored as it came, or (squash) any value, stored as 0 / 1.  get returns the field.  The options
-// that are more than that -- a counter on the device, a value in other units, a side effect, two fields -- are the explicit
+// that are more than that -- a counter on the device or of the handle, a value in other units, a side effect, two fields -- are the explicit
 // cases of the two functions.
 struct OptionRow {
   int id;
@@ -262,6 +262,7 @@ int mmh_set_option(mmh_handle_t h, int option, int value) {
       h->dma_edge = value ? 1 : 0;     //    for rows that are 16-byte aligned; 2 (default): for any 4-byte aligned rows
       h->dma_dword_rows = value >= 2 ? 1 : 0;
       return MMH_OK;
+    case MMH_OPT_RETIRED_BUFFERS:   // read-only
     default:
       return MMH_ERR_INVALID_ARG;
   }
@@ -297,6 +298,7 @@ int mmh_get_option(mmh_handle_t h, int option, int *value) {
       return MMH_OK;
     }
     case MMH_OPT_DMA_EDGE: *value = h->dma_edge ? (h->dma_dword_rows ? 2 : 1) : 0; return MMH_OK;
+    case MMH_OPT_RETIRED_BUFFERS: *value = (int)h->retired.size(); return MMH_OK;   // (host state: no synchronisation)
     default:
       return MMH_ERR_INVALID_ARG;
   }

@@ -1,6 +1,10 @@
 // igemm.hip -- BASELINE.json config 5 and the callers either side of it: mmh_igemm_s8 (int8 x int8 -> int32 on
 // v_mfma_i32_16x16x64_i8), mmh_quantize_sym_s8 and mmh_qgemm_f32 (symmetric per-tensor quantisation, dequantisation
-// fused into the GEMM's epilogue).  The reference holds no int8 code (README.md:71-85 is prose): parity unpinned.
+// fused into the GEMM's epilogue).  The reference project holds no int8 code (its README.md:71-85 is prose): every
+// instantiation is pinned to an exact integer reference by tests/test_gpu_int8_parity.py, and the handle-owned scratch under
+// graph capture and growth by tests/test_gpu_int8_graph.py.
+// The scratch (qa / qb / qc / qs, bt in the tools build) grows through reserve_scratch only: each entry point states ALL it needs
+// before its first memset or launch, so a call on a capturing stream that would have to allocate is refused with nothing done.
 // Part of libmmult_hip.so (see internal.hpp).
 #include <algorithm>
 
@@ -28,14 +32,45 @@ static int pp_grid_cap(const mmh_context *h, int mode, int k, int cus) {
 // mmh_last_launch of the quantiser passes: which path a tensor took (quant_vec_ok: 16-byte rows, float4 loads; else the row loop)
 static const char *quant_path(bool vec) { return vec ? "vector" : "row"; }
 
+// qs: [0, 2 AMAX_WORDS) abs-max words of a quantised GEMM's A and B, then its two scales, then the abs-max words of
+// stand-alone mmh_quantize_sym_s8 calls, then 2 AMAX_WORDS words that are zero for as long as the buffer lives
+constexpr size_t kQsWords = 4 * AMAX_WORDS + 16;
+constexpr size_t kAmaxBytes = 2 * AMAX_WORDS * sizeof(unsigned);
+constexpr size_t kQsBytes = kQsWords * sizeof(unsigned) + kAmaxBytes;
+
+// Zero a call's abs-max words on its stream.  A COPY of the zero block, not a memset: a captured hipMemsetAsync node was seen
+// (ROCm 7.0, MI355X) to fill with a stale 8-byte pattern from the second replay of its graph on -- the first replay is right --
+// which left words above every real maximum (tests/test_gpu_int8_graph.py replays every form three times on new data).  The
+// zero block is written once per allocation, which reserve_scratch never makes on a capturing stream.
+static int zero_amax(mmh_context *h, unsigned *amax, hipStream_t s) {
+  unsigned *zeros = static_cast<unsigned *>(h->qs.p) + kQsWords;
+  if (h->qs_zeros_of != h->qs.p) {
+    HIP_TRY(hipMemsetAsync(zeros, 0, kAmaxBytes, s));
+    HIP_TRY(hipStreamSynchronize(s));   // (once per handle: later calls may come on any stream)
+    h->qs_zeros_of = h->qs.p;
+  }
+  HIP_TRY(hipMemcpyAsync(amax, zeros, kAmaxBytes, hipMemcpyDeviceToDevice, s));
+  return MMH_OK;
+}
+
+// tools build: what launch_ab_modes needs of bt for `mode` (0: nothing -- always, in the product)
+static size_t ab_bt_bytes(int mode, int n, int k) {
+#ifdef MMH_AB_BUILD
+  if ((mode == 1 || mode == 3 || mode == 4 || (mode >= 10 && mode <= 13)) && igemm_s8_needs_pack(mode, nullptr, 0, nullptr, 0, k))
+    return igemm_s8_pack_bytes(n, k);
+#else
+  (void)mode; (void)n; (void)k;
+#endif
+  return 0;
+}
+
 // tools build: the rungs that left the product (tools/ab/igemm_s8_k3.hpp).  Returns 1 when `mode` is not one of theirs.
+// (the caller has reserved ab_bt_bytes of bt)
 static int launch_ab_modes(mmh_context *h, int mode, int m, int n, int k, const int8_t *A, int lda, const int8_t *B, int ldb, int32_t *C,
                            int ldc, int acc, hipStream_t s) {
 #ifdef MMH_AB_BUILD
   if (mode == 1 || mode == 3 || mode == 4 || (mode >= 10 && mode <= 13)) {
-    int8_t *bt = nullptr;
-    if (igemm_s8_needs_pack(mode, A, lda, B, ldb, k) && h->bt.reserve(igemm_s8_pack_bytes(n, k)) == MMH_OK)
-      bt = static_cast<int8_t *>(h->bt.p);
+    int8_t *bt = ab_bt_bytes(mode, n, k) ? static_cast<int8_t *>(h->bt.p) : nullptr;
     const hipError_t e = launch_igemm_s8_ab(m, n, k, A, lda, B, ldb, C, ldc, acc, s, bt, mode);
     if (e == hipErrorNotSupported) return 1;   // an operand those kernels cannot take: the product's path
     HIP_TRY(e);
@@ -94,13 +129,13 @@ int mmh_igemm_s8(mmh_handle_t h, int m, int n, int k, const int8_t *dA, int lda,
     const bool b_ok = (ldb % 4 == 0) && ((reinterpret_cast<uintptr_t>(dB) & 3) == 0);
     const int ka = a_ok ? lda : (k + 15) & ~15, nb = b_ok ? ldb : (n + 15) & ~15;
     const int8_t *sa = dA, *sb = dB;
+    rc = reserve_scratch(h, s, "mmh_igemm_s8", {{&h->qa, a_ok ? 0 : (size_t)m * ka}, {&h->qb, b_ok ? 0 : (size_t)k * nb}});
+    if (rc != MMH_OK) return rc;
     if (!a_ok) {
-      if ((rc = h->qa.reserve((size_t)m * ka)) != MMH_OK) return rc;
       HIP_TRY(hipMemcpy2DAsync(h->qa.p, (size_t)ka, dA, (size_t)lda, (size_t)k, (size_t)m, hipMemcpyDeviceToDevice, s));
       sa = static_cast<const int8_t *>(h->qa.p);
     }
     if (!b_ok) {
-      if ((rc = h->qb.reserve((size_t)k * nb)) != MMH_OK) return rc;
       HIP_TRY(hipMemcpy2DAsync(h->qb.p, (size_t)nb, dB, (size_t)ldb, (size_t)n, (size_t)k, hipMemcpyDeviceToDevice, s));
       sb = static_cast<const int8_t *>(h->qb.p);
     }
@@ -111,6 +146,7 @@ int mmh_igemm_s8(mmh_handle_t h, int m, int n, int k, const int8_t *dA, int lda,
     }
     // (operands beyond the descriptors' 2 GiB window: the correctness-first kernel below)
   }
+  if ((rc = reserve_scratch(h, s, "mmh_igemm_s8", {{&h->bt, ab_bt_bytes(h->igemm_mode, n, k)}})) != MMH_OK) return rc;
   if ((rc = launch_ab_modes(h, h->igemm_mode, m, n, k, dA, lda, dB, ldb, dC, ldc, accumulate ? 1 : 0, s)) <= 0) return rc;
   HIP_TRY(launch_igemm_s8(m, n, k, dA, lda, dB, ldb, dC, ldc, accumulate ? 1 : 0, s, h->igemm_mode, cus_, &what));
   set_last_launch(what);
@@ -124,13 +160,9 @@ int mmh_quantize_sym_s8(mmh_handle_t h, int rows, int cols, const float *dX, int
   if (!dX || !dQ || !d_scale || ldx < cols || ldq < cols) return MMH_ERR_INVALID_ARG;
   ENTER(h);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  // qs: [0, 2 AMAX_WORDS) abs-max words of a quantised GEMM's A and B, then its two scales, then the
-  // abs-max words of stand-alone calls
-  constexpr size_t qs_words = 4 * AMAX_WORDS + 16;
-  int rc = h->qs.reserve(qs_words * sizeof(unsigned));
-  if (rc != MMH_OK) return rc;
+  if (int rc = reserve_scratch(h, s, "mmh_quantize_sym_s8", {{&h->qs, kQsBytes}}); rc != MMH_OK) return rc;
   unsigned *amax = static_cast<unsigned *>(h->qs.p) + 2 * AMAX_WORDS + 16;
-  HIP_TRY(hipMemsetAsync(amax, 0, 2 * AMAX_WORDS * sizeof(unsigned), s));
+  if (int rc = zero_amax(h, amax, s); rc != MMH_OK) return rc;
   const QuantTensor t{dX, rows, cols, ldx, dQ, ldq}, none{nullptr, 0, 0, 0, nullptr, 0};
   const bool v_in = quant_vec_ok(t, false), v_out = quant_vec_ok(t, true);
   hipLaunchKernelGGL(absmax_kernel, dim3(quant_grid(t, v_in), 1), dim3(256), 0, s, t, none, v_in ? 1 : 0, 0, amax);
@@ -158,14 +190,17 @@ int mmh_qgemm_f32(mmh_handle_t h, int m, int n, int k, const float *dA, int lda,
   }
   // dense, 16-byte-friendly workspace images: int8 A (m x ka), int8 B (k x nb), int32 C (m x nb)
   const int ka = (k + 15) & ~15, nb = (n + 3) & ~3;
-  if ((rc = h->qa.reserve((size_t)m * ka)) != MMH_OK) return rc;
-  if ((rc = h->qb.reserve((size_t)k * nb)) != MMH_OK) return rc;
-  constexpr size_t qs_words = 4 * AMAX_WORDS + 16;
-  if ((rc = h->qs.reserve(qs_words * sizeof(unsigned))) != MMH_OK) return rc;
+  // the fused form dequantises in the int8 GEMM's epilogue; the two-pass form (A/B modes, images beyond the descriptors' window)
+  // also needs the int32 image -- known before the images exist: they are hipMalloc'ed, so their alignment never decides
+  const bool fused = h->igemm_mode == 0 && igemm_s8_inplace_ok(nullptr, ka, nullptr, nb, k);
+  rc = reserve_scratch(h, s, "mmh_qgemm_f32",
+                       {{&h->qa, (size_t)m * ka}, {&h->qb, (size_t)k * nb}, {&h->qs, kQsBytes},
+                        {&h->qc, fused ? 0 : (size_t)m * nb * sizeof(int32_t)}, {&h->bt, fused ? 0 : ab_bt_bytes(h->igemm_mode, n, k)}});
+  if (rc != MMH_OK) return rc;
   int8_t *qa = static_cast<int8_t *>(h->qa.p), *qb = static_cast<int8_t *>(h->qb.p);
   unsigned *amax = static_cast<unsigned *>(h->qs.p);                           // A's words, then B's
   float *scales = reinterpret_cast<float *>(amax + 2 * AMAX_WORDS);       // [0] A, [1] B
-  HIP_TRY(hipMemsetAsync(amax, 0, 2 * AMAX_WORDS * sizeof(unsigned), s));
+  if ((rc = zero_amax(h, amax, s)) != MMH_OK) return rc;
   // A and B share one abs-max launch and one quantisation launch (blockIdx.y picks the tensor)
   const QuantTensor ta{dA, m, k, lda, qa, ka}, tb{dB, k, n, ldb, qb, nb};
   const bool va_in = quant_vec_ok(ta, false), vb_in = quant_vec_ok(tb, false);
@@ -179,7 +214,7 @@ int mmh_qgemm_f32(mmh_handle_t h, int m, int n, int k, const float *dA, int lda,
   snprintf(buf, sizeof buf, "qgemm: absmax_kernel + quantize_kernel (A on the %s path, B on the %s path), then ", quant_path(va_out),
            quant_path(vb_out));
   std::string what;
-  if (h->igemm_mode == 0 && igemm_s8_inplace_ok(qa, ka, qb, nb, k)) {
+  if (fused) {
     // the int8 GEMM dequantises in its epilogue: no int32 image of C at all
     if (igemm_s8_big_tile(m, n, cus))
       HIP_TRY(launch_igemm_s8_pp<64>(m, n, k, qa, ka, qb, nb, reinterpret_cast<int32_t *>(dC), ldc, 0, s, pp_grid_cap(h, 0, k, cus), scales,
@@ -190,7 +225,6 @@ int mmh_qgemm_f32(mmh_handle_t h, int m, int n, int k, const float *dA, int lda,
     return MMH_OK;
   }
   // two-pass form (A/B modes of the int8 kernel): int32 C, then the dequantisation pass
-  if ((rc = h->qc.reserve((size_t)m * nb * sizeof(int32_t))) != MMH_OK) return rc;
   int32_t *qc = static_cast<int32_t *>(h->qc.p);
   if ((rc = launch_ab_modes(h, h->igemm_mode, m, n, k, qa, ka, qb, nb, qc, nb, 0, s)) < 0) return rc;
   if (rc == 1) HIP_TRY(launch_igemm_s8(m, n, k, qa, ka, qb, nb, qc, nb, 0, s, h->igemm_mode, cus, &what));

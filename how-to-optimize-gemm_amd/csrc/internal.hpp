@@ -31,6 +31,7 @@
 #include <stdio.h>
 #include <string.h>
 
+#include <initializer_list>
 #include <string>
 #include <utility>
 #include <vector>
@@ -60,6 +61,16 @@ struct DevBuf {
   // that has to grow is RETIRED (freed with the handle), never freed under the graph
   int reserve(size_t need, std::vector<void *> *retire_to = nullptr);
   void release();
+};
+
+// Handle-owned scratch that is per handle, not per stream, and grows on demand: the int8 / quantisation images and the
+// partial rows of mmh_relu_grad_colsum.  It grows through reserve_scratch (state.hip) only, which holds the capture rule.
+struct Scratch : DevBuf {
+  bool captured = false;   // a captured launch points at p: retire on growth, never free under the graph
+};
+struct ScratchNeed {
+  Scratch *buf;
+  size_t bytes;            // 0: the call does not use buf
 };
 
 // Entry points run on the HANDLE's device and leave the caller's current device as they found it
@@ -108,12 +119,12 @@ struct mmh_context {
   int kernel = MMH_KERNEL_AUTO;
   int cu_count = 0;
   mmh::DevBuf a, b, c;     // staging for the host-pointer flavour
-  mmh::DevBuf bt;          // int8 GEMM: packed (transposed, padded) B
+  mmh::Scratch bt;         // int8 GEMM: packed (transposed, padded) B (tools build)
   int igemm_mode = 0;      // 0 auto, see MMH_OPT_IGEMM_MODE
   int i8_grid_cap = 0;     // test hook (environment MMH_I8_GRID_CAP, read at mmh_create): K3p's persistent grid, so that small shapes walk several tiles per workgroup
-  mmh::DevBuf qa, qb, qc, qs;   // quantised GEMM workspace: int8 A, int8 B, int32 C, {amax bits, scales}
-  mmh::DevBuf colsum_parts;     // mmh_relu_grad_colsum: the row blocks' partial column sums (ceil(rows / R) x cols floats)
-  bool colsum_parts_captured = false;   // a captured launch points at colsum_parts: retire on growth, never free under the graph
+  mmh::Scratch qa, qb, qc, qs;  // quantised GEMM workspace: int8 A, int8 B, int32 C, {amax bits, scales, a zero block}
+  void *qs_zeros_of = nullptr;  // the allocation of qs whose zero block has been written (igemm.hip, zero_amax)
+  mmh::Scratch colsum_parts;    // mmh_relu_grad_colsum: the row blocks' partial column sums (ceil(rows / R) x cols floats)
   // stream-K / split-K workspaces, one set PER STREAM the handle has launched on: launches on different streams
   // never share hand-off words or partial tiles, so nothing has to order one stream behind another and the handle
   // never touches a stream again after the call that used it returns (the caller may destroy it).
@@ -247,6 +258,12 @@ inline bool is_family(int kernel, Launcher l) {
 int workspace_for(mmh_context *ctx, hipStream_t s, long tiles, size_t parts_bytes, int **flags, float **parts);
 int reserve_stream(mmh_context *ctx, hipStream_t s, int m, int n, int k);   // mmh_reserve_stream
 void workspaces_suspect(mmh_context *ctx);   // a launch may have died half-way: every set is memset before its next use
+// ---- per-handle scratch (state.hip) ----
+// Everything ONE call needs of the handle's scratch, before the call launches or records anything.  On a capturing stream a
+// call that would have to allocate or grow any of it is MMH_ERR_UNSUPPORTED (`who` names the entry point in the message) with
+// nothing allocated, freed or marked; otherwise every buffer is at least its size when this returns MMH_OK.  From the first
+// captured call that uses a buffer, growth retires the old allocation to ctx->retired instead of freeing it.
+int reserve_scratch(mmh_context *ctx, hipStream_t s, const char *who, std::initializer_list<ScratchNeed> needs);
 bool build_sk_tables(long tiles, int nk, int grid, int *order, int *place);
 int sk_tables_for(mmh_context *ctx, long tiles, int nk, int grid, hipStream_t s, const int **order, const int **place, int min10 = 0);
 

@@ -2,7 +2,8 @@
 // symmetric per-tensor quantisation fp32 -> int8 and dequantisation int32 -> fp32.
 //
 // Contract (the reference only has prose for this, README.md:71-85 -- chgemm
-// "symmetric quantisation", inputs in [-127,127]; parity unpinned):
+// "symmetric quantisation", inputs in [-127,127]; the reference project holds no int8 code -- the passes are pinned bit for
+// bit to oracle.quantize_sym_s8 by tests/test_gpu_int8_parity.py, under graph capture by tests/test_gpu_int8_graph.py):
 //   scale = 127 / max|x|   over the FINITE elements (1 if that maximum is 0; clamped to FLT_MAX when
 //                           the maximum is so small -- below ~3.7e-37 -- that the quotient overflows)
 //   q     = clamp(rint(x * scale), -127, 127)          round-half-even, never -128;

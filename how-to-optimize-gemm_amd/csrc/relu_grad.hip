@@ -49,16 +49,9 @@ int relu_grad_colsum_on(mmh_context *h, int rows, int cols, const float *dG, int
     // buffers are.  Nothing can be allocated while the stream is capturing: such a call is refused (mmult_hip.h).
     a.ldo = ((long long)cols + 3) & ~3ll;
     const size_t need = (size_t)nblocks * (size_t)a.ldo * sizeof(float);
-    const bool cap = capturing(s);
-    if (need > h->colsum_parts.bytes && cap) {
-      set_last_error("mmh_relu_grad_colsum: the partial-sum workspace would have to grow while the stream is capturing -- make one "
-                     "uncaptured call at the largest size first");
-      return MMH_ERR_UNSUPPORTED;
-    }
     // A captured launch bakes the workspace's address into its graph: from the first such call on, a buffer that has to grow
     // is RETIRED (freed with the handle), never freed under the graph -- the rule of the stream-K sets (state.hip).
-    if (cap) h->colsum_parts_captured = true;
-    if (int rc = h->colsum_parts.reserve(need, h->colsum_parts_captured ? &h->retired : nullptr); rc != MMH_OK) return rc;
+    if (int rc = reserve_scratch(h, s, "mmh_relu_grad_colsum", {{&h->colsum_parts, need}}); rc != MMH_OK) return rc;
     a.out = static_cast<float *>(h->colsum_parts.p);
     a.direct = 0;
   }

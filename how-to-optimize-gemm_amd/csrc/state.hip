@@ -46,6 +46,29 @@ void DevBuf::release() {
   bytes = 0;
 }
 
+// The rule of the stream-K sets (workspace_for) for the scratch that is per handle: nothing is allocated while a stream is
+// capturing, and what a graph points at is never freed under it.  All of a call's needs are looked at before any is met, so a
+// refusal leaves the handle exactly as it was.
+int reserve_scratch(mmh_context *ctx, hipStream_t s, const char *who, std::initializer_list<ScratchNeed> needs) {
+  bool any = false;
+  for (const ScratchNeed &n : needs) any = any || n.bytes > 0;
+  if (!any) return MMH_OK;
+  const bool cap = capturing(s);
+  if (cap)
+    for (const ScratchNeed &n : needs)
+      if (n.bytes > n.buf->bytes) {
+        set_last_error(std::string(who) + ": a handle-owned workspace would have to be allocated or grown while the stream is "
+                       "capturing -- make one uncaptured call at the largest size first");
+        return MMH_ERR_UNSUPPORTED;
+      }
+  for (const ScratchNeed &n : needs) {
+    if (n.bytes == 0) continue;
+    if (cap) n.buf->captured = true;
+    if (const int rc = n.buf->reserve(n.bytes, n.buf->captured ? &ctx->retired : nullptr); rc != MMH_OK) return rc;
+  }
+  return MMH_OK;
+}
+
 hipError_t DeviceGuard::enter(int device) {
   hipError_t e = hipGetDevice(&prev);
   if (e != hipSuccess) return e;

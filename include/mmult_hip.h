@@ -202,7 +202,15 @@ int mmh_device_info(int device, char *name, int *cu_count, int *clock_mhz);
  * the graph and pins them.  A set a graph points at is never released; a buffer of it that must grow is replaced and
  * the old one lives as long as the handle.  While a graph with stream-K launches RUNS it owns the capture stream's
  * set, like any buffer it was captured with: do not launch the same handle eagerly on the capture stream while a replay
- * may be running on another stream.  Synchronise a stream before destroying it (its set is found by the stream's
+ * may be running on another stream.
+ * The scratch that is per HANDLE (the int8 / quantisation images of mmh_igemm_s8, mmh_quantize_sym_s8 and mmh_qgemm_f32, the
+ * partial rows of mmh_relu_grad_colsum) follows one rule.  A call on a capturing stream that would have to allocate or grow
+ * any of its scratch is MMH_ERR_UNSUPPORTED before anything is launched, recorded, allocated or freed -- the handle is as it
+ * was, no output is touched, the capture goes on: make one uncaptured call at the largest size first (torch's own warm-up
+ * rule).  From the first captured call that uses a buffer, a later call that has to grow it RETIRES the old allocation -- kept
+ * until mmh_destroy, never freed under the graph (MMH_OPT_RETIRED_BUFFERS counts them) --, so a graph stays replayable
+ * whatever sizes run eagerly afterwards; a handle that never captures frees on growth.  A replay shares this scratch with every
+ * other call of the handle: order them on one stream.  Synchronise a stream before destroying it (its set is found by the stream's
  * handle value, which the runtime may reuse).  Every entry point runs on the handle's device and restores the
  * caller's current device before it returns. */
 int mmh_create(mmh_handle_t *handle, int device);
@@ -295,6 +303,12 @@ int mmh_kernel_id(const char *short_name);
  * K-slices in LDS.  Correct to the bit, and measured 2.2x slower per edge tile than a whole tile (the f32 MFMA shares
  * the vector ALU's FMA lanes): the product runs thin edge tiles instead (sgemm_dma5.hpp). */
 #define MMH_OPT_RIM5 14
+/* MMH_OPT_RETIRED_BUFFERS (diagnostic, read-only: set is MMH_ERR_INVALID_ARG): how many allocations the handle has RETIRED --
+ * buffers that a captured graph may point at and that had to grow afterwards: they are replaced, kept, and freed with the
+ * handle, never under the graph (the hipGraphs paragraph above).  Every site that retires counts: a capture stream's stream-K
+ * set, pinned phase-order tables, the partial-row workspace of mmh_relu_grad_colsum, the int8 / quantisation scratch.  0 on a
+ * handle that never captured, whatever sizes it ran; get does not synchronise. */
+#define MMH_OPT_RETIRED_BUFFERS 15
 int mmh_set_option(mmh_handle_t handle, int option, int value);
 /* The two tables of a phase-ordered stream-K launch (MMH_OPT_STREAMK_ORDER) for `tiles` tile slots of `nk`
  * K-slices on `grid` persistent workgroups, computed on the host (no device needed): order[grid] = the range
@@ -491,17 +505,24 @@ int mmh_sgemm_host_timed(mmh_handle_t handle, int m, int n, int k, const float *
 /* int8 x int8 -> int32, C = A*B (+ C), row-major, any int8 (-128 included); every sum must fit in
  * int32.  Bit-exact integer arithmetic on v_mfma_i32_16x16x64_i8.  4-byte aligned operands
  * (bases and leading dimensions) are read in place; others are first copied into dense aligned
- * images in a handle-owned workspace (or, for B only, packed transposed) -- see MMH_OPT_IGEMM_MODE. */
+ * images in a handle-owned workspace (or, for B only, packed transposed) -- see MMH_OPT_IGEMM_MODE.
+ * That workspace is per-handle scratch under the capture rule of the hipGraphs paragraph: a captured call whose copies would
+ * have to allocate or grow it is MMH_ERR_UNSUPPORTED with nothing copied or launched; operands read in place need none. */
 int mmh_igemm_s8(mmh_handle_t handle, int m, int n, int k, const int8_t *dA, int lda,
                  const int8_t *dB, int ldb, int32_t *dC, int ldc, int accumulate,
                  void *stream);
 
 /* The callers either side of the int8 GEMM (chgemm's contract as the
- * reference README.md:71-85 words it; parity unpinned -- no reference code):
+ * reference README.md:71-85 words it; the reference project holds no int8 code: tests/test_gpu_int8_parity.py pins
+ * every instantiation to oracle.quantize_sym_s8 and exact integer sums, tests/test_gpu_int8_graph.py under capture):
  *   mmh_quantize_sym_s8: q = clamp(rint(x * s), -127, 127), s = 127 / max|x| written to
  *                        *d_scale (device float); rows x cols windows with leading dims.
  *   mmh_qgemm_f32      : C_f32 = dequant( quant(A) * quant(B) ), per-tensor symmetric
- *                        scales, int32 accumulation, C = acc * (1 / (sa * sb)). */
+ *                        scales, int32 accumulation, C = acc * (1 / (sa * sb)).
+ * Both keep their abs-max words and scales, mmh_qgemm_f32 also its int8 images of A and B (and an int32 image of C in the
+ * two-pass form of a forced MMH_OPT_IGEMM_MODE), in per-handle scratch: one call at a time per handle, and under the capture
+ * rule of the hipGraphs paragraph -- every need of a call is checked before its first memset or launch, so a captured call
+ * that would have to allocate or grow (a handle's first int8 call included) is MMH_ERR_UNSUPPORTED with nothing recorded. */
 int mmh_quantize_sym_s8(mmh_handle_t handle, int rows, int cols, const float *dX, int ldx,
                         int8_t *dQ, int ldq, float *d_scale, void *stream);
 int mmh_qgemm_f32(mmh_handle_t handle, int m, int n, int k, const float *dA, int lda,

@@ -123,6 +123,7 @@ def test_a_graph_survives_a_later_call_that_grows_the_workspace():
         dzb, sb = own.relu_grad_colsum(gb, yb)                     # grows the workspace
         torch.cuda.synchronize()
         assert ref.same_bits(dzb.cpu().numpy(), big[3]) and ref.same_bits(sb.cpu().numpy(), big[4])
+        assert own.get_option(H.OPT_RETIRED_BUFFERS) == 1          # retired, not freed: seen before the graph is replayed
         for rep in range(2):
             small = _inputs(SMALL, 402 + rep)
             _put(torch, g, small[0]), _put(torch, y, small[1])

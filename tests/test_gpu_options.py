@@ -93,8 +93,12 @@ def test_every_option_reads_back_what_set_made_of_the_value(opts):
             assert get(option) == (H.OK, 0), option
             for value in (1, -1, INT_MAX, INT_MIN):
                 refused(H, set_, get, option, value)
+        # MMH_OPT_RETIRED_BUFFERS: read-only -- 0 on a handle that has captured nothing; no value can be written, 0 included
+        assert get(H.OPT_RETIRED_BUFFERS) == (H.OK, 0)
+        for value in (0, 1, -1, INT_MAX, INT_MIN):
+            refused(H, set_, get, H.OPT_RETIRED_BUFFERS, value)
         # ids that are no option of the product: below and above the public ones, and the tools build's 100 .. 108
-        for option in [0, -1, 15, 16, 99, INT_MAX, INT_MIN] + list(range(100, 110)):
+        for option in [0, -1, 16, 17, 99, INT_MAX, INT_MIN] + list(range(100, 110)):
             for value in (0, 1):
                 assert set_(option, value) == H.ERR_INVALID_ARG, (option, value)
             assert get(option) == (H.ERR_INVALID_ARG, -12345), option
@@ -106,7 +110,7 @@ def test_every_option_reads_back_what_set_made_of_the_value(opts):
         set_(H.OPT_DMA_EDGE, 2)
         set_(H.OPT_IGEMM_MODE, 0)
     defaults = {**{o: r[2] for o, r in ranges.items()}, **switches, H.OPT_DMA_EDGE: 2, H.OPT_IGEMM_MODE: 0,
-                H.OPT_STREAMK_TIMEOUTS: 0, H.OPT_STREAMK_DELEGATIONS: 0}
-    assert sorted(defaults) == list(range(1, 15))   # every public MMH_OPT_* was covered
+                H.OPT_STREAMK_TIMEOUTS: 0, H.OPT_STREAMK_DELEGATIONS: 0, H.OPT_RETIRED_BUFFERS: 0}
+    assert sorted(defaults) == list(range(1, 16))   # every public MMH_OPT_* was covered
     for option, default in defaults.items():
         assert get(option) == (H.OK, default), option

@@ -1,7 +1,7 @@
 """Every int8 GEMM and quantiser instantiation in the built product library has a row in the exact-reference table
 (tests/test_gpu_int8_parity.py::INSTANTIATIONS), and every row names an instantiation that is there -- read on the CPU from
 the library's code objects (tools/kernel_resources.py).  Every case of every row is also checked here, on the launchers'
-host arithmetic restated in that module (c_fast, igemm_s8_big_tile at 256 CUs, igemm_s8_inplace_ok, quant_vec_ok and
+host arithmetic restated in tests/int8_ops.py (c_fast, igemm_s8_big_tile at 256 CUs, igemm_s8_inplace_ok, quant_vec_ok and
 K3p's grid): it must reach its row's instantiation, and the table must cover the classes the rows promise."""
 import math
 import re
@@ -9,6 +9,7 @@ import re
 import pytest
 
 import built_lib
+import int8_ops
 
 pytestmark = built_lib.needs_library
 
@@ -43,15 +44,15 @@ def test_every_case_reaches_its_row(row):
     for c in cases:
         entry = c.entry or inst.entry
         mode = inst.mode if c.mode is None else c.mode
-        syms, _ = T.reach(entry, mode, c, CUS)
+        syms, _ = int8_ops.reach(entry, mode, c, CUS)
         assert inst.symbol in syms, (inst.symbol, c, syms)
     if inst.worst:
         c = inst.worst(CUS)
-        assert inst.entry == "igemm" and T.reach("igemm", c.mode, c, CUS)[0] == [inst.symbol], (inst.symbol, c)
-        assert 16384 * c.k <= T.INT32_MAX and 16384 * (c.k + 64) > T.INT32_MAX, c.k   # the deepest k the kernel takes
+        assert inst.entry == "igemm" and int8_ops.reach("igemm", c.mode, c, CUS)[0] == [inst.symbol], (inst.symbol, c)
+        assert 16384 * c.k <= int8_ops.INT32_MAX and 16384 * (c.k + 64) > int8_ops.INT32_MAX, c.k   # the deepest k the kernel takes
     if inst.persistent:
         for c in T._persistent_cases(inst, CUS):
-            syms, words = T.reach(inst.entry, inst.mode, c, CUS, env_cap=T.GRID_CAP)
+            syms, words = int8_ops.reach(inst.entry, inst.mode, c, CUS, env_cap=T.GRID_CAP)
             assert inst.symbol in syms and any(w.startswith("persistent") for w in words), (inst.symbol, c, words)
 
 
@@ -86,14 +87,14 @@ def test_the_quantiser_rows_cover_both_paths_and_the_lopsided_pairs():
     quant = [c for c in by["absmax_kernel"].cases(CUS)]
     words = set()
     for c in quant:
-        words |= set(T.reach("quantize", 0, c, CUS)[1])
+        words |= set(int8_ops.reach("quantize", 0, c, CUS)[1])
     assert {"absmax_kernel (vector path)", "absmax_kernel (row path)", "quantize_kernel (vector path)",
             "quantize_kernel (row path)"} <= words
     assert {1, 2, 3, 4, 5, 4097} <= {c.n for c in quant}
-    vec_thin = [c for c in quant if c.n < 4 and T.quant_vec_ok(c.lds("quantize")[0], 4 * c.oa) and c.m > 1]
+    vec_thin = [c for c in quant if c.n < 4 and int8_ops.quant_vec_ok(c.lds("quantize")[0], 4 * c.oa) and c.m > 1]
     assert vec_thin, "no 1 - 3 column tensor on the vector path"
     wg = [math.ceil(c.m * max(1, math.ceil((c.n // 4) / 1024)) / 4) for c in quant
-          if T.quant_vec_ok(c.lds("quantize")[0], 4 * c.oa)]
+          if int8_ops.quant_vec_ok(c.lds("quantize")[0], 4 * c.oa)]
     assert max(wg) > 64, "no vector-path tensor spreads over more than AMAX_WORDS workgroups"
     values = by["quantize_kernel"].cases(CUS)
     assert any(c.values == "ties" for c in values)
