@@ -70,7 +70,7 @@ EXPORTS = [
     "mmh_sgemm_batched", "mmh_time_sgemm_batched", "mmh_auto_plan_batched",
     "mmh_sgemm_ex", "mmh_time_sgemm_ex", "mmh_auto_plan_ex",
     "mmh_sgemm_batched_ex", "mmh_time_sgemm_batched_ex", "mmh_auto_plan_batched_ex",
-    "mmh_relu_grad_colsum", "mmh_time_relu_grad_colsum", "mmh_kernel_has_op_forms",
+    "mmh_relu_grad_colsum", "mmh_time_relu_grad_colsum", "mmh_kernel_has_op_forms", "mmh_igemm_plan",
 ]
 
 
@@ -121,6 +121,18 @@ def auto_plan(m: int, n: int, k: int, lda: int = 0, ldb: int = 0, ldc: int = 0, 
     _check(lib().mmh_auto_plan(m, n, k, *_dense_ld(OP_N, OP_N, m, n, k, lda, ldb, ldc), base_align, cu_count, C.byref(kern),
                                C.byref(tiles), C.byref(grid)), "mmh_auto_plan")
     return _SHORT_NAMES.get(kern.value, str(kern.value)), tiles.value, grid.value
+
+
+def igemm_plan(entry: str, mode: int, m: int, n: int, k: int, lda: int = 0, ldb: int = 0, ldc: int = 0, a_mod16: int = 0,
+               b_mod16: int = 0, c_mod16: int = 0, cu_count: int = 256, grid_cap: int = 0):
+    """What MMult.igemm_s8 (entry "igemm") or MMult.qgemm ("qgemm") would do in MMH_OPT_IGEMM_MODE `mode` (host arithmetic only,
+    no device): (what last_launch() says after the call, {"qa", "qb", "qc", "qs", "bt": bytes of the handle's scratch the call
+    needs}).  x_mod16: the operands' base addresses modulo 16; grid_cap: the MMH_I8_GRID_CAP test hook.  Raises for a mode this
+    build does not accept, as set_igemm_mode does."""
+    text, sizes = C.create_string_buffer(256), (C.c_size_t * 5)()
+    _check(lib().mmh_igemm_plan({"igemm": 0, "qgemm": 1}[entry], mode, m, n, k, lda or k, ldb or n, ldc or n, a_mod16, b_mod16, c_mod16,
+                                cu_count, grid_cap, text, len(text), sizes), "mmh_igemm_plan")
+    return text.value.decode(), dict(zip(("qa", "qb", "qc", "qs", "bt"), sizes))
 
 
 def _plan_op(name, transa, transb, m, n, k, lda, ldb, ldc, base_align, cu_count):
@@ -292,6 +304,7 @@ def lib() -> C.CDLL:
     L.mmh_probe_lds_read.argtypes = [vp, C.c_int, fp]
     L.mmh_streamk_plan.argtypes = [C.c_long, C.c_int, C.c_int, ip, ip]
     L.mmh_auto_plan.argtypes = [C.c_int] * 8 + [ip, C.POINTER(C.c_long), ip]
+    L.mmh_igemm_plan.argtypes = [C.c_int] * 13 + [C.c_char_p, C.c_int, C.POINTER(C.c_size_t)]
     L.mmh_probe_mfma_f32.argtypes = [vp, fp]
     L.mmh_probe_valu_f32.argtypes = [vp, C.c_int, C.c_int, fp]
     L.mmh_probe_mfma_i8.argtypes = [vp, fp]
@@ -415,11 +428,12 @@ class MMult:
         _check(lib().mmh_set_option(self._h, OPT_STREAMK, int(on)), "mmh_set_option")
 
     def set_igemm_mode(self, mode: int) -> None:
-        """0 B read in place (default; packed B for unaligned operands): the ping-pong 256x256 kernel from one tile
-        per CU up, 128x128 tiles below; 1 in-kernel transpose; 2 correctness-first kernel; 3 / 4 packed-B + LDS-DMA
-        with 128x128 / 256x256 tiles; 5 / 6 the lockstep in-place kernel likewise; 7 / 8 the ping-pong kernel with
-        16 / 32 MFMAs per phase.  (10..13, timing-only ablations with wrong results, exist only in
-        the tools build libmmult_hip_ab.so; the product library rejects them.)"""
+        """By value and name in csrc/igemm_plan.hpp's mode table (kI8Modes): 0 "auto" B read in place (default; dense copies
+        of unaligned operands first): the ping-pong 256x256 kernel K3p where its rounds of tiles are cheaper, 128x128 tiles of
+        K3t otherwise; 2 "simple" the correctness-first kernel; 5 / 6 "k3t_128" / "k3t_256" the lockstep in-place kernel; 7
+        "k3p_mfma32", 8 "k3p_persistent", 9 "k3p_per_tile" the ping-pong kernel on the 32-deep MFMA / as a persistent launch / one
+        workgroup per tile.  (1 "k3", 3 / 4 "k3d_128" / "k3d_256" and 10..13, timing-only ablations with wrong results, exist
+        only in the tools build libmmult_hip_ab.so; the product library rejects them.)  igemm_plan says what a call will run."""
         _check(lib().mmh_set_option(self._h, OPT_IGEMM_MODE, int(mode)), "mmh_set_option")
 
     def streamk_timeouts(self) -> int:
@@ -1128,7 +1142,7 @@ def sgemm_sharded(ngpus: int, a: np.ndarray, b: np.ndarray, kernel="mfma"):
 
 
 __all__ = ["MMult", "ShardedMMult", "MMultError", "lib", "use_ab_library", "device_count", "rccl_version", "shard_rows", "shard_chunks",
-           "kernel_name", "last_launch", "use_timeline_library", "streamk_plan", "auto_plan", "auto_plan_op", "auto_plan_ex", "auto_plan_batched", "auto_plan_batched_ex", "BIAS_NONE", "BIAS_COL", "BIAS_ROW", "ACT_NONE", "ACT_RELU", "BATCH_FORMS", "BATCHED_MAX_WORKGROUPS", "COLSUM_BLOCK_ROWS", "OP_N", "OP_T", "sgemm_sharded", "KERNELS", "CHAIN_KERNELS", "AB_LIB_PATH",
+           "kernel_name", "last_launch", "use_timeline_library", "streamk_plan", "auto_plan", "igemm_plan", "auto_plan_op", "auto_plan_ex", "auto_plan_batched", "auto_plan_batched_ex", "BIAS_NONE", "BIAS_COL", "BIAS_ROW", "ACT_NONE", "ACT_RELU", "BATCH_FORMS", "BATCHED_MAX_WORKGROUPS", "COLSUM_BLOCK_ROWS", "OP_N", "OP_T", "sgemm_sharded", "KERNELS", "CHAIN_KERNELS", "AB_LIB_PATH",
            "OPT_SPLITK", "OPT_HOST_PANELS", "OPT_STREAMK_SPIN_LIMIT", "OPT_FAULT_INJECT", "OPT_STREAMK_ORDER", "OPT_DMA_EDGE", "OPT_STREAMK_DELEGATIONS", "OPT_RIM", "OPT_STREAMK_CHAIN", "OPT_PERSIST", "OPT_RIM5", "OPT_RETIRED_BUFFERS", "KERNEL_AUTO", "KERNEL_VALU", "KERNEL_MFMA", "KERNEL_MFMA_256", "KERNEL_NAIVE", "KERNEL_MFMA_SIMPLE", "KERNEL_MFMA_PIPE",
            "EXPORTS", "LIB_PATH", "OPT_STREAMK", "OPT_STREAMK_TIMEOUTS", "OPT_IGEMM_MODE", "OK", "ERR_INVALID_ARG", "ERR_HIP", "ERR_NO_DEVICE",
            "ERR_UNSUPPORTED", "ERR_ALLOC", "ERR_COMM"]

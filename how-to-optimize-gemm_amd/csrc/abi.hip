@@ -5,6 +5,7 @@
 #include <algorithm>
 
 #include "internal.hpp"
+#include "igemm_plan.hpp"
 #ifdef MMH_AB_BUILD
 #include "ab_kernels.hpp"   // tools/ab/: the MMH_KERNEL_* numbers of the tools build's tile families
 #endif
@@ -237,8 +238,8 @@ int mmh_set_option(mmh_handle_t h, int option, int value) {
       if (h->sticky) *reinterpret_cast<volatile int *>(h->sticky) = 0;
       workspaces_suspect(h);   // a launch that timed out may have left hand-off counters behind
       return MMH_OK;
-    case MMH_OPT_IGEMM_MODE:   // (1, 3, 4 and the timing-only 10 .. 13: the tools build's, tools/ab/igemm_s8_k3.hpp)
-      if (value < 0 || (kAbBuild ? value > 13 : value > 9 || value == 1 || value == 3 || value == 4)) return MMH_ERR_INVALID_ARG;
+    case MMH_OPT_IGEMM_MODE:   // the rows of kI8Modes (igemm_plan.hpp) that this build has
+      if (!i8_mode_row(value)) return MMH_ERR_INVALID_ARG;
       h->igemm_mode = value;
       return MMH_OK;
     case MMH_OPT_STREAMK_SPIN_LIMIT:   // in units of 1024 polls

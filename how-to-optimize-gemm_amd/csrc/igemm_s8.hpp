@@ -43,9 +43,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <stdio.h>
 
-#include <string>
 #include <type_traits>
 
 #include "ab_build.hpp"
@@ -538,108 +536,6 @@ igemm_s8_simple_kernel(int m, int n, int k, const int8_t *__restrict__ A, int ld
           if (ccol + u < n) C[(size_t)row * ldc + ccol + u] = v[u];
       }
     }
-}
-
-template <int BM, int BN, int TM, bool EDGE, int ABLATE, bool BTR = false>
-inline hipError_t launch_igemm_s8_dma_edge(int m, int n, int k, const int8_t *A, int lda, const int8_t *Bt,
-                                           int kp, int n_pad, int32_t *C, int ldc, int acc, hipStream_t s,
-                                           const float *deq = nullptr, std::string *what = nullptr) {
-  const int nbm = (m + BM - 1) / BM, nbn = (n + BN - 1) / BN;
-  constexpr int threads = BM / (16 * TM) * (BN / 64) * 64;
-  constexpr size_t lds = 2 * (size_t)(BM + BN) * IK;
-  if (lds > 64 * 1024) {   // > 64 KiB of dynamic LDS must be opted into (remembered per device)
-    const hipError_t e = opt_in_big_lds(reinterpret_cast<const void *>(&igemm_s8_dma_kernel<BM, BN, TM, EDGE, ABLATE, BTR>),
-                                lds);
-    if (e != hipSuccess) return e;
-  }
-  hipLaunchKernelGGL((igemm_s8_dma_kernel<BM, BN, TM, EDGE, ABLATE, BTR>), dim3((unsigned)(nbm * nbn)), dim3(threads),
-                     lds, s, m, n, k, A, lda, Bt, kp, n_pad, C, ldc, acc, nbm, nbn, deq);
-  if (what) {   // mmh_last_launch: the instantiation, spelled as tools/kernel_resources.py demangles it
-    char buf[96];
-    snprintf(buf, sizeof buf, "igemm_s8_dma_kernel<%d,%d,%d,%s,%d,%s>, %s%d workgroups", BM, BN, TM, EDGE ? "true" : "false",
-             ABLATE, BTR ? "true" : "false", BTR ? "B in place, " : "", nbm * nbn);
-    *what = buf;
-  }
-  return hipGetLastError();
-}
-
-template <int BM, int BN, int TM, bool BTR = false>
-inline hipError_t launch_igemm_s8_dma(int m, int n, int k, const int8_t *A, int lda, const int8_t *Bt, int kp,
-                                      int n_pad, int32_t *C, int ldc, int acc, hipStream_t s,
-                                      const float *deq = nullptr, std::string *what = nullptr) {
-  const bool c_fast = (m % BM == 0) && (n % BN == 0) && (ldc % 4 == 0) &&
-                      ((reinterpret_cast<uintptr_t>(C) & 15) == 0);
-  return c_fast
-             ? launch_igemm_s8_dma_edge<BM, BN, TM, false, 0, BTR>(m, n, k, A, lda, Bt, kp, n_pad, C, ldc, acc, s,
-                                                                  deq, what)
-             : launch_igemm_s8_dma_edge<BM, BN, TM, true, 0, BTR>(m, n, k, A, lda, Bt, kp, n_pad, C, ldc, acc, s,
-                                                                 deq, what);
-}
-
-// K3t (B read in place) needs 4-byte aligned operands and byte offsets inside the descriptors' 2 GiB
-inline bool igemm_s8_inplace_ok(const int8_t *A, int lda, const int8_t *B, int ldb, int k) {
-  const size_t lim = (1ull << 31) - 4096;
-  return (lda % 4 == 0) && ((reinterpret_cast<uintptr_t>(A) & 3) == 0) && (ldb % 4 == 0) &&
-         ((reinterpret_cast<uintptr_t>(B) & 3) == 0) && ((size_t)256 * lda + k) < lim &&
-         ((size_t)(k + 256) * ldb + 256) < lim;
-}
-// C_f32 = (float)(A x B) * (1 / (scales[0] * scales[1])) with the dequantisation in the epilogue; in-place
-// kernel only (the caller checks igemm_s8_inplace_ok and otherwise runs the two-pass form).
-// Tile choice of the in-place kernels: 256x256 tiles (K3p) run one per CU, 128x128 tiles (K3t) two per CU, and a full
-// round of 128x128 tiles takes 0.58 of a 256x256 round's time for half its work (4096^3: 68.5 us in two rounds against
-// 58.7 in one).  Rounds 3 - 5 never chose the big tile below one tile per CU; with the C stores coalesced (round 6) a
-// part-filled chip of big tiles beats two rounds of small ones: 3072^3 31.8 against 43.1 us, 3584^3 42.9 / 53.0, 6144^3
-// 205 / 217 -- and a single round of small tiles wins where there is one: 2048^3 14.1 / 22.5, 1024^3 9.8 / 13.1
-// (profiles/r06_i8_persist_ab.txt).
-inline bool igemm_s8_big_tile(int m, int n, int num_cus) {
-  const long tiles256 = (long)((m + 255) / 256) * ((n + 255) / 256);
-  const long tiles128 = (long)((m + 127) / 128) * ((n + 127) / 128);
-  const long r256 = (tiles256 + num_cus - 1) / num_cus, r128 = (tiles128 + 2L * num_cus - 1) / (2L * num_cus);
-  return (double)r256 <= 0.6 * (double)r128 + 1e-9;
-}
-
-inline hipError_t launch_igemm_s8_dequant(int m, int n, int k, const int8_t *A, int lda, const int8_t *B, int ldb,
-                                          float *C, int ldc, const float *scales, hipStream_t s, int num_cus,
-                                          std::string *what = nullptr) {
-  int32_t *Ci = reinterpret_cast<int32_t *>(C);
-  if (igemm_s8_big_tile(m, n, num_cus))
-    return launch_igemm_s8_dma<256, 256, 8, true>(m, n, k, A, lda, B, ldb, n, Ci, ldc, 0, s, scales, what);
-  return launch_igemm_s8_dma<128, 128, 4, true>(m, n, k, A, lda, B, ldb, n, Ci, ldc, 0, s, scales, what);
-}
-
-// mode: 0 = K3t (B read in place by transposing LDS reads; the tile by igemm_s8_big_tile) when the operands are 4-byte
-//           aligned and inside the descriptors' window, else the simple kernel; 5 / 6 = K3t with 128x128 / 256x256 tiles
-//       forced (A/B switches); 2 (and anything K3t cannot take) = the simple kernel.
-// (The ping-pong kernel K3p is launched by igemm.hip; K3 and the packed-B kernel K3d -- modes 1, 3, 4, and the timing-only
-// ablations 10..13 -- by tools/ab/igemm_s8_k3.hpp in the tools build.)
-inline hipError_t launch_igemm_s8(int m, int n, int k, const int8_t *A, int lda, const int8_t *B,
-                                  int ldb, int32_t *C, int ldc, int acc, hipStream_t s, int mode = 0, int num_cus = 256,
-                                  std::string *what = nullptr) {
-  const int nbm = (m + 127) / 128, nbn = (n + 127) / 128;
-  dim3 grid((unsigned)(nbm * nbn)), block(256);
-  const bool shape_ok = (m % 128 == 0) && (n % 128 == 0);
-  if ((mode == 0 || mode == 5 || mode == 6) && igemm_s8_inplace_ok(A, lda, B, ldb, k)) {
-    // K3t: B read in place (no packing, no workspace)
-    const bool big = mode == 6 || (mode == 0 && igemm_s8_big_tile(m, n, num_cus));
-    if (big) return launch_igemm_s8_dma<256, 256, 8, true>(m, n, k, A, lda, B, ldb, n, C, ldc, acc, s, nullptr, what);
-    return launch_igemm_s8_dma<128, 128, 4, true>(m, n, k, A, lda, B, ldb, n, C, ldc, acc, s, nullptr, what);
-  }
-  const bool fast = shape_ok && (k % IBK == 0) && (lda % 16 == 0) && (ldb % 4 == 0) && (ldc % 4 == 0) &&
-                    ((reinterpret_cast<uintptr_t>(A) & 15) == 0) &&
-                    ((reinterpret_cast<uintptr_t>(B) & 3) == 0) &&
-                    ((reinterpret_cast<uintptr_t>(C) & 15) == 0);
-  if (fast)
-    hipLaunchKernelGGL(igemm_s8_simple_kernel<false>, grid, block, 0, s, m, n, k, A, lda, B, ldb, C,
-                       ldc, acc, nbm, nbn);
-  else
-    hipLaunchKernelGGL(igemm_s8_simple_kernel<true>, grid, block, 0, s, m, n, k, A, lda, B, ldb, C,
-                       ldc, acc, nbm, nbn);
-  if (what) {
-    char buf[64];
-    snprintf(buf, sizeof buf, "igemm_s8_simple_kernel<%s>, %d workgroups", fast ? "false" : "true", nbm * nbn);
-    *what = buf;
-  }
-  return hipGetLastError();
 }
 
 }  // namespace mmh

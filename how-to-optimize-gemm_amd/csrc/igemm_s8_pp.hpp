@@ -362,49 +362,4 @@ igemm_s8_pp_kernel(int m, int n, int k, const int8_t *__restrict__ A, int lda, c
   }
 }
 
-// `grid_cap`: workgroups at most (the CUs of the device: one persistent workgroup each); 0 = one workgroup per tile,
-// round 5's launch form (MMH_OPT_IGEMM_MODE 9, the A/B switch).
-template <int MFMA_K = 64>
-inline hipError_t launch_igemm_s8_pp(int m, int n, int k, const int8_t *A, int lda, const int8_t *B, int ldb, int32_t *C,
-                                     int ldc, int acc, hipStream_t s, int grid_cap, const float *deq = nullptr,
-                                     std::string *what = nullptr) {
-  constexpr int BM = 256, BN = 256;
-  const int nbm = (m + BM - 1) / BM, nbn = (n + BN - 1) / BN;
-  constexpr size_t lds = 2 * (size_t)(BM + BN) * IK + 8 * 4096;   // the ring and the eight waves' C transposers: 160 KiB
-  const bool c_fast = (m % BM == 0) && (n % BN == 0) && (ldc % 4 == 0) && ((reinterpret_cast<uintptr_t>(C) & 15) == 0);
-  // the XCD map of block_to_tile reads the XCD off the (virtual) block index: a persistent grid is a multiple of NXCD
-  int grid = nbm * nbn;
-  if (grid_cap > 0 && grid > grid_cap) grid = grid_cap >= NXCD ? grid_cap / NXCD * NXCD : grid_cap;
-#define MMH_PP_LAUNCH(E, D)                                                                                           \
-  do {                                                                                                                \
-    const hipError_t e = opt_in_big_lds(reinterpret_cast<const void *>(&igemm_s8_pp_kernel<E, D, MFMA_K>), lds);      \
-    if (e != hipSuccess) return e;                                                                                    \
-    hipLaunchKernelGGL((igemm_s8_pp_kernel<E, D, MFMA_K>), dim3((unsigned)grid), dim3(512), lds, s, m, n, k, A, lda, B, \
-                       ldb, C, ldc, acc, nbm, nbn, deq);                                                              \
-  } while (0)
-  if constexpr (MFMA_K == 64) {
-    if (deq) {
-      if (c_fast) MMH_PP_LAUNCH(false, true);
-      else MMH_PP_LAUNCH(true, true);
-    } else {
-      if (c_fast) MMH_PP_LAUNCH(false, false);
-      else MMH_PP_LAUNCH(true, false);
-    }
-  } else {   // the config-named instruction: a forced mode of mmh_igemm_s8 only (no dequantising epilogue)
-    if (c_fast) MMH_PP_LAUNCH(false, false);
-    else MMH_PP_LAUNCH(true, false);
-  }
-#undef MMH_PP_LAUNCH
-  if (what) {   // mmh_last_launch: the instantiation, spelled as tools/kernel_resources.py demangles it, and its launch form
-    char buf[128];
-    const char *e = c_fast ? "false" : "true", *d = deq ? "true" : "false";
-    if (grid < nbm * nbn)
-      snprintf(buf, sizeof buf, "igemm_s8_pp_kernel<%s,%s,%d>, persistent: %d workgroups walk %d tiles", e, d, MFMA_K, grid, nbm * nbn);
-    else
-      snprintf(buf, sizeof buf, "igemm_s8_pp_kernel<%s,%s,%d>, %d workgroups, one per tile", e, d, MFMA_K, grid);
-    *what = buf;
-  }
-  return hipGetLastError();
-}
-
 }  // namespace mmh

@@ -244,7 +244,10 @@ int mmh_kernel_id(const char *short_name);
  * one workgroup per tile (mode 0 picks by K), 7 K3p on v_mfma_i32_16x16x32_i8 -- the instruction BASELINE.json
  * configs[4] names: the same integers at half the matrix pipe's rate (A/B switches).
  * (Modes 1, 3, 4 -- the in-kernel-transpose and packed-B rungs of rounds 1-2 -- and 10..13, timing-only ablations with
- * wrong results, exist in libmmult_hip_ab.so only; the product library rejects them.) */
+ * wrong results, exist in libmmult_hip_ab.so only; the product library rejects them.)
+ * One row per value in csrc/igemm_plan.hpp's kI8Modes, by name: 0 auto, 2 simple, 5 k3t_128, 6 k3t_256, 7 k3p_mfma32,
+ * 8 k3p_persistent, 9 k3p_per_tile (tools build: 1 k3, 3 k3d_128, 4 k3d_256, 10..13 k3d_no_dma / _no_reads / _no_dma_no_reads /
+ * _no_store); mmh_igemm_plan says what a call in a mode will run. */
 #define MMH_OPT_IGEMM_MODE 3
 /* MMH_OPT_SPLITK (default 0 = off): 1 lets MMH_KERNEL_AUTO run shapes with fewer 128x128 tiles than
  * CUs as a split-K launch with as many concurrent K parts as fill the chip; 2..16 asks for that many
@@ -527,6 +530,17 @@ int mmh_quantize_sym_s8(mmh_handle_t handle, int rows, int cols, const float *dX
                         int8_t *dQ, int ldq, float *d_scale, void *stream);
 int mmh_qgemm_f32(mmh_handle_t handle, int m, int n, int k, const float *dA, int lda,
                   const float *dB, int ldb, float *dC, int ldc, void *stream);
+/* What mmh_igemm_s8 (entry MMH_I8_IGEMM) or mmh_qgemm_f32 (MMH_I8_QGEMM) would do with MMH_OPT_IGEMM_MODE = mode: the plan both
+ * are launched from (csrc/igemm_plan.hpp), host arithmetic only -- needs no device and no handle.  m, n, k > 0; a / b / c_mod16:
+ * the base addresses of the call's dA, dB, dC modulo 16; cu_count <= 0: 256;
+ * grid_cap: 0, or the MMH_I8_GRID_CAP test hook's value.  text receives what mmh_last_launch says after the call (cut to
+ * text_bytes; 256 always suffice), scratch_bytes[0..4] the bytes the call needs of the handle's qa, qb, qc, qs, bt (int8 images of
+ * A and B, int32 image of C, abs-max words and scales, the tools build's packed B).  MMH_ERR_INVALID_ARG: a mode this build
+ * does not accept (as mmh_set_option), or arguments the entry point itself refuses. */
+#define MMH_I8_IGEMM 0
+#define MMH_I8_QGEMM 1
+int mmh_igemm_plan(int entry, int mode, int m, int n, int k, int lda, int ldb, int ldc, int a_mod16, int b_mod16, int c_mod16,
+                   int cu_count, int grid_cap, char *text, int text_bytes, size_t *scratch_bytes);
 
 /* The linear layer's backward beside its two GEMMs: the ReLU gate on the incoming gradient and the bias gradient, in ONE
  * memory-bound pass over rows x cols floats (cuBLASLt / hipBLASLt know the pair as the DRELU and BGRAD epilogues).  With

@@ -22,14 +22,14 @@ def _b(x):
 
 # ---- the launchers' host arithmetic (igemm.hip, igemm_s8.hpp, igemm_s8_pp.hpp, quant_s8.hpp) ---------------------------
 def inplace_ok(lda, oa, ldb, ob, k):
-    """igemm_s8_inplace_ok: dword-aligned operands whose byte offsets stay inside the descriptors' 2 GiB window."""
+    """i8_dword and i8_window: dword-aligned operands whose byte offsets stay inside the descriptors' 2 GiB window."""
     lim = (1 << 31) - 4096
     return lda % 4 == 0 and oa % 4 == 0 and ldb % 4 == 0 and ob % 4 == 0 and 256 * lda + k < lim and \
         (k + 256) * ldb + 256 < lim
 
 
 def big_tile(m, n, cus):
-    """igemm_s8_big_tile: rounds of 256x256 tiles (one per CU) against rounds of 128x128 ones (two per CU)."""
+    """i8_big_tile: rounds of 256x256 tiles (one per CU) against rounds of 128x128 ones (two per CU)."""
     t256 = math.ceil(m / 256) * math.ceil(n / 256)
     t128 = math.ceil(m / 128) * math.ceil(n / 128)
     return math.ceil(t256 / cus) <= 0.6 * math.ceil(t128 / (2 * cus)) + 1e-9

@@ -1,7 +1,7 @@
 """Every int8 GEMM and quantiser instantiation in the built product library has a row in the exact-reference table
 (tests/test_gpu_int8_parity.py::INSTANTIATIONS), and every row names an instantiation that is there -- read on the CPU from
 the library's code objects (tools/kernel_resources.py).  Every case of every row is also checked here, on the launchers'
-host arithmetic restated in tests/int8_ops.py (c_fast, igemm_s8_big_tile at 256 CUs, igemm_s8_inplace_ok, quant_vec_ok and
+host arithmetic restated in tests/int8_ops.py (whole tiles, the tile rule at 256 CUs, the in-place test, quant_vec_ok and
 K3p's grid): it must reach its row's instantiation, and the table must cover the classes the rows promise."""
 import math
 import re

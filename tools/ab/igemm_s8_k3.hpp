@@ -5,6 +5,7 @@
 //        ablations of the packed 256x256 kernel (modes 10..13: WRONG results).
 // The descriptions of both are in csrc/igemm_s8.hpp's header, where they were written.
 #pragma once
+#include "igemm_plan.hpp"
 #include "igemm_s8.hpp"
 
 namespace mmh {
@@ -240,55 +241,37 @@ __global__ void __launch_bounds__(256) pack_bt_s8_kernel(const int8_t *__restric
   }
 }
 
-// Workspace bytes mmh_igemm_s8 needs for the packed B of a (k x n) problem.
-inline size_t igemm_s8_pack_bytes(int n, int k) {
-  const size_t n_pad = ((size_t)n + 127) & ~(size_t)127, kp = ((size_t)k + 255) & ~(size_t)255;
-  return n_pad * kp;
-}
-
-// mode: 0 = K3d when eligible (needs `bt_ws`, >= igemm_s8_pack_bytes; 256x256 tiles when there
-//           is at least one per CU, else 128x128), else K3 / simple;
-//       1 = K3 (in-kernel transpose), 2 = the simple kernel,
-//       3 / 4 = K3d with 128x128 / 256x256 tiles forced (A/B switch).
-// does this call need the packed-B workspace (igemm_s8_pack_bytes)?
-inline bool igemm_s8_needs_pack(int mode, const int8_t *A, int lda, const int8_t *B, int ldb, int k) {
-  (void)A; (void)lda; (void)B; (void)ldb; (void)k;
-  return mode == 3 || mode == 4 || mode >= 10;
-}
-
-
-// modes 1, 3, 4, 10..13; anything else (or an operand these kernels cannot take): hipErrorNotSupported
-inline hipError_t launch_igemm_s8_ab(int m, int n, int k, const int8_t *A, int lda, const int8_t *B, int ldb, int32_t *C, int ldc,
-                                     int acc, hipStream_t s, int8_t *bt_ws, int mode) {
-  const int nbm = (m + 127) / 128, nbn = (n + 127) / 128;
-  dim3 grid((unsigned)(nbm * nbn)), block(256);
-  const bool shape_ok = (m % 128 == 0) && (n % 128 == 0);
-  const bool a4 = (lda % 4 == 0) && ((reinterpret_cast<uintptr_t>(A) & 3) == 0);
-  const bool b4 = (ldb % 4 == 0) && ((reinterpret_cast<uintptr_t>(B) & 3) == 0);
-  const size_t lim = (1ull << 31) - 4096;
-  const size_t kp = ((size_t)k + 255) & ~(size_t)255, n_pad = ((size_t)n + 127) & ~(size_t)127;
-  constexpr size_t lds = 4 * ITILE;   // 64 KiB
-  const bool c_fast = shape_ok && (ldc % 4 == 0) && ((reinterpret_cast<uintptr_t>(C) & 15) == 0);
-  if ((mode == 3 || mode == 4 || mode >= 10) && bt_ws && a4 && ((size_t)256 * lda + k) < lim && 256 * kp < lim) {
-    dim3 pgrid((unsigned)(n_pad / 64), (unsigned)((kp + 255) / 256));
-    hipLaunchKernelGGL(pack_bt_s8_kernel, pgrid, dim3(256), 0, s, B, ldb, k, n, bt_ws, (int)kp, (int)n_pad, b4 ? 1 : 0);
-    const int kpi = (int)kp, npi = (int)n_pad;
-    const bool whole256 = (m % 256 == 0) && (n % 256 == 0) && (ldc % 4 == 0) && ((reinterpret_cast<uintptr_t>(C) & 15) == 0);
-    if (mode >= 10 && !whole256) return hipErrorInvalidValue;
-    if (mode == 10) return launch_igemm_s8_dma_edge<256, 256, 8, false, 1>(m, n, k, A, lda, bt_ws, kpi, npi, C, ldc, acc, s);
-    if (mode == 11) return launch_igemm_s8_dma_edge<256, 256, 8, false, 2>(m, n, k, A, lda, bt_ws, kpi, npi, C, ldc, acc, s);
-    if (mode == 12) return launch_igemm_s8_dma_edge<256, 256, 8, false, 3>(m, n, k, A, lda, bt_ws, kpi, npi, C, ldc, acc, s);
-    if (mode == 13) return launch_igemm_s8_dma_edge<256, 256, 8, false, 4>(m, n, k, A, lda, bt_ws, kpi, npi, C, ldc, acc, s);
-    if (mode == 3) return launch_igemm_s8_dma<128, 128, 4>(m, n, k, A, lda, bt_ws, kpi, npi, C, ldc, acc, s);
-    return launch_igemm_s8_dma<256, 256, 8>(m, n, k, A, lda, bt_ws, kpi, npi, C, ldc, acc, s);
-  }
-  const bool window_ok = ((size_t)128 * lda + k) < lim && ((size_t)k * ldb + 128) < lim;
-  if (mode == 1 && a4 && b4 && window_ok) {
-    if (c_fast) hipLaunchKernelGGL(igemm_s8_kernel<false>, grid, block, lds, s, m, n, k, A, lda, B, ldb, C, ldc, acc, nbm, nbn);
-    else hipLaunchKernelGGL(igemm_s8_kernel<true>, grid, block, lds, s, m, n, k, A, lda, B, ldb, C, ldc, acc, nbm, nbn);
+// The plans of the K3 / K3d families (igemm_plan.hpp: modes 1, 3, 4, 10..13 on operands these kernels can take -- the plan has
+// checked; `bt_ws`: the plan's bt bytes, K3d's packed B).
+inline hipError_t launch_igemm_s8_ab(const I8Plan &p, const int8_t *A, const int8_t *B, int32_t *C, int acc, int8_t *bt_ws,
+                                     hipStream_t s) {
+  const dim3 grid((unsigned)p.grid);
+  if (p.family == I8Family::K3) {
+    constexpr size_t lds = 4 * ITILE;   // 64 KiB
+    if (p.edge) hipLaunchKernelGGL(igemm_s8_kernel<true>, grid, dim3(256), lds, s, p.m, p.n, p.k, A, p.lda, B, p.ldb, C, p.ldc, acc, p.nbm, p.nbn);
+    else hipLaunchKernelGGL(igemm_s8_kernel<false>, grid, dim3(256), lds, s, p.m, p.n, p.k, A, p.lda, B, p.ldb, C, p.ldc, acc, p.nbm, p.nbn);
     return hipGetLastError();
   }
-  return hipErrorNotSupported;
+  const int kp = (int)i8_pack_k(p.k), n_pad = (p.n + 127) & ~127;
+  const bool b4 = (p.ldb % 4 == 0) && ((reinterpret_cast<uintptr_t>(B) & 3) == 0);
+  hipLaunchKernelGGL(pack_bt_s8_kernel, dim3((unsigned)(n_pad / 64), (unsigned)((kp + 255) / 256)), dim3(256), 0, s, B, p.ldb, p.k, p.n,
+                     bt_ws, kp, n_pad, b4 ? 1 : 0);
+  if (p.ablate && p.edge) return hipErrorInvalidValue;   // the ablations: whole 256x256 tiles only
+  auto go = [&](auto kern, unsigned threads, size_t lds) -> hipError_t {
+    if (lds > 64 * 1024)
+      if (const hipError_t e = opt_in_big_lds(reinterpret_cast<const void *>(kern), lds); e != hipSuccess) return e;
+    hipLaunchKernelGGL(kern, grid, dim3(threads), lds, s, p.m, p.n, p.k, A, p.lda, bt_ws, kp, n_pad, C, p.ldc, acc, p.nbm, p.nbn,
+                       (const float *)nullptr);
+    return hipGetLastError();
+  };
+  switch (p.ablate) {
+    case 1: return go(igemm_s8_dma_kernel<256, 256, 8, false, 1>, 512, 4 * 256 * IK);
+    case 2: return go(igemm_s8_dma_kernel<256, 256, 8, false, 2>, 512, 4 * 256 * IK);
+    case 3: return go(igemm_s8_dma_kernel<256, 256, 8, false, 3>, 512, 4 * 256 * IK);
+    case 4: return go(igemm_s8_dma_kernel<256, 256, 8, false, 4>, 512, 4 * 256 * IK);
+  }
+  if (p.tile == 128) return p.edge ? go(igemm_s8_dma_kernel<128, 128, 4, true, 0>, 256, 4 * 128 * IK) : go(igemm_s8_dma_kernel<128, 128, 4, false, 0>, 256, 4 * 128 * IK);
+  return p.edge ? go(igemm_s8_dma_kernel<256, 256, 8, true, 0>, 512, 4 * 256 * IK) : go(igemm_s8_dma_kernel<256, 256, 8, false, 0>, 512, 4 * 256 * IK);
 }
 
 }  // namespace mmh
