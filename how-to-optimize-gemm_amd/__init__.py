@@ -3,7 +3,8 @@
 Layout (only what the hot path needs):
   csrc/      hand-written gfx950 HIP kernels + the C-ABI shim (libmmult_hip.so)
   harness/   C++ host side: MY_MMult forwarder and the test_MMult sweep driver
-  api.py     ctypes mirror of include/mmult_hip.h (+ torch device-pointer glue)
+  abi_header.py  include/mmult_hip.h parsed: every MMH_* constant, every prototype as ctypes types
+  api.py     the ctypes binding, made from abi_header -- no hand-kept mirror -- (+ torch device-pointer glue)
   autograd.py torch.autograd glue: a linear layer (+ ReLU) that trains through MMult.linear / linear_backward
   shard.py   one-process-per-GPU row-panel shard over torch.distributed (RCCL)
   build.py   hipcc recipe

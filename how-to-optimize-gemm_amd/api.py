@@ -19,59 +19,27 @@ from typing import Optional
 
 import numpy as np
 
+from . import abi_header as _abi
+
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(PKG_DIR, "libmmult_hip.so")
 AB_LIB_PATH = os.path.join(PKG_DIR, "libmmult_hip_ab.so")   # tools-only build (see use_ab_library)
 
-# status codes / kernel ids (include/mmult_hip.h)
-OK, ERR_INVALID_ARG, ERR_HIP, ERR_NO_DEVICE, ERR_UNSUPPORTED, ERR_ALLOC, ERR_COMM = 0, -1, -2, -3, -4, -5, -6
-KERNEL_AUTO, KERNEL_VALU, KERNEL_MFMA, KERNEL_MFMA_256, KERNEL_NAIVE, KERNEL_MFMA_SIMPLE, KERNEL_MFMA_PIPE = 0, 1, 2, 3, 4, 5, 6
-OPT_STREAMK, OPT_STREAMK_TIMEOUTS, OPT_IGEMM_MODE = 1, 2, 3
-OPT_SPLITK, OPT_HOST_PANELS, OPT_STREAMK_SPIN_LIMIT, OPT_FAULT_INJECT, OPT_STREAMK_ORDER, OPT_DMA_EDGE, OPT_STREAMK_DELEGATIONS = 4, 5, 6, 7, 8, 9, 10
-OPT_RIM = 11
-OPT_STREAMK_CHAIN = 12
-OPT_PERSIST = 13
-OPT_RIM5 = 14
-OPT_RETIRED_BUFFERS = 15   # read-only: allocations retired because a captured graph may point at them
-OP_N, OP_T = 0, 1   # mmh_sgemm_op's operand layouts (include/mmult_hip.h)
-BIAS_NONE, BIAS_COL, BIAS_ROW = 0, 1, 2   # mmh_sgemm_ex's MMH_BIAS_*: no bias, bias[j] (n floats), bias[i] (m floats)
-ACT_NONE, ACT_RELU = 0, 1                 # ... and MMH_ACT_*
-BATCH_FORMS = {1: "fold", 2: "one_launch", 3: "loop"}   # mmh_sgemm_batched's MMH_BATCH_FORM_*
-BATCHED_MAX_WORKGROUPS = 1 << 22   # MMH_BATCHED_MAX_WORKGROUPS: one batched launch holds at most this many workgroups
-COLSUM_BLOCK_ROWS = 128            # MMH_COLSUM_BLOCK_ROWS: the row blocks of mmh_relu_grad_colsum's column sum (part of its numerics)
-KERNELS = {"auto": KERNEL_AUTO, "valu": KERNEL_VALU, "mfma": KERNEL_MFMA,
-           "mfma256": KERNEL_MFMA_256, "naive": KERNEL_NAIVE, "mfma_simple": KERNEL_MFMA_SIMPLE,
-           "mfma_pipe": KERNEL_MFMA_PIPE, "mfma_tiles": 10, "mfma_128x64": 8, "mfma_64x64": 11, "mfma_256x256": 12,
-           "valu_128x128": 13, "valu_64x64": 14, "valu_128x64": 9, "mfma_splitk": 15, "mfma_splitk_128x64": 20,
-           "mfma_64x64_dma": 25, "mfma_128x64_dma": 27, "mfma_128x128_dma": 28,
-           "mfma_64x64_dma5": 29, "mfma_128x64_dma5": 30, "mfma_128x128_dma5": 31,
-           "mfma_96x96_dma5": 7, "mfma_96x64_dma5": 26, "mfma_160x160_dma5": 100,
-           }
+# Every MMH_* constant and every prototype comes from include/mmult_hip.h itself (abi_header.py).  These are module names here,
+# the header's values under the header's names less the MMH_ prefix: OK, ERR_COMM, KERNEL_AUTO, OPT_STREAMK, OP_T, BIAS_ROW, ...
+_CONSTANT_PREFIXES = ("OK", "ERR_", "KERNEL_", "OPT_", "OP_", "BIAS_", "ACT_", "BATCHED_MAX_WORKGROUPS", "COLSUM_BLOCK_ROWS")
+_CONSTANTS = {name: v for name, v in _abi.constants("MMH_").items() if name.startswith(_CONSTANT_PREFIXES)}
+globals().update(_CONSTANTS)
+BATCH_FORMS = {v: name.lower() for name, v in _abi.constants("MMH_BATCH_FORM_").items()}   # mmh_sgemm_batched's forms, by value
+# short name -> id: the header's MMH_KERNEL_ names in lower case ("mfma256" is the library's own short name of MMH_KERNEL_MFMA_256)
+KERNELS = {{"mfma_256": "mfma256"}.get(name.lower(), name.lower()): v for name, v in _abi.constants("MMH_KERNEL_").items()}
 # (tools build only, libmmult_hip_ab.so: the 32x32x2 tiles mfma32_* / mfma32b_* (ids 48-51, 60-62), exp5_*, the rim --
 # their names resolve through the library's own table, mmh_kernel_id)
 # kernels that keep the one-chain-per-element contract (bit-identical results); the split-K ids do not
 CHAIN_KERNELS = [k for k in KERNELS if "splitk" not in k]
 _SHORT_NAMES = {v: name for name, v in KERNELS.items() if name != "mfma256"}   # what the plan functions (auto_plan*) call a kernel id
 
-# every symbol include/mmult_hip.h declares (tests assert the .so exports them all)
-EXPORTS = [
-    "mmh_strerror", "mmh_last_error", "mmh_last_launch", "mmh_version", "mmh_is_ab_build", "mmh_device_count",
-    "mmh_device_info",
-    "mmh_create", "mmh_destroy", "mmh_warm", "mmh_reserve_stream", "mmh_set_kernel", "mmh_get_kernel", "mmh_kernel_name", "mmh_kernel_id",
-    "mmh_set_option", "mmh_get_option",
-    "mmh_sgemm", "mmh_sgemm_host", "mmh_sgemm_host_timed", "mmh_igemm_s8", "mmh_quantize_sym_s8", "mmh_qgemm_f32",
-    "mmh_sgemm_rocblas", "mmh_sgemm_hipblaslt", "mmh_shard_rows",
-    "mmh_shard_create", "mmh_shard_destroy", "mmh_shard_set_kernel", "mmh_shard_info", "mmh_shard_sgemm", "mmh_shard_sgemm_streamed", "mmh_shard_chunks", "mmh_shard_pin",
-    "mmh_shard_unpin",
-    "mmh_rccl_version",
-    "mmh_sgemm_sharded", "mmh_time_sgemm", "mmh_time_comparator", "mmh_trace_sgemm", "mmh_probe_mfma_f32", "mmh_probe_valu_f32", "mmh_probe_mfma_i8",
-    "mmh_probe_mfma_i8_sustained", "mmh_probe_hbm_copy", "mmh_probe_hbm_read", "mmh_probe_lds_read", "mmh_streamk_plan", "mmh_auto_plan",
-    "mmh_sgemm_op", "mmh_time_sgemm_op", "mmh_auto_plan_op",
-    "mmh_sgemm_batched", "mmh_time_sgemm_batched", "mmh_auto_plan_batched",
-    "mmh_sgemm_ex", "mmh_time_sgemm_ex", "mmh_auto_plan_ex",
-    "mmh_sgemm_batched_ex", "mmh_time_sgemm_batched_ex", "mmh_auto_plan_batched_ex",
-    "mmh_relu_grad_colsum", "mmh_time_relu_grad_colsum", "mmh_kernel_has_op_forms", "mmh_igemm_plan",
-]
+EXPORTS = list(_abi.PROTOTYPES)   # every symbol include/mmult_hip.h declares (tests assert the .so exports them all)
 
 
 class MMultError(RuntimeError):
@@ -130,7 +98,7 @@ def igemm_plan(entry: str, mode: int, m: int, n: int, k: int, lda: int = 0, ldb:
     needs}).  x_mod16: the operands' base addresses modulo 16; grid_cap: the MMH_I8_GRID_CAP test hook.  Raises for a mode this
     build does not accept, as set_igemm_mode does."""
     text, sizes = C.create_string_buffer(256), (C.c_size_t * 5)()
-    _check(lib().mmh_igemm_plan({"igemm": 0, "qgemm": 1}[entry], mode, m, n, k, lda or k, ldb or n, ldc or n, a_mod16, b_mod16, c_mod16,
+    _check(lib().mmh_igemm_plan(_abi.constants("MMH_I8_")[entry.upper()], mode, m, n, k, lda or k, ldb or n, ldc or n, a_mod16, b_mod16, c_mod16,
                                 cu_count, grid_cap, text, len(text), sizes), "mmh_igemm_plan")
     return text.value.decode(), dict(zip(("qa", "qb", "qc", "qs", "bt"), sizes))
 
@@ -233,83 +201,9 @@ def lib() -> C.CDLL:
                          f"{_lib_path} is missing -- run __graft_entry__.build(); "
                          "there is no CPU fallback")
     L = C.CDLL(_lib_path)
-    vp, ip, fp = C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_float)
-    L.mmh_strerror.argtypes = [C.c_int]
-    L.mmh_strerror.restype = C.c_char_p
-    L.mmh_last_error.restype = C.c_char_p
-    L.mmh_last_launch.restype = C.c_char_p
-    L.mmh_version.restype = C.c_int
-    L.mmh_is_ab_build.restype = C.c_int
-    L.mmh_device_count.argtypes = [ip]
-    L.mmh_device_info.argtypes = [C.c_int, C.c_char_p, ip, ip]
-    L.mmh_create.argtypes = [C.POINTER(vp), C.c_int]
-    L.mmh_destroy.argtypes = [vp]
-    L.mmh_warm.argtypes = [vp]
-    L.mmh_reserve_stream.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int]
-    L.mmh_kernel_id.argtypes = [C.c_char_p]
-    L.mmh_kernel_has_op_forms.argtypes = [C.c_int]
-    L.mmh_set_kernel.argtypes = [vp, C.c_int]
-    L.mmh_get_kernel.argtypes = [vp, ip]
-    L.mmh_set_option.argtypes = [vp, C.c_int, C.c_int]
-    L.mmh_get_option.argtypes = [vp, C.c_int, ip]
-    L.mmh_kernel_name.argtypes = [C.c_int]
-    L.mmh_kernel_name.restype = C.c_char_p
-    gemm = [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp, C.c_int, vp, C.c_int]
-    L.mmh_sgemm.argtypes = gemm + [C.c_int, vp]
-    L.mmh_sgemm_op.argtypes = [vp, C.c_int, C.c_int] + gemm[1:] + [C.c_int, vp]
-    L.mmh_time_sgemm_op.argtypes = [vp, C.c_int, C.c_int] + gemm[1:] + [C.c_int, C.c_int, vp, fp]
-    L.mmh_auto_plan_op.argtypes = [C.c_int] * 10 + [ip, C.POINTER(C.c_long), ip]
-    L.mmh_auto_plan_ex.argtypes = L.mmh_auto_plan_op.argtypes
-    ex = [vp] + [C.c_int] * 5 + [C.c_float, vp, C.c_int, vp, C.c_int, C.c_float, vp, C.c_int, vp, C.c_int, C.c_int]
-    L.mmh_sgemm_ex.argtypes = ex + [vp]
-    L.mmh_time_sgemm_ex.argtypes = ex + [C.c_int, C.c_int, vp, fp]
-    ll = C.c_longlong
-    batched = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, ll, vp, C.c_int, ll, vp, C.c_int, ll, C.c_int]
-    L.mmh_sgemm_batched.argtypes = batched + [C.c_int, vp]
-    L.mmh_time_sgemm_batched.argtypes = batched + [C.c_int, C.c_int, vp, fp]
-    L.mmh_auto_plan_batched.argtypes = [C.c_int] * 8 + [ll] * 3 + [C.c_int] * 3 + [ip, ip, C.POINTER(C.c_long)]
-    # (handle, transa, transb, m, n, k, alpha, A, lda, strideA, B, ldb, strideB, beta, C, ldc, strideC, bias, strideBias, bias_mode, activation, batch)
-    batched_ex = [vp] + [C.c_int] * 5 + [C.c_float, vp, C.c_int, ll, vp, C.c_int, ll, C.c_float, vp, C.c_int, ll, vp, ll] + [C.c_int] * 3
-    L.mmh_sgemm_batched_ex.argtypes = batched_ex + [vp]
-    L.mmh_time_sgemm_batched_ex.argtypes = batched_ex + [C.c_int, C.c_int, vp, fp]
-    L.mmh_auto_plan_batched_ex.argtypes = [C.c_int] * 8 + [ll] * 4 + [C.c_int] * 4 + [ip, ip, C.POINTER(C.c_long)]
-    # (handle, rows, cols, G, ldg, Y, ldy, Z, ldz, colsum, accumulate)
-    relu_grad = [vp, C.c_int, C.c_int, vp, C.c_int, vp, C.c_int, vp, C.c_int, vp, C.c_int]
-    L.mmh_relu_grad_colsum.argtypes = relu_grad + [vp]
-    L.mmh_time_relu_grad_colsum.argtypes = relu_grad + [C.c_int, C.c_int, vp, fp]
-    L.mmh_sgemm_host.argtypes = gemm + [C.c_int]
-    L.mmh_sgemm_host_timed.argtypes = gemm + [C.c_int, C.POINTER(C.c_float)]
-    L.mmh_igemm_s8.argtypes = gemm + [C.c_int, vp]
-    L.mmh_sgemm_rocblas.argtypes = gemm + [vp]
-    L.mmh_sgemm_hipblaslt.argtypes = gemm + [vp]
-    L.mmh_qgemm_f32.argtypes = gemm + [vp]
-    L.mmh_quantize_sym_s8.argtypes = [vp, C.c_int, C.c_int, vp, C.c_int, vp, C.c_int, vp, vp]
-    L.mmh_shard_rows.argtypes = [C.c_int, C.c_int, C.c_int, ip, ip]
-    L.mmh_sgemm_sharded.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp, C.c_int,
-                                    vp, C.c_int, C.c_int, fp]
-    L.mmh_shard_create.argtypes = [C.POINTER(vp), C.c_int, ip]
-    L.mmh_shard_destroy.argtypes = [vp]
-    L.mmh_shard_set_kernel.argtypes = [vp, C.c_int]
-    L.mmh_shard_info.argtypes = [vp, ip, ip]
-    L.mmh_shard_sgemm.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp, C.c_int, vp, C.c_int, C.c_int, fp]
-    L.mmh_shard_sgemm_streamed.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, fp]
-    L.mmh_shard_chunks.argtypes = [C.c_int, C.c_int, ip]
-    L.mmh_shard_pin.argtypes = [vp, vp, C.c_size_t]
-    L.mmh_shard_unpin.argtypes = [vp, vp]
-    L.mmh_rccl_version.argtypes = [ip]
-    L.mmh_time_sgemm.argtypes = gemm + [C.c_int, C.c_int, vp, fp]
-    L.mmh_time_comparator.argtypes = [vp, C.c_int] + gemm[1:] + [C.c_int, C.c_int, vp, fp]
-    L.mmh_trace_sgemm.argtypes = gemm + [C.c_int, vp, fp]
-    L.mmh_probe_hbm_read.argtypes = [vp, C.c_size_t, fp]
-    L.mmh_probe_lds_read.argtypes = [vp, C.c_int, fp]
-    L.mmh_streamk_plan.argtypes = [C.c_long, C.c_int, C.c_int, ip, ip]
-    L.mmh_auto_plan.argtypes = [C.c_int] * 8 + [ip, C.POINTER(C.c_long), ip]
-    L.mmh_igemm_plan.argtypes = [C.c_int] * 13 + [C.c_char_p, C.c_int, C.POINTER(C.c_size_t)]
-    L.mmh_probe_mfma_f32.argtypes = [vp, fp]
-    L.mmh_probe_valu_f32.argtypes = [vp, C.c_int, C.c_int, fp]
-    L.mmh_probe_mfma_i8.argtypes = [vp, fp]
-    L.mmh_probe_mfma_i8_sustained.argtypes = [vp, C.c_int, C.c_float, fp]
-    L.mmh_probe_hbm_copy.argtypes = [vp, C.c_size_t, fp]
+    for name, (restype, argtypes) in _abi.PROTOTYPES.items():
+        fn = getattr(L, name)
+        fn.restype, fn.argtypes = restype, argtypes
     _lib = L
     return L
 
@@ -1005,7 +899,7 @@ class MMult:
 
     def time_comparator(self, which: str, m, n, k, dA, lda, dB, ldb, dC, ldc, warmup=1, reps=20, stream: int = 0) -> float:
         """time_sgemm for a vendor comparator ("rocblas" / "hipblaslt"): calls issued from C, one event pair."""
-        return self._time("mmh_time_comparator", {"rocblas": 1, "hipblaslt": 2}[which], m, n, k, dA, lda, dB, ldb, dC, ldc, warmup, reps,
+        return self._time("mmh_time_comparator", _abi.constants("MMH_COMPARATOR_")[which.upper()], m, n, k, dA, lda, dB, ldb, dC, ldc, warmup, reps,
                           stream)
 
     def trace_sgemm(self, m, n, k, dA, lda, dB, ldb, dC, ldc, count=400, stream: int = 0):
@@ -1142,7 +1036,6 @@ def sgemm_sharded(ngpus: int, a: np.ndarray, b: np.ndarray, kernel="mfma"):
 
 
 __all__ = ["MMult", "ShardedMMult", "MMultError", "lib", "use_ab_library", "device_count", "rccl_version", "shard_rows", "shard_chunks",
-           "kernel_name", "last_launch", "use_timeline_library", "streamk_plan", "auto_plan", "igemm_plan", "auto_plan_op", "auto_plan_ex", "auto_plan_batched", "auto_plan_batched_ex", "BIAS_NONE", "BIAS_COL", "BIAS_ROW", "ACT_NONE", "ACT_RELU", "BATCH_FORMS", "BATCHED_MAX_WORKGROUPS", "COLSUM_BLOCK_ROWS", "OP_N", "OP_T", "sgemm_sharded", "KERNELS", "CHAIN_KERNELS", "AB_LIB_PATH",
-           "OPT_SPLITK", "OPT_HOST_PANELS", "OPT_STREAMK_SPIN_LIMIT", "OPT_FAULT_INJECT", "OPT_STREAMK_ORDER", "OPT_DMA_EDGE", "OPT_STREAMK_DELEGATIONS", "OPT_RIM", "OPT_STREAMK_CHAIN", "OPT_PERSIST", "OPT_RIM5", "OPT_RETIRED_BUFFERS", "KERNEL_AUTO", "KERNEL_VALU", "KERNEL_MFMA", "KERNEL_MFMA_256", "KERNEL_NAIVE", "KERNEL_MFMA_SIMPLE", "KERNEL_MFMA_PIPE",
-           "EXPORTS", "LIB_PATH", "OPT_STREAMK", "OPT_STREAMK_TIMEOUTS", "OPT_IGEMM_MODE", "OK", "ERR_INVALID_ARG", "ERR_HIP", "ERR_NO_DEVICE",
-           "ERR_UNSUPPORTED", "ERR_ALLOC", "ERR_COMM"]
+           "kernel_name", "last_launch", "use_timeline_library", "streamk_plan", "auto_plan", "igemm_plan", "auto_plan_op", "auto_plan_ex",
+           "auto_plan_batched", "auto_plan_batched_ex", "sgemm_sharded", "BATCH_FORMS", "KERNELS", "CHAIN_KERNELS", "EXPORTS", "LIB_PATH",
+           "AB_LIB_PATH", *_CONSTANTS]

@@ -40,6 +40,45 @@ int time_calls(mmh_context *h, void *stream, int warmup, int reps, float *ms_per
   return check_sticky(h);
 }
 
+// The GEMM calls' C parameters as call_on takes them (policy.hip): the one place per call kind where a parameter meets its
+// GemmArgs / BatchArgs field -- pack_X takes mmh_sgemm_X's parameters between the handle and the stream, in their order, and
+// mmh_sgemm_X and mmh_time_sgemm_X (accumulate = 0) both go through it.  The stream is set where the call is made.
+struct PackedCall {
+  Call call;
+  GemmArgs g;
+  BatchArgs b = {};
+};
+PackedCall pack_op(int transa, int transb, int m, int n, int k, const float *dA, int lda, const float *dB, int ldb, float *dC, int ldc,
+                   int accumulate) {
+  return {Call::Op, op_args(transa, transb, m, n, k, dA, lda, dB, ldb, dC, ldc, accumulate, nullptr)};
+}
+PackedCall pack_ex(int transa, int transb, int m, int n, int k, float alpha, const float *dA, int lda, const float *dB, int ldb,
+                   float beta, float *dC, int ldc, const float *dBias, int bias_mode, int activation) {
+  return {Call::Ex, ex_args_of(pack_op(transa, transb, m, n, k, dA, lda, dB, ldb, dC, ldc, 0).g, alpha, beta, dBias, bias_mode, activation)};
+}
+PackedCall pack_batched(int transa, int transb, int m, int n, int k, const float *dA, int lda, long long strideA, const float *dB,
+                        int ldb, long long strideB, float *dC, int ldc, long long strideC, int batch, int accumulate) {
+  return {Call::Batched, pack_op(transa, transb, m, n, k, dA, lda, dB, ldb, dC, ldc, accumulate).g, {strideA, strideB, strideC, batch}};
+}
+PackedCall pack_batched_ex(int transa, int transb, int m, int n, int k, float alpha, const float *dA, int lda, long long strideA,
+                           const float *dB, int ldb, long long strideB, float beta, float *dC, int ldc, long long strideC,
+                           const float *dBias, long long strideBias, int bias_mode, int activation, int batch) {
+  return {Call::BatchedEx, pack_ex(transa, transb, m, n, k, alpha, dA, lda, dB, ldb, beta, dC, ldc, dBias, bias_mode, activation).g,
+          {strideA, strideB, strideC, batch, strideBias}};
+}
+int run_call(mmh_context *h, PackedCall c, void *stream) {
+  if (!h) return MMH_ERR_INVALID_ARG;
+  ENTER(h);
+  c.g.s = static_cast<hipStream_t>(stream);
+  return call_on(h, c.call, h->kernel, c.g, c.b);
+}
+int time_call(mmh_context *h, PackedCall c, int warmup, int reps, void *stream, float *ms_per_call, const char *what) {
+  return time_calls(h, stream, warmup, reps, ms_per_call, what, [&](hipStream_t s) {
+    c.g.s = s;
+    return call_on(h, c.call, h->kernel, c.g, c.b);
+  });
+}
+
 // The catalogue (internal.hpp, KernelRow): every id this build accepts.  A new kernel id is one row here -- name, the family
 // whose launcher takes it, the register-staged tile that takes the shapes the family refuses -- plus its tile's row in
 // internal.hpp's tile table and its number in mmult_hip.h.
@@ -346,35 +385,25 @@ int mmh_sgemm(mmh_handle_t h, int m, int n, int k, const float *dA, int lda, con
 }
 int mmh_sgemm_op(mmh_handle_t h, int transa, int transb, int m, int n, int k, const float *dA, int lda, const float *dB,
                  int ldb, float *dC, int ldc, int accumulate, void *stream) {
-  if (!h) return MMH_ERR_INVALID_ARG;
-  ENTER(h);
-  return sgemm_op_on(h, h->kernel, transa, transb, m, n, k, dA, lda, dB, ldb, dC, ldc, accumulate,
-                     static_cast<hipStream_t>(stream));
+  return run_call(h, pack_op(transa, transb, m, n, k, dA, lda, dB, ldb, dC, ldc, accumulate), stream);
 }
 int mmh_sgemm_ex(mmh_handle_t h, int transa, int transb, int m, int n, int k, float alpha, const float *dA, int lda,
                  const float *dB, int ldb, float beta, float *dC, int ldc, const float *dBias, int bias_mode, int activation,
                  void *stream) {
-  if (!h) return MMH_ERR_INVALID_ARG;
-  ENTER(h);
-  return sgemm_ex_on(h, h->kernel, transa, transb, m, n, k, alpha, dA, lda, dB, ldb, beta, dC, ldc, dBias, bias_mode, activation,
-                     static_cast<hipStream_t>(stream));
+  return run_call(h, pack_ex(transa, transb, m, n, k, alpha, dA, lda, dB, ldb, beta, dC, ldc, dBias, bias_mode, activation), stream);
 }
 int mmh_sgemm_batched(mmh_handle_t h, int transa, int transb, int m, int n, int k, const float *dA, int lda, long long strideA,
                       const float *dB, int ldb, long long strideB, float *dC, int ldc, long long strideC, int batch, int accumulate,
                       void *stream) {
-  if (!h) return MMH_ERR_INVALID_ARG;
-  ENTER(h);
-  return sgemm_batched_on(h, h->kernel, transa, transb, m, n, k, dA, lda, strideA, dB, ldb, strideB, dC, ldc, strideC, batch,
-                          accumulate, static_cast<hipStream_t>(stream));
+  return run_call(h, pack_batched(transa, transb, m, n, k, dA, lda, strideA, dB, ldb, strideB, dC, ldc, strideC, batch, accumulate),
+                  stream);
 }
 int mmh_sgemm_batched_ex(mmh_handle_t h, int transa, int transb, int m, int n, int k, float alpha, const float *dA, int lda,
                          long long strideA, const float *dB, int ldb, long long strideB, float beta, float *dC, int ldc,
                          long long strideC, const float *dBias, long long strideBias, int bias_mode, int activation, int batch,
                          void *stream) {
-  if (!h) return MMH_ERR_INVALID_ARG;
-  ENTER(h);
-  return sgemm_batched_ex_on(h, h->kernel, transa, transb, m, n, k, alpha, dA, lda, strideA, dB, ldb, strideB, beta, dC, ldc, strideC,
-                             dBias, strideBias, bias_mode, activation, batch, static_cast<hipStream_t>(stream));
+  return run_call(h, pack_batched_ex(transa, transb, m, n, k, alpha, dA, lda, strideA, dB, ldb, strideB, beta, dC, ldc, strideC, dBias,
+                                     strideBias, bias_mode, activation, batch), stream);
 }
 int mmh_time_sgemm(mmh_handle_t h, int m, int n, int k, const float *dA, int lda, const float *dB,
                    int ldb, float *dC, int ldc, int warmup, int reps, void *stream,
@@ -383,16 +412,14 @@ int mmh_time_sgemm(mmh_handle_t h, int m, int n, int k, const float *dA, int lda
 }
 int mmh_time_sgemm_op(mmh_handle_t h, int transa, int transb, int m, int n, int k, const float *dA, int lda, const float *dB,
                       int ldb, float *dC, int ldc, int warmup, int reps, void *stream, float *ms_per_call) {
-  return time_calls(h, stream, warmup, reps, ms_per_call, "mmh_time_sgemm_op", [&](hipStream_t s) {
-    return sgemm_op_on(h, h->kernel, transa, transb, m, n, k, dA, lda, dB, ldb, dC, ldc, 0, s);
-  });
+  return time_call(h, pack_op(transa, transb, m, n, k, dA, lda, dB, ldb, dC, ldc, 0), warmup, reps, stream, ms_per_call,
+                   "mmh_time_sgemm_op");
 }
 int mmh_time_sgemm_ex(mmh_handle_t h, int transa, int transb, int m, int n, int k, float alpha, const float *dA, int lda,
                       const float *dB, int ldb, float beta, float *dC, int ldc, const float *dBias, int bias_mode, int activation,
                       int warmup, int reps, void *stream, float *ms_per_call) {
-  return time_calls(h, stream, warmup, reps, ms_per_call, "mmh_time_sgemm_ex", [&](hipStream_t s) {
-    return sgemm_ex_on(h, h->kernel, transa, transb, m, n, k, alpha, dA, lda, dB, ldb, beta, dC, ldc, dBias, bias_mode, activation, s);
-  });
+  return time_call(h, pack_ex(transa, transb, m, n, k, alpha, dA, lda, dB, ldb, beta, dC, ldc, dBias, bias_mode, activation), warmup,
+                   reps, stream, ms_per_call, "mmh_time_sgemm_ex");
 }
 int mmh_time_relu_grad_colsum(mmh_handle_t h, int rows, int cols, const float *dG, int ldg, const float *dY, int ldy, float *dZ, int ldz,
                               float *dColsum, int accumulate, int warmup, int reps, void *stream, float *ms_per_call) {
@@ -403,18 +430,16 @@ int mmh_time_relu_grad_colsum(mmh_handle_t h, int rows, int cols, const float *d
 int mmh_time_sgemm_batched(mmh_handle_t h, int transa, int transb, int m, int n, int k, const float *dA, int lda,
                            long long strideA, const float *dB, int ldb, long long strideB, float *dC, int ldc, long long strideC,
                            int batch, int warmup, int reps, void *stream, float *ms_per_call) {
-  return time_calls(h, stream, warmup, reps, ms_per_call, "mmh_time_sgemm_batched", [&](hipStream_t s) {
-    return sgemm_batched_on(h, h->kernel, transa, transb, m, n, k, dA, lda, strideA, dB, ldb, strideB, dC, ldc, strideC, batch, 0, s);
-  });
+  return time_call(h, pack_batched(transa, transb, m, n, k, dA, lda, strideA, dB, ldb, strideB, dC, ldc, strideC, batch, 0), warmup,
+                   reps, stream, ms_per_call, "mmh_time_sgemm_batched");
 }
 int mmh_time_sgemm_batched_ex(mmh_handle_t h, int transa, int transb, int m, int n, int k, float alpha, const float *dA, int lda,
                               long long strideA, const float *dB, int ldb, long long strideB, float beta, float *dC, int ldc,
                               long long strideC, const float *dBias, long long strideBias, int bias_mode, int activation,
                               int batch, int warmup, int reps, void *stream, float *ms_per_call) {
-  return time_calls(h, stream, warmup, reps, ms_per_call, "mmh_time_sgemm_batched_ex", [&](hipStream_t s) {
-    return sgemm_batched_ex_on(h, h->kernel, transa, transb, m, n, k, alpha, dA, lda, strideA, dB, ldb, strideB, beta, dC, ldc, strideC,
-                               dBias, strideBias, bias_mode, activation, batch, s);
-  });
+  return time_call(h, pack_batched_ex(transa, transb, m, n, k, alpha, dA, lda, strideA, dB, ldb, strideB, beta, dC, ldc, strideC,
+                                      dBias, strideBias, bias_mode, activation, batch), warmup, reps, stream, ms_per_call,
+                   "mmh_time_sgemm_batched_ex");
 }
 
 // per-launch durations of `count` back-to-back calls (one event pair each): the clock-ramp trace

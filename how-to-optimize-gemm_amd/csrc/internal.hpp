@@ -5,7 +5,7 @@
 // kernels of this directory.  Translation units (build.py compiles them in parallel):
 //   state.hip        handle life cycle, sticky error, stream-K workspaces and phase tables, mmh_warm
 //   policy.hip       sgemm_on(): MMH_KERNEL_AUTO's tile choice -- the reference's `NEW := MMult_xxx`
-//                    makefile switch (cuda/makefile:1-3) made a run-time choice; the op / ex / batched calls' one front end;
+//                    makefile switch (cuda/makefile:1-3) made a run-time choice; call_on(): the op / ex / batched calls' one front end;
 //                    the plans behind mmh_auto_plan* (plan_batched: both batched ones).  Pure host code.
 //   launch_reg.hip   register-staged MFMA tiles (sgemm_mfma.hpp): plain, stream-K, split-K
 //   launch_dma.hip   LDS-DMA tiles (sgemm_dma.hpp): plain, stream-K; whole and guarded shapes
@@ -22,7 +22,8 @@
 //   relu_grad.hip    mmh_relu_grad_colsum: the linear layer's backward beside its GEMMs (ReLU gate, bias gradient)
 //   vendor.hip       rocBLAS / hipBLASLt comparators, RCCL loader
 //   probes.hip       peak probes
-//   abi.hip          the remaining extern "C" entry points; the catalogue of kernel ids; the table of handle options
+//   abi.hip          the remaining extern "C" entry points -- the GEMM calls' C parameters become a GemmArgs / BatchArgs there,
+//                    once per call kind, for the call and its timing twin --; the catalogue of kernel ids; the table of handle options
 // No torch, no CPU fallback: without a gfx950 device every compute entry point returns
 // MMH_ERR_NO_DEVICE / MMH_ERR_HIP.
 #pragma once
@@ -111,6 +112,26 @@ struct GemmArgs {
   const float *bias = nullptr;
   int bias_mode = MMH_BIAS_NONE, act = MMH_ACT_NONE;
 };
+// A call's operands with their stored layouts (mmh_sgemm_op: ta / tb as they came, checked by call_on) ...
+inline GemmArgs op_args(int ta, int tb, int m, int n, int k, const float *dA, int lda, const float *dB, int ldb, float *dC, int ldc,
+                        int accumulate, hipStream_t s) {
+  GemmArgs g{m, n, k, dA, lda, dB, ldb, dC, ldc, accumulate ? 1 : 0, s};
+  g.ta = ta;
+  g.tb = tb;
+  return g;
+}
+// ... and the fused epilogue of an `ex` call on them: C = act(alpha op(A) op(B) + beta C + bias); acc is 0 -- the chain starts at
+// +0, beta C is the epilogue's
+inline GemmArgs ex_args_of(GemmArgs g, float alpha, float beta, const float *dBias, int bias_mode, int activation) {
+  g.acc = 0;
+  g.ex = 1;
+  g.alpha = alpha;
+  g.beta = beta;
+  g.bias = dBias;
+  g.bias_mode = bias_mode;
+  g.act = activation;
+  return g;
+}
 
 }  // namespace mmh
 
@@ -272,15 +293,8 @@ int auto_plan(int m, int n, int k, int lda, int ldb, int ldc, int base_align, in
               int *streamk_grid);   // policy.hip: mmh_auto_plan
 int sgemm_on(mmh_context *ctx, int kernel, int m, int n, int k, const float *dA, int lda, const float *dB, int ldb,
              float *dC, int ldc, int accumulate, hipStream_t s);
-// mmh_sgemm_op: C = op(A) op(B) (+ C); ta = tb = 0 is sgemm_on
-int sgemm_op_on(mmh_context *ctx, int kernel, int ta, int tb, int m, int n, int k, const float *dA, int lda, const float *dB,
-                int ldb, float *dC, int ldc, int accumulate, hipStream_t s);
 int auto_plan_op(int ta, int tb, int m, int n, int k, int lda, int ldb, int ldc, int base_align, int cu_count, int *kernel,
                  long *tiles, int *streamk_grid, int ex = 0);   // mmh_auto_plan_op; ex: mmh_auto_plan_ex
-// mmh_sgemm_ex: C = act(alpha op(A) op(B) + beta C + bias)
-int sgemm_ex_on(mmh_context *ctx, int kernel, int ta, int tb, int m, int n, int k, float alpha, const float *dA, int lda,
-                const float *dB, int ldb, float beta, float *dC, int ldc, const float *dBias, int bias_mode, int activation,
-                hipStream_t s);
 // launch_reg.hip: `kernel` is one of the register-staged ids (MFMA, MFMA_TILES, MFMA_256, MFMA_256X256, MFMA_128X64,
 // MFMA_64X64, MFMA_SIMPLE, MFMA_PIPE, the split-K ids and, in the A/B build, the ablation ids)
 int launch_reg(mmh_context *ctx, int kernel, const GemmArgs &g);
@@ -440,14 +454,11 @@ int warm_dma5_batched();   // LDS opt-ins only (nothing is launched)
 int launch_dma5_batched_ex(mmh_context *ctx, int kernel, const GemmArgs &g, const BatchArgs &b);   // 1: the matrices do not qualify
 int launch_naive_batched_ex(const GemmArgs &g, const BatchArgs &b);
 int warm_dma5_batched_ex();   // LDS opt-ins only
-// policy.hip: mmh_sgemm_batched and mmh_sgemm_batched_ex (the same with the fused epilogue: g.ex, b.sBias) ...
-int sgemm_batched_on(mmh_context *ctx, int kernel, int ta, int tb, int m, int n, int k, const float *dA, int lda, long long sA,
-                     const float *dB, int ldb, long long sB, float *dC, int ldc, long long sC, int batch, int accumulate,
-                     hipStream_t s);
-int sgemm_batched_ex_on(mmh_context *ctx, int kernel, int ta, int tb, int m, int n, int k, float alpha, const float *dA, int lda,
-                        long long sA, const float *dB, int ldb, long long sB, float beta, float *dC, int ldc, long long sC,
-                        const float *dBias, long long sBias, int bias_mode, int activation, int batch, hipStream_t s);
-// ... and the plan of both: mmh_auto_plan_batched (ex = 0, MMH_BIAS_NONE, sBias = 0) and mmh_auto_plan_batched_ex (ex = 1)
+// policy.hip: the one front end of mmh_sgemm_op, _ex, _batched and _batched_ex.  g: the call's arguments as they came (op_args /
+// ex_args_of: ta / tb, bias and its mode unchecked; acc 0 / 1), b: a batched call's; (Op, N, N) is sgemm_on
+enum class Call { Op, Ex, Batched, BatchedEx };
+int call_on(mmh_context *ctx, Call call, int kernel, GemmArgs g, const BatchArgs &b = BatchArgs{});
+// ... and the plan of both batched calls: mmh_auto_plan_batched (ex = 0, MMH_BIAS_NONE, sBias = 0) and mmh_auto_plan_batched_ex (ex = 1)
 int plan_batched(int ta, int tb, int m, int n, int k, int lda, int ldb, int ldc, long long sA, long long sB, long long sC,
                  long long sBias, int bias_mode, int ex, int batch, int base_align, int cu_count, int *kernel, int *form,
                  long *workgroups);

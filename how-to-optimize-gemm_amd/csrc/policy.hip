@@ -1,6 +1,6 @@
 // policy.hip -- sgemm_on(): argument checks, the empty contraction, and MMH_KERNEL_AUTO's tile choice (the
 // reference's `NEW := MMult_xxx` makefile switch, cuda/makefile:1-3, as a run-time decision); call_on(): the same for
-// mmh_sgemm_op / _ex / _batched / _batched_ex, one front end behind op_args / ex_args_of, which fill a call's GemmArgs; the plan
+// mmh_sgemm_op / _ex / _batched / _batched_ex, one front end on the GemmArgs / BatchArgs the entry points pack (abi.hip); the plan
 // entry points (plan_batched: both batched ones).  Pure host code; the kernels are launched by the launch_*.hip units.
 #include <algorithm>
 
@@ -283,27 +283,6 @@ BatchPlan batched_plan_for(const mmh_context *ctx, const GemmArgs &g, const Batc
   return bp;
 }
 
-// A call's operands with their stored layouts (mmh_sgemm_op: ta / tb as they came, checked by op_flags_ok) ...
-GemmArgs op_args(int ta, int tb, int m, int n, int k, const float *dA, int lda, const float *dB, int ldb, float *dC, int ldc,
-                 int accumulate, hipStream_t s) {
-  GemmArgs g{m, n, k, dA, lda, dB, ldb, dC, ldc, accumulate ? 1 : 0, s};
-  g.ta = ta;
-  g.tb = tb;
-  return g;
-}
-// ... and the fused epilogue of an `ex` call on them: C = act(alpha op(A) op(B) + beta C + bias); acc is 0 -- the chain starts at
-// +0, beta C is the epilogue's
-GemmArgs ex_args_of(GemmArgs g, float alpha, float beta, const float *dBias, int bias_mode, int activation) {
-  g.acc = 0;
-  g.ex = 1;
-  g.alpha = alpha;
-  g.beta = beta;
-  g.bias = dBias;
-  g.bias_mode = bias_mode;
-  g.act = activation;
-  return g;
-}
-
 bool op_flags_ok(int ta, int tb) { return (ta == MMH_OP_N || ta == MMH_OP_T) && (tb == MMH_OP_N || tb == MMH_OP_T); }
 
 // the argument rules of mmh_sgemm_batched that need no pointer (mmh_auto_plan_batched shares them)
@@ -334,7 +313,6 @@ int plan_inputs(int ta, int tb, int m, int n, int k, int lda, int ldb, int ldc, 
 // anything is launched.  Split-K and MMH_OPT_STREAMK_CHAIN = 0 are NN A/B switches: these forms run the chained stream-K
 // kernels, which keep the bits.  What differs between them: their own argument rules, the empty contraction, the naive
 // kernel, AUTO's plan, the launcher -- and the subject of the two refusals.
-enum class Call { Op, Ex, Batched, BatchedEx };
 struct CallText {
   const char *run, *need, *what, *why;
 };
@@ -361,7 +339,6 @@ int tile_call(Call call, mmh_context *ctx, int kernel, const GemmArgs &g, const 
     default: return launch_dma5_op(ctx, kernel, g);
   }
 }
-int call_on(mmh_context *ctx, Call call, int kernel, GemmArgs g, const BatchArgs &b = BatchArgs{});
 // one GEMM of a batched call's fold or loop form: m rows at A, C (and bias), as the unbatched call of the same kind runs it
 int one_gemm(mmh_context *ctx, GemmArgs g, int m, const float *A, const float *B, float *C, const float *bias) {
   g.m = m;
@@ -371,6 +348,7 @@ int one_gemm(mmh_context *ctx, GemmArgs g, int m, const float *A, const float *B
   g.bias = bias;
   return call_on(ctx, g.ex ? Call::Ex : Call::Op, MMH_KERNEL_AUTO, g);
 }
+}  // namespace
 
 // g: the call's arguments as they came (ta / tb, bias and its mode unchecked; acc 0 / 1); b: a batched call's
 int call_on(mmh_context *ctx, Call call, int kernel, GemmArgs g, const BatchArgs &b) {
@@ -446,38 +424,6 @@ int call_on(mmh_context *ctx, Call call, int kernel, GemmArgs g, const BatchArgs
                  "MMH_OPT_DMA_EDGE keeps this shape off them" + text.why);
   return MMH_ERR_UNSUPPORTED;
 }
-}  // namespace
-
-int sgemm_op_on(mmh_context *ctx, int kernel, int ta, int tb, int m, int n, int k, const float *dA, int lda, const float *dB,
-                int ldb, float *dC, int ldc, int accumulate, hipStream_t s) {
-  return call_on(ctx, Call::Op, kernel, op_args(ta, tb, m, n, k, dA, lda, dB, ldb, dC, ldc, accumulate, s));
-}
-
-// mmh_sgemm_ex: C = act(alpha op(A) op(B) + beta C + bias)
-int sgemm_ex_on(mmh_context *ctx, int kernel, int ta, int tb, int m, int n, int k, float alpha, const float *dA, int lda,
-                const float *dB, int ldb, float beta, float *dC, int ldc, const float *dBias, int bias_mode, int activation,
-                hipStream_t s) {
-  return call_on(ctx, Call::Ex, kernel,
-                 ex_args_of(op_args(ta, tb, m, n, k, dA, lda, dB, ldb, dC, ldc, 0, s), alpha, beta, dBias, bias_mode, activation));
-}
-
-// mmh_sgemm_batched (AUTO: batched_plan_for; 29 / 30 / 31: one launch on that tile; MMH_KERNEL_NAIVE: the naive batched kernel)
-int sgemm_batched_on(mmh_context *ctx, int kernel, int ta, int tb, int m, int n, int k, const float *dA, int lda, long long sA,
-                     const float *dB, int ldb, long long sB, float *dC, int ldc, long long sC, int batch, int accumulate,
-                     hipStream_t s) {
-  return call_on(ctx, Call::Batched, kernel, op_args(ta, tb, m, n, k, dA, lda, dB, ldb, dC, ldc, accumulate, s),
-                 BatchArgs{sA, sB, sC, batch});
-}
-
-// mmh_sgemm_batched_ex: C_i = act(alpha op(A_i) op(B_i) + beta C_i + bias_i)
-int sgemm_batched_ex_on(mmh_context *ctx, int kernel, int ta, int tb, int m, int n, int k, float alpha, const float *dA, int lda,
-                        long long sA, const float *dB, int ldb, long long sB, float beta, float *dC, int ldc, long long sC,
-                        const float *dBias, long long sBias, int bias_mode, int activation, int batch, hipStream_t s) {
-  return call_on(ctx, Call::BatchedEx, kernel,
-                 ex_args_of(op_args(ta, tb, m, n, k, dA, lda, dB, ldb, dC, ldc, 0, s), alpha, beta, dBias, bias_mode, activation),
-                 BatchArgs{sA, sB, sC, batch, sBias});
-}
-
 // mmh_auto_plan_batched (ex = 0, no bias) and mmh_auto_plan_batched_ex: batched_plan_for on a default handle, as host arithmetic
 int plan_batched(int ta, int tb, int m, int n, int k, int lda, int ldb, int ldc, long long sA, long long sB, long long sC,
                  long long sBias, int bias_mode, int ex, int batch, int base_align, int cu_count, int *kernel, int *form,

@@ -9,6 +9,7 @@ import re
 import pytest
 
 import how_to_optimize_gemm_amd as H
+from how_to_optimize_gemm_amd import abi_header
 from conftest import REPO
 
 
@@ -25,6 +26,71 @@ def test_library_exports_every_declared_symbol():
     for s in syms:
         assert hasattr(L, s), f"{s} declared in include/mmult_hip.h but not exported"
     assert set(syms) == set(H.EXPORTS)
+
+
+def header_text():
+    return re.sub(r"/\*.*?\*/", "", open(os.path.join(REPO, "include", "mmult_hip.h")).read(), flags=re.S)
+
+
+# What the binding must be, written by hand from the header: between them these prototypes use every type spelling it has.
+_I, _L, _LL, _F, _Z, _S, _P = (ctypes.c_int, ctypes.c_long, ctypes.c_longlong, ctypes.c_float, ctypes.c_size_t, ctypes.c_char_p,
+                               ctypes.c_void_p)
+SIGNATURES = {
+    # (handle, transa, transb, m, n, k, alpha, A, lda, strideA, B, ldb, strideB, beta, C, ldc, strideC, bias, strideBias, bias_mode,
+    #  activation, batch, stream)
+    "mmh_sgemm_batched_ex": (_I, [_P, _I, _I, _I, _I, _I, _F, _P, _I, _LL, _P, _I, _LL, _F, _P, _I, _LL, _P, _LL, _I, _I, _I, _P]),
+    "mmh_igemm_plan": (_I, [_I] * 13 + [_S, _I, _P]),                       # char *text, size_t *scratch_bytes
+    "mmh_streamk_plan": (_I, [_L, _I, _I, _P, _P]),                         # long tiles
+    "mmh_auto_plan": (_I, [_I] * 8 + [_P, _P, _P]),                         # long *tiles
+    "mmh_probe_hbm_read": (_I, [_P, _Z, _P]),                               # size_t bytes, float *gbps
+    "mmh_kernel_name": (_S, [_I]),                                          # returns const char *
+    "mmh_kernel_id": (_I, [_S]),                                            # const char *short_name
+    "mmh_device_info": (_I, [_I, _S, _P, _P]),
+    "mmh_create": (_I, [_P, _I]),                                           # mmh_handle_t *
+    "mmh_shard_create": (_I, [_P, _I, _P]),                                 # mmh_shard_t *, const int *
+    "mmh_shard_pin": (_I, [_P, _P, _Z]),                                    # mmh_shard_t, void *
+    "mmh_igemm_s8": (_I, [_P, _I, _I, _I, _P, _I, _P, _I, _P, _I, _I, _P]),   # const int8_t *, int32_t *
+    "mmh_quantize_sym_s8": (_I, [_P, _I, _I, _P, _I, _P, _I, _P, _P]),      # int8_t *
+}
+
+
+def test_the_parsed_prototypes_match_a_hand_written_table():
+    for name, want in SIGNATURES.items():
+        assert abi_header.PROTOTYPES[name] == want, name
+    assert abi_header.ctype_of("long") is ctypes.c_long and abi_header.ctype_of("long long") is ctypes.c_longlong
+
+
+def test_no_prototype_and_no_constant_of_the_header_is_skipped():
+    text = header_text()
+    assert list(abi_header.PROTOTYPES) == H.EXPORTS and sorted(H.EXPORTS) == declared_symbols()
+    assert len(abi_header.PROTOTYPES) == len(declared_symbols()) >= 65
+    defines = re.findall(r"^[ \t]*#define[ \t]+(MMH_\w+)[ \t]+\S", text, flags=re.M)
+    assert sorted(abi_header.CONSTANTS) == sorted(defines) and len(defines) == len(set(defines))
+    assert H.ERR_COMM == -6 and H.BATCHED_MAX_WORKGROUPS == 4194304 and H.OPT_RETIRED_BUFFERS == 15
+    assert H.BATCH_FORMS == {1: "fold", 2: "one_launch", 3: "loop"}
+
+
+def test_what_the_parser_does_not_know_raises_and_names_the_place():
+    with pytest.raises(abi_header.HeaderError, match=r":2: #define MMH_NEW \(1 \+ 2\)"):
+        abi_header.parse_constants("\n#define MMH_NEW (1 + 2)\n")
+    with pytest.raises(abi_header.HeaderError, match="unbalanced"):
+        abi_header.parse_constants("#define MMH_NEW (1L << 3\n")
+    with pytest.raises(abi_header.HeaderError, match="mmh_new: unknown type 'unsigned'"):
+        abi_header.parse_prototypes("int mmh_new(mmh_handle_t handle, unsigned flags);")
+    with pytest.raises(abi_header.HeaderError, match="mmh_new: unknown type 'double'"):
+        abi_header.parse_prototypes("double mmh_new(void);")
+    with pytest.raises(abi_header.HeaderError, match="mmh_new: unnamed"):
+        abi_header.parse_prototypes("int mmh_new(int, long long);")
+    with pytest.raises(abi_header.HeaderError, match="not a prototype"):
+        abi_header.parse_prototypes("struct mmh_thing { int x; };")
+
+
+def test_every_export_of_the_loaded_library_is_bound_to_its_prototype():
+    L = H.lib()
+    for name in H.EXPORTS:
+        restype, argtypes = abi_header.PROTOTYPES[name]
+        fn = getattr(L, name)
+        assert fn.restype is restype and len(fn.argtypes) == len(argtypes) and list(fn.argtypes) == argtypes, name
 
 
 def test_library_is_in_tree_and_has_gfx950_code_object():
@@ -94,11 +160,10 @@ def test_options_and_kernel_ids_validate_without_a_device():
     assert L.mmh_get_option(None, H.OPT_STREAMK, ctypes.byref(v)) == H.ERR_INVALID_ARG
     for name, kid in H.KERNELS.items():
         assert H.kernel_name(kid) is not None, name
-    # the header's kernel ids and the Python mirror agree
-    text = open(os.path.join(REPO, "include", "mmult_hip.h")).read()
-    ids = {m.group(1).lower(): int(m.group(2)) for m in re.finditer(r"#define MMH_KERNEL_(\w+) (\d+)", text)}
-    for name, kid in ids.items():
-        assert H.KERNELS[{"mfma_256": "mfma256"}.get(name, name)] == kid, name
+    # the header's kernel ids (H.KERNELS is read from it) and the library's own catalogue agree, names included
+    for name, kid in H.KERNELS.items():
+        assert L.mmh_kernel_id(name.encode()) == kid, name
+        assert L.mmh_kernel_name(kid) == b"MMult_hip_" + name.encode(), name
 
 
 def test_rccl_is_loadable_and_every_entry_point_the_shard_needs_resolves():
