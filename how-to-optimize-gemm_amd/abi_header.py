@@ -2,7 +2,7 @@
 definitions to it, and api.py binds from what is parsed here, so no constant, export name or argument list is kept by hand.
   CONSTANTS   {"MMH_ERR_COMM": -6, ...}: every `#define MMH_<NAME> <integer expression>`, in header order
   PROTOTYPES  {"mmh_sgemm": (restype, [argtypes]), ...}: every mmh_* prototype as ctypes types, in header order
-Parsed once at import; pure Python (ctypes for its type objects only: no library is loaded, no torch).  What the parser does
+parse(path) reads any header of the same grammar (include/mmult_hip_q8.h: q8.py).  Parsed once at import; pure Python (ctypes for its type objects only: no library is loaded, no torch).  What the parser does
 not know -- an operator in a constant, a type spelling in a prototype -- raises here, on the CPU, and names the place.
 """
 from __future__ import annotations
@@ -58,7 +58,7 @@ def eval_int(expr: str) -> int:
     return v
 
 
-def parse_constants(text: str) -> dict:
+def parse_constants(text: str, where: str = HEADER) -> dict:
     out = {}
     for no, line in enumerate(text.splitlines(), 1):
         m = re.match(r"\s*#\s*define\s+(MMH_\w+)\s+(\S.*)$", line)
@@ -66,12 +66,13 @@ def parse_constants(text: str) -> dict:
             try:
                 out[m.group(1)] = eval_int(m.group(2))
             except HeaderError as e:
-                raise HeaderError(f"{HEADER}:{no}: #define {m.group(1)} {m.group(2).strip()}: {e}") from None
+                raise HeaderError(f"{where}:{no}: #define {m.group(1)} {m.group(2).strip()}: {e}") from None
     return out
 
 
 _SCALARS = {"int": C.c_int, "long": C.c_long, "long long": C.c_longlong, "float": C.c_float, "size_t": C.c_size_t}
-_POINTEES = {"void", "int", "long", "float", "size_t", "int8_t", "int32_t", "mmh_handle_t", "mmh_shard_t"}
+_POINTEES = {"void", "int", "long", "float", "size_t", "int8_t", "int32_t"}
+_HANDLE = re.compile(r"mmh_\w+_t")   # an opaque handle type: mmh_handle_t, mmh_shard_t, mmh_q8_weight_t
 
 
 def ctype_of(spelling: str):
@@ -83,12 +84,14 @@ def ctype_of(spelling: str):
     words = spelling.split()
     if words[:1] == ["const"]:
         words = words[1:]
-    if spelling in ("mmh_handle_t", "mmh_shard_t") or (len(words) == 2 and words[0] in _POINTEES and words[1] == "*"):
+    # a handle, or one or two levels of pointer to a handle or a known pointee (const float **: where a pointer is returned)
+    if _HANDLE.fullmatch(spelling) or (len(words) in (2, 3) and (words[0] in _POINTEES or _HANDLE.fullmatch(words[0]))
+                                       and set(words[1:]) == {"*"}):
         return C.c_void_p
     raise HeaderError(f"unknown type {spelling!r}")
 
 
-def parse_prototypes(text: str) -> dict:
+def parse_prototypes(text: str, where: str = HEADER) -> dict:
     text = re.sub(r"^\s*#.*$", "", text, flags=re.M)                  # preprocessor lines
     text = re.sub(r'extern\s+"C"\s*\{|^\s*\}\s*$', "", text, flags=re.M)
     out = {}
@@ -98,7 +101,7 @@ def parse_prototypes(text: str) -> dict:
             continue
         m = re.fullmatch(r"(.+?)\b(mmh_\w+) ?\((.*)\)", stmt)
         if not m:
-            raise HeaderError(f"{HEADER}: not a prototype: {stmt!r}")
+            raise HeaderError(f"{where}: not a prototype: {stmt!r}")
         ret, name, params = m.groups()
         try:
             argtypes = []
@@ -109,14 +112,18 @@ def parse_prototypes(text: str) -> dict:
                 argtypes.append(ctype_of(" ".join(re.findall(r"\w+|\*", pm.group(1)))))
             out[name] = (ctype_of(" ".join(re.findall(r"\w+|\*", ret))), argtypes)
         except HeaderError as e:
-            raise HeaderError(f"{HEADER}: {name}: {e}") from None
+            raise HeaderError(f"{where}: {name}: {e}") from None
     return out
 
 
-with open(HEADER) as _f:
-    _text = strip_comments(_f.read())
-CONSTANTS = parse_constants(_text)
-PROTOTYPES = parse_prototypes(_text)
+def parse(path: str):
+    """(CONSTANTS, PROTOTYPES) of the header at `path`: its own #defines and prototypes (an #include is not followed)."""
+    with open(path) as f:
+        text = strip_comments(f.read())
+    return parse_constants(text, path), parse_prototypes(text, path)
+
+
+CONSTANTS, PROTOTYPES = parse(HEADER)
 
 
 def constants(prefix: str) -> dict:

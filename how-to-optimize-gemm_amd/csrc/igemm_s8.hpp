@@ -110,11 +110,19 @@ struct LdsDma {
 // bytes, pieces 2j and 2j+1 form row j of an 8 x 16 byte block, lane i receives column i).  The
 // MFMA operands are swapped (D = tile^T), which leaves every lane with four consecutive COLUMNS of
 // one C row: 16-byte C accesses without the column-interleave trick of the packed path.
-template <int BM, int BN, int TM, bool EDGE, int ABLATE, bool BTR = false>
+// EP (BTR, ABLATE 0 only): what the transposed C rows go through on their way out.  I8NoEpilogue -- every kernel of this
+// library -- compiles to what was here before it.  A fused epilogue (csrc_q8/qlinear_s8.hpp) is told the lane's four
+// columns once per tile (ep.columns) and turns each transposed row vector into the bits to store (ep.row): behind the
+// transposer a lane holds four consecutive columns of one row, so it needs four column factors and one row factor.
+struct I8NoEpilogue {
+  static constexpr bool kFused = false;
+};
+template <int BM, int BN, int TM, bool EDGE, int ABLATE, bool BTR = false, class EP = I8NoEpilogue>
 __device__ __forceinline__ void igemm_s8_dma_tile(int m, int n, int k, const int8_t *__restrict__ A, int lda,
                                                   const int8_t *__restrict__ Bt, int kp, int n_pad,
                                                   int32_t *__restrict__ C, int ldc, int accumulate, int nbm,
-                                                  int nbn, const float *__restrict__ deq) {
+                                                  int nbn, const float *__restrict__ deq, EP ep = EP{}) {
+  static_assert(!EP::kFused || (BTR && ABLATE == 0), "a fused epilogue sits behind the C transposer");
   // deq != nullptr: C receives fp32 = (float)acc * (1 / (deq[0] * deq[1])) -- the dequantisation of a
   // symmetric-quantised GEMM (quant_s8.hpp) fused into the epilogue instead of an int32 round trip
   constexpr int ABL = ABLATE;
@@ -380,10 +388,14 @@ __device__ __forceinline__ void igemm_s8_dma_tile(int m, int n, int k, const int
     int8_t *cx = ilds + wave * 4096;
     const int eg = lane >> 4, eli = lane & 15;
     const int drow = row0 + wm * 16 * TM + eg, dcol = col0 + wn * 64 + 4 * eli;
+    if constexpr (EP::kFused) ep.columns(dcol, n, whole_c);
 #pragma unroll
     for (int t = 0; t < TM; ++t) {
 #pragma unroll
-      for (int u = 0; u < TN; ++u) *reinterpret_cast<i32x4 *>(cx + li * 256 + 16 * ((4 * u + g) ^ li)) = to_c(acc[t][u]);
+      for (int u = 0; u < TN; ++u) {
+        if constexpr (EP::kFused) *reinterpret_cast<i32x4 *>(cx + li * 256 + 16 * ((4 * u + g) ^ li)) = acc[t][u];
+        else *reinterpret_cast<i32x4 *>(cx + li * 256 + 16 * ((4 * u + g) ^ li)) = to_c(acc[t][u]);
+      }
       i32x4 out[4];
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
@@ -391,7 +403,10 @@ __device__ __forceinline__ void igemm_s8_dma_tile(int m, int n, int k, const int
         out[q] = *reinterpret_cast<const i32x4 *>(cx + rr * 256 + 16 * (eli ^ rr));
       }
 #pragma unroll
-      for (int q = 0; q < 4; ++q) put(drow + 16 * t + 4 * q, dcol, out[q]);
+      for (int q = 0; q < 4; ++q) {
+        if constexpr (EP::kFused) put(drow + 16 * t + 4 * q, dcol, ep.row(out[q], drow + 16 * t + 4 * q, m, whole_c));
+        else put(drow + 16 * t + 4 * q, dcol, out[q]);
+      }
     }
   } else {
 #pragma unroll

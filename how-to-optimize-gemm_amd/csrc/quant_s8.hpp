@@ -18,21 +18,11 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "quant_rules_s8.hpp"   // finite_abs, abs4, scale_of_amax, quantize_one, quantize4: the rules, per element
+
 namespace mmh {
 
-typedef float qf32x4 __attribute__((ext_vector_type(4)));
-typedef int qi32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int AMAX_WORDS = 64;   // abs-max accumulator words per tensor (reduced by the quantise pass)
-
-// |x| for the abs-max: non-finite elements do not take part (NaN never wins an fmaxf; inf is dropped)
-__device__ __forceinline__ float finite_abs(float x) {
-  const float a = fabsf(x);
-  return a <= 3.402823466e+38f ? a : 0.0f;
-}
-__device__ __forceinline__ float abs4(qf32x4 v) {
-  return fmaxf(fmaxf(finite_abs(v[0]), finite_abs(v[1])), fmaxf(finite_abs(v[2]), finite_abs(v[3])));
-}
 
 // One launch covers up to two tensors (blockIdx.y): A and B of a quantised GEMM.
 struct QuantTensor {
@@ -125,20 +115,7 @@ __device__ __forceinline__ float quant_scale(const unsigned *__restrict__ amax_b
   float amax = __uint_as_float(amax_bits[y * AMAX_WORDS + (threadIdx.x & (AMAX_WORDS - 1))]);
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) amax = fmaxf(amax, __shfl_xor(amax, off, 64));
-  if (!(amax > 0.0f)) return 1.0f;
-  const float s = 127.0f / amax;
-  return s <= 3.402823466e+38f ? s : 3.402823466e+38f;
-}
-
-__device__ __forceinline__ int quantize_one(float x, float scale) {
-  const float y = x == x ? x * scale : 0.0f;   // NaN -> 0 (0 * inf cannot occur: scale is finite)
-  return (int)fminf(fmaxf(rintf(y), -127.0f), 127.0f);
-}
-
-// `vec`: additionally q 4-byte aligned and ldq % 4 == 0 -> one dword of four int8 per float4.
-__device__ __forceinline__ unsigned quantize4(qf32x4 v, float scale) {
-  return (unsigned)(quantize_one(v[0], scale) & 255) | ((unsigned)(quantize_one(v[1], scale) & 255) << 8) |
-         ((unsigned)(quantize_one(v[2], scale) & 255) << 16) | ((unsigned)(quantize_one(v[3], scale) & 255) << 24);
+  return scale_of_amax(amax);
 }
 
 __global__ void __launch_bounds__(256) quantize_kernel(QuantTensor ta, QuantTensor tb, int vec_a, int vec_b,

@@ -1,0 +1,278 @@
+// q8.hip -- the host side of libmmult_hip_q8.so: the extern "C" entry points of include/mmult_hip_q8.h, the weight object and
+// its scratch, the row quantiser's and the weight image's launches.  The GEMM's instantiations live in qlinear_*.hip.
+// Every argument is checked before the first device call; every entry point that touches the device restores the caller's.
+#include <new>
+#include <string>
+#include <vector>
+
+#include "../../include/mmult_hip_q8.h"
+#include "qlinear_launch.hpp"
+#include "qlinear_plan.hpp"
+#include "quant_rows_s8.hpp"
+
+using namespace mmh;
+
+static_assert(kQrWaveCols == QR_WAVE_COLS, "qlinear_plan.hpp restates the kernels' constants");
+
+struct mmh_q8_weight {
+  int device = 0, out = 0, in = 0, pitch = 0, cus = 256;
+  int8_t *q = nullptr;                          // in x pitch
+  float *scale = nullptr, *inv_scale = nullptr; // out floats each
+  // the activations' image and row scales of the call in flight: grown on demand, under the capture rule
+  void *scratch = nullptr;
+  size_t scratch_bytes = 0;
+  bool captured = false;                        // a captured launch points at scratch: retire on growth, never free
+  std::vector<void *> retired;
+};
+
+namespace {
+
+thread_local std::string g_error, g_launch;
+
+int fail(int status, const std::string &text) {
+  g_error = text;
+  return status;
+}
+int hip_fail(hipError_t e, const char *what) { return fail(MMH_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e)); }
+#define Q8_TRY(expr)                                  \
+  do {                                                \
+    hipError_t e_ = (expr);                           \
+    if (e_ != hipSuccess) return hip_fail(e_, #expr); \
+  } while (0)
+
+struct DeviceGuard {
+  int prev = -1;
+  bool switched = false;
+  hipError_t enter(int device) {
+    hipError_t e = hipGetDevice(&prev);
+    if (e != hipSuccess || prev == device) return e;
+    e = hipSetDevice(device);
+    switched = e == hipSuccess;
+    return e;
+  }
+  ~DeviceGuard() {
+    if (switched) (void)hipSetDevice(prev);
+  }
+};
+
+bool capturing(hipStream_t s) {
+  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+  (void)hipStreamIsCapturing(s, &cap);
+  return cap != hipStreamCaptureStatusNone;
+}
+int base16(const void *p) { return (int)(reinterpret_cast<uintptr_t>(p) & 15); }
+
+// quant_vec_ok's convention for the row quantiser's operands (q NULL: scales only)
+bool rows_vec_ok(const float *x, int ldx, const int8_t *q, int ldq) {
+  return base16(x) == 0 && ldx % 4 == 0 && (!q || ((reinterpret_cast<uintptr_t>(q) & 3) == 0 && ldq % 4 == 0));
+}
+
+hipError_t launch_row_quant(const RowQuantArgs &a, const RowQuantPlan &p, hipStream_t s) {
+  const size_t lds = row_quant_lds(p.wide, a.cols);
+  if (p.wide) hipLaunchKernelGGL(quantize_rows_s8_kernel<true>, dim3(p.grid), dim3(256), lds, s, a);
+  else hipLaunchKernelGGL(quantize_rows_s8_kernel<false>, dim3(p.grid), dim3(256), lds, s, a);
+  return hipGetLastError();
+}
+
+// The object's scratch holds `need` bytes when this returns MMH_OK; refused, with the object as it was, where that takes an
+// allocation on a capturing stream
+int reserve(mmh_q8_weight *w, size_t need, hipStream_t s, const char *who) {
+  const bool cap = capturing(s);
+  if (need <= w->scratch_bytes) {
+    w->captured = w->captured || cap;
+    return MMH_OK;
+  }
+  if (cap)
+    return fail(MMH_ERR_UNSUPPORTED, std::string(who) + ": the weight object's scratch would have to be allocated or grown while the "
+                "stream is capturing -- make one uncaptured call at the largest size, or mmh_q8_linear_reserve, first");
+  void *p = nullptr;
+  if (const hipError_t e = hipMalloc(&p, need); e != hipSuccess) return fail(MMH_ERR_ALLOC, std::string("hipMalloc: ") + hipGetErrorString(e));
+  if (w->scratch) {
+    if (w->captured) w->retired.push_back(w->scratch);
+    else (void)hipFree(w->scratch);
+  }
+  w->scratch = p;
+  w->scratch_bytes = need;
+  return MMH_OK;
+}
+
+void release(mmh_q8_weight *w) {
+  for (void *p : {static_cast<void *>(w->q), static_cast<void *>(w->scale), static_cast<void *>(w->inv_scale), w->scratch})
+    if (p) (void)hipFree(p);
+  for (void *p : w->retired) (void)hipFree(p);
+  delete w;
+}
+
+bool act_ok(int activation) { return activation == MMH_ACT_NONE || activation == MMH_ACT_RELU; }
+
+int linear_args(const mmh_q8_weight *w, int rows, const float *dX, int ldx, int activation, const float *dY, int ldy) {
+  if (!w || rows < 0 || !act_ok(activation)) return MMH_ERR_INVALID_ARG;
+  if (rows == 0) return MMH_OK;
+  if ((w->in > 0 && !dX) || !dY || ldx < w->in || ldx < 1 || ldy < w->out) return MMH_ERR_INVALID_ARG;   // (in == 0: x is not read)
+  return MMH_OK;
+}
+
+// mmh_q8_linear behind its argument checks, on the object's device
+int linear_on(mmh_q8_weight *w, int rows, const float *dX, int ldx, const float *dBias, int activation, float *dY, int ldy, hipStream_t s) {
+  const Q8Plan p = plan_qlinear(rows, w->out, w->in, ldx, ldy, base16(dX), base16(dY), w->cus, dBias != nullptr, activation == MMH_ACT_RELU);
+  if (const int rc = reserve(w, p.scratch, s, "mmh_q8_linear"); rc != MMH_OK) return rc;
+  char *base = static_cast<char *>(w->scratch);
+  int8_t *xq = reinterpret_cast<int8_t *>(base);
+  float *sx = reinterpret_cast<float *>(base + p.off_scale), *rx = reinterpret_cast<float *>(base + p.off_inv);
+  const RowQuantArgs qa{dX, rows, w->in, ldx, xq, p.pitch_k, p.pitch_k, sx, rx, p.quant.vec ? 1 : 0};
+  Q8_TRY(launch_row_quant(qa, p.quant, s));
+  const QlinearArgs g{rows, w->out, w->in, xq, p.pitch_k, w->q, w->pitch, rx, w->inv_scale, dBias, activation == MMH_ACT_RELU ? 1 : 0,
+                      dY, ldy, p.nbm, p.nbn};
+  Q8_TRY(p.tile == 256 ? (p.edge ? launch_qlinear_256_edge(g, s) : launch_qlinear_256(g, s))
+                       : (p.edge ? launch_qlinear_128_edge(g, s) : launch_qlinear_128(g, s)));
+  g_launch = p.text;
+  return MMH_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+const char *mmh_q8_last_error(void) { return g_error.c_str(); }
+const char *mmh_q8_last_launch(void) { return g_launch.c_str(); }
+
+int mmh_q8_weight_create(mmh_q8_weight_t *weight, int device, int out, int in, const float *dW, int ldw, void *stream) {
+  if (!weight || device < 0 || out <= 0 || in < 0 || ldw < in || ldw < 1 || (in > 0 && !dW)) return MMH_ERR_INVALID_ARG;
+  *weight = nullptr;
+  int devices = 0;
+  if (hipGetDeviceCount(&devices) != hipSuccess || device >= devices) return fail(MMH_ERR_NO_DEVICE, "mmh_q8_weight_create: no such device");
+  if (!q8_window(out, in)) return fail(MMH_ERR_UNSUPPORTED, "mmh_q8_weight_create: the image lies beyond the GEMM's 2 GiB descriptor window");
+  DeviceGuard guard;
+  Q8_TRY(guard.enter(device));
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (capturing(s)) return fail(MMH_ERR_UNSUPPORTED, "mmh_q8_weight_create allocates: not on a capturing stream");
+  mmh_q8_weight *w = new (std::nothrow) mmh_q8_weight;
+  if (!w) return MMH_ERR_ALLOC;
+  w->device = device, w->out = out, w->in = in, w->pitch = q8_pitch(out);
+  int cus = 0;
+  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && cus > 0) w->cus = cus;
+  const size_t image = (size_t)in * w->pitch, floats = (size_t)w->pitch * sizeof(float);
+  hipError_t e = hipMalloc(reinterpret_cast<void **>(&w->q), image ? image : 16);
+  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&w->scale), floats);
+  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&w->inv_scale), floats);
+  if (e != hipSuccess) {
+    release(w);
+    return fail(MMH_ERR_ALLOC, std::string("hipMalloc: ") + hipGetErrorString(e));
+  }
+  // the channel scales: the row quantiser without an image; then the image, tile by tile
+  const bool vec = rows_vec_ok(dW, ldw, nullptr, 0);
+  const RowQuantArgs qa{dW, out, in, ldw, nullptr, 0, 0, w->scale, w->inv_scale, vec ? 1 : 0};
+  e = launch_row_quant(qa, plan_row_quant(out, in, vec), s);
+  if (e == hipSuccess && in > 0) {
+    const dim3 grid((unsigned)((w->pitch + PW_TILE - 1) / PW_TILE), (unsigned)((in + PW_TILE - 1) / PW_TILE));
+    if (grid.y > 65535u) e = hipErrorInvalidValue;
+    else {
+      hipLaunchKernelGGL(prepare_weight_s8_kernel, grid, dim3(256), 0, s, dW, out, in, ldw, w->scale, w->q, w->pitch, vec ? 1 : 0);
+      e = hipGetLastError();
+    }
+  }
+  if (e != hipSuccess) {
+    (void)hipStreamSynchronize(s);
+    release(w);
+    return hip_fail(e, "mmh_q8_weight_create");
+  }
+  *weight = w;
+  return MMH_OK;
+}
+
+int mmh_q8_weight_destroy(mmh_q8_weight_t w) {
+  if (!w) return MMH_OK;
+  DeviceGuard guard;
+  Q8_TRY(guard.enter(w->device));
+  release(w);   // (hipFree waits for the device: no launch still reads what goes)
+  return MMH_OK;
+}
+
+int mmh_q8_weight_info(mmh_q8_weight_t w, int *out, int *in, int *pitch, const int8_t **dQ, const float **d_scale,
+                       const float **d_inv_scale) {
+  if (!w) return MMH_ERR_INVALID_ARG;
+  if (out) *out = w->out;
+  if (in) *in = w->in;
+  if (pitch) *pitch = w->pitch;
+  if (dQ) *dQ = w->q;
+  if (d_scale) *d_scale = w->scale;
+  if (d_inv_scale) *d_inv_scale = w->inv_scale;
+  return MMH_OK;
+}
+
+int mmh_q8_quantize_rows(int device, int rows, int cols, const float *dX, int ldx, int8_t *dQ, int ldq, float *d_scale,
+                         float *d_inv_scale, void *stream) {
+  if (device < 0 || rows < 0 || cols < 0) return MMH_ERR_INVALID_ARG;
+  if (rows == 0) return MMH_OK;
+  if (!dQ || !d_scale || !d_inv_scale || (cols > 0 && !dX) || ldx < cols || ldx < 1 || ldq < cols) return MMH_ERR_INVALID_ARG;
+  DeviceGuard guard;
+  Q8_TRY(guard.enter(device));
+  const bool vec = rows_vec_ok(dX, ldx, dQ, ldq);
+  const RowQuantPlan p = plan_row_quant(rows, cols, vec);
+  const int pad_to = ldq < q8_pitch(cols) ? ldq : q8_pitch(cols);
+  const RowQuantArgs a{dX, rows, cols, ldx, dQ, ldq, pad_to, d_scale, d_inv_scale, vec ? 1 : 0};
+  Q8_TRY(launch_row_quant(a, p, static_cast<hipStream_t>(stream)));
+  char text[128];
+  snprintf(text, sizeof text, "quantize_rows_s8_kernel<%s> (%s path), %u workgroups", p.wide ? "true" : "false", vec ? "vector" : "scalar", p.grid);
+  g_launch = text;
+  return MMH_OK;
+}
+
+int mmh_q8_linear(mmh_q8_weight_t w, int rows, const float *dX, int ldx, const float *dBias, int activation, float *dY, int ldy,
+                  void *stream) {
+  if (const int rc = linear_args(w, rows, dX, ldx, activation, dY, ldy); rc != MMH_OK || rows == 0) return rc;
+  DeviceGuard guard;
+  Q8_TRY(guard.enter(w->device));
+  return linear_on(w, rows, dX, ldx, dBias, activation, dY, ldy, static_cast<hipStream_t>(stream));
+}
+
+int mmh_q8_linear_reserve(mmh_q8_weight_t w, int max_rows, void *stream) {
+  if (!w || max_rows < 0) return MMH_ERR_INVALID_ARG;
+  if (max_rows == 0) return MMH_OK;
+  DeviceGuard guard;
+  Q8_TRY(guard.enter(w->device));
+  const Q8Plan p = plan_qlinear(max_rows, w->out, w->in, w->in > 0 ? w->in : 1, w->out, 0, 0, w->cus, false, false);
+  return reserve(w, p.scratch, static_cast<hipStream_t>(stream), "mmh_q8_linear_reserve");
+}
+
+int mmh_q8_linear_plan(int rows, int out, int in, int ldx, int ldy, int x_mod16, int y_mod16, int has_bias, int activation, int cu_count,
+                       char *text, int text_bytes, size_t *scratch_bytes) {
+  if (rows <= 0 || out <= 0 || in < 0 || ldx < in || ldx < 1 || ldy < out || ((x_mod16 | y_mod16) & ~15) || !act_ok(activation) || !text ||
+      text_bytes <= 0 || !scratch_bytes)
+    return MMH_ERR_INVALID_ARG;
+  if (!q8_window(out, in)) return MMH_ERR_UNSUPPORTED;
+  const Q8Plan p = plan_qlinear(rows, out, in, ldx, ldy, x_mod16, y_mod16, cu_count > 0 ? cu_count : 256, has_bias != 0, activation == MMH_ACT_RELU);
+  snprintf(text, (size_t)text_bytes, "%s", p.text);
+  *scratch_bytes = p.scratch;
+  return MMH_OK;
+}
+
+int mmh_time_q8_linear(mmh_q8_weight_t w, int rows, const float *dX, int ldx, const float *dBias, int activation, float *dY, int ldy,
+                       int warmup, int reps, void *stream, float *ms_per_call) {
+  if (reps <= 0 || warmup < 0 || !ms_per_call) return MMH_ERR_INVALID_ARG;
+  if (const int rc = linear_args(w, rows, dX, ldx, activation, dY, ldy); rc != MMH_OK) return rc;
+  if (rows == 0) return MMH_ERR_INVALID_ARG;   // (nothing to time)
+  DeviceGuard guard;
+  Q8_TRY(guard.enter(w->device));
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  int rc = MMH_OK;
+  for (int i = 0; i < warmup && rc == MMH_OK; ++i) rc = linear_on(w, rows, dX, ldx, dBias, activation, dY, ldy, s);
+  if (rc != MMH_OK) return rc;
+  hipEvent_t t0 = nullptr, t1 = nullptr;
+  hipError_t e = hipEventCreate(&t0);
+  if (e == hipSuccess) e = hipEventCreate(&t1);
+  if (e == hipSuccess) e = hipEventRecord(t0, s);
+  for (int i = 0; i < reps && rc == MMH_OK && e == hipSuccess; ++i) rc = linear_on(w, rows, dX, ldx, dBias, activation, dY, ldy, s);
+  float ms = 0.f;
+  if (rc == MMH_OK && e == hipSuccess) e = hipEventRecord(t1, s);
+  if (rc == MMH_OK && e == hipSuccess) e = hipEventSynchronize(t1);
+  if (rc == MMH_OK && e == hipSuccess) e = hipEventElapsedTime(&ms, t0, t1);
+  if (t0) (void)hipEventDestroy(t0);
+  if (t1) (void)hipEventDestroy(t1);
+  if (rc != MMH_OK) return rc;
+  if (e != hipSuccess) return hip_fail(e, "mmh_time_q8_linear");
+  *ms_per_call = ms / reps;
+  return MMH_OK;
+}
+
+}  // extern "C"

@@ -1,0 +1,6 @@
+// qlinear_256.hip -- qlinear_s8_kernel<256,256,8,false,*,*> (see qlinear_launch.hpp).  Part of libmmult_hip_q8.so.
+#include "qlinear_launch.hpp"
+
+namespace mmh {
+hipError_t launch_qlinear_256(const QlinearArgs &a, hipStream_t s) { return launch_qlinear_tile<256, false>(a, s); }
+}  // namespace mmh

@@ -1,0 +1,6 @@
+// qlinear_256_edge.hip -- qlinear_s8_kernel<256,256,8,true,*,*> (see qlinear_launch.hpp).  Part of libmmult_hip_q8.so.
+#include "qlinear_launch.hpp"
+
+namespace mmh {
+hipError_t launch_qlinear_256_edge(const QlinearArgs &a, hipStream_t s) { return launch_qlinear_tile<256, true>(a, s); }
+}  // namespace mmh

@@ -1,0 +1,410 @@
+"""The int8 linear layer on the GPU (libmmult_hip_q8.so, how_to_optimize_gemm_amd.q8), bit for bit against tests/qlinear_ref.py.
+
+Q8_INSTANTIATIONS holds one row per kernel symbol of the library (tests/test_q8_kernel_census.py holds the table to the
+library, both ways): the GEMM's sixteen instantiations -- tile x guarded x bias x ReLU --, the row quantiser's two forms and
+the weight image's kernel.  A GEMM row runs every shape of its (tile, guarded) class; mmh_q8_last_launch must name the row's
+symbol.  x has a padded leading dimension, y a padded one poisoned with NaN that must survive.
+
+The 256x256 shapes are chosen by csrc/igemm_plan.hpp's i8_big_tile with the test device's CU count (qlinear_ref.big_tile):
+the smallest multiple-of-256 shape that takes the big tile, and a ragged neighbour."""
+import collections
+import functools
+
+import numpy as np
+import pytest
+
+import qlinear_ref as R
+from bitcmp import first_difference, same_bits
+from gpu_operands import _padded, cus_fixture, handle_fixture
+
+pytestmark = pytest.mark.gpu
+
+amm = handle_fixture()        # asked for the device's CU count only
+cus = cus_fixture("amm")
+
+Row = collections.namedtuple("Row", "symbol kind tile edge bias relu")
+_B = {False: "false", True: "true"}
+Q8_INSTANTIATIONS = [Row(f"qlinear_s8_kernel<{t},{t},{t // 32},{_B[e]},{_B[b]},{_B[r]}>", "gemm", t, e, b, r)
+                     for t in (128, 256) for e in (False, True) for b in (False, True) for r in (False, True)]
+Q8_INSTANTIATIONS += [Row("quantize_rows_s8_kernel<false>", "rows", 0, False, False, False),
+                      Row("quantize_rows_s8_kernel<true>", "rows", 0, False, False, False),
+                      Row("prepare_weight_s8_kernel", "weight", 0, False, False, False)]
+
+SHAPES_128 = {False: [(128, 128, 128), (128, 128, 64)], True: [(129, 130, 131), (5, 3, 7), (1, 1, 1)]}
+IN_256 = 192
+# stand-alone quantiser / weight shapes: wave per row (1, 1023 columns), workgroup per row (1024, 5000), and a row longer than
+# the workgroup form keeps in LDS (16392 > 16380: its rest is read again)
+ALONE = [(3, 1), (7, 1023), (4, 1024), (2, 5000), (2, 16392)]
+
+
+def shapes_256(cu_count):
+    """((rows, out, in) whole, ragged): the multiple-of-256 shape of the fewest elements that i8_big_tile sends to the 256x256
+    tile on this device, and its neighbour three rows and five columns short (the same tiles)."""
+    best = None
+    for a in range(1, 33):
+        for b in range(a, 65):
+            if R.big_tile(256 * a, 256 * b, cu_count) and (best is None or a * b < best[0] * best[1]):
+                best = (a, b)
+    assert best, cu_count
+    m, n = 256 * best[0], 256 * best[1]
+    assert R.big_tile(m - 3, n - 5, cu_count)
+    return (m, n, IN_256), (m - 3, n - 5, IN_256)
+
+
+@functools.lru_cache(maxsize=4)
+def problem(rows, out, in_):
+    """Inputs of a shape and the parts of its reference every epilogue shares."""
+    rng = np.random.default_rng(rows * 7 + out * 3 + in_)
+    x = (rng.standard_normal((rows, in_)) * 3).astype(np.float32)
+    w = rng.uniform(-0.5, 0.5, (out, in_)).astype(np.float32)
+    bias = rng.uniform(-4, 4, out).astype(np.float32)
+    return x, w, bias, parts(x, w)
+
+
+def parts(x, w):
+    qx, _, rx = R.quantize_rows_ref(x)
+    qw, _, rw = R.quantize_rows_ref(w)
+    return R.int_sums(qx, qw), rx, rw
+
+
+_weights = {}
+
+
+def weight_of(key, w):
+    """One prepared weight per shape (the epilogue variants of a shape share it)."""
+    import torch
+    from how_to_optimize_gemm_amd import q8
+    if key not in _weights:
+        _weights.clear()
+        _weights[key] = q8.QWeight(torch.from_numpy(w).cuda())
+    return _weights[key]
+
+
+def run(qw, x, bias, relu, guarded, off=None):
+    """qlinear on padded operands: guarded -- odd leading dimensions, bases 4 bytes past 16-byte alignment; else leading
+    dimensions that are multiples of 4 floats past the row, 16-byte aligned bases.  Returns (y's window, nothing outside it
+    was written, the launch text)."""
+    import torch
+    from how_to_optimize_gemm_amd import q8
+    rows, in_ = x.shape
+    out = qw.out_features
+    off = (1 if guarded else 4) if off is None else off
+    ldx = in_ + (3 if guarded else 4) if in_ else 4
+    ldy = out + (1 if guarded else 4)
+    _, xv = _padded(rows, in_, ldx, off, x)
+    yflat, yv = _padded(rows, out, ldy, off)
+    q8.qlinear(xv[:, :in_], qw, None if bias is None else torch.from_numpy(bias).cuda(), "relu" if relu else None, out=yv[:, :out])
+    launched = q8.last_launch()
+    torch.cuda.synchronize()
+    untouched = bool(torch.isnan(yv[:, out:]).all()) and bool(torch.isnan(yflat[:off]).all()) and \
+        bool(torch.isnan(yflat[off + rows * ldy:]).all())
+    return yv[:, :out].cpu().numpy(), untouched, launched
+
+
+def check(shape, bias, relu, guarded, symbol, cu_count, off=None):
+    rows, out, in_ = shape
+    x, w, b, (acc, rx, rw) = problem(*shape)
+    got, untouched, launched = run(weight_of(shape, w), x, b if bias else None, relu, guarded, off)
+    want = R.epilogue_ref(acc, rx, rw, b if bias else None, relu)
+    assert symbol in launched, (shape, symbol, launched)
+    assert same_bits(got, want), (shape, launched, first_difference(got, want))
+    assert untouched, (shape, "wrote outside y's window")
+    return launched
+
+
+@pytest.mark.parametrize("row", [r for r in Q8_INSTANTIATIONS if r.kind == "gemm"], ids=lambda r: r.symbol)
+def test_every_instantiation_is_reached_and_is_the_contract(row, cus):
+    if row.tile == 128:
+        shapes = SHAPES_128[row.edge]
+    else:
+        shapes = [shapes_256(cus)[1 if row.edge else 0]]
+    for shape in shapes:
+        launched = check(shape, row.bias, row.relu, row.edge, row.symbol, cus)
+        # ... and the launch is what mmh_q8_linear_plan says for the call
+        rows, out, in_ = shape
+        off = 4 if row.edge else 0
+        text, _ = R.plan_text(rows, out, in_, in_ + (3 if row.edge else 4), out + (1 if row.edge else 4), off, off, row.bias, row.relu, cus)
+        assert launched == text
+
+
+def test_operands_four_bytes_past_alignment_take_the_guarded_tile_and_the_scalar_quantiser(cus):
+    """A whole-tile shape with multiple-of-4 leading dimensions whose x and y start 4 bytes past a 16-byte boundary."""
+    launched = check((128, 128, 64), True, True, False, "qlinear_s8_kernel<128,128,4,true,true,true>", cus, off=1)
+    assert launched.startswith("quantize_rows_s8_kernel<false> (scalar path)")
+    launched = check((128, 128, 64), True, True, False, "qlinear_s8_kernel<128,128,4,false,true,true>", cus, off=4)
+    assert launched.startswith("quantize_rows_s8_kernel<false> (vector path)")
+
+
+def test_an_empty_inner_dimension_is_the_formula_on_zero_sums(cus):
+    import torch
+    from how_to_optimize_gemm_amd import q8
+    w, x = np.zeros((3, 0), np.float32), np.zeros((4, 0), np.float32)
+    bias = np.array([1.5, -0.0, -2.0], np.float32)
+    qw = q8.QWeight(_padded(3, 0, 4, 4)[1][:, :0])   # (a (3, 0) window with a row stride: numpy's own has stride 0)
+    for b, relu in ((None, False), (bias, False), (bias, True)):
+        got, untouched, _ = run(qw, x, b, relu, True)
+        want = R.qlinear_ref(x, w, b, relu)
+        assert same_bits(got, want) and untouched, (relu, got, want)
+    assert same_bits(R.qlinear_ref(x, w, bias, True), np.tile(np.array([1.5, 0.0, 0.0], np.float32), (4, 1)))
+
+
+def test_large_sums_round_to_nearest_even(cus):
+    """(64, 64, 2048), every |element| its row's maximum: every q is +-127, |acc| up to 127^2 * 2048 > 2^24."""
+    import torch
+    from how_to_optimize_gemm_amd import q8
+    rng = np.random.default_rng(11)
+    x = np.where(rng.random((64, 2048)) < 0.05, -1.5, 1.5).astype(np.float32) * rng.uniform(0.5, 2, (64, 1)).astype(np.float32)
+    w = np.where(rng.random((64, 2048)) < 0.05, -0.25, 0.25).astype(np.float32) * rng.uniform(0.5, 2, (64, 1)).astype(np.float32)
+    x[0], w[0] = 1.5, 0.25
+    acc, rx, rw = parts(x, w)
+    assert acc[0, 0] == 127 * 127 * 2048 and (np.abs(acc) > 1 << 24).sum() > 1000
+    check_large(x, w, acc, rx, rw)
+    # 127^2 times an even count is even, and below 2^25 every even integer is a float32: the sums above convert exactly.  One
+    # element per row of x at 2 / 127 of the maximum (q = 2: 127^2 times an odd count, plus or minus 254) makes them odd: now float32(acc) has to round
+    x[:, 5] *= np.float32(2.0 / 127.0)
+    acc, rx, rw = parts(x, w)
+    assert (np.abs(acc) > 1 << 24).sum() > 1000 and (acc.astype(np.float32).astype(np.int64) != acc).sum() > 1000
+    check_large(x, w, acc, rx, rw)
+
+
+def check_large(x, w, acc, rx, rw):
+    import torch
+    from how_to_optimize_gemm_amd import q8
+    got, untouched, launched = run(q8.QWeight(torch.from_numpy(w).cuda()), x, None, False, False)
+    want = R.epilogue_ref(acc, rx, rw)
+    assert same_bits(got, want) and untouched, (launched, first_difference(got, want))
+
+
+def test_special_values_as_activation_rows_and_as_weight_channels(cus):
+    import torch
+    from how_to_optimize_gemm_amd import q8
+    rng = np.random.default_rng(5)
+    special = np.stack([r for _, r, _, _ in R.special_rows(40, rng)])
+    plain = rng.uniform(-1, 1, (6, 40)).astype(np.float32)
+    bias = rng.uniform(-1, 1, 11).astype(np.float32)
+    both = np.concatenate([special, plain])
+    for x, w in ((both, both), (plain, both), (both, plain)):
+        b = bias[:w.shape[0]]
+        qw = q8.QWeight(torch.from_numpy(w).cuda())
+        for relu in (False, True):
+            got, untouched, launched = run(qw, x, b, relu, True)
+            want = R.qlinear_ref(x, w, b, relu)
+            assert same_bits(got, want) and untouched, (launched, first_difference(got, want))
+
+
+def _quant_input(rows, cols, seed):
+    rng = np.random.default_rng(seed)
+    x = (rng.standard_normal((rows, cols)) * 2).astype(np.float32)
+    if cols >= 9:
+        x[0, :9] = [np.nan, np.inf, -np.inf, 0.0, -0.0, 1e-38, -1e-38, 5.0, -5.0]
+    if rows > 1:
+        x[1] = 0.0
+    return x
+
+
+@pytest.mark.parametrize("rows,cols", ALONE)
+@pytest.mark.parametrize("aligned", [True, False], ids=["vector", "scalar"])
+def test_the_row_quantiser_alone(rows, cols, aligned):
+    """q, scale, inv_scale and the zeroed pad bytes; x with a padded leading dimension, q in a poisoned buffer whose bytes
+    beyond the pad must survive."""
+    import torch
+    from how_to_optimize_gemm_amd import q8
+    x = _quant_input(rows, cols, rows + cols)
+    ldx = ((cols + 3) & ~3) + 4 if aligned else cols + 3
+    _, xv = _padded(rows, cols, ldx, 4 if aligned else 1, x)
+    pitch = (cols + 15) & ~15
+    ldq = pitch + 32 if aligned else cols + 5          # (the second: fewer bytes behind the row than the pad asks for)
+    qflat = torch.full((16 + rows * ldq + 16,), 0x55, dtype=torch.int8, device="cuda")
+    off = 16 if aligned else 17
+    qv = qflat[off:off + rows * ldq].view(rows, ldq)
+    q, s, r = q8.quantize_rows(xv[:, :cols], out=qv[:, :cols])
+    launched = q8.last_launch()
+    torch.cuda.synchronize()
+    assert launched == f"quantize_rows_s8_kernel<{_B[cols >= 1024]}> ({'vector' if aligned else 'scalar'} path), " \
+                       f"{rows if cols >= 1024 else (rows + 3) // 4} workgroups"
+    wq, ws, wr = R.quantize_rows_ref(x)
+    got = qv.cpu().numpy()
+    pad_to = min(ldq, pitch)
+    assert np.array_equal(got[:, :cols], wq) and not got[:, cols:pad_to].any() and (got[:, pad_to:] == 0x55).all()
+    flat = qflat.cpu().numpy()
+    assert (flat[:off] == 0x55).all() and (flat[off + rows * ldq:] == 0x55).all()
+    assert same_bits(s.cpu().numpy(), ws) and same_bits(r.cpu().numpy(), wr)
+    # the default output: rows of `pitch` bytes
+    q2, s2, r2 = q8.quantize_rows(xv[:, :cols])
+    assert np.array_equal(q2.cpu().numpy(), wq) and same_bits(s2.cpu().numpy(), ws) and same_bits(r2.cpu().numpy(), wr)
+
+
+@pytest.mark.parametrize("out,in_", ALONE + [(130, 70)])
+@pytest.mark.parametrize("aligned", [True, False], ids=["vector", "scalar"])
+def test_the_weight_image_alone(out, in_, aligned):
+    """QWeight: the image is the per-channel quantisation transposed, pad columns 0; scale and inv_scale per channel."""
+    import torch
+    from how_to_optimize_gemm_amd import q8
+    w = _quant_input(out, in_, out * 3 + in_)
+    ldw = ((in_ + 3) & ~3) + 4 if aligned else in_ + 3
+    _, wv = _padded(out, in_, ldw, 4 if aligned else 1, w)
+    qw = q8.QWeight(wv[:, :in_])
+    img, s, r = qw.q.cpu().numpy(), qw.scale.cpu().numpy(), qw.inv_scale.cpu().numpy()
+    wq, ws, wr = R.quantize_rows_ref(w)
+    assert qw.pitch == (out + 15) & ~15 and img.shape == (in_, qw.pitch) and img.dtype == np.int8
+    assert np.array_equal(img[:, :out], wq.T) and not img[:, out:].any()
+    assert same_bits(s, ws) and same_bits(r, wr)
+    qw.close()
+
+
+def test_one_weight_serves_calls_of_different_rows_and_grows_its_scratch(cus):
+    import torch
+    from how_to_optimize_gemm_amd import q8
+    rng = np.random.default_rng(3)
+    w = rng.uniform(-1, 1, (70, 50)).astype(np.float32)
+    bias = rng.uniform(-1, 1, 70).astype(np.float32)
+    qw = q8.QWeight(torch.from_numpy(w).cuda())
+    qw.reserve(16)
+    for rows in (16, 3, 200):   # (200: past what was reserved, eagerly)
+        x = rng.standard_normal((rows, 50)).astype(np.float32)
+        got, untouched, launched = run(qw, x, bias, True, True)
+        want = R.qlinear_ref(x, w, bias, True)
+        assert same_bits(got, want) and untouched, (rows, launched, first_difference(got, want))
+
+
+def _side_stream():
+    import torch
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    return side
+
+
+def _capture(side, body):
+    import torch
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.stream(side):
+        with torch.cuda.graph(graph, stream=side):
+            body()
+    torch.cuda.current_stream().wait_stream(side)
+    return graph
+
+
+def test_growth_under_capture_is_refused_and_growth_after_it_retires():
+    """A captured call that would have to grow the weight's scratch is MMH_ERR_UNSUPPORTED with y untouched and the capture
+    goes on; once a captured call has used the scratch, eager growth keeps the old buffer for the graph."""
+    import torch
+    import how_to_optimize_gemm_amd as H
+    from how_to_optimize_gemm_amd import q8
+    rng = np.random.default_rng(9)
+    w = rng.uniform(-1, 1, (40, 36)).astype(np.float32)
+    qw = q8.QWeight(torch.from_numpy(w).cuda())
+    xs, xl = torch.zeros((8, 36), device="cuda"), torch.zeros((64, 36), device="cuda")
+    ys, yl = torch.full((8, 40), float("nan"), device="cuda"), torch.full((64, 40), float("nan"), device="cuda")
+    side = _side_stream()
+    with torch.cuda.stream(side):
+        q8.qlinear(xs, qw, out=ys)   # the eager warm-up: sizes the scratch for 8 rows
+    side.synchronize()
+    seen = []
+
+    def body():
+        q8.qlinear(xs, qw, out=ys)
+        # (no `pytest.raises(...) as e` here: its ExceptionInfo and this frame would form a cycle that keeps _capture's graph
+        # alive until some later garbage collection -- possibly inside another test's capture, where destroying a
+        # torch.cuda.CUDAGraph is not safe on ROCm)
+        try:
+            q8.qlinear(xl, qw, out=yl)
+        except H.MMultError as err:
+            seen.append(err.status)
+
+    graph = _capture(side, body)
+    assert seen == [H.ERR_UNSUPPORTED]
+    a = rng.standard_normal((8, 36)).astype(np.float32)
+    xs.copy_(torch.from_numpy(a))
+    graph.replay()
+    torch.cuda.synchronize()
+    assert same_bits(ys.cpu().numpy(), R.qlinear_ref(a, w)) and bool(torch.isnan(yl).all())
+    # eager growth after the capture: exact, and the graph still replays on the buffer it points at
+    b = rng.standard_normal((64, 36)).astype(np.float32)
+    xl.copy_(torch.from_numpy(b))
+    q8.qlinear(xl, qw, out=yl)
+    torch.cuda.synchronize()
+    assert same_bits(yl.cpu().numpy(), R.qlinear_ref(b, w))
+    a = rng.standard_normal((8, 36)).astype(np.float32)
+    xs.copy_(torch.from_numpy(a))
+    graph.replay()
+    torch.cuda.synchronize()
+    assert same_bits(ys.cpu().numpy(), R.qlinear_ref(a, w))
+    del graph
+
+
+def test_a_captured_call_replays_the_contract_on_new_inputs():
+    """One qlinear captured after an eager warm-up on the capture stream (a single-stream chain: the row quantiser, then the
+    GEMM), replayed three times on new x: each replay is the eager result and the reference, bit for bit."""
+    import torch
+    from how_to_optimize_gemm_amd import q8
+    rng = np.random.default_rng(21)
+    w = rng.uniform(-1, 1, (130, 200)).astype(np.float32)
+    bias = rng.uniform(-1, 1, 130).astype(np.float32)
+    qw, db = q8.QWeight(torch.from_numpy(w).cuda()), torch.from_numpy(bias).cuda()
+    x = torch.zeros((77, 200), device="cuda")
+    y = torch.full((77, 130), float("nan"), device="cuda")
+    side = _side_stream()
+    with torch.cuda.stream(side):
+        q8.qlinear(x, qw, db, "relu", out=y)
+    side.synchronize()
+    graph = _capture(side, lambda: q8.qlinear(x, qw, db, "relu", out=y))
+    for rep in range(3):
+        a = (rng.standard_normal((77, 200)) * (rep + 1)).astype(np.float32)
+        x.copy_(torch.from_numpy(a))
+        y.fill_(float("nan"))
+        graph.replay()
+        torch.cuda.synchronize()
+        got = y.cpu().numpy()
+        eager = q8.qlinear(x.clone(), qw, db, "relu").cpu().numpy()
+        assert same_bits(got, eager), (rep, first_difference(got, eager))
+        assert same_bits(got, R.qlinear_ref(a, w, bias, True)), rep
+    del graph
+
+
+def test_the_module_is_the_contract_and_lies_within_the_quantisation_bound():
+    """QLinear.from_float(nn.Linear(96, 80)) on a (2, 5, 96) input equals qlinear_ref, and lies within the analytic bound of
+    the fp32 layer.
+
+    The bound.  For a vector v with finite elements, a = max|v|, s = 127 / a: v_k * s lies in [-127, 127], so rint moves it by
+    at most 1/2 and never clamps: |Q(v)_k / s - v_k| <= 1 / (2 s) = a / 254 =: d(v).  Write xq_k = Q(x)_k / sx = x_k + ex_k and
+    wq_k = Q(w)_k / sw = w_k + ew_k with |ex_k| <= d(x), |ew_k| <= d(w).  The exact layer on the quantised operands differs from
+    the exact layer by
+        |sum_k xq_k wq_k - sum_k x_k w_k| = |sum_k (x_k ew_k + ex_k w_k + ex_k ew_k)|
+                                         <= d(w) sum_k |x_k| + d(x) sum_k |w_k| + K d(x) d(w)                      (tight)
+    and, since max|v| <= sum_k |v_k| =: S(v) and |ex_k| <= |x_k| as well (an element that rounds to 0 is off by itself, any
+    other by at most half a step, which is below it), sum_k |ex_k ew_k| <= S(x) d(w):
+                                         <= S(x) S(w) (1/254 + 1/254 + 1/254) < S(x) S(w) (1/127 + 1/127 + 1/127^2)  (the issue's)
+    with S(x) S(w) the product of the two rows' absolute sums.  Both are asserted.  fp32 slack: y is three roundings of that
+    exact value (and two rounded reciprocals) and the fp32 layer a K-term fp32 sum: (K + 8) 2^-24 (sum_k |x_k w_k| (1 + 3/127) + |b_j|)."""
+    import torch
+    from how_to_optimize_gemm_amd import q8
+    torch.manual_seed(4)
+    linear = torch.nn.Linear(96, 80).cuda()
+    layer = q8.QLinear.from_float(linear)
+    x = torch.randn(2, 5, 96, device="cuda")
+    y = layer(x)
+    assert tuple(y.shape) == (2, 5, 80)
+    xn, wn, bn = x.reshape(10, 96).cpu().numpy(), linear.weight.detach().cpu().numpy(), linear.bias.detach().cpu().numpy()
+    got = y.reshape(10, 80).cpu().numpy()
+    want = R.qlinear_ref(xn, wn, bn)
+    assert same_bits(got, want), first_difference(got, want)
+    with torch.no_grad():
+        fp32 = linear(x).reshape(10, 80).cpu().numpy().astype(np.float64)
+    ax, aw = np.abs(xn).astype(np.float64), np.abs(wn).astype(np.float64)
+    dx, dw = ax.max(axis=1) / 254, aw.max(axis=1) / 254
+    tight = ax.sum(axis=1)[:, None] * dw[None, :] + dx[:, None] * aw.sum(axis=1)[None, :] + 96 * dx[:, None] * dw[None, :]
+    issue = ax.sum(axis=1)[:, None] * aw.sum(axis=1)[None, :] * (2 / 127 + 1 / 127 ** 2)
+    slack = (96 + 8) * 2.0 ** -24 * ((ax @ aw.T) * (1 + 3 / 127) + np.abs(bn)[None, :])
+    err = np.abs(got.astype(np.float64) - fp32)
+    assert (err <= tight + slack).all(), (err - tight - slack).max()
+    assert (err <= issue + slack).all(), (err - issue - slack).max()
+    # ReLU in the module, no bias, and what it refuses
+    plain = torch.nn.Linear(96, 80, bias=False).cuda()
+    relu = q8.QLinear.from_float(plain, activation="relu")
+    assert relu.bias is None
+    assert same_bits(relu(x).reshape(10, 80).cpu().numpy(), R.qlinear_ref(xn, plain.weight.detach().cpu().numpy(), None, True))
+    import how_to_optimize_gemm_amd as H
+    with pytest.raises(H.MMultError):
+        layer(x.clone().requires_grad_())
+    with pytest.raises(H.MMultError):
+        q8.QLinear(96, 80)(x)   # no weight prepared
