@@ -6,9 +6,16 @@ the weight image's kernel.  A GEMM row runs every shape of its (tile, guarded) c
 symbol.  x has a padded leading dimension, y a padded one poisoned with NaN that must survive.
 
 The 256x256 shapes are chosen by csrc/igemm_plan.hpp's i8_big_tile with the test device's CU count (qlinear_ref.big_tile):
-the smallest multiple-of-256 shape that takes the big tile, and a ragged neighbour."""
+the smallest multiple-of-256 shape that takes the big tile, a ragged neighbour, and the smallest shapes whose last tiles are
+THIN wide.
+
+Every GEMM row also has a case table (Row.cases; tests/test_q8_coverage.py holds the classes it promises, on the CPU): one
+test id per (tile, guarded, case) runs the class's four epilogues on inputs whose every 128-byte slice of k moves the sums.
+The tile's K loop requests slice kt + 2 while it works on slice kt, so only an inner dimension beyond 256 refills an LDS
+buffer with data inside the loop: KS_Q8 / KS_256 reach one to four trips and every tail of the last pair of slices."""
 import collections
 import functools
+import math
 
 import numpy as np
 import pytest
@@ -22,7 +29,18 @@ pytestmark = pytest.mark.gpu
 amm = handle_fixture()        # asked for the device's CU count only
 cus = cus_fixture("amm")
 
-Row = collections.namedtuple("Row", "symbol kind tile edge bias relu")
+
+class Row(collections.namedtuple("Row", "symbol kind tile edge bias relu")):
+    __slots__ = ()
+
+    def cases(self, cu_count):
+        """The row's cases (a GEMM row: those of its (tile, guarded) class; a quantiser row: (rows, cols, vector path))."""
+        if self.kind == "gemm":
+            return gemm_cases(self.tile, self.edge, cu_count)
+        wide = self.symbol.endswith("<true>")
+        return [c for c in quant_cases() if (c[1] >= 1024) == wide] if self.kind == "rows" else []
+
+
 _B = {False: "false", True: "true"}
 Q8_INSTANTIATIONS = [Row(f"qlinear_s8_kernel<{t},{t},{t // 32},{_B[e]},{_B[b]},{_B[r]}>", "gemm", t, e, b, r)
                      for t in (128, 256) for e in (False, True) for b in (False, True) for r in (False, True)]
@@ -32,9 +50,27 @@ Q8_INSTANTIATIONS += [Row("quantize_rows_s8_kernel<false>", "rows", 0, False, Fa
 
 SHAPES_128 = {False: [(128, 128, 128), (128, 128, 64)], True: [(129, 130, 131), (5, 3, 7), (1, 1, 1)]}
 IN_256 = 192
-# stand-alone quantiser / weight shapes: wave per row (1, 1023 columns), workgroup per row (1024, 5000), and a row longer than
-# the workgroup form keeps in LDS (16392 > 16380: its rest is read again)
+# stand-alone quantiser / weight shapes (rows x cols).  Wave per row: 1 - 5 and 1023 columns (five rows: the last one alone in
+# a second workgroup); workgroup per row from 1024 on, with and without columns behind the last float4, and on both sides of
+# the 16380 floats the workgroup form keeps in LDS (a longer row's rest is read again)
 ALONE = [(3, 1), (7, 1023), (4, 1024), (2, 5000), (2, 16392)]
+ALONE += [(5, 3), (1, 4), (2, 5)]
+ALONE += [(2, 1025), (5, 1027), (2, 5003), (5, 16379), (1, 16380), (2, 16381), (5, 16383), (1, 16384), (2, 16393), (5, 20001)]
+
+# ---- the GEMM rows' case table ----------------------------------------------------------------------------------------------
+# a slice is 128 bytes and a loop trip two slices: trips 1 .. 4, the odd slice of the last pair empty, one byte, full; tails
+# that are no multiple of 64, 16 or 4
+KS_Q8 = (1, 3, 4, 15, 16, 17, 63, 64, 65, 127, 128, 129, 255, 256, 257, 385, 512, 513, 641, 777)
+KS_256 = (129, 257, 513, 777)
+KS_256_EDGE = (192, 129, 257, 385, 513, 641, 777)
+THIN = (1, 3, 4, 5, 15, 16, 17)   # last tiles: y's stores go in 4 columns, the transposer in 16 rows
+
+# (ldx_pad, ldy_pad, off_x, off_y): floats behind a row of x / y, floats between the allocation and the base
+Case = collections.namedtuple("Case", "rows out in_ ldx_pad ldy_pad off_x off_y")
+WHOLE_LAYOUT, EDGE_LAYOUT = (4, 4, 4, 4), (3, 1, 1, 1)
+# whole tiles need ldy % 4 == 0 and a 16-byte aligned y; x only decides the quantiser's path.  The first is fully dense
+WHOLE_LAYOUTS = ((0, 0, 0, 0), (4, 4, 4, 4), (3, 0, 1, 4), (1, 4, 2, 0), (0, 4, 0, 4))
+GEMM_CLASSES = [(t, e) for t in (128, 256) for e in (False, True)]
 
 
 def shapes_256(cu_count):
@@ -49,6 +85,82 @@ def shapes_256(cu_count):
     m, n = 256 * best[0], 256 * best[1]
     assert R.big_tile(m - 3, n - 5, cu_count)
     return (m, n, IN_256), (m - 3, n - 5, IN_256)
+
+
+def thin_256(a, b, cu_count):
+    """(rows, out) of the fewest elements that i8_big_tile sends to the 256x256 tile with a last tile `a` rows high and `b`
+    columns wide.  (One tile row and column more than shapes_256's shape, not its neighbour a + 256 by b + 256 short of the
+    next multiple: that one fills fewer 128x128 rounds and goes to the small tile.)"""
+    best = None
+    for i in range(1, 34):
+        for j in range(i, 66):
+            rows, out = 256 * (i - 1) + a, 256 * (j - 1) + b
+            if R.big_tile(rows, out, cu_count) and (best is None or rows * out < best[0] * best[1]):
+                best = (rows, out)
+    assert best and R.big_tile(best[0], best[1], cu_count), (a, b, cu_count)
+    return best
+
+
+def gemm_cases(tile, edge, cu_count):
+    """The Cases of a (tile, guarded) class; the same number on every device."""
+    cases = []
+    if tile == 128 and not edge:
+        cases += [Case(*s, *WHOLE_LAYOUT) for s in SHAPES_128[False]]
+        cases += [Case(128, 128, k, *WHOLE_LAYOUTS[i % 5]) for i, k in enumerate(KS_Q8)]
+        # grids: 9 tiles (no multiple of the 8 XCDs), 1 x 17, 17 x 1
+        cases += [Case(384, 384, 64, *WHOLE_LAYOUT), Case(128, 2176, 64, *WHOLE_LAYOUTS[0]), Case(2176, 128, 64, *WHOLE_LAYOUTS[2])]
+    elif tile == 128:
+        cases += [Case(*s, *EDGE_LAYOUT) for s in SHAPES_128[True]]
+        cases += [Case(128 + THIN[i % 7], 128 + THIN[(i + 3) % 7], k, (3, 0, 4, 1)[i % 4], (1, 2, 3)[i % 3], (1, 0, 4, 2)[i % 4], i % 2)
+                  for i, k in enumerate(KS_Q8)]
+        cases += [Case(128, 128, 64, 4, 1, 4, 0),              # guarded on whole tiles by an odd ldy alone, the base aligned
+                  Case(637, 379, 65, *EDGE_LAYOUT),            # 5 x 3 tiles
+                  Case(100, 2177, 64, 0, 2, 0, 1), Case(2177, 100, 64, 4, 3, 4, 0)]   # 1 x 18, 18 x 1
+    elif not edge:
+        m, n, _ = shapes_256(cu_count)[0]
+        cases += [Case(m, n, IN_256, *WHOLE_LAYOUT)]
+        cases += [Case(m, n, k, *WHOLE_LAYOUTS[i]) for i, k in enumerate(KS_256)]
+    else:
+        (m, n, _), ragged = shapes_256(cu_count)
+        cases += [Case(*ragged, *EDGE_LAYOUT)]
+        cases += [Case(*thin_256(THIN[i], THIN[(i + 3) % 7], cu_count), k, (3, 0, 4, 1)[i % 4], (1, 2, 3)[i % 3], (1, 0, 4, 2)[i % 4], i % 2)
+                  for i, k in enumerate(KS_256_EDGE)]
+        cases += [Case(m, n, IN_256, 4, 1, 4, 0)]
+    return cases
+
+
+def quant_cases():
+    """(rows, cols, vector path) of the stand-alone row quantiser: every shape of ALONE on both paths."""
+    return [(rows, cols, aligned) for aligned in (True, False) for rows, cols in ALONE]
+
+
+def layout_of(c):
+    """(ldx, ldy, x's base modulo 16, y's) of a Case."""
+    return c.in_ + c.ldx_pad if c.in_ else 4, c.out + c.ldy_pad, 4 * c.off_x % 16, 4 * c.off_y % 16
+
+
+def every_slice_matters(qx, qw):
+    """Zeroing any one 128-byte slice of qx changes at least 99 % of the sums (of the first 128 x 128 of them)."""
+    qx, qw = qx[:128], qw[:128]
+    for k0 in range(0, qx.shape[1], 128):
+        unchanged = float((R.int_sums(qx[:, k0:k0 + 128], qw[:, k0:k0 + 128]) == 0).mean())
+        assert unchanged <= 0.01, (qx.shape, qw.shape, k0, unchanged)
+
+
+@functools.lru_cache(maxsize=1)
+def deep_problem(rows, out, in_):
+    """problem()'s distributions; the last column of every row of x and of w is plus or minus that row's maximum (a dropped
+    last byte moves every sum by 127^2).  Asserts on the host that every slice matters."""
+    rng = np.random.default_rng(rows * 7 + out * 3 + in_ + 1)
+    x = (rng.standard_normal((rows, in_)) * 3).astype(np.float32)
+    w = rng.uniform(-0.5, 0.5, (out, in_)).astype(np.float32)
+    bias = rng.uniform(-4, 4, out).astype(np.float32)
+    for v in (x, w):
+        v[:, -1] = np.abs(v).max(axis=1) * rng.choice(np.array([-1, 1], np.float32), v.shape[0])
+    qx, _, rx = R.quantize_rows_ref(x)
+    qw, _, rw = R.quantize_rows_ref(w)
+    every_slice_matters(qx, qw)
+    return x, w, bias, (R.int_sums(qx, qw), rx, rw)
 
 
 @functools.lru_cache(maxsize=4)
@@ -80,31 +192,41 @@ def weight_of(key, w):
     return _weights[key]
 
 
-def run(qw, x, bias, relu, guarded, off=None):
-    """qlinear on padded operands: guarded -- odd leading dimensions, bases 4 bytes past 16-byte alignment; else leading
-    dimensions that are multiples of 4 floats past the row, 16-byte aligned bases.  Returns (y's window, nothing outside it
-    was written, the launch text)."""
+def _layout(guarded, off=None):
+    """EDGE_LAYOUT -- odd leading dimensions, bases 4 bytes past 16-byte alignment -- or WHOLE_LAYOUT -- leading dimensions
+    that are multiples of 4 floats past the row, 16-byte aligned bases; `off`: both bases that many floats in instead."""
+    lay = EDGE_LAYOUT if guarded else WHOLE_LAYOUT
+    return lay if off is None else (lay[0], lay[1], off, off)
+
+
+def run(qw, x, bias, relu, ldx_pad, ldy_pad, off_x, off_y, bias_off=0):
+    """qlinear on NaN-padded operands: ldx_pad / ldy_pad floats behind every row of x / y, the bases off_x / off_y floats
+    into their allocations, the bias bias_off floats into its own.  Returns (y's window, nothing outside it was written, the
+    launch text)."""
     import torch
     from how_to_optimize_gemm_amd import q8
     rows, in_ = x.shape
     out = qw.out_features
-    off = (1 if guarded else 4) if off is None else off
-    ldx = in_ + (3 if guarded else 4) if in_ else 4
-    ldy = out + (1 if guarded else 4)
-    _, xv = _padded(rows, in_, ldx, off, x)
-    yflat, yv = _padded(rows, out, ldy, off)
-    q8.qlinear(xv[:, :in_], qw, None if bias is None else torch.from_numpy(bias).cuda(), "relu" if relu else None, out=yv[:, :out])
+    ldx = in_ + ldx_pad if in_ else 4
+    ldy = out + ldy_pad
+    _, xv = _padded(rows, in_, ldx, off_x, x)
+    yflat, yv = _padded(rows, out, ldy, off_y)
+    db = None
+    if bias is not None:
+        db = torch.full((bias_off + out + 4,), float("nan"), device="cuda")[bias_off:bias_off + out]
+        db.copy_(torch.from_numpy(bias))
+    q8.qlinear(xv[:, :in_], qw, db, "relu" if relu else None, out=yv[:, :out])
     launched = q8.last_launch()
     torch.cuda.synchronize()
-    untouched = bool(torch.isnan(yv[:, out:]).all()) and bool(torch.isnan(yflat[:off]).all()) and \
-        bool(torch.isnan(yflat[off + rows * ldy:]).all())
+    untouched = bool(torch.isnan(yv[:, out:]).all()) and bool(torch.isnan(yflat[:off_y]).all()) and \
+        bool(torch.isnan(yflat[off_y + rows * ldy:]).all())
     return yv[:, :out].cpu().numpy(), untouched, launched
 
 
 def check(shape, bias, relu, guarded, symbol, cu_count, off=None):
     rows, out, in_ = shape
     x, w, b, (acc, rx, rw) = problem(*shape)
-    got, untouched, launched = run(weight_of(shape, w), x, b if bias else None, relu, guarded, off)
+    got, untouched, launched = run(weight_of(shape, w), x, b if bias else None, relu, *_layout(guarded, off))
     want = R.epilogue_ref(acc, rx, rw, b if bias else None, relu)
     assert symbol in launched, (shape, symbol, launched)
     assert same_bits(got, want), (shape, launched, first_difference(got, want))
@@ -127,6 +249,83 @@ def test_every_instantiation_is_reached_and_is_the_contract(row, cus):
         assert launched == text
 
 
+def check_case(c, x, w, b, acc, rx, rw, qw, row, cu_count, bias_off=0):
+    """One Case in one epilogue: the launch is the row's symbol and the plan's text, y is the contract, nothing else is written."""
+    got, untouched, launched = run(qw, x, b if row.bias else None, row.relu, *c[3:], bias_off=bias_off)
+    want = R.epilogue_ref(acc, rx, rw, b if row.bias else None, row.relu)
+    text, _ = R.plan_text(c.rows, c.out, c.in_, *layout_of(c), row.bias, row.relu, cu_count)
+    assert row.symbol in launched and launched == text, (c, row.symbol, launched, text)
+    assert same_bits(got, want), (c, launched, first_difference(got, want))
+    assert untouched, (c, launched, "wrote outside y's window")
+
+
+def rows_of(tile, edge):
+    return [r for r in Q8_INSTANTIATIONS if r.kind == "gemm" and (r.tile, r.edge) == (tile, edge)]
+
+
+@pytest.mark.parametrize("tile,edge,index", [(t, e, i) for t, e in GEMM_CLASSES for i in range(len(gemm_cases(t, e, 256)))],
+                         ids=lambda v: {False: "whole", True: "guarded"}[v] if isinstance(v, bool) else str(v))
+def test_every_case_of_the_table_is_the_contract_in_its_four_epilogues(tile, edge, index, cus):
+    """K depth and tails, thin last tiles, grids, leading dimensions and bases (gemm_cases) on deep_problem's inputs."""
+    import torch
+    from how_to_optimize_gemm_amd import q8
+    cases = gemm_cases(tile, edge, cus)
+    assert len(cases) == len(gemm_cases(tile, edge, 256))
+    c = cases[index]
+    x, w, b, (acc, rx, rw) = deep_problem(c.rows, c.out, c.in_)
+    qw = q8.QWeight(torch.from_numpy(w).cuda())
+    for row in rows_of(tile, edge):
+        check_case(c, x, w, b, acc, rx, rw, qw, row, cus)
+    qw.close()
+
+
+@pytest.mark.parametrize("edge", [False, True], ids=["whole", "guarded"])
+def test_a_bias_four_bytes_past_alignment(edge, cus):
+    """The header allows any 4-byte aligned bias: a unit-stride view that starts 4 bytes past a 16-byte boundary."""
+    import torch
+    from how_to_optimize_gemm_amd import q8
+    c = Case(128, 128, 257, *WHOLE_LAYOUT) if not edge else Case(133, 143, 257, *EDGE_LAYOUT)
+    x, w, b, (acc, rx, rw) = deep_problem(c.rows, c.out, c.in_)
+    qw = q8.QWeight(torch.from_numpy(w).cuda())
+    for row in rows_of(128, edge):
+        if row.bias:
+            check_case(c, x, w, b, acc, rx, rw, qw, row, cus, bias_off=1)
+    qw.close()
+
+
+# (rows, out, in), the quantiser's path: the workgroup-per-row quantiser feeding the GEMM -- at its first width, with columns
+# behind the last float4, and beyond what it keeps in LDS (whole tiles on the vector path; the scalar path, 79 loop trips)
+WIDE_LAYER = [((5, 3, 1024), True), ((5, 3, 1024), False), ((130, 70, 1027), True), ((130, 70, 1027), False),
+              ((128, 128, 16393), True), ((129, 130, 20001), False)]
+
+
+@pytest.mark.parametrize("shape,vector", WIDE_LAYER, ids=lambda v: "x".join(map(str, v)) if isinstance(v, tuple) else ("scalar", "vector")[v])
+def test_the_wide_row_quantiser_feeds_the_gemm(shape, vector, cus):
+    """Ordinary random data through quantize_rows_s8_kernel<true> and the GEMM; in the long shapes one row of x (and one channel
+    of w) has NaN, +inf, -inf, -0.0 and its maximum in columns the quantiser does not keep in LDS."""
+    import torch
+    from how_to_optimize_gemm_amd import q8
+    rows, out, in_ = shape
+    rng = np.random.default_rng(in_ + rows)
+    x = (rng.standard_normal((rows, in_)) * 3).astype(np.float32)
+    w = rng.uniform(-0.5, 0.5, (out, in_)).astype(np.float32)
+    b = rng.uniform(-4, 4, out).astype(np.float32)
+    if in_ > 16384:
+        for v, r, top in ((x, rows - 2, 40.0), (w, 1, -2.0)):
+            v[r, 16380:16384] = [np.nan, np.inf, -np.inf, -0.0]
+            v[r, in_ - 1] = top
+            assert np.abs(v[r, :16380]).max() < abs(top)
+    c = Case(rows, out, in_, -in_ % 4, 4, 4, 4) if vector else Case(rows, out, in_, *EDGE_LAYOUT)
+    qw = q8.QWeight(torch.from_numpy(w).cuda())
+    for bias, relu in ((None, False), (b, True)):
+        got, untouched, launched = run(qw, x, bias, relu, *c[3:])
+        text, _ = R.plan_text(rows, out, in_, *layout_of(c), bias is not None, relu, cus)
+        assert launched == text and launched.startswith(f"quantize_rows_s8_kernel<true> ({'vector' if vector else 'scalar'} path)"), launched
+        want = R.qlinear_ref(x, w, bias, relu)
+        assert same_bits(got, want) and untouched, (launched, first_difference(got, want))
+    qw.close()
+
+
 def test_operands_four_bytes_past_alignment_take_the_guarded_tile_and_the_scalar_quantiser(cus):
     """A whole-tile shape with multiple-of-4 leading dimensions whose x and y start 4 bytes past a 16-byte boundary."""
     launched = check((128, 128, 64), True, True, False, "qlinear_s8_kernel<128,128,4,true,true,true>", cus, off=1)
@@ -142,7 +341,7 @@ def test_an_empty_inner_dimension_is_the_formula_on_zero_sums(cus):
     bias = np.array([1.5, -0.0, -2.0], np.float32)
     qw = q8.QWeight(_padded(3, 0, 4, 4)[1][:, :0])   # (a (3, 0) window with a row stride: numpy's own has stride 0)
     for b, relu in ((None, False), (bias, False), (bias, True)):
-        got, untouched, _ = run(qw, x, b, relu, True)
+        got, untouched, _ = run(qw, x, b, relu, *EDGE_LAYOUT)
         want = R.qlinear_ref(x, w, b, relu)
         assert same_bits(got, want) and untouched, (relu, got, want)
     assert same_bits(R.qlinear_ref(x, w, bias, True), np.tile(np.array([1.5, 0.0, 0.0], np.float32), (4, 1)))
@@ -165,12 +364,36 @@ def test_large_sums_round_to_nearest_even(cus):
     acc, rx, rw = parts(x, w)
     assert (np.abs(acc) > 1 << 24).sum() > 1000 and (acc.astype(np.float32).astype(np.int64) != acc).sum() > 1000
     check_large(x, w, acc, rx, rw)
+    # the same below -2^24: every other channel of w negated
+    w[::2] = -w[::2]
+    acc, rx, rw = parts(x, w)
+    low = acc < -(1 << 24)
+    assert low.sum() > 1000 and (acc.astype(np.float32).astype(np.int64) != acc)[low].sum() > 1000
+    check_large(x, w, acc, rx, rw)
+
+
+def test_special_values_in_the_bias(cus):
+    """+inf, -inf, NaN, -0.0 and +0.0 as biases of non-zero sums, with and without ReLU (NaN stays, -inf and -0.0 give +0)."""
+    import torch
+    from how_to_optimize_gemm_amd import q8
+    rng = np.random.default_rng(17)
+    x = rng.standard_normal((9, 40)).astype(np.float32)
+    w = rng.uniform(-1, 1, (11, 40)).astype(np.float32)
+    bias = rng.uniform(-1, 1, 11).astype(np.float32)
+    bias[[0, 2, 4, 6, 8]] = [np.inf, -np.inf, np.nan, -0.0, 0.0]
+    assert np.count_nonzero(parts(x, w)[0]) > 90
+    qw = q8.QWeight(torch.from_numpy(w).cuda())
+    for relu in (False, True):
+        got, untouched, launched = run(qw, x, bias, relu, *EDGE_LAYOUT)
+        want = R.qlinear_ref(x, w, bias, relu)
+        assert same_bits(got, want) and untouched, (launched, first_difference(got, want))
+        assert np.isnan(want[:, 4]).all() and (want[:, 2] == (0 if relu else -np.inf)).all()
 
 
 def check_large(x, w, acc, rx, rw):
     import torch
     from how_to_optimize_gemm_amd import q8
-    got, untouched, launched = run(q8.QWeight(torch.from_numpy(w).cuda()), x, None, False, False)
+    got, untouched, launched = run(q8.QWeight(torch.from_numpy(w).cuda()), x, None, False, *WHOLE_LAYOUT)
     want = R.epilogue_ref(acc, rx, rw)
     assert same_bits(got, want) and untouched, (launched, first_difference(got, want))
 
@@ -187,7 +410,7 @@ def test_special_values_as_activation_rows_and_as_weight_channels(cus):
         b = bias[:w.shape[0]]
         qw = q8.QWeight(torch.from_numpy(w).cuda())
         for relu in (False, True):
-            got, untouched, launched = run(qw, x, b, relu, True)
+            got, untouched, launched = run(qw, x, b, relu, *EDGE_LAYOUT)
             want = R.qlinear_ref(x, w, b, relu)
             assert same_bits(got, want) and untouched, (launched, first_difference(got, want))
 
@@ -197,8 +420,12 @@ def _quant_input(rows, cols, seed):
     x = (rng.standard_normal((rows, cols)) * 2).astype(np.float32)
     if cols >= 9:
         x[0, :9] = [np.nan, np.inf, -np.inf, 0.0, -0.0, 1e-38, -1e-38, 5.0, -5.0]
+    if cols > 9:   # the same at the end of the row, where a long row is not kept in LDS, with the row's maximum in the last column
+        x[0, -9:] = [np.nan, np.inf, -np.inf, 0.0, -0.0, 1e-38, -1e-38, 50.0, -50.0]
     if rows > 1:
         x[1] = 0.0
+    if cols > 9 and rows > 2:   # a later row: ordinary data, the maximum in the last column
+        x[rows - 1, -1] = 100.0
     return x
 
 
@@ -220,11 +447,13 @@ def test_the_row_quantiser_alone(rows, cols, aligned):
     q, s, r = q8.quantize_rows(xv[:, :cols], out=qv[:, :cols])
     launched = q8.last_launch()
     torch.cuda.synchronize()
-    assert launched == f"quantize_rows_s8_kernel<{_B[cols >= 1024]}> ({'vector' if aligned else 'scalar'} path), " \
+    # (a one-row tensor has no row stride: the binding passes its width as the leading dimension, and nothing lies behind the row)
+    vector = aligned and (rows > 1 or cols % 4 == 0)
+    assert launched == f"quantize_rows_s8_kernel<{_B[cols >= 1024]}> ({'vector' if vector else 'scalar'} path), " \
                        f"{rows if cols >= 1024 else (rows + 3) // 4} workgroups"
     wq, ws, wr = R.quantize_rows_ref(x)
     got = qv.cpu().numpy()
-    pad_to = min(ldq, pitch)
+    pad_to = min(ldq, pitch) if rows > 1 else cols
     assert np.array_equal(got[:, :cols], wq) and not got[:, cols:pad_to].any() and (got[:, pad_to:] == 0x55).all()
     flat = qflat.cpu().numpy()
     assert (flat[:off] == 0x55).all() and (flat[off + rows * ldq:] == 0x55).all()
@@ -234,7 +463,8 @@ def test_the_row_quantiser_alone(rows, cols, aligned):
     assert np.array_equal(q2.cpu().numpy(), wq) and same_bits(s2.cpu().numpy(), ws) and same_bits(r2.cpu().numpy(), wr)
 
 
-@pytest.mark.parametrize("out,in_", ALONE + [(130, 70)])
+# (the image is in_ x out rounded up to 16 bytes: shapes whose image stays below 4 MB)
+@pytest.mark.parametrize("out,in_", [s for s in ALONE + [(130, 70)] if s[1] * ((s[0] + 15) & ~15) < 4 << 20])
 @pytest.mark.parametrize("aligned", [True, False], ids=["vector", "scalar"])
 def test_the_weight_image_alone(out, in_, aligned):
     """QWeight: the image is the per-channel quantisation transposed, pad columns 0; scale and inv_scale per channel."""
@@ -262,7 +492,7 @@ def test_one_weight_serves_calls_of_different_rows_and_grows_its_scratch(cus):
     qw.reserve(16)
     for rows in (16, 3, 200):   # (200: past what was reserved, eagerly)
         x = rng.standard_normal((rows, 50)).astype(np.float32)
-        got, untouched, launched = run(qw, x, bias, True, True)
+        got, untouched, launched = run(qw, x, bias, True, *EDGE_LAYOUT)
         want = R.qlinear_ref(x, w, bias, True)
         assert same_bits(got, want) and untouched, (rows, launched, first_difference(got, want))
 
@@ -408,3 +638,70 @@ def test_the_module_is_the_contract_and_lies_within_the_quantisation_bound():
         layer(x.clone().requires_grad_())
     with pytest.raises(H.MMultError):
         q8.QLinear(96, 80)(x)   # no weight prepared
+
+
+def test_reserve_sizes_the_scratch_for_a_captured_call_larger_than_any_eager_one():
+    """What QWeight.reserve is for: an eager 8-row call loads the kernels (8 and 64 rows are both guarded: one instantiation),
+    reserve(64), then a 64-row call that never ran eagerly is captured and replayed twice on new x."""
+    import torch
+    from how_to_optimize_gemm_amd import q8
+    rng = np.random.default_rng(29)
+    w = rng.uniform(-1, 1, (40, 36)).astype(np.float32)
+    qw = q8.QWeight(torch.from_numpy(w).cuda())
+    xs, xl = torch.zeros((8, 36), device="cuda"), torch.zeros((64, 36), device="cuda")
+    ys, yl = torch.full((8, 40), float("nan"), device="cuda"), torch.full((64, 40), float("nan"), device="cuda")
+    side = _side_stream()
+    with torch.cuda.stream(side):
+        q8.qlinear(xs, qw, out=ys)   # the eager warm-up: sizes the scratch for 8 rows
+    side.synchronize()
+    with torch.cuda.stream(side):
+        qw.reserve(64)
+    side.synchronize()
+    graph = _capture(side, lambda: q8.qlinear(xl, qw, out=yl))
+    for rep in range(2):
+        a = (rng.standard_normal((64, 36)) * (rep + 1)).astype(np.float32)
+        xl.copy_(torch.from_numpy(a))
+        yl.fill_(float("nan"))
+        graph.replay()
+        torch.cuda.synchronize()
+        got, want = yl.cpu().numpy(), R.qlinear_ref(a, w)
+        assert same_bits(got, want), (rep, first_difference(got, want))
+    del graph
+
+
+def test_time_qlinear_leaves_the_contract_in_y_and_returns_a_time(cus):
+    import torch
+    from how_to_optimize_gemm_amd import q8
+    rng = np.random.default_rng(31)
+    x = rng.standard_normal((37, 300)).astype(np.float32)
+    w = rng.uniform(-1, 1, (50, 300)).astype(np.float32)
+    bias = rng.uniform(-1, 1, 50).astype(np.float32)
+    qw, dx, db = q8.QWeight(torch.from_numpy(w).cuda()), torch.from_numpy(x).cuda(), torch.from_numpy(bias).cuda()
+    y = torch.full((37, 50), float("nan"), device="cuda")
+    ms = q8.time_qlinear(dx, qw, db, "relu", out=y, warmup=1, reps=3)
+    torch.cuda.synchronize()
+    got, want = y.cpu().numpy(), R.qlinear_ref(x, w, bias, True)
+    assert same_bits(got, want), first_difference(got, want)
+    assert math.isfinite(ms) and ms > 0, ms
+
+
+def test_the_module_takes_a_strided_last_dimension_and_a_vector():
+    """QLinear.forward: an input whose last dimension is not unit stride goes through contiguous(); a 1-D input of in_features
+    gives a 1-D output."""
+    import torch
+    from how_to_optimize_gemm_amd import q8
+    torch.manual_seed(6)
+    linear = torch.nn.Linear(96, 80).cuda()
+    layer = q8.QLinear.from_float(linear, activation="relu")
+    wn, bn = linear.weight.detach().cpu().numpy(), linear.bias.detach().cpu().numpy()
+    x = torch.randn(96, 10, device="cuda").t()
+    assert tuple(x.shape) == (10, 96) and x.stride(1) != 1
+    y = layer(x)
+    assert tuple(y.shape) == (10, 80)
+    want = R.qlinear_ref(x.cpu().numpy(), wn, bn, True)
+    assert same_bits(y.cpu().numpy(), want), first_difference(y.cpu().numpy(), want)
+    v = torch.randn(96, device="cuda")
+    y = layer(v)
+    assert tuple(y.shape) == (80,)
+    want = R.qlinear_ref(v.cpu().numpy()[None, :], wn, bn, True)[0]
+    assert same_bits(y.cpu().numpy(), want), first_difference(y.cpu().numpy(), want)

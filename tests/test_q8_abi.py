@@ -5,6 +5,7 @@ import ctypes as C
 import itertools
 import os
 import struct
+import threading
 
 import pytest
 
@@ -62,7 +63,12 @@ def test_every_prototype_binds():
     assert q8.PROTOTYPES["mmh_q8_weight_create"] == (_I, [_P, _I, _I, _I, _P, _I, _P])        # mmh_q8_weight_t *
     assert q8.PROTOTYPES["mmh_q8_linear_plan"] == (_I, [_I] * 10 + [_S, _I, _P])
     assert q8.PROTOTYPES["mmh_q8_last_launch"] == (_S, [])
-    assert L.mmh_q8_last_launch() == b"" and b"gfx950" in open(q8.LIB_PATH, "rb").read()
+    # (the launch text is per thread: a thread that has launched nothing reads "", whatever this one ran before)
+    fresh = []
+    reader = threading.Thread(target=lambda: fresh.append(L.mmh_q8_last_launch()))
+    reader.start()
+    reader.join()
+    assert fresh == [b""] and b"gfx950" in open(q8.LIB_PATH, "rb").read()
 
 
 ROWS = (1, 5, 128, 129, 512, 2048, 2560, 4096)
