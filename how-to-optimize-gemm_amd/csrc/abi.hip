@@ -303,6 +303,7 @@ int mmh_set_option(mmh_handle_t h, int option, int value) {
       h->dma_dword_rows = value >= 2 ? 1 : 0;
       return MMH_OK;
     case MMH_OPT_RETIRED_BUFFERS:   // read-only
+    case MMH_OPT_WARMED:            // read-only
     default:
       return MMH_ERR_INVALID_ARG;
   }
@@ -339,6 +340,7 @@ int mmh_get_option(mmh_handle_t h, int option, int *value) {
     }
     case MMH_OPT_DMA_EDGE: *value = h->dma_edge ? (h->dma_dword_rows ? 2 : 1) : 0; return MMH_OK;
     case MMH_OPT_RETIRED_BUFFERS: *value = (int)h->retired.size(); return MMH_OK;   // (host state: no synchronisation)
+    case MMH_OPT_WARMED: *value = h->warmed ? 1 : 0; return MMH_OK;
     default:
       return MMH_ERR_INVALID_ARG;
   }

@@ -312,6 +312,10 @@ int mmh_kernel_id(const char *short_name);
  * set, pinned phase-order tables, the partial-row workspace of mmh_relu_grad_colsum, the int8 / quantisation scratch.  0 on a
  * handle that never captured, whatever sizes it ran; get does not synchronise. */
 #define MMH_OPT_RETIRED_BUFFERS 15
+/* MMH_OPT_WARMED (diagnostic, read-only: set is MMH_ERR_INVALID_ARG): 1 once the handle has been warmed -- by mmh_create or
+ * mmh_warm --, 0 on a handle created with MMH_LAZY=1 that has not been yet: its launches opt in, query and allocate as they
+ * go, and launch what a warmed handle launches (tests/test_gpu_cold_start.py).  get does not synchronise. */
+#define MMH_OPT_WARMED 16
 int mmh_set_option(mmh_handle_t handle, int option, int value);
 /* The two tables of a phase-ordered stream-K launch (MMH_OPT_STREAMK_ORDER) for `tiles` tile slots of `nk`
  * K-slices on `grid` persistent workgroups, computed on the host (no device needed): order[grid] = the range

@@ -16,6 +16,7 @@ captured mmh_quantize_sym_s8 with max|x| = 100, 60, 80, 40, 90 over five replays
 times.  The words are now zeroed by a device copy of a zero block (csrc/igemm.hip, zero_amax); three replays on new data per
 form are what holds that."""
 import ctypes
+import gc
 
 import numpy as np
 import pytest
@@ -199,7 +200,14 @@ def _eager(mm, side, ops, rng, what="eager"):
 
 
 def _capture(side, body):
+    """The graph of body() captured on `side`.  No CUDAGraph may die while a stream is capturing: destroying one there took the
+    whole pytest process down (an abort inside the collector, which _captured_nodes' set of thousands of strings tends to start
+    during the capture).  `del graph` does not free the graph of a body that keeps its `pytest.raises(...) as e`: e holds the
+    traceback, that holds body's frame and through f_back this frame and its `graph` -- a dead cycle only the collector frees,
+    at a time of its choosing.  So such bodies end with `del e`, and whatever other tests left behind is collected here, before
+    the capture begins (torch.cuda.graph did that itself until it became an option)."""
     import torch
+    gc.collect()
     graph = torch.cuda.CUDAGraph()
     with torch.cuda.stream(side):
         with torch.cuda.graph(graph, stream=side):
@@ -351,6 +359,7 @@ def _refused_and_disturbs_nothing(small, large, seed):
                 large.call(own)
             nodes.append(_captured_nodes(side))
             nodes.append(e.value.status)
+            del e   # (see _capture)
 
         graph = _capture(side, body)
         assert nodes[2] == H.ERR_UNSUPPORTED
@@ -402,6 +411,7 @@ def test_a_handle_without_scratch_refuses_a_captured_quantize():
                 op.call(own)
             seen.append(_captured_nodes(side))
             seen.append(e.value.status)
+            del e   # (see _capture)
 
         graph = _capture(side, body)
         assert seen[2] == H.ERR_UNSUPPORTED and seen[1] == seen[0]

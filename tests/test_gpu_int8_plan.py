@@ -64,6 +64,7 @@ def test_a_call_launches_its_plan_and_grows_the_scratch_the_plan_states(mm, kind
                 with pytest.raises(H.MMultError) as e:
                     op.call(own)
                 assert e.value.status == H.ERR_UNSUPPORTED
+                del e   # (tests/test_gpu_int8_graph.py _capture: no dead cycle may hold this capture's graph)
             else:
                 op.call(own)
             seen.append(_captured_nodes(side))

@@ -19,6 +19,7 @@ def opts(monkeypatch):
     """set(option, value) -> status and get(option) -> (status, value) on a fresh handle, plus the module."""
     import how_to_optimize_gemm_amd as H
     monkeypatch.delenv("MMH_NO_SK_ORDER", raising=False)   # (read at mmh_create: it would change MMH_OPT_STREAMK_ORDER's default)
+    monkeypatch.delenv("MMH_LAZY", raising=False)          # (read at mmh_create: MMH_OPT_WARMED would read 0)
     assert H.lib().mmh_is_ab_build() == 0
     mm = H.MMult(0, "auto")
 
@@ -97,8 +98,12 @@ def test_every_option_reads_back_what_set_made_of_the_value(opts):
         assert get(H.OPT_RETIRED_BUFFERS) == (H.OK, 0)
         for value in (0, 1, -1, INT_MAX, INT_MIN):
             refused(H, set_, get, H.OPT_RETIRED_BUFFERS, value)
+        # MMH_OPT_WARMED: read-only -- 1 on a handle mmh_create has warmed (0 only under MMH_LAZY=1, tests/test_gpu_cold_start.py)
+        assert get(H.OPT_WARMED) == (H.OK, 1)
+        for value in (0, 1, -1, INT_MAX, INT_MIN):
+            refused(H, set_, get, H.OPT_WARMED, value)
         # ids that are no option of the product: below and above the public ones, and the tools build's 100 .. 108
-        for option in [0, -1, 16, 17, 99, INT_MAX, INT_MIN] + list(range(100, 110)):
+        for option in [0, -1, 17, 18, 99, INT_MAX, INT_MIN] + list(range(100, 110)):
             for value in (0, 1):
                 assert set_(option, value) == H.ERR_INVALID_ARG, (option, value)
             assert get(option) == (H.ERR_INVALID_ARG, -12345), option
@@ -110,7 +115,7 @@ def test_every_option_reads_back_what_set_made_of_the_value(opts):
         set_(H.OPT_DMA_EDGE, 2)
         set_(H.OPT_IGEMM_MODE, 0)
     defaults = {**{o: r[2] for o, r in ranges.items()}, **switches, H.OPT_DMA_EDGE: 2, H.OPT_IGEMM_MODE: 0,
-                H.OPT_STREAMK_TIMEOUTS: 0, H.OPT_STREAMK_DELEGATIONS: 0, H.OPT_RETIRED_BUFFERS: 0}
-    assert sorted(defaults) == list(range(1, 16))   # every public MMH_OPT_* was covered
+                H.OPT_STREAMK_TIMEOUTS: 0, H.OPT_STREAMK_DELEGATIONS: 0, H.OPT_RETIRED_BUFFERS: 0, H.OPT_WARMED: 1}
+    assert sorted(defaults) == list(range(1, 17))   # every public MMH_OPT_* was covered
     for option, default in defaults.items():
         assert get(option) == (H.OK, default), option

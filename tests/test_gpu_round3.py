@@ -261,6 +261,7 @@ def test_a_capture_never_borrows_another_streams_workspaces(oracle):
             except Exception:
                 pass                                     # an empty capture may not instantiate: not what is tested
         assert refused is not None and refused.status == H.ERR_UNSUPPORTED, refused
+        del refused   # (its traceback holds this frame: a dead cycle would keep `graph` until the collector runs, perhaps inside a later capture)
         torch.cuda.current_stream().wait_stream(side)
         h.reserve_stream(side.cuda_stream, m, n, k)
         graph = torch.cuda.CUDAGraph()

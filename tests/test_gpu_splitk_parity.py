@@ -389,6 +389,7 @@ def test_split_k_captures_into_a_graph_on_a_stream_with_a_set_of_its_own(oracle)
             except Exception:
                 pass                                   # an empty capture may not instantiate: not what is tested
         assert refused is not None and refused.status == H.ERR_UNSUPPORTED, refused
+        del refused   # (its traceback holds this frame: a dead cycle would keep `graph` until the collector runs, perhaps inside a later capture)
         torch.cuda.synchronize()
         assert bool(torch.isnan(c).all()), "a refused capture launched something"
         h.reserve_stream(side.cuda_stream, m, n, k)
