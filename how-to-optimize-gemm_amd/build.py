@@ -17,6 +17,8 @@ LIB = os.path.join(PKG_DIR, "libmmult_hip.so")
 AB_LIB = os.path.join(PKG_DIR, "libmmult_hip_ab.so")   # tools-only build: A/B variants + timing-only ablations
 CSRC_Q8 = os.path.join(PKG_DIR, "csrc_q8")
 Q8_LIB = os.path.join(PKG_DIR, "libmmult_hip_q8.so")   # the second product library: the int8 linear layer (include/mmult_hip_q8.h)
+CSRC_Q8O = os.path.join(PKG_DIR, "csrc_q8o")
+Q8O_LIB = os.path.join(PKG_DIR, "libmmult_hip_q8o.so")   # the third: the int8 layer with an int8 output (include/mmult_hip_q8o.h)
 HARNESS = os.path.join(PKG_DIR, "harness")
 ARCH = "gfx950"
 
@@ -118,6 +120,34 @@ def build_q8_library(force: bool = False, verbose: bool = False) -> str:
     return Q8_LIB
 
 
+def build_q8o_library(force: bool = False, verbose: bool = False) -> str:
+    """csrc_q8o/*.hip -> how-to-optimize-gemm_amd/libmmult_hip_q8o.so, with the q8 library's flags (-I csrc_q8o -I csrc_q8 -I csrc:
+    its kernels sit on csrc/'s int8 tile and quantisation rules).  Objects under build/q8o/; an object is stale when its .hip, a
+    header of csrc_q8o/, csrc_q8/ or csrc/, or a C header has changed.  At most 16 compile jobs at a time."""
+    from concurrent.futures import ThreadPoolExecutor
+    headers = [s for s in library_sources() if s.endswith((".hpp", ".h", ".inc"))]
+    headers += [os.path.join(REPO, "include", "mmult_hip_q8.h"), os.path.join(REPO, "include", "mmult_hip_q8o.h")]
+    for d in (CSRC_Q8, CSRC_Q8O):
+        headers += [os.path.join(d, f) for f in sorted(os.listdir(d)) if f.endswith(".hpp")]
+    tus = sorted(os.path.join(CSRC_Q8O, f) for f in os.listdir(CSRC_Q8O) if f.endswith(".hip"))
+    odir = os.path.join(PKG_DIR, "build", "q8o")
+    os.makedirs(odir, exist_ok=True)
+    flags = [f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-result", "-I" + CSRC_Q8O, "-I" + CSRC_Q8, "-I" + CSRC]
+    objs = [os.path.join(odir, os.path.basename(tu)[:-4] + ".o") for tu in tus]
+    jobs = [[hipcc()] + flags + ["-c", tu, "-o", obj] for tu, obj in zip(tus, objs) if force or _stale(obj, [tu] + headers)]
+    def run(cmd):
+        if verbose:
+            print(" ".join(cmd))
+        subprocess.check_call(cmd)
+    if jobs:
+        with ThreadPoolExecutor(max_workers=min(len(jobs), os.cpu_count() or 4, 16)) as pool:
+            list(pool.map(run, jobs))
+    version_script = os.path.join(CSRC_Q8O, "exports_q8o.map")
+    if force or jobs or _stale(Q8O_LIB, objs + [version_script]):
+        run([hipcc(), f"--offload-arch={ARCH}", "-shared", "-fPIC"] + objs + ["-o", Q8O_LIB, "-Wl,--version-script=" + version_script])
+    return Q8O_LIB
+
+
 def build_timeline_library(force: bool = False) -> str:
     """-DMMH_AB_BUILD -DMMH_DMA_TIMELINE -> libmmult_hip_tl.so: the A/B library whose plain LDS-DMA kernels
     also write per-workgroup wall-clock stamps (tools/dma_timeline.py only; the stamps perturb the
@@ -147,6 +177,7 @@ def build_harness(force: bool = False) -> str:
 def build_all(force: bool = False) -> None:
     build_library(force)
     build_q8_library(force)
+    build_q8o_library(force)
     if os.path.isdir(HARNESS):
         build_harness(force)
 

@@ -114,9 +114,16 @@ struct LdsDma {
 // library -- compiles to what was here before it.  A fused epilogue (csrc_q8/qlinear_s8.hpp) is told the lane's four
 // columns once per tile (ep.columns) and turns each transposed row vector into the bits to store (ep.row): behind the
 // transposer a lane holds four consecutive columns of one row, so it needs four column factors and one row factor.
+// An epilogue that declares `kStoresRows = true` (csrc_q8o/qlinear_s8o.hpp: four int8 per lane, not sixteen bytes) is handed
+// each transposed row vector with its row and first column and stores it itself (ep.store); the tile's own `put` is then unused.
+// The trait defaults to false for an epilogue that does not name it.
 struct I8NoEpilogue {
   static constexpr bool kFused = false;
 };
+template <class EP, class = void>
+struct I8EpStoresRows : std::false_type {};
+template <class EP>
+struct I8EpStoresRows<EP, std::void_t<decltype(EP::kStoresRows)>> : std::bool_constant<EP::kStoresRows> {};
 template <int BM, int BN, int TM, bool EDGE, int ABLATE, bool BTR = false, class EP = I8NoEpilogue>
 __device__ __forceinline__ void igemm_s8_dma_tile(int m, int n, int k, const int8_t *__restrict__ A, int lda,
                                                   const int8_t *__restrict__ Bt, int kp, int n_pad,
@@ -404,7 +411,8 @@ __device__ __forceinline__ void igemm_s8_dma_tile(int m, int n, int k, const int
       }
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
-        if constexpr (EP::kFused) put(drow + 16 * t + 4 * q, dcol, ep.row(out[q], drow + 16 * t + 4 * q, m, whole_c));
+        if constexpr (I8EpStoresRows<EP>::value) ep.store(out[q], drow + 16 * t + 4 * q, dcol, m, n, whole_c);
+        else if constexpr (EP::kFused) put(drow + 16 * t + 4 * q, dcol, ep.row(out[q], drow + 16 * t + 4 * q, m, whole_c));
         else put(drow + 16 * t + 4 * q, dcol, out[q]);
       }
     }

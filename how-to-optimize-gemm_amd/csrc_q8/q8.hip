@@ -1,6 +1,8 @@
 // q8.hip -- the host side of libmmult_hip_q8.so: the extern "C" entry points of include/mmult_hip_q8.h, the weight object and
 // its scratch, the row quantiser's and the weight image's launches.  The GEMM's instantiations live in qlinear_*.hip.
 // Every argument is checked before the first device call; every entry point that touches the device restores the caller's.
+#include <string.h>
+
 #include <new>
 #include <string>
 #include <vector>
@@ -224,6 +226,28 @@ int mmh_q8_linear(mmh_q8_weight_t w, int rows, const float *dX, int ldx, const f
   DeviceGuard guard;
   Q8_TRY(guard.enter(w->device));
   return linear_on(w, rows, dX, ldx, dBias, activation, dY, ldy, static_cast<hipStream_t>(stream));
+}
+
+int mmh_q8_linear_s8(mmh_q8_weight_t w, int rows, const int8_t *dXq, int ldq, const float *d_inv_scale, const float *dBias,
+                     int activation, float *dY, int ldy, void *stream) {
+  if (!w || rows < 0 || !act_ok(activation)) return MMH_ERR_INVALID_ARG;
+  if (rows == 0) return MMH_OK;
+  if ((w->in > 0 && !dXq) || !d_inv_scale || !dY || ldq < w->in || ldy < w->out) return MMH_ERR_INVALID_ARG;   // (in == 0: xq is not read)
+  if (w->in > 0 && !i8_dword(ldq, base16(dXq)))
+    return fail(MMH_ERR_UNSUPPORTED, "mmh_q8_linear_s8: the tile reads the int8 rows in dwords -- ldq and dXq's address must be multiples of 4");
+  if (!i8_window(ldq, w->pitch, w->in))
+    return fail(MMH_ERR_UNSUPPORTED, "mmh_q8_linear_s8: the int8 rows lie beyond the GEMM's 2 GiB descriptor window");
+  DeviceGuard guard;
+  Q8_TRY(guard.enter(w->device));
+  // the plan of the fp32 call on these rows, without its quantiser: the same tile, guard and grid, launched straight on dXq
+  const Q8Plan p = plan_qlinear(rows, w->out, w->in, w->in > 0 ? w->in : 1, ldy, 0, base16(dY), w->cus, dBias != nullptr, activation == MMH_ACT_RELU);
+  const QlinearArgs g{rows, w->out, w->in, dXq, ldq, w->q, w->pitch, d_inv_scale, w->inv_scale, dBias, activation == MMH_ACT_RELU ? 1 : 0,
+                      dY, ldy, p.nbm, p.nbn};
+  Q8_TRY(p.tile == 256 ? (p.edge ? launch_qlinear_256_edge(g, static_cast<hipStream_t>(stream)) : launch_qlinear_256(g, static_cast<hipStream_t>(stream)))
+                       : (p.edge ? launch_qlinear_128_edge(g, static_cast<hipStream_t>(stream)) : launch_qlinear_128(g, static_cast<hipStream_t>(stream))));
+  const char *then = strstr(p.text, "then ");
+  g_launch = then ? then + 5 : p.text;
+  return MMH_OK;
 }
 
 int mmh_q8_linear_reserve(mmh_q8_weight_t w, int max_rows, void *stream) {

@@ -1,0 +1,6 @@
+// qlinear_s8o_128_edge.hip -- qlinear_s8o_kernel<128,128,4,true> (see qlinear_s8o.hpp).  Part of libmmult_hip_q8o.so.
+#include "qlinear_s8o.hpp"
+
+namespace mmh {
+hipError_t launch_qlinear_s8o_128_edge(const QlinearS8oArgs &a, hipStream_t s) { return launch_qlinear_s8o_tile<128, true>(a, s); }
+}  // namespace mmh

@@ -1,0 +1,6 @@
+// qlinear_s8o_256.hip -- qlinear_s8o_kernel<256,256,8,false> (see qlinear_s8o.hpp).  Part of libmmult_hip_q8o.so.
+#include "qlinear_s8o.hpp"
+
+namespace mmh {
+hipError_t launch_qlinear_s8o_256(const QlinearS8oArgs &a, hipStream_t s) { return launch_qlinear_s8o_tile<256, false>(a, s); }
+}  // namespace mmh

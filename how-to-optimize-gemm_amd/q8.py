@@ -4,8 +4,13 @@
     qw = q8.QWeight(linear.weight.detach())            # once per layer: int8 image (transposed), one scale per output channel
     y = q8.qlinear(x, qw, bias, activation="relu")     # per call: one scale per row of x, int8 MFMA GEMM, fused epilogue
     layer = q8.QLinear.from_float(linear)              # the same as an inference-only torch.nn.Module
+    xq = q8.quantize(x)                                # a QRows: one quantisation for any number of weights (Q/K/V, gate/up)
+    y = q8.qlinear(xq, qw, bias)                       # ... straight into the GEMM: no quantiser pass
+    hq = q8.qlinear(xq, qw, bias, "relu", out_scale=s) # int8 out (libmmult_hip_q8o.so): the next layer's QRows, no fp32 round trip
+    mlp = q8.QMLP.from_float([fc1, fc2]); mlp.calibrate(x); y = mlp(x)    # one quantiser, int8 -> int8 hidden layers, fp32 out
 
-The binding is read from include/mmult_hip_q8.h (abi_header.parse); the numeric contract is in that header.  Everything runs
+The binding is read from include/mmult_hip_q8.h (abi_header.parse); the numeric contract is in that header.  The int8-output
+library is loaded on first use, its binding read from include/mmult_hip_q8o.h.  Everything runs
 on torch's current stream; there is no CPU path and no backward.  torch is imported on first use, not with this module.
 """
 from __future__ import annotations
@@ -53,6 +58,51 @@ def lib() -> C.CDLL:
         fn.restype, fn.argtypes = restype, argtypes
     _lib = L
     return L
+
+
+Q8O_HEADER = os.path.join(os.path.dirname(_abi.HEADER), "mmult_hip_q8o.h")
+Q8O_LIB_PATH = os.path.join(_api.PKG_DIR, "libmmult_hip_q8o.so")
+_lib_q8o = None
+
+
+def lib_q8o() -> C.CDLL:
+    """Load libmmult_hip_q8o.so (the int8-output layer) on first use, bound from its own header.  Fails loudly."""
+    global _lib_q8o
+    if _lib_q8o is not None:
+        return _lib_q8o
+    _api._share_hip_runtime_with_torch()
+    if not os.path.exists(Q8O_LIB_PATH):
+        raise MMultError(ERR_UNSUPPORTED, "load", f"{Q8O_LIB_PATH} is missing -- run __graft_entry__.build(); there is no CPU fallback")
+    L = C.CDLL(Q8O_LIB_PATH)
+    for name, (restype, argtypes) in _abi.parse(Q8O_HEADER)[1].items():
+        fn = getattr(L, name)
+        fn.restype, fn.argtypes = restype, argtypes
+    _lib_q8o = L
+    return L
+
+
+def _check_q8o(status: int, where: str) -> None:
+    if status != OK:
+        last = lib_q8o().mmh_q8o_last_error().decode()
+        detail = _STATUS_NAMES.get(status, "unknown status")
+        raise MMultError(status, where, f"{detail}; {last}" if last else detail)
+
+
+def last_launch_q8o() -> str:
+    """What the last int8-output qlinear on this thread launched."""
+    return lib_q8o().mmh_q8o_last_launch().decode()
+
+
+def qlinear_s8o_plan(rows: int, out_features: int, in_features: int, ldq: int = 0, pitch_n: int = 0, ldyq: int = 0, xq_mod4: int = 0,
+                     wq_mod4: int = 0, yq_mod4: int = 0, cu_count: int = 256) -> str:
+    """The launch text of an int8-output qlinear call.  Host arithmetic only.  ldq / pitch_n / ldyq 0: rows of the default
+    pitch (the length rounded up to 16)."""
+    p16 = lambda n: (n + 15) & ~15
+    text = C.create_string_buffer(128)
+    _check_q8o(lib_q8o().mmh_q8o_linear_plan(rows, out_features, in_features, ldq or p16(in_features), pitch_n or p16(out_features),
+                                             ldyq or p16(out_features), xq_mod4, wq_mod4, yq_mod4, cu_count, text, len(text)),
+               "mmh_q8o_linear_plan")
+    return text.value.decode()
 
 
 def _check(status: int, where: str) -> None:
@@ -179,6 +229,120 @@ def quantize_rows(x, out=None):
     return out, scale, inv_scale
 
 
+class QRows:
+    """A quantised activation: `q` (rows, cols) int8 on a GPU -- unit column stride, a row stride that is a multiple of 4, a
+    4-byte aligned base: what the GEMM's tile reads in place --, and `inv_scale` (rows,) fp32, the reciprocal of each row's
+    scale (the contract's rx).  What quantize() and an int8-output qlinear return and what qlinear takes as x."""
+
+    def __init__(self, q, inv_scale):
+        import torch
+        if not (torch.is_tensor(q) and q.dim() == 2):
+            raise MMultError(ERR_INVALID_ARG, "QRows", "q is a 2-D int8 tensor")
+        self.rows, self.cols = int(q.shape[0]), int(q.shape[1])
+        self.device = q.device.index
+        if self.cols == 0:   # (nothing is read: any int8 tensor of that shape on a GPU)
+            if not q.is_cuda or q.dtype != torch.int8:
+                raise MMultError(ERR_INVALID_ARG, "QRows", "q is a 2-D int8 tensor on a GPU")
+            ptr, ld = None, 0
+        else:
+            ptr, ld = tensor_args(q, self.rows, self.cols, "QRows(q)", torch.int8, self.device)
+            if self.rows <= 1:   # (one row has no row stride to go by: its view's, where that holds the row, else the row's length)
+                ld = q.stride(0) if self.rows == 1 and q.stride(0) >= self.cols and q.stride(0) % 4 == 0 else (self.cols + 3) & ~3
+            if ld % 4 or ptr % 4:
+                raise MMultError(ERR_INVALID_ARG, "QRows", "the GEMM reads q in dwords: a row stride that is a multiple of 4 and a 4-byte aligned base")
+        if not (torch.is_tensor(inv_scale) and inv_scale.is_cuda and inv_scale.device.index == self.device and inv_scale.dtype == torch.float32
+                and inv_scale.dim() == 1 and inv_scale.shape[0] == self.rows and (self.rows <= 1 or inv_scale.stride(0) == 1)):
+            raise MMultError(ERR_INVALID_ARG, "QRows", "inv_scale is a dense (rows,) fp32 tensor on q's device")
+        self.q, self.inv_scale, self._ptr, self._ld = q, inv_scale, ptr, ld
+
+    @classmethod
+    def _of_window(cls, q, inv_scale, ptr, ld):
+        """What an int8-output qlinear wrote into a caller's window: any pitch, any base.  Whether the GEMM can read it in place
+        is asked when it is used as x (_rows_args)."""
+        self = cls.__new__(cls)
+        self.rows, self.cols, self.device = int(q.shape[0]), int(q.shape[1]), q.device.index
+        self.q, self.inv_scale, self._ptr, self._ld = q, inv_scale, ptr, ld
+        return self
+
+
+def quantize(x) -> QRows:
+    """quantize_rows(x) with its default pitch, as the QRows qlinear reads."""
+    q, _, inv_scale = quantize_rows(x)
+    return QRows(q, inv_scale)
+
+
+def _bias_ptr(what, bias, qweight):
+    import torch
+    if bias is None:
+        return None
+    if not bias.is_cuda or bias.device.index != qweight.device or bias.dtype != torch.float32 or bias.dim() != 1 or \
+            bias.shape[0] != qweight.out_features or (bias.shape[0] > 1 and bias.stride(0) != 1):
+        raise MMultError(ERR_INVALID_ARG, what, "the bias is a dense 1-D fp32 tensor on the weight's device, one float per output column")
+    return bias.data_ptr()
+
+
+def _rows_args(what, x: QRows, qweight):
+    if x.cols != qweight.in_features or x.device != qweight.device:
+        raise MMultError(ERR_INVALID_ARG, what, f"need QRows of {qweight.in_features} columns on the weight's device")
+    if x.cols and (x._ld % 4 or x._ptr % 4):
+        raise MMultError(ERR_INVALID_ARG, what, "the GEMM reads x.q in dwords: a row stride that is a multiple of 4 and a 4-byte aligned base")
+    return x.rows, x._ptr, x._ld, x.inv_scale.data_ptr()
+
+
+def _linear_s8_args(what, x: QRows, qweight, bias, activation, out):
+    """mmh_q8_linear_s8's arguments between the object and the stream, and `out`."""
+    import torch
+    act = _activation_id(activation, what)
+    rows, pxq, ldq, prx = _rows_args(what, x, qweight)
+    if out is None:
+        out = torch.empty((rows, qweight.out_features), dtype=torch.float32, device=x.q.device)
+    py, ldy = tensor_args(out, rows, qweight.out_features, what + "(out)", torch.float32, qweight.device)
+    return (rows, pxq, ldq, prx, _bias_ptr(what, bias, qweight), act, py, ldy), out
+
+
+def _scale_vectors(what, out_scale, rows, device):
+    """(so, fl(1 / so)): two (rows,) fp32 device tensors of an out_scale given as a Python float or as such a tensor."""
+    import numpy as np
+    import torch
+    if torch.is_tensor(out_scale):
+        if not (out_scale.is_cuda and out_scale.device.index == device and out_scale.dtype == torch.float32 and out_scale.dim() == 1
+                and out_scale.shape[0] == rows and (rows <= 1 or out_scale.stride(0) == 1)):
+            raise MMultError(ERR_INVALID_ARG, what, "out_scale is a Python float or a dense (rows,) fp32 tensor on the weight's device")
+        # the double quotient rounded to float IS the float quotient (53 >= 2 * 24 + 2 bits: the second rounding is innocuous)
+        return out_scale, (1.0 / out_scale.double()).float()
+    so = np.float32(out_scale)
+    if not np.isfinite(so):
+        raise MMultError(ERR_INVALID_ARG, what, "out_scale must be finite")
+    with np.errstate(all="ignore"):
+        inv = np.float32(1.0) / so
+    dev = f"cuda:{device}"
+    return torch.full((rows,), float(so), dtype=torch.float32, device=dev), torch.full((rows,), float(inv), dtype=torch.float32, device=dev)
+
+
+def _linear_s8o(what, x: QRows, qweight, bias, activation, so, inv, out=None, time=None):
+    """mmh_q8o_linear (time = (warmup, reps): mmh_time_q8o_linear) on a QRows with the output scales `so` and their
+    reciprocals `inv` (rows floats each): the QRows of the output, in `out` or in new rows of pitch out_features rounded up to 16."""
+    import torch
+    act = _activation_id(activation, what)
+    rows, pxq, ldq, prx = _rows_args(what, x, qweight)
+    n = qweight.out_features
+    if out is None:
+        out = torch.empty((rows, (n + 15) & ~15), dtype=torch.int8, device=x.q.device)[:, :n]
+    pyq, ldyq = tensor_args(out, rows, n, what + "(out)", torch.int8, qweight.device)
+    if rows == 1 and out.stride(0) >= n:
+        ldyq = out.stride(0)
+    pq, _, pr = qweight._ptrs
+    args = (qweight.device, rows, n, qweight.in_features, pxq, ldq, prx, pq, qweight.pitch, pr, _bias_ptr(what, bias, qweight), act,
+            so.data_ptr(), pyq, ldyq)
+    if time is not None:
+        ms = C.c_float(0.0)
+        _check_q8o(lib_q8o().mmh_time_q8o_linear(*args, time[0], time[1], _stream(qweight.device), C.byref(ms)), "mmh_time_q8o_linear")
+        return ms.value
+    if rows > 0:
+        _check_q8o(lib_q8o().mmh_q8o_linear(*args, _stream(qweight.device)), "mmh_q8o_linear")
+    return QRows._of_window(out, inv[:rows], pyq, ldyq)
+
+
 def _linear_args(what, x, qweight, bias, activation, out):
     """mmh_q8_linear's arguments between the object and the stream, and `out`."""
     import torch
@@ -192,18 +356,30 @@ def _linear_args(what, x, qweight, bias, activation, out):
         out = torch.empty((rows, qweight.out_features), dtype=torch.float32, device=x.device)
     px, ldx = tensor_args(x, rows, qweight.in_features, what + "(x)", torch.float32, dev)
     py, ldy = tensor_args(out, rows, qweight.out_features, what + "(out)", torch.float32, dev)
-    pbias = None
-    if bias is not None:
-        if not bias.is_cuda or bias.device.index != dev or bias.dtype != torch.float32 or bias.dim() != 1 or \
-                bias.shape[0] != qweight.out_features or (bias.shape[0] > 1 and bias.stride(0) != 1):
-            raise MMultError(ERR_INVALID_ARG, what, "the bias is a dense 1-D fp32 tensor on the weight's device, one float per output column")
-        pbias = bias.data_ptr()
-    return (rows, px, ldx, pbias, act, py, ldy), out
+    return (rows, px, ldx, _bias_ptr(what, bias, qweight), act, py, ldy), out
 
 
-def qlinear(x, qweight: QWeight, bias=None, activation=None, out=None):
-    """y = act(x @ w.t() + bias) in int8 (the header's contract): x (rows, in_features) fp32, quantised per row on the way in;
-    bias (out_features,) or None; activation None or "relu"; `out` (rows, out_features) fp32, any row stride."""
+def qlinear(x, qweight: QWeight, bias=None, activation=None, out=None, out_scale=None):
+    """y = act(x @ w.t() + bias) in int8 (the headers' contracts).  x: (rows, in_features) fp32, quantised per row on the way
+    in, or a QRows, read as it is (no quantiser pass; one QRows may feed any number of weights).  bias (out_features,) or
+    None; activation None or "relu".  out_scale None: y is fp32, `out` (rows, out_features) fp32 of any row stride.
+    out_scale a Python float or a (rows,) fp32 device tensor: y is quantised with that scale per row and returned as a QRows
+    -- q in `out`, an int8 (rows, out_features) window of any pitch and base, or in new rows of pitch out_features rounded up to 16; inv_scale =
+    fl(1 / out_scale) --, which the next qlinear reads in place."""
+    if out_scale is not None:
+        if not isinstance(x, QRows):
+            if x.dim() != 2 or x.shape[1] != qweight.in_features:
+                raise MMultError(ERR_INVALID_ARG, "qlinear", f"need a 2-D x (rows, {qweight.in_features})")
+            if x.requires_grad:
+                raise MMultError(ERR_INVALID_ARG, "qlinear", "the int8 layer has no backward: x requires grad")
+            x = quantize(x)
+        so, inv = _scale_vectors("qlinear", out_scale, x.rows, qweight.device)
+        return _linear_s8o("qlinear", x, qweight, bias, activation, so, inv, out)
+    if isinstance(x, QRows):
+        args, out = _linear_s8_args("qlinear", x, qweight, bias, activation, out)
+        if args[0] > 0:
+            _check(lib().mmh_q8_linear_s8(qweight._handle, *args, _stream(qweight.device)), "mmh_q8_linear_s8")
+        return out
     args, out = _linear_args("qlinear", x, qweight, bias, activation, out)
     if args[0] > 0:
         _check(lib().mmh_q8_linear(qweight._handle, *args, _stream(qweight.device)), "mmh_q8_linear")
@@ -216,6 +392,129 @@ def time_qlinear(x, qweight: QWeight, bias=None, activation=None, out=None, warm
     ms = C.c_float(0.0)
     _check(lib().mmh_time_q8_linear(qweight._handle, *args, warmup, reps, _stream(qweight.device), C.byref(ms)), "mmh_time_q8_linear")
     return ms.value
+
+
+def time_qlinear_s8o(x: QRows, qweight: QWeight, bias=None, activation=None, out=None, out_scale=1.0, warmup: int = 1, reps: int = 20) -> float:
+    """Mean milliseconds per int8-output qlinear call on a QRows (one event pair around `reps` calls)."""
+    so, inv = _scale_vectors("time_qlinear_s8o", out_scale, x.rows, qweight.device)
+    return _linear_s8o("time_qlinear_s8o", x, qweight, bias, activation, so, inv, out, time=(warmup, reps))
+
+
+def scale_of_amax(amax: float) -> float:
+    """The quantiser's scale of a maximum, in float32: 127 / amax; 1 when amax is not above 0; clamped to FLT_MAX."""
+    import numpy as np
+    a = np.float32(amax)
+    if not a > 0:
+        return 1.0
+    with np.errstate(all="ignore"):
+        s = np.float32(127.0) / a
+    return float(min(s, np.finfo(np.float32).max))
+
+
+def _make_qmlp_class():
+    import torch
+
+    class QMLP(torch.nn.Module):
+        """A stack of linear layers in int8, inference only: one row quantiser, then int8 -> int8 for every hidden layer (the
+        GEMM's epilogue writes the next layer's rows: no fp32 activation ever reaches memory), then int8 -> fp32 for the last.
+        The hidden activations are quantised with one static scale per layer (`out_scales`): calibrate(x) measures them, or
+        set them by hand.  `activation` follows every hidden layer, `last_activation` the last."""
+
+        def __init__(self, qweights, biases=None, activation="relu", last_activation=None):
+            super().__init__()
+            _activation_id(activation, "QMLP")
+            _activation_id(last_activation, "QMLP")
+            self.qweights = list(qweights)
+            if not self.qweights:
+                raise MMultError(ERR_INVALID_ARG, "QMLP", "need at least one QWeight")
+            biases = list(biases) if biases is not None else [None] * len(self.qweights)
+            for a, b in zip(self.qweights, self.qweights[1:]):
+                if a.out_features != b.in_features or a.device != b.device:
+                    raise MMultError(ERR_INVALID_ARG, "QMLP", "each layer reads what the one before it writes, on one device")
+            if len(biases) != len(self.qweights):
+                raise MMultError(ERR_INVALID_ARG, "QMLP", "one bias (or None) per layer")
+            for i, b in enumerate(biases):
+                self.register_buffer(f"bias{i}", b)
+            self.activation, self.last_activation = activation, last_activation
+            self.in_features, self.out_features = self.qweights[0].in_features, self.qweights[-1].out_features
+            self._out_scales = [] if len(self.qweights) == 1 else None
+            self._vectors, self._vector_rows = [], 0   # per hidden layer (so, fl(1 / so)), constant vectors of _vector_rows rows
+
+        @classmethod
+        def from_float(cls, linears, activation="relu", last_activation=None):
+            """The int8 stack of torch.nn.Linear layers whose weights live on a GPU."""
+            linears = list(linears)
+            dev = linears[0].weight.device
+            return cls([QWeight(l.weight.detach()) for l in linears],
+                       [None if l.bias is None else l.bias.detach().to(torch.float32).to(dev).contiguous() for l in linears],
+                       activation, last_activation)
+
+        def _bias(self, i):
+            return getattr(self, f"bias{i}")
+
+        @property
+        def out_scales(self):
+            """One output scale per hidden layer (Python floats, float32 values), or None before calibrate()."""
+            return None if self._out_scales is None else list(self._out_scales)
+
+        @out_scales.setter
+        def out_scales(self, scales):
+            import numpy as np
+            scales = [float(np.float32(s)) for s in scales]
+            if len(scales) != len(self.qweights) - 1 or not all(np.isfinite(s) and s > 0 for s in scales):
+                raise MMultError(ERR_INVALID_ARG, "QMLP.out_scales", "one finite positive scale per hidden layer")
+            self._out_scales, self._vectors, self._vector_rows = scales, [], 0
+
+        def _rows(self, x):
+            if x.requires_grad:
+                raise MMultError(ERR_INVALID_ARG, "QMLP", "the int8 layers have no backward: x requires grad")
+            rows = x.reshape(-1, self.in_features)
+            if rows.shape[0] > 1 and rows.shape[1] > 1 and rows.stride(1) != 1:
+                rows = rows.contiguous()
+            return rows
+
+        def _grow(self, rows):
+            """The constant scale and reciprocal vectors hold `rows` rows (they allocate: not while capturing)."""
+            if rows <= self._vector_rows:
+                return
+            dev = self.qweights[0].device
+            if torch.cuda.is_current_stream_capturing():
+                raise MMultError(ERR_UNSUPPORTED, "QMLP", "the scale vectors would have to grow while the stream is capturing -- "
+                                 "run one uncaptured forward at the largest size first")
+            self._vectors = [_scale_vectors("QMLP", s, rows, dev) for s in self._out_scales]
+            self._vector_rows = rows
+
+        def calibrate(self, x):
+            """Run the layers with fp32 outputs on `x` and set each hidden layer's output scale to scale_of_amax of the
+            largest finite |h| it produced.  Returns the scales."""
+            h = self._rows(x)
+            scales = []
+            for i, qw in enumerate(self.qweights[:-1]):
+                h = qlinear(h, qw, self._bias(i), self.activation)
+                a = h.abs()
+                amax = torch.where(torch.isfinite(a), a, torch.zeros_like(a)).max().item() if h.numel() else 0.0
+                scales.append(scale_of_amax(amax))
+            self.out_scales = scales
+            self._grow(h.shape[0])
+            return self.out_scales
+
+        def forward(self, x):
+            if self._out_scales is None:
+                raise MMultError(ERR_INVALID_ARG, "QMLP", "no output scales: calibrate(x), or set out_scales, first")
+            rows = self._rows(x)
+            self._grow(rows.shape[0])
+            h = quantize(rows)
+            for i, qw in enumerate(self.qweights[:-1]):
+                so, inv = self._vectors[i]
+                h = _linear_s8o("QMLP", h, qw, self._bias(i), self.activation, so, inv)
+            y = qlinear(h, self.qweights[-1], self._bias(len(self.qweights) - 1), self.last_activation)
+            return y.reshape(*x.shape[:-1], self.out_features)
+
+        def extra_repr(self) -> str:
+            dims = [self.in_features] + [q.out_features for q in self.qweights]
+            return f"{' -> '.join(map(str, dims))}, activation={self.activation}, last_activation={self.last_activation}, out_scales={self._out_scales}"
+
+    return QMLP
 
 
 def _make_qlinear_class():
@@ -264,11 +563,13 @@ def _make_qlinear_class():
     return QLinear
 
 
-def __getattr__(name):   # QLinear is a torch.nn.Module: made when first asked for, so that importing this module does not import torch
-    if name == "QLinear":
-        cls = globals()["QLinear"] = _make_qlinear_class()
+def __getattr__(name):   # QLinear / QMLP are torch.nn.Modules: made when first asked for, so that importing this module does not import torch
+    if name in ("QLinear", "QMLP"):
+        cls = globals()[name] = (_make_qlinear_class if name == "QLinear" else _make_qmlp_class)()
         return cls
     raise AttributeError(name)
 
 
-__all__ = ["QWeight", "QLinear", "quantize_rows", "qlinear", "time_qlinear", "qlinear_plan", "last_launch", "lib", "EXPORTS", "LIB_PATH", "HEADER"]
+__all__ = ["QWeight", "QLinear", "QRows", "QMLP", "quantize_rows", "quantize", "qlinear", "time_qlinear", "time_qlinear_s8o", "qlinear_plan",
+           "qlinear_s8o_plan", "scale_of_amax", "last_launch", "last_launch_q8o", "lib", "lib_q8o", "EXPORTS", "LIB_PATH", "HEADER",
+           "Q8O_LIB_PATH", "Q8O_HEADER"]

@@ -71,6 +71,15 @@ int mmh_q8_quantize_rows(int device, int rows, int cols, const float *dX, int ld
  * out floats at any 4-byte aligned address, or NULL.  activation: MMH_ACT_NONE or MMH_ACT_RELU.  rows == 0: MMH_OK. */
 int mmh_q8_linear(mmh_q8_weight_t weight, int rows, const float *dX, int ldx, const float *dBias, int activation, float *dY,
                   int ldy, void *stream);
+/* mmh_q8_linear on rows that are quantised already: dXq is rows x in int8 with ldq >= in, d_inv_scale rows floats -- the rx
+ * of the contract, with Q(x[i,:]) the caller's row i.  With mmh_q8_quantize_rows' outputs the result is bit-equal to
+ * mmh_q8_linear on the fp32 x, and one quantisation can feed any number of weights.  One launch, the GEMM of mmh_q8_linear's
+ * plan straight on dXq: no quantiser pass, no scratch, no allocation -- nothing to reserve before a capture; mmh_q8_last_launch
+ * reads as the part of mmh_q8_linear_plan's text after "then ".  The tile reads dXq through a buffer descriptor in dwords: an
+ * ldq that is no multiple of 4, a dXq that is not 4-byte aligned, or rows beyond the 2 GiB window (256 * ldq + in >= 2^31 -
+ * 4096) are MMH_ERR_UNSUPPORTED with a message, nothing launched or touched.  Bytes of a row beyond `in` need not be zero. */
+int mmh_q8_linear_s8(mmh_q8_weight_t weight, int rows, const int8_t *dXq, int ldq, const float *d_inv_scale, const float *dBias,
+                     int activation, float *dY, int ldy, void *stream);
 /* Size the object's scratch for calls of up to max_rows rows (see Capture above). */
 int mmh_q8_linear_reserve(mmh_q8_weight_t weight, int max_rows, void *stream);
 
