@@ -60,10 +60,20 @@ def problem(rows, out, in_):
     xq, _, rx = R.quantize_rows_ref(x)
     qw, _, rw = R.quantize_rows_ref(w)
     acc = R.int_sums(xq, qw)
-    a = np.abs(R.epilogue_ref(acc, rx, rw, bias, False))
+    return w, bias, xq, rx, acc, rw, out_scales(acc, rx, rw, bias)
+
+
+def out_scales(acc, rx, rw, bias):
+    """problem()'s scale rule: one output scale per row from the fp32 layer's |y| (its 99.8th percentile where there are a
+    thousand outputs, else just above its maximum), stepped down by up to 10 % from row to row."""
+    return scales_of(R.epilogue_ref(acc, rx, rw, bias, False))
+
+
+def scales_of(y):
+    """out_scales of the fp32 layer's outputs themselves."""
+    a = np.abs(y)
     top = np.float32(np.percentile(a, 99.8)) if a.size >= 1000 else np.float32(a.max() * 1.03 + 1e-3)
-    so = (np.float32(127.0) / top * (1 - 0.1 * ((np.arange(rows) * 37) % 16) / 16)).astype(np.float32)
-    return w, bias, xq, rx, acc, rw, so
+    return (np.float32(127.0) / top * (1 - 0.1 * ((np.arange(y.shape[0]) * 37) % 16) / 16)).astype(np.float32)
 
 
 def want_of(p, bias, relu):
@@ -97,24 +107,26 @@ def poisoned_rows(values, ld, off=0):
     return flat, view
 
 
-def device_rows(xq, rx, pad=4):
-    """The QRows of reference rows: pitch = cols rounded up to 4, plus `pad`, poisoned behind every row."""
+def device_rows(xq, rx, pad=4, off=0):
+    """The QRows of reference rows: pitch = cols rounded up to 4, plus `pad`, poisoned behind every row; the base `off` bytes
+    past a 16-byte boundary."""
     import torch
     from how_to_optimize_gemm_amd import q8
     ld = ((xq.shape[1] + 3) & ~3) + pad
-    _, view = poisoned_rows(xq, ld)
+    _, view = poisoned_rows(xq, ld, off)
     return q8.QRows(view[:, :xq.shape[1]], torch.from_numpy(np.ascontiguousarray(rx)).cuda())
 
 
-def run_s8o(qw, xq, rx, bias, relu, so, ldyq, off_y, x_pad=4):
+def run_s8o(qw, xq, rx, bias, relu, so, ldyq, off_y, x_pad=4, x_off=0):
     """The int8-output layer into a poisoned buffer: yq's window starts off_y bytes past a 16-byte boundary, its rows are ldyq
-    bytes apart.  Returns (yq's window, nothing outside it was written, the launch text)."""
+    bytes apart; x's rows have x_pad poisoned bytes behind them and start x_off bytes past a 16-byte boundary.  Returns (yq's
+    window, nothing outside it was written, the launch text)."""
     import torch
     from how_to_optimize_gemm_amd import q8
     rows, out = xq.shape[0], qw.out_features
     flat, yv = poisoned_rows(np.zeros((rows, 0), np.int8), ldyq, off_y)
     db = None if bias is None else torch.from_numpy(bias).cuda()
-    got = q8.qlinear(device_rows(xq, rx, x_pad), qw, db, "relu" if relu else None, out=yv[:, :out], out_scale=torch.from_numpy(so).cuda())
+    got = q8.qlinear(device_rows(xq, rx, x_pad, x_off), qw, db, "relu" if relu else None, out=yv[:, :out], out_scale=torch.from_numpy(so).cuda())
     launched = q8.last_launch_q8o()
     torch.cuda.synchronize()
     assert got.q.data_ptr() == yv.data_ptr() and same_bits(got.inv_scale.cpu().numpy(), Q.inv_scale_ref(so))
@@ -125,11 +137,11 @@ def run_s8o(qw, xq, rx, bias, relu, so, ldyq, off_y, x_pad=4):
     return result, bool((after == POISON).all()), launched
 
 
-def check_s8o(shape, p, qw, bias, relu, ldyq, off_y, symbol, cu_count, want=None):
+def check_s8o(shape, p, qw, bias, relu, ldyq, off_y, symbol, cu_count, want=None, x_pad=4, x_off=0):
     rows, out, in_ = shape
     w, b, xq, rx, acc, rw, so = p
     want = want_of(p, bias, relu) if want is None else want
-    got, untouched, launched = run_s8o(qw, xq, rx, b if bias else None, relu, so, ldyq, off_y)
+    got, untouched, launched = run_s8o(qw, xq, rx, b if bias else None, relu, so, ldyq, off_y, x_pad, x_off)
     assert launched == Q.plan_text_s8o(rows, out, ldyq, off_y % 4, cu_count) and symbol in launched, (shape, symbol, launched)
     assert np.array_equal(got, want), (shape, launched, int((got != want).sum()), np.argwhere(got != want)[:4])
     assert untouched, (shape, launched, "wrote outside yq's rows x out bytes")

@@ -74,6 +74,33 @@ def test_requant_ref_scales_each_row_with_its_own_scale():
     assert (np.abs(got) == 127).any() and (np.abs(got) < 127).any()
 
 
+def test_requant_ref_at_the_edges_of_the_scale():
+    """What quantize_one gives where the header's "so must be finite" still holds but the product is not a number of the
+    range -- written down value by value, so that the reference's own edge behaviour can be reviewed: rintf keeps a NaN, fmaxf
+    and fminf return their other argument for one, so a NaN PRODUCT (inf * 0) leaves the lower bound, -127; a NaN y is 0."""
+    inf, nan, fmax = np.inf, np.nan, R.F32_MAX
+    y = np.array([inf, -inf, nan, 0.0, -0.0, 1.5, -2.5, 1e-38, -1e-38, 3e38], f32)
+    table = [
+        (0.0,         [-127, -127, 0, 0, 0, 0, 0, 0, 0, 0]),                 # inf * 0 is NaN: -127; finite * 0: 0
+        (-0.0,        [-127, -127, 0, 0, 0, 0, 0, 0, 0, 0]),
+        (fmax,        [127, -127, 0, 0, 0, 127, -127, 3, -3, 127]),          # overflow to +-inf clamps; 1e-38 * FLT_MAX = 3.4
+        (-fmax,       [-127, 127, 0, 0, 0, -127, 127, -3, 3, -127]),
+        (-1.0,        [-127, 127, 0, 0, 0, -2, 2, 0, 0, -127]),              # a negative scale mirrors: ties still go to even
+        (-0.5,        [-127, 127, 0, 0, 0, -1, 1, 0, 0, -127]),              # -0.75 -> -1, 1.25 -> 1
+        (2.0 ** -140, [127, -127, 0, 0, 0, 0, 0, 0, 0, 0]),                  # a denormal scale: inf stays inf, the rest underflows
+        (1e30,        [127, -127, 0, 0, 0, 127, -127, 0, 0, 127]),
+        (1e-30,       [127, -127, 0, 0, 0, 0, 0, 0, 0, 127]),               # 3e38 * 1e-30 = 3e8
+    ]
+    for scale, want in table:
+        got = Q.requant_ref(y[None, :], np.array([scale], f32))[0]
+        assert list(got) == want, (scale, list(got), want)
+        # the per-element rule agrees wherever the product is not NaN (it has no fmaxf to ask)
+        with np.errstate(all="ignore"):
+            number = ~np.isnan(y * f32(scale)) | np.isnan(y)
+        assert [slow_requant(v, scale) for v in y[number]] == list(got[number]), scale
+    # a scale that is not finite is outside the contract; requant_ref is not asked about it
+
+
 def test_the_scale_rule_is_the_quantisers():
     for v in ([0.0], [1e-38], [2.5, -7.0], [np.inf, 3.0], [np.nan, 0.25]):
         a = np.abs(np.array(v, f32))
