@@ -19,6 +19,8 @@ CSRC_Q8 = os.path.join(PKG_DIR, "csrc_q8")
 Q8_LIB = os.path.join(PKG_DIR, "libmmult_hip_q8.so")   # the second product library: the int8 linear layer (include/mmult_hip_q8.h)
 CSRC_Q8O = os.path.join(PKG_DIR, "csrc_q8o")
 Q8O_LIB = os.path.join(PKG_DIR, "libmmult_hip_q8o.so")   # the third: the int8 layer with an int8 output (include/mmult_hip_q8o.h)
+CSRC_Q8D = os.path.join(PKG_DIR, "csrc_q8d")
+Q8D_LIB = os.path.join(PKG_DIR, "libmmult_hip_q8d.so")   # the fourth: the int8 layer for 1 - 16 rows, split-K (include/mmult_hip_q8d.h)
 HARNESS = os.path.join(PKG_DIR, "harness")
 ARCH = "gfx950"
 
@@ -148,6 +150,35 @@ def build_q8o_library(force: bool = False, verbose: bool = False) -> str:
     return Q8O_LIB
 
 
+def build_q8d_library(force: bool = False, verbose: bool = False) -> str:
+    """csrc_q8d/*.hip -> how-to-optimize-gemm_amd/libmmult_hip_q8d.so, with the q8o library's flags and -I csrc_q8d in front (its
+    kernels use csrc/'s LDS-DMA loader, plan rules and quantisation rules).  Objects under build/q8d/; an object is stale when its
+    .hip, a header of csrc_q8d/, csrc_q8o/, csrc_q8/ or csrc/, or a C header has changed.  At most 16 compile jobs at a time."""
+    from concurrent.futures import ThreadPoolExecutor
+    headers = [s for s in library_sources() if s.endswith((".hpp", ".h", ".inc"))]
+    headers += [os.path.join(REPO, "include", h) for h in ("mmult_hip_q8.h", "mmult_hip_q8o.h", "mmult_hip_q8d.h")]
+    for d in (CSRC_Q8, CSRC_Q8O, CSRC_Q8D):
+        headers += [os.path.join(d, f) for f in sorted(os.listdir(d)) if f.endswith(".hpp")]
+    tus = sorted(os.path.join(CSRC_Q8D, f) for f in os.listdir(CSRC_Q8D) if f.endswith(".hip"))
+    odir = os.path.join(PKG_DIR, "build", "q8d")
+    os.makedirs(odir, exist_ok=True)
+    flags = [f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-result", "-I" + CSRC_Q8D, "-I" + CSRC_Q8O, "-I" + CSRC_Q8,
+             "-I" + CSRC]
+    objs = [os.path.join(odir, os.path.basename(tu)[:-4] + ".o") for tu in tus]
+    jobs = [[hipcc()] + flags + ["-c", tu, "-o", obj] for tu, obj in zip(tus, objs) if force or _stale(obj, [tu] + headers)]
+    def run(cmd):
+        if verbose:
+            print(" ".join(cmd))
+        subprocess.check_call(cmd)
+    if jobs:
+        with ThreadPoolExecutor(max_workers=min(len(jobs), os.cpu_count() or 4, 16)) as pool:
+            list(pool.map(run, jobs))
+    version_script = os.path.join(CSRC_Q8D, "exports_q8d.map")
+    if force or jobs or _stale(Q8D_LIB, objs + [version_script]):
+        run([hipcc(), f"--offload-arch={ARCH}", "-shared", "-fPIC"] + objs + ["-o", Q8D_LIB, "-Wl,--version-script=" + version_script])
+    return Q8D_LIB
+
+
 def build_timeline_library(force: bool = False) -> str:
     """-DMMH_AB_BUILD -DMMH_DMA_TIMELINE -> libmmult_hip_tl.so: the A/B library whose plain LDS-DMA kernels
     also write per-workgroup wall-clock stamps (tools/dma_timeline.py only; the stamps perturb the
@@ -178,6 +209,7 @@ def build_all(force: bool = False) -> None:
     build_library(force)
     build_q8_library(force)
     build_q8o_library(force)
+    build_q8d_library(force)
     if os.path.isdir(HARNESS):
         build_harness(force)
 

@@ -8,6 +8,7 @@
     y = q8.qlinear(xq, qw, bias)                       # ... straight into the GEMM: no quantiser pass
     hq = q8.qlinear(xq, qw, bias, "relu", out_scale=s) # int8 out (libmmult_hip_q8o.so): the next layer's QRows, no fp32 round trip
     mlp = q8.QMLP.from_float([fc1, fc2]); mlp.calibrate(x); y = mlp(x)    # one quantiser, int8 -> int8 hidden layers, fp32 out
+    y = q8.qlinear_decode(xq, qw, bias)                # 1 - 16 rows (libmmult_hip_q8d.so): split-K strips, the same bits as qlinear
 
 The binding is read from include/mmult_hip_q8.h (abi_header.parse); the numeric contract is in that header.  The int8-output
 library is loaded on first use, its binding read from include/mmult_hip_q8o.h.  Everything runs
@@ -105,6 +106,53 @@ def qlinear_s8o_plan(rows: int, out_features: int, in_features: int, ldq: int = 
     return text.value.decode()
 
 
+Q8D_HEADER = os.path.join(os.path.dirname(_abi.HEADER), "mmult_hip_q8d.h")
+Q8D_LIB_PATH = os.path.join(_api.PKG_DIR, "libmmult_hip_q8d.so")
+Q8D_MAX_ROWS = _abi.parse(Q8D_HEADER)[0]["MMH_Q8D_MAX_ROWS"]
+_lib_q8d = None
+
+
+def lib_q8d() -> C.CDLL:
+    """Load libmmult_hip_q8d.so (the small-batch layer) on first use, bound from its own header.  Fails loudly."""
+    global _lib_q8d
+    if _lib_q8d is not None:
+        return _lib_q8d
+    _api._share_hip_runtime_with_torch()
+    if not os.path.exists(Q8D_LIB_PATH):
+        raise MMultError(ERR_UNSUPPORTED, "load", f"{Q8D_LIB_PATH} is missing -- run __graft_entry__.build(); there is no CPU fallback")
+    L = C.CDLL(Q8D_LIB_PATH)
+    for name, (restype, argtypes) in _abi.parse(Q8D_HEADER)[1].items():
+        fn = getattr(L, name)
+        fn.restype, fn.argtypes = restype, argtypes
+    _lib_q8d = L
+    return L
+
+
+def _check_q8d(status: int, where: str) -> None:
+    if status != OK:
+        last = lib_q8d().mmh_q8d_last_error().decode()
+        detail = _STATUS_NAMES.get(status, "unknown status")
+        raise MMultError(status, where, f"{detail}; {last}" if last else detail)
+
+
+def last_launch_q8d() -> str:
+    """What the last qlinear_decode on this thread launched."""
+    return lib_q8d().mmh_q8d_last_launch().decode()
+
+
+def qlinear_decode_plan(rows: int, out_features: int, in_features: int, ldq: int = 0, pitch_n: int = 0, out8: bool = False, ldo: int = 0,
+                        xq_mod4: int = 0, wq_mod4: int = 0, o_mod16: int = 0, splits: int = 0, cu_count: int = 256):
+    """(text, work bytes) of a qlinear_decode call: what last_launch_q8d() says after it and the workspace it needs.  Host
+    arithmetic only.  ldq / pitch_n 0: rows of the default pitch (the length rounded up to 16); ldo 0: dense fp32 rows, int8
+    rows of the default pitch."""
+    p16 = lambda n: (n + 15) & ~15
+    text, work = C.create_string_buffer(192), C.c_size_t(0)
+    _check_q8d(lib_q8d().mmh_q8d_linear_plan(rows, out_features, in_features, ldq or p16(in_features), pitch_n or p16(out_features),
+                                             int(bool(out8)), ldo or (p16(out_features) if out8 else out_features), xq_mod4, wq_mod4,
+                                             o_mod16, splits, cu_count, text, len(text), C.byref(work)), "mmh_q8d_linear_plan")
+    return text.value.decode(), work.value
+
+
 def _check(status: int, where: str) -> None:
     if status != OK:
         last = lib().mmh_q8_last_error().decode()
@@ -168,6 +216,7 @@ class QWeight:
         _check(lib().mmh_q8_weight_info(h, None, None, C.byref(pitch), C.byref(q), C.byref(s), C.byref(r)), "mmh_q8_weight_info")
         self.pitch = pitch.value
         self._ptrs = (q.value, s.value, r.value)
+        self._decode_work = None   # qlinear_decode's split-K partials: a torch uint8 tensor, grown outside capture
 
     def _view(self, ptr, shape, typestr):
         import torch
@@ -194,7 +243,27 @@ class QWeight:
         """Size the object's scratch for calls of up to max_rows rows (before capturing a graph of larger calls than were run)."""
         _check(lib().mmh_q8_linear_reserve(self._handle, int(max_rows), _stream(self.device)), "mmh_q8_linear_reserve")
 
+    def _decode_workspace(self, nbytes: int):
+        """The cached workspace of qlinear_decode, at least nbytes long (torch's allocations are 16-byte aligned)."""
+        import torch
+        if self._decode_work is None or self._decode_work.numel() < nbytes:
+            if torch.cuda.is_current_stream_capturing():
+                raise MMultError(ERR_UNSUPPORTED, "qlinear_decode", "the workspace would have to grow while the stream is capturing -- "
+                                 "call QWeight.reserve_decode() first")
+            self._decode_work = torch.empty((max(int(nbytes), 16),), dtype=torch.uint8, device=f"cuda:{self.device}")
+        return self._decode_work
+
+    def reserve_decode(self, splits: int = 0) -> None:
+        """Size qlinear_decode's workspace for every call of 1 - 16 rows on this weight (before capturing a graph): the plan's
+        own split count, or a forced one."""
+        if self.in_features == 0 or self.out_features == 0:
+            return
+        cus = _cu_count(self.device)
+        self._decode_workspace(max(qlinear_decode_plan(rows, self.out_features, self.in_features, pitch_n=self.pitch, splits=splits,
+                                                       cu_count=cus)[1] for rows in range(1, Q8D_MAX_ROWS + 1)))
+
     def close(self) -> None:
+        self._decode_work = None
         if self._handle is not None:
             lib().mmh_q8_weight_destroy(self._handle)
             self._handle = None
@@ -400,6 +469,89 @@ def time_qlinear_s8o(x: QRows, qweight: QWeight, bias=None, activation=None, out
     return _linear_s8o("time_qlinear_s8o", x, qweight, bias, activation, so, inv, out, time=(warmup, reps))
 
 
+_cu_counts = {}
+
+
+def _cu_count(device: int) -> int:
+    """The device's compute units (what the decode plan fills), asked of torch once per device."""
+    import torch
+    if device not in _cu_counts:
+        _cu_counts[device] = int(torch.cuda.get_device_properties(device).multi_processor_count)
+    return _cu_counts[device]
+
+
+def _linear_q8d(what, x: QRows, qweight, bias, activation, so, inv, out=None, splits=0, time=None):
+    """mmh_q8d_linear (time = (warmup, reps): mmh_time_q8d_linear) on a QRows of at most 16 rows.  so None: the fp32 result in
+    `out` or a new dense tensor; else the output scales `so` and their reciprocals `inv` (rows floats each) and the QRows of the
+    output, in `out` or in new rows of pitch out_features rounded up to 16.  The partials go through the weight's workspace."""
+    import torch
+    act = _activation_id(activation, what)
+    rows, pxq, ldq, prx = _rows_args(what, x, qweight)
+    if rows > Q8D_MAX_ROWS:
+        raise MMultError(ERR_UNSUPPORTED, what, f"at most {Q8D_MAX_ROWS} rows -- larger batches are qlinear's")
+    n, k = qweight.out_features, qweight.in_features
+    out8 = so is not None
+    if out is None:
+        out = torch.empty((rows, (n + 15) & ~15), dtype=torch.int8, device=x.q.device)[:, :n] if out8 else \
+            torch.empty((rows, n), dtype=torch.float32, device=x.q.device)
+    po, ldo = tensor_args(out, rows, n, what + "(out)", torch.int8 if out8 else torch.float32, qweight.device)
+    if rows == 1 and out.stride(0) >= n:
+        ldo = out.stride(0)
+    if rows == 0 or n == 0:
+        if time is not None:
+            raise MMultError(ERR_INVALID_ARG, what, "nothing to time")
+        return QRows._of_window(out, inv[:rows], po, ldo) if out8 else out
+    pq, _, pr = qweight._ptrs
+    work_bytes = 0
+    if k > 0:
+        work_bytes = qlinear_decode_plan(rows, n, k, ldq, qweight.pitch, out8, ldo, 0, pq % 4, po % 16, splits, _cu_count(qweight.device))[1]
+    work = qweight._decode_workspace(work_bytes) if k > 0 else None
+    args = (qweight.device, rows, n, k, pxq, ldq, prx, pq, qweight.pitch, pr, _bias_ptr(what, bias, qweight), act,
+            so.data_ptr() if out8 else None, None if out8 else po, 0 if out8 else ldo, po if out8 else None, ldo if out8 else 0,
+            work.data_ptr() if work is not None else None, work.numel() if work is not None else 0, splits)
+    if time is not None:
+        ms = C.c_float(0.0)
+        _check_q8d(lib_q8d().mmh_time_q8d_linear(*args, time[0], time[1], _stream(qweight.device), C.byref(ms)), "mmh_time_q8d_linear")
+        return ms.value
+    _check_q8d(lib_q8d().mmh_q8d_linear(*args, _stream(qweight.device)), "mmh_q8d_linear")
+    return QRows._of_window(out, inv[:rows], po, ldo) if out8 else out
+
+
+def _decode_rows(what, x, qweight) -> QRows:
+    """x as the QRows the decode kernels read: itself, or quantize(x) of an fp32 (rows <= 16, in_features) tensor."""
+    if isinstance(x, QRows):
+        return x
+    if x.dim() != 2 or x.shape[1] != qweight.in_features:
+        raise MMultError(ERR_INVALID_ARG, what, f"need a 2-D x (rows, {qweight.in_features})")
+    if x.requires_grad:
+        raise MMultError(ERR_INVALID_ARG, what, "the int8 layer has no backward: x requires grad")
+    if x.shape[0] > Q8D_MAX_ROWS:
+        raise MMultError(ERR_UNSUPPORTED, what, f"at most {Q8D_MAX_ROWS} rows -- larger batches are qlinear's")
+    return quantize(x)
+
+
+def qlinear_decode(x, qweight: QWeight, bias=None, activation=None, out=None, out_scale=None, splits: int = 0):
+    """qlinear for 1 - 16 rows (libmmult_hip_q8d.so): the same arguments, the same bits -- the weight is streamed once by
+    strips x K ranges of workgroups (split-K; int32 partials add up exactly), a second kernel applies the epilogue.  x fp32 is
+    quantised first with quantize(); a QRows is read in place.  More than 16 rows raise MMultError.  splits: 0 the plan's
+    choice, > 0 that many K ranges.  The partials live in a workspace cached on `qweight`: it grows on demand, but not under
+    graph capture -- QWeight.reserve_decode() sizes it first."""
+    x = _decode_rows("qlinear_decode", x, qweight)
+    so = inv = None
+    if out_scale is not None:
+        so, inv = _scale_vectors("qlinear_decode", out_scale, x.rows, qweight.device)
+    return _linear_q8d("qlinear_decode", x, qweight, bias, activation, so, inv, out, splits)
+
+
+def time_qlinear_decode(x: QRows, qweight: QWeight, bias=None, activation=None, out=None, out_scale=None, splits: int = 0,
+                        warmup: int = 1, reps: int = 20) -> float:
+    """Mean milliseconds per qlinear_decode call on a QRows (one event pair around `reps` calls)."""
+    so = inv = None
+    if out_scale is not None:
+        so, inv = _scale_vectors("time_qlinear_decode", out_scale, x.rows, qweight.device)
+    return _linear_q8d("time_qlinear_decode", x, qweight, bias, activation, so, inv, out, splits, time=(warmup, reps))
+
+
 def scale_of_amax(amax: float) -> float:
     """The quantiser's scale of a maximum, in float32: 127 / amax; 1 when amax is not above 0; clamped to FLT_MAX."""
     import numpy as np
@@ -420,8 +572,9 @@ def _make_qmlp_class():
         The hidden activations are quantised with one static scale per layer (`out_scales`): calibrate(x) measures them, or
         set them by hand.  `activation` follows every hidden layer, `last_activation` the last."""
 
-        def __init__(self, qweights, biases=None, activation="relu", last_activation=None):
+        def __init__(self, qweights, biases=None, activation="relu", last_activation=None, decode=False):
             super().__init__()
+            self.decode = bool(decode)   # batches of at most 16 rows go through qlinear_decode (the same bits)
             _activation_id(activation, "QMLP")
             _activation_id(last_activation, "QMLP")
             self.qweights = list(qweights)
@@ -441,13 +594,13 @@ def _make_qmlp_class():
             self._vectors, self._vector_rows = [], 0   # per hidden layer (so, fl(1 / so)), constant vectors of _vector_rows rows
 
         @classmethod
-        def from_float(cls, linears, activation="relu", last_activation=None):
+        def from_float(cls, linears, activation="relu", last_activation=None, decode=False):
             """The int8 stack of torch.nn.Linear layers whose weights live on a GPU."""
             linears = list(linears)
             dev = linears[0].weight.device
             return cls([QWeight(l.weight.detach()) for l in linears],
                        [None if l.bias is None else l.bias.detach().to(torch.float32).to(dev).contiguous() for l in linears],
-                       activation, last_activation)
+                       activation, last_activation, decode)
 
         def _bias(self, i):
             return getattr(self, f"bias{i}")
@@ -504,10 +657,12 @@ def _make_qmlp_class():
             rows = self._rows(x)
             self._grow(rows.shape[0])
             h = quantize(rows)
+            decode = self.decode and rows.shape[0] <= Q8D_MAX_ROWS
             for i, qw in enumerate(self.qweights[:-1]):
                 so, inv = self._vectors[i]
-                h = _linear_s8o("QMLP", h, qw, self._bias(i), self.activation, so, inv)
-            y = qlinear(h, self.qweights[-1], self._bias(len(self.qweights) - 1), self.last_activation)
+                h = _linear_q8d("QMLP", h, qw, self._bias(i), self.activation, so, inv) if decode else \
+                    _linear_s8o("QMLP", h, qw, self._bias(i), self.activation, so, inv)
+            y = (qlinear_decode if decode else qlinear)(h, self.qweights[-1], self._bias(len(self.qweights) - 1), self.last_activation)
             return y.reshape(*x.shape[:-1], self.out_features)
 
         def extra_repr(self) -> str:
@@ -524,8 +679,9 @@ def _make_qlinear_class():
         """torch.nn.Linear (+ ReLU) in int8, inference only: the weight is a QWeight (set_weight / from_float), the bias an
         fp32 buffer.  forward flattens leading dimensions to rows; an input that requires grad raises."""
 
-        def __init__(self, in_features: int, out_features: int, bias: bool = True, activation=None):
+        def __init__(self, in_features: int, out_features: int, bias: bool = True, activation=None, decode: bool = False):
             super().__init__()
+            self.decode = bool(decode)   # batches of at most 16 rows go through qlinear_decode (the same bits)
             _activation_id(activation, "QLinear")
             self.in_features, self.out_features, self.activation = in_features, out_features, activation
             self.qweight = None
@@ -541,9 +697,9 @@ def _make_qlinear_class():
             return self
 
         @classmethod
-        def from_float(cls, linear, activation=None):
+        def from_float(cls, linear, activation=None, decode=False):
             """The int8 layer of a torch.nn.Linear whose weight lives on a GPU."""
-            return cls(linear.in_features, linear.out_features, linear.bias is not None, activation).set_weight(
+            return cls(linear.in_features, linear.out_features, linear.bias is not None, activation, decode).set_weight(
                 linear.weight.detach(), None if linear.bias is None else linear.bias.detach())
 
         def forward(self, x):
@@ -554,7 +710,8 @@ def _make_qlinear_class():
             rows = x.reshape(-1, self.in_features)
             if rows.shape[0] > 1 and rows.shape[1] > 1 and rows.stride(1) != 1:
                 rows = rows.contiguous()
-            y = qlinear(rows, self.qweight, self.bias, self.activation)
+            layer = qlinear_decode if self.decode and rows.shape[0] <= Q8D_MAX_ROWS else qlinear
+            y = layer(rows, self.qweight, self.bias, self.activation)
             return y.reshape(*x.shape[:-1], self.out_features)
 
         def extra_repr(self) -> str:
@@ -572,4 +729,5 @@ def __getattr__(name):   # QLinear / QMLP are torch.nn.Modules: made when first 
 
 __all__ = ["QWeight", "QLinear", "QRows", "QMLP", "quantize_rows", "quantize", "qlinear", "time_qlinear", "time_qlinear_s8o", "qlinear_plan",
            "qlinear_s8o_plan", "scale_of_amax", "last_launch", "last_launch_q8o", "lib", "lib_q8o", "EXPORTS", "LIB_PATH", "HEADER",
-           "Q8O_LIB_PATH", "Q8O_HEADER"]
+           "Q8O_LIB_PATH", "Q8O_HEADER", "qlinear_decode", "time_qlinear_decode", "qlinear_decode_plan", "last_launch_q8d", "lib_q8d",
+           "Q8D_LIB_PATH", "Q8D_HEADER", "Q8D_MAX_ROWS"]
