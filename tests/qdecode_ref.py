@@ -4,8 +4,10 @@ tests/bitcmp.py.)
 The numeric contract is inherited -- tests/qchain_ref.py's qlinear_s8_ref is the complete reference -- so what is restated here
 is only what is new: plan() is csrc_q8d/qdecode_plan.hpp's arithmetic in Python, valid_splits says which forced split counts
 leave no K range empty, and cases() is the table tests/test_gpu_qdecode.py runs (tests/test_q8d_coverage.py holds the classes
-it promises, on the CPU).  Also here: the table's inputs -- problem() (a real weight; every 128-byte slice of k moves the
-sums), image_problem() (a caller-made image and rows over the full int8 range, -128 included) and large_sums_problem()."""
+it promises, on the CPU); wide_deep_cases() is its second table, at the sizes the kernels are built for: outputs wider than one
+finish workgroup, many K ranges, deep ranges, every row count; window_ok and its two largest_* say where the descriptor
+window ends.  Also here: the tables' inputs -- problem() (a real weight; every 128-byte slice of k moves the sums),
+image_problem() (a caller-made image and rows over the full int8 range, -128 included) and large_sums_problem()."""
 import collections
 import functools
 
@@ -62,6 +64,24 @@ def plan(rows, out, in_, out8=False, ldo=0, o_mod16=0, splits=0, cus=256):
             work_bytes(splits, rows, out), splits, k_len)
 
 
+# ---- the descriptor window (csrc/igemm_plan.hpp: i8_window, as tests/int8_ops.py restates it) ----------------------------------------
+WINDOW = (1 << 31) - 4096
+
+
+def window_ok(ldq, pitch_n, in_):
+    return 256 * ldq + in_ < WINDOW and (in_ + 256) * pitch_n + 256 < WINDOW
+
+
+def largest_pitch_n(in_):
+    """The largest multiple of 4 with (in + 256) * pitch_n + 256 < WINDOW."""
+    return (WINDOW - 256 - 1) // (in_ + 256) & ~3
+
+
+def largest_ldq(in_):
+    """The largest multiple of 4 with 256 * ldq + in < WINDOW."""
+    return (WINDOW - in_ - 1) // 256 & ~3
+
+
 # ---- the GPU table ----------------------------------------------------------------------------------------------------------
 ROWS = (1, 2, 15, 16)
 INS = (0, 1, 63, 64, 65, 127, 128, 129, 384, 385, 1153)
@@ -107,6 +127,47 @@ def cases():
 
 
 PLAN_SHAPE = (16, 256, 8192)   # splits = 0 here: the plan splits on the device's CU count (2 strips: 16 ranges at 256 CUs)
+
+
+# ---- the second table: what the kernels are built for -------------------------------------------------------------------------
+WIDE_OUTS = (FINISH_COLS, FINISH_COLS + 1, FINISH_COLS + 3, FINISH_COLS + 4, 2 * FINISH_COLS + 1, 17 * STRIP + 1, 4 * FINISH_COLS + 4)
+WIDE_ROWS = (16, 1, 15, 2, 7, 3, 12, 5)                          # two neighbours per out
+SHALLOW = ((129, 2), (257, 2), (385, 4), (257, 3), (385, 2))     # (in, forced ranges) behind the wide outputs
+MANY_RANGES_INS = (1153, 1280)                                   # forced counts above 3, up to one range per slice
+OWN_CHOICE = ((1, 130, 8192), (2, 130, 8192), (1, FINISH_COLS + 1, 4224))   # splits == 0: one slice per range at 256 CUs
+DEEP = ((4224, 1), (11008, 1), (11008, 2))                       # (in, forced ranges) at 16 rows, 130 columns: 33, 86, 43 slices
+LADDER = (130, 257, 2)                                           # (out, in, forced ranges) at every row count 1 - 16
+RESERVE_SHAPE = (257, 1153)                                      # (out, in) whose own split count varies with the rows
+
+
+@functools.lru_cache(maxsize=None)
+def wide_deep_cases():
+    """The finish grid (every WIDE_OUTS at two row counts behind two or three shallow ranges, then 1027 columns on the two
+    layouts whose stores are wide although out is no multiple of 4), then every forced count above 3 that leaves no range of
+    MANY_RANGES_INS empty, the plan's own choice where it is one slice per range, the deep ranges (the middle one on a
+    caller-made image), and LADDER at every row count.  Layouts, weights and epilogues rotate as in cases()."""
+    out = []
+
+    def add(rows, n, in_, s, **fixed):
+        out.append(_case(len(out), rows, n, in_, s)._replace(**fixed))
+
+    for j, n in enumerate(WIDE_OUTS):
+        for r in (0, 1):
+            add(WIDE_ROWS[(2 * j + r) % len(WIDE_ROWS)], n, *SHALLOW[len(out) % len(SHALLOW)])
+    # ldy = out + 1 at a 16-byte base, ldyq = out + 5 at a 4-byte base: whole rows of dwords, the last three columns one by one
+    add(16, FINISH_COLS + 3, 257, 2, y=Y_LAYOUTS.index((1, 0)), yq=YQ_LAYOUTS.index((5, 0)))
+    add(1, FINISH_COLS + 3, 129, 2, y=Y_LAYOUTS.index((1, 0)), yq=YQ_LAYOUTS.index((5, 0)))
+    for in_ in MANY_RANGES_INS:
+        for s in range(FORCED[-1] + 1, -(-in_ // SLICE) + 1):
+            if valid_splits(in_, s):
+                add(ROWS[len(out) % 4], OUTS[len(out) % len(OUTS)], in_, s)
+    for rows, n, in_ in OWN_CHOICE:
+        add(rows, n, in_, 0)
+    for j, (in_, s) in enumerate(DEEP):
+        add(MAX_ROWS, 130, in_, s, weight="image" if j == 1 else "qweight")
+    for rows in range(1, MAX_ROWS + 1):
+        add(rows, *LADDER)
+    return tuple(out)
 
 
 def case_id(c):

@@ -7,8 +7,10 @@ rows' worth of memory behind the last row poisoned with 0x55; a weight that is a
 pitch and base, pad columns poisoned); the output -- fp32 y and int8 yq in turn -- inside a buffer of 0x55 that is compared WHOLE
 with what the reference says it holds afterwards (so the guards in front of, behind and between the rows are part of every
 comparison); the workspace pre-filled with 0x7f and followed by 64 guard bytes.  The launch text is held to the Python plan
-(tests/qdecode_ref.py) at the device's CU count.  tests/qdecode_ref.py has the case table, tests/test_q8d_coverage.py what it
-promises."""
+(tests/qdecode_ref.py) at the device's CU count.  tests/qdecode_ref.py has the two case tables -- cases(), thorough in the small,
+and wide_deep_cases(), the sizes the kernels are built for --, tests/test_q8d_coverage.py what they promise.  Three more calls
+run operands at the edge of the descriptor window (the largest pitch_n and ldq shape_status admits), built on the device inside
+one 0.72 GB buffer of 0x55; the Python layer's timer and its cached workspace follow at the end."""
 import ctypes as C
 
 import numpy as np
@@ -83,9 +85,9 @@ class Weight:
             self.qweight.close()
 
 
-def run(p, weight, bias, relu, out8, splits, cus, x_pad=0, x_off=0, o_pad=0, o_off=0):
+def run(p, weight, bias, relu, out8, splits, cus, x_pad=0, x_off=0, o_pad=0, o_off=0, x_rows=None):
     """One mmh_q8d_linear call on the layouts above; asserts the status, the launch text, the whole output buffer, the
-    workspace's guard.  Returns the launch text."""
+    workspace's guard.  Returns the launch text.  x_rows: device_rows' triple where the caller has laid x out itself."""
     import torch
     import how_to_optimize_gemm_amd as H
     from how_to_optimize_gemm_amd import q8
@@ -94,7 +96,7 @@ def run(p, weight, bias, relu, out8, splits, cus, x_pad=0, x_off=0, o_pad=0, o_o
     out = p.qw.shape[0]
     item = 1 if out8 else 4
     ldo = out + o_pad
-    keep_x, pxq, ldq = device_rows(p.xq, x_pad, x_off)
+    keep_x, pxq, ldq = x_rows or device_rows(p.xq, x_pad, x_off)
     rx, so, db = dev(p.rx), dev(p.so), dev(p.bias)
     planned = D.plan(rows, out, in_, out8, ldo, (item * o_off) % 16, splits, cus)
     assert planned is not None, "the table forces a split count the plan refuses"
@@ -126,9 +128,9 @@ def run(p, weight, bias, relu, out8, splits, cus, x_pad=0, x_off=0, o_pad=0, o_o
     return launched
 
 
-def run_both(p, weight, bias, relu, splits, cus, x_pad=0, x_off=0, y=0, yq=0):
-    a = run(p, weight, bias, relu, False, splits, cus, x_pad, x_off, *D.Y_LAYOUTS[y])
-    b = run(p, weight, bias, relu, True, splits, cus, x_pad, x_off, *D.YQ_LAYOUTS[yq])
+def run_both(p, weight, bias, relu, splits, cus, x_pad=0, x_off=0, y=0, yq=0, x_rows=None):
+    a = run(p, weight, bias, relu, False, splits, cus, x_pad, x_off, *D.Y_LAYOUTS[y], x_rows=x_rows)
+    b = run(p, weight, bias, relu, True, splits, cus, x_pad, x_off, *D.YQ_LAYOUTS[yq], x_rows=x_rows)
     return a, b
 
 
@@ -139,6 +141,114 @@ def test_every_case_of_the_table_is_the_contract_on_both_outputs(index, cus):
     w = Weight(p, c.weight, index)
     try:
         run_both(p, w, c.bias, c.relu, c.splits, cus, c.x_pad, c.x_off, c.y, c.yq)
+    finally:
+        w.close()
+
+
+@pytest.mark.parametrize("index", range(len(D.wide_deep_cases())), ids=[D.case_id(c) for c in D.wide_deep_cases()])
+def test_every_case_of_the_second_table_is_the_contract_on_both_outputs(index, cus):
+    """More than one finish workgroup per row (blockIdx.x of the finish kernel's column is no longer 0), up to 33 strips, up
+    to one K range per slice -- the plan's own choice at one and two rows included, whatever it is on this device --, ranges
+    of 33, 43 and 86 slices, every row count."""
+    c = D.wide_deep_cases()[index]
+    p = (D.problem if c.weight == "qweight" else D.image_problem)(c.rows, c.out, c.in_)
+    w = Weight(p, c.weight, index)
+    try:
+        run_both(p, w, c.bias, c.relu, c.splits, cus, c.x_pad, c.x_off, c.y, c.yq)
+    finally:
+        w.close()
+
+
+# ---- operands at the edge of the descriptor window --------------------------------------------------------------------------
+EDGE_IN, EDGE_OUT = 129, 130
+EDGE_BYTES = 16 + 12 + EDGE_IN * D.largest_pitch_n(EDGE_IN) + 64   # the largest of the three operands below: 0.72 GB
+
+
+@pytest.fixture(scope="module")
+def edge():
+    """The flat 0x55 buffer the operands at the window's edge are strided views of: they are written on the device, there is
+    never a host array of that size."""
+    import torch
+    buf = torch.full((EDGE_BYTES,), POISON, dtype=torch.uint8, device="cuda")
+    yield buf
+    del buf
+    torch.cuda.empty_cache()
+
+
+def edge_operand(buf, values, ld, off, rows_behind=0):
+    """(keep-alive, pointer, ld) of int8 `values` as rows of pitch ld, 16 + off bytes into buf; everything else of the
+    max(its rows, rows_behind) rows' worth of bytes and 64 behind them is 0x55 (again)."""
+    import torch
+    rows, cols = values.shape
+    end = 16 + off + max((rows - 1) * ld + cols, rows_behind * ld) + 64
+    assert off % 4 == 0 and ld % 4 == 0 and end <= buf.numel(), (values.shape, ld, off, buf.numel())
+    buf[:end].fill_(POISON)
+    torch.as_strided(buf.view(torch.int8), (rows, cols), (ld, 1), 16 + off).copy_(dev(values))
+    return buf, buf.data_ptr() + 16 + off, ld
+
+
+class EdgeImage:
+    """Weight's interface for a caller-made image[k][j] = qw[j][k] of pitch `pitch` inside the edge buffer."""
+    qweight = None
+
+    def __init__(self, buf, p, pitch, off):
+        _, self.ptr, self.pitch = edge_operand(buf, np.ascontiguousarray(p.qw.T), pitch, off)
+        self.rw_t = dev(p.rw)
+        self.rw = self.rw_t.data_ptr()
+
+
+@pytest.mark.parametrize("splits", [1, 2])
+def test_the_largest_image_pitch_inside_the_window(edge, cus, splits):
+    """in 129, out 130, 16 rows, pitch_n = P = 5 577 868: the largest multiple of 4 that shape_status admits (the next one is
+    refused: tests/test_q8d_abi.py).  The image spans 128 P + 130 bytes = 0.71 GB, of which 130 per k row are written.
+
+    The offsets of qdecode_partial_kernel's weight descriptor, written down before the first run.  A lane's offset is
+    voff + soff with voff = r P + 16 slot, r <= 127, and soff = kt 128 P; the descriptor's extent is ext_w = (kr - 1) P + 132
+    (strip 0; 4 for strip 1, whose base is 128 bytes further).  With one range kr = 129, nk = 2, ext_w = 128 P + 132 =
+    713 967 236, and the slices issued are 0 - 3:
+      slice 0   offsets 0 .. 127 P + 127 = 708 389 363 < ext_w: image rows 0 - 127, all inside the image;
+      slice 1   soff 128 P = 713 967 104; offsets 128 P .. 255 P + 127 = 1 422 356 467: row 128 (r = 0, 128 P + 0 .. 127) is
+                below ext_w and inside the image, every r >= 1 is at or beyond 129 P > ext_w: zeros;
+      slice 2   soff 256 P = 1 427 934 208; offsets .. 383 P + 127 = 2 136 323 571 < 2^31, all >= 256 P > ext_w: zeros;
+      slice 3   soff 384 P = 2 141 901 312 < 2^31 (the int product does not overflow); offsets 384 P .. 511 P + 127 =
+                2 850 290 675: above 2^31, below 2^32 -- an unsigned 32-bit sum that does not wrap --, all > ext_w: zeros.
+    Slices 2 and 3 are issued behind the range's end and never consumed; nothing of them is fetched.  With two ranges range 0
+    has kr = 128, nk = 1, ext_w = 127 P + 132, and its slice 1 (soff 128 P >= ext_w: zeros) IS consumed -- the second ring
+    stage of an odd slice count; range 1's base is 128 P further, kr = 1, ext_w = 132, its slices 1 and 2 reach 383 P + 127
+    past that base and are out of range from the first row on.  x is 16 dense rows: its offsets stay below 15 ldq + 512.
+    The case is one the contract admits; every offset beyond ext_w must read zeros, and the asserts below are the arithmetic."""
+    pitch = D.largest_pitch_n(EDGE_IN)
+    assert D.window_ok(132, pitch, EDGE_IN) and not D.window_ok(132, pitch + 4, EDGE_IN)
+    assert 3 * 128 * pitch < 1 << 31 and (1 << 31) < 511 * pitch + 127 < 1 << 32 and 128 * pitch + 132 < 256 * pitch
+    p = D.image_problem(16, EDGE_OUT, EDGE_IN)
+    w = EdgeImage(edge, p, pitch, 4)
+    run_both(p, w, True, False, splits, cus, 4, 8, 2, 2)
+
+
+def test_one_image_row_at_the_largest_pitch_inside_the_window(edge, cus):
+    """in 1, out 130, 2 rows, pitch_n = P = 8 355 948: one image row, so the operand is 130 bytes, while the kernel's offsets
+    are as large as at any depth: kr = 1, ext_w = 132 (strip 0), slice 0's rows r >= 1 start at voff = r P up to 127 P + 127 =
+    1 061 205 523, the zero slices 1 and 2 add soff = 128 P = 1 069 561 344 and 256 P = 2 139 122 688 < 2^31; the largest sum is
+    383 P + 127 = 3 200 328 211 < 2^32.  All of it beyond ext_w: zeros, nothing fetched."""
+    pitch = D.largest_pitch_n(1)
+    assert D.window_ok(4, pitch, 1) and not D.window_ok(4, pitch + 4, 1)
+    assert 2 * 128 * pitch < 1 << 31 and 383 * pitch + 127 < 1 << 32
+    p = D.image_problem(2, EDGE_OUT, 1)
+    w = EdgeImage(edge, p, pitch, 12)
+    run_both(p, w, False, True, 0, cus, 0, 4, 1, 1)
+
+
+def test_the_largest_row_pitch_inside_the_window(edge, cus):
+    """in 129, out 130, 16 rows of x at ldq = 8 388 588, the largest multiple of 4 with 256 ldq + in < 2^31 - 4096: x spans
+    134 MB.  The x descriptor's extent is 15 ldq + 132 = 125 828 952; a lane's offset is li ldq + k + 16 g + 128 kt (+ 64) <=
+    15 ldq + 48 + 448: far below 2^31, and beyond the extent only in the last row's bytes past `in` (zeros)."""
+    ldq = D.largest_ldq(EDGE_IN)
+    assert D.window_ok(ldq, 144, EDGE_IN) and not D.window_ok(ldq + 4, 144, EDGE_IN)
+    p = D.problem(16, EDGE_OUT, EDGE_IN)
+    w = Weight(p, "qweight")
+    try:
+        for splits in (1, 2):
+            run_both(p, w, True, True, splits, cus, y=3, yq=3, x_rows=edge_operand(edge, p.xq, ldq, 8, D.MAX_ROWS))
     finally:
         w.close()
 
@@ -189,12 +299,13 @@ def test_caller_made_rows_and_image_that_hold_minus_128(cus):
 
 
 # ---- the Python interface: the same bits as the tile path ---------------------------------------------------------------
-def qrows(p, pad=0):
+def qrows(p, pad=0, rows=None):
+    """The QRows of a Problem's rows (rows: of its first so many) at a pitch of `in` rounded up to 4 plus pad."""
     import torch
     from how_to_optimize_gemm_amd import q8
-    rows, in_ = p.xq.shape
-    keep, _, ldq = device_rows(p.xq, pad, 0)
-    return q8.QRows(keep[16:16 + rows * ldq].view(torch.int8).view(rows, ldq)[:, :in_], dev(p.rx))
+    rows, in_ = rows or p.xq.shape[0], p.xq.shape[1]
+    keep, _, ldq = device_rows(p.xq[:rows], pad, 0)
+    return q8.QRows(keep[16:16 + rows * ldq].view(torch.int8).view(rows, ldq)[:, :in_], dev(p.rx[:rows]))
 
 
 @pytest.mark.parametrize("shape", [(16, 256, 512), (5, 130, 257), (1, 128, 128)], ids=lambda s: "x".join(map(str, s)))
@@ -325,3 +436,84 @@ def test_the_modules_with_decode_give_the_tile_paths_bits(rows, cus):
     yb = mb(x)
     assert q8.last_launch_q8d() == (D.plan(rows, 130, 272, cus=cus)[0] if rows <= 16 else before)
     assert torch.equal(ya.view(torch.int32), yb.view(torch.int32))
+
+
+# ---- the Python layer: the timer, the cached workspace ------------------------------------------------------------------
+@pytest.mark.parametrize("out8", [False, True], ids=["fp32", "int8"])
+def test_time_qlinear_decode_launches_the_plan_and_leaves_the_result(out8, cus):
+    """mmh_time_q8d_linear behind its argument checks: one warm-up and three timed calls; no bound on the time itself."""
+    import math
+    import torch
+    from how_to_optimize_gemm_amd import q8
+    rows, out, in_ = 16, 257, 385
+    p = D.problem(rows, out, in_)
+    qw = q8.QWeight(dev(p.w))
+    x, bias = qrows(p, 4), dev(p.bias)
+    ldo = (out + 15) & ~15 if out8 else out
+    y = torch.full((rows, ldo), POISON, dtype=torch.int8, device="cuda") if out8 else torch.full((rows, ldo), float("nan"), device="cuda")
+    ms = q8.time_qlinear_decode(x, qw, bias, "relu", out=y[:, :out], out_scale=dev(p.so) if out8 else None, warmup=1, reps=3)
+    assert isinstance(ms, float) and math.isfinite(ms) and ms > 0, ms
+    assert q8.last_launch_q8d() == D.plan(rows, out, in_, out8, ldo, cus=cus)[0]
+    got = y.cpu().numpy()
+    want = Q.qlinear_s8_ref(p.xq, p.rx, p.w, p.bias, True, p.so if out8 else None)
+    if out8:
+        assert np.array_equal(got[:, :out], want) and bool((got[:, out:] == POISON).all())
+    else:
+        assert same_bits(got, want)
+    qw.close()
+
+
+def test_the_workspace_grows_between_two_calls_that_nothing_separates(cus):
+    """1 row, then 16 rows with no synchronise in between: the second call replaces the cached workspace while the first may
+    still be running on it (the old tensor goes back to torch's allocator, which hands it to nobody ahead of the stream's
+    work).  Then 1 row again: what is large enough stays.  (in 385 has no 3 ranges without an empty one: 4, one per slice.)"""
+    import torch
+    from how_to_optimize_gemm_amd import q8
+    out, in_, splits = D.FINISH_COLS + 1, 385, 4
+    assert D.valid_splits(in_, splits) and not D.valid_splits(in_, 3)
+    assert D.work_bytes(splits, 1, out) < D.work_bytes(splits, 16, out)
+    p = D.problem(16, out, in_)
+    qw = q8.QWeight(dev(p.w))
+    bias = dev(p.bias)
+    x1, x16 = qrows(p, 4, 1), qrows(p, 4)
+    torch.cuda.synchronize()
+    y1 = q8.qlinear_decode(x1, qw, bias, splits=splits)
+    first = qw._decode_work
+    assert first.numel() >= D.work_bytes(splits, 1, out) and first.numel() < D.work_bytes(splits, 16, out)
+    y16 = q8.qlinear_decode(x16, qw, bias, splits=splits)
+    second = qw._decode_work
+    assert second is not first and second.numel() >= D.work_bytes(splits, 16, out)
+    assert q8.last_launch_q8d() == D.plan(16, out, in_, splits=splits, cus=cus)[0]
+    torch.cuda.synchronize()
+    want = Q.qlinear_s8_ref(p.xq, p.rx, p.w, p.bias)
+    assert same_bits(y1.cpu().numpy(), want[:1]) and same_bits(y16.cpu().numpy(), want)
+    again = q8.qlinear_decode(x1, qw, bias, splits=splits)
+    assert qw._decode_work is second
+    assert same_bits(again.cpu().numpy(), want[:1])
+    qw.close()
+
+
+@pytest.mark.parametrize("splits", [0, 3], ids=["own-choice", "forced-3"])
+def test_reserve_decode_is_enough_for_every_row_count_on_both_outputs(splits, cus):
+    """After reserve_decode() no call of 1 - 16 rows replaces the workspace, on a shape whose own split count -- and with it
+    rows x splits, largest in the middle of the range, not at 16 rows -- varies with the rows (tests/test_q8d_coverage.py)."""
+    from how_to_optimize_gemm_amd import q8
+    out, in_ = D.RESERVE_SHAPE
+    p = D.problem(D.MAX_ROWS, out, in_)
+    qw = q8.QWeight(dev(p.w))
+    bias = dev(p.bias)
+    assert qw._decode_work is None
+    qw.reserve_decode(splits=splits)
+    reserved = qw._decode_work
+    need = max(D.plan(rows, out, in_, splits=splits, cus=cus)[1] for rows in range(1, D.MAX_ROWS + 1))
+    assert reserved.numel() >= need
+    for rows in range(1, D.MAX_ROWS + 1):
+        x = qrows(p, 8, rows)
+        y = q8.qlinear_decode(x, qw, bias, splits=splits)
+        assert q8.last_launch_q8d() == D.plan(rows, out, in_, splits=splits, cus=cus)[0]
+        yq = q8.qlinear_decode(x, qw, bias, out_scale=dev(p.so[:rows]), splits=splits)
+        assert q8.last_launch_q8d() == D.plan(rows, out, in_, True, (out + 15) & ~15, splits=splits, cus=cus)[0]
+        assert qw._decode_work is reserved and qw._decode_work.data_ptr() == reserved.data_ptr(), rows
+        assert same_bits(y.cpu().numpy(), Q.qlinear_s8_ref(p.xq[:rows], p.rx[:rows], p.w, p.bias))
+        assert np.array_equal(yq.q.cpu().numpy(), Q.qlinear_s8_ref(p.xq[:rows], p.rx[:rows], p.w, p.bias, False, p.so[:rows]))
+    qw.close()

@@ -142,6 +142,32 @@ def test_the_plan_is_the_python_restatement(cus):
         "qdecode_partial_kernel, 32 strips x 8 splits of 512 k; qdecode_finish_kernel<false>, 64 workgroups, wide stores"
 
 
+def test_the_windows_edge_is_where_the_formula_puts_it():
+    """shape_status admits the largest pitch_n and the largest ldq of i8_window's formula and refuses the next multiple of 4
+    (tests/test_gpu_qdecode.py runs the admitted ones)."""
+    L = q8.lib_q8d()
+    text, work = C.create_string_buffer(192), C.c_size_t(0)
+    lim = (1 << 31) - 4096
+
+    def status(in_, ldq, pitch_n):
+        return L.mmh_q8d_linear_plan(16, 130, in_, ldq, pitch_n, 0, 130, 0, 0, 0, 1, 256, text, 192, C.byref(work))
+
+    for in_ in (129, 1):
+        pitch = D.largest_pitch_n(in_)
+        assert pitch % 4 == 0 and (in_ + 256) * pitch + 256 < lim <= (in_ + 256) * (pitch + 4) + 256, (in_, pitch)
+        assert D.window_ok(132, pitch, in_) and not D.window_ok(132, pitch + 4, in_)
+        assert status(in_, 132, pitch) == H.OK, (in_, pitch, L.mmh_q8d_last_error())
+        assert status(in_, 132, pitch + 4) == H.ERR_UNSUPPORTED and b"window" in L.mmh_q8d_last_error(), (in_, pitch)
+    assert (D.largest_pitch_n(129), D.largest_pitch_n(1)) == (5577868, 8355948)
+    ldq = D.largest_ldq(129)
+    assert ldq % 4 == 0 and 256 * ldq + 129 < lim <= 256 * (ldq + 4) + 129 and ldq == 8388588
+    assert D.window_ok(ldq, 132, 129) and not D.window_ok(ldq + 4, 132, 129)
+    assert status(129, ldq, 132) == H.OK, L.mmh_q8d_last_error()
+    assert status(129, ldq + 4, 132) == H.ERR_UNSUPPORTED and b"window" in L.mmh_q8d_last_error()
+    # both at once are admitted too: the two conditions are independent
+    assert status(129, ldq, D.largest_pitch_n(129)) == H.OK
+
+
 def test_argument_errors_are_refused_without_a_device():
     L, INV, UNS = q8.lib_q8d(), H.ERR_INVALID_ARG, H.ERR_UNSUPPORTED
     x = 4096   # (a non-NULL, 16-byte aligned address that is never read)
