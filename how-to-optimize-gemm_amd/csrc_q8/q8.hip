@@ -206,7 +206,8 @@ int mmh_q8_quantize_rows(int device, int rows, int cols, const float *dX, int ld
                          float *d_inv_scale, void *stream) {
   if (device < 0 || rows < 0 || cols < 0) return MMH_ERR_INVALID_ARG;
   if (rows == 0) return MMH_OK;
-  if (!dQ || !d_scale || !d_inv_scale || (cols > 0 && !dX) || ldx < cols || ldx < 1 || ldq < cols) return MMH_ERR_INVALID_ARG;
+  // (cols == 0: neither x nor q has a byte to read or write -- an empty tensor's address is NULL --, the scales are 1)
+  if ((cols > 0 && !dQ) || !d_scale || !d_inv_scale || (cols > 0 && !dX) || ldx < cols || ldx < 1 || ldq < cols) return MMH_ERR_INVALID_ARG;
   DeviceGuard guard;
   Q8_TRY(guard.enter(device));
   const bool vec = rows_vec_ok(dX, ldx, dQ, ldq);

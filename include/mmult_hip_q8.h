@@ -63,7 +63,7 @@ int mmh_q8_weight_info(mmh_q8_weight_t weight, int *out, int *in, int *pitch, co
  * ldq >= cols and dQ holds rows * ldq bytes: the bytes [cols, min(ldq, (cols + 15) & ~15)) of every row, the last one
  * included, are written as 0.  One pass over dX.  16-byte
  * loads when dX is 16-byte aligned, ldx % 4 == 0, dQ 4-byte aligned and ldq % 4 == 0; a scalar path otherwise -- same bits.
- * rows == 0: MMH_OK, nothing launched. */
+ * rows == 0: MMH_OK, nothing launched.  cols == 0: every scale is 1, dX and dQ are neither read nor written and may be NULL. */
 int mmh_q8_quantize_rows(int device, int rows, int cols, const float *dX, int ldx, int8_t *dQ, int ldq, float *d_scale,
                          float *d_inv_scale, void *stream);
 
@@ -95,8 +95,8 @@ int mmh_q8_linear_plan(int rows, int out, int in, int ldx, int ldy, int x_mod16,
 int mmh_time_q8_linear(mmh_q8_weight_t weight, int rows, const float *dX, int ldx, const float *dBias, int activation,
                        float *dY, int ldy, int warmup, int reps, void *stream, float *ms_per_call);
 
-/* Argument errors (every entry point): a NULL object, out-pointer or operand (dW / dX may be NULL where in == 0: they are
- * not read), a negative size, a leading dimension below the row length, an activation outside {MMH_ACT_NONE, MMH_ACT_RELU}: MMH_ERR_INVALID_ARG, checked before any device
+/* Argument errors (every entry point): a NULL object, out-pointer or operand (dW / dX, and mmh_q8_quantize_rows' dQ, may be
+ * NULL where in == 0: they are not read or written), a negative size, a leading dimension below the row length, an activation outside {MMH_ACT_NONE, MMH_ACT_RELU}: MMH_ERR_INVALID_ARG, checked before any device
  * call -- nothing is launched and no output is touched. */
 
 #ifdef __cplusplus

@@ -6,7 +6,8 @@ oracle.ref_igemm_s8's exact int32; the epilogue is np.float32 operations in the 
     y = act(fl(fl(fl(float32(acc) * rx[i]) * rw[j]) + bias[j])),   rx = fl(1 / sx), rw = fl(1 / sw)
 float32(acc) rounds to nearest even (numpy's int32 -> float32 cast), no bias: no sum, ReLU: y if (y > 0 or y is NaN) else +0.
 
-Also here: the special rows every test of the contract uses, and plan_text -- mmh_q8_linear_plan's arithmetic in Python."""
+Also here: the special rows every test of the contract uses, plan_text -- mmh_q8_linear_plan's arithmetic in Python --, and
+shapes_256 / thin_256: the smallest shapes the plan sends to the 256x256 tile on a device (the tables' and the fuzzer's)."""
 import numpy as np
 
 F32_MAX = np.float32(3.4028234663852886e38)
@@ -82,6 +83,37 @@ def big_tile(m, n, cus):
     tiles128 = ((m + 127) // 128) * ((n + 127) // 128)
     r256, r128 = (tiles256 + cus - 1) // cus, (tiles128 + 2 * cus - 1) // (2 * cus)
     return r256 <= 0.6 * r128 + 1e-9
+
+
+IN_256 = 192
+
+
+def shapes_256(cu_count):
+    """((rows, out, in) whole, ragged): the multiple-of-256 shape of the fewest elements that i8_big_tile sends to the 256x256
+    tile on this device, and its neighbour three rows and five columns short (the same tiles)."""
+    best = None
+    for a in range(1, 33):
+        for b in range(a, 65):
+            if big_tile(256 * a, 256 * b, cu_count) and (best is None or a * b < best[0] * best[1]):
+                best = (a, b)
+    assert best, cu_count
+    m, n = 256 * best[0], 256 * best[1]
+    assert big_tile(m - 3, n - 5, cu_count)
+    return (m, n, IN_256), (m - 3, n - 5, IN_256)
+
+
+def thin_256(a, b, cu_count):
+    """(rows, out) of the fewest elements that i8_big_tile sends to the 256x256 tile with a last tile `a` rows high and `b`
+    columns wide.  (One tile row and column more than shapes_256's shape, not its neighbour a + 256 by b + 256 short of the
+    next multiple: that one fills fewer 128x128 rounds and goes to the small tile.)"""
+    best = None
+    for i in range(1, 34):
+        for j in range(i, 66):
+            rows, out = 256 * (i - 1) + a, 256 * (j - 1) + b
+            if big_tile(rows, out, cu_count) and (best is None or rows * out < best[0] * best[1]):
+                best = (rows, out)
+    assert best and big_tile(best[0], best[1], cu_count), (a, b, cu_count)
+    return best
 
 
 def plan_text(rows, out, in_, ldx=0, ldy=0, x_mod16=0, y_mod16=0, bias=False, relu=False, cus=256):

@@ -18,6 +18,7 @@ import qchain_ref as Q
 import qlinear_ref as R
 from bitcmp import first_difference, same_bits
 from gpu_operands import cus_fixture, handle_fixture
+from qlinear_ref import IN_256, shapes_256
 
 pytestmark = pytest.mark.gpu
 
@@ -29,23 +30,8 @@ _B = {False: "false", True: "true"}
 Q8O_INSTANTIATIONS = [Row(f"qlinear_s8o_kernel<{t},{t},{t // 32},{_B[e]}>", t, e) for t in (128, 256) for e in (False, True)]
 
 SHAPES_128 = {False: [(128, 128, 128), (128, 128, 64)], True: [(129, 130, 131), (5, 3, 7), (1, 1, 1)]}
-IN_256 = 192
 EPILOGUES = [(False, False), (True, False), (False, True), (True, True)]   # (bias, ReLU)
 POISON = 0x55
-
-
-def shapes_256(cu_count):
-    """((rows, out, in) whole, ragged): the multiple-of-256 shape of the fewest elements that i8_big_tile sends to the 256x256
-    tile on this device, and its neighbour three rows and five columns short (the same tiles)."""
-    best = None
-    for a in range(1, 33):
-        for b in range(a, 65):
-            if R.big_tile(256 * a, 256 * b, cu_count) and (best is None or a * b < best[0] * best[1]):
-                best = (a, b)
-    assert best, cu_count
-    m, n = 256 * best[0], 256 * best[1]
-    assert R.big_tile(m - 3, n - 5, cu_count)
-    return (m, n, IN_256), (m - 3, n - 5, IN_256)
 
 
 @functools.lru_cache(maxsize=4)

@@ -23,6 +23,7 @@ import pytest
 import qlinear_ref as R
 from bitcmp import first_difference, same_bits
 from gpu_operands import _padded, cus_fixture, handle_fixture
+from qlinear_ref import IN_256, shapes_256, thin_256   # (shared with tests/q8_fuzz.py)
 
 pytestmark = pytest.mark.gpu
 
@@ -49,7 +50,6 @@ Q8_INSTANTIATIONS += [Row("quantize_rows_s8_kernel<false>", "rows", 0, False, Fa
                       Row("prepare_weight_s8_kernel", "weight", 0, False, False, False)]
 
 SHAPES_128 = {False: [(128, 128, 128), (128, 128, 64)], True: [(129, 130, 131), (5, 3, 7), (1, 1, 1)]}
-IN_256 = 192
 # stand-alone quantiser / weight shapes (rows x cols).  Wave per row: 1 - 5 and 1023 columns (five rows: the last one alone in
 # a second workgroup); workgroup per row from 1024 on, with and without columns behind the last float4, and on both sides of
 # the 16380 floats the workgroup form keeps in LDS (a longer row's rest is read again)
@@ -71,34 +71,6 @@ WHOLE_LAYOUT, EDGE_LAYOUT = (4, 4, 4, 4), (3, 1, 1, 1)
 # whole tiles need ldy % 4 == 0 and a 16-byte aligned y; x only decides the quantiser's path.  The first is fully dense
 WHOLE_LAYOUTS = ((0, 0, 0, 0), (4, 4, 4, 4), (3, 0, 1, 4), (1, 4, 2, 0), (0, 4, 0, 4))
 GEMM_CLASSES = [(t, e) for t in (128, 256) for e in (False, True)]
-
-
-def shapes_256(cu_count):
-    """((rows, out, in) whole, ragged): the multiple-of-256 shape of the fewest elements that i8_big_tile sends to the 256x256
-    tile on this device, and its neighbour three rows and five columns short (the same tiles)."""
-    best = None
-    for a in range(1, 33):
-        for b in range(a, 65):
-            if R.big_tile(256 * a, 256 * b, cu_count) and (best is None or a * b < best[0] * best[1]):
-                best = (a, b)
-    assert best, cu_count
-    m, n = 256 * best[0], 256 * best[1]
-    assert R.big_tile(m - 3, n - 5, cu_count)
-    return (m, n, IN_256), (m - 3, n - 5, IN_256)
-
-
-def thin_256(a, b, cu_count):
-    """(rows, out) of the fewest elements that i8_big_tile sends to the 256x256 tile with a last tile `a` rows high and `b`
-    columns wide.  (One tile row and column more than shapes_256's shape, not its neighbour a + 256 by b + 256 short of the
-    next multiple: that one fills fewer 128x128 rounds and goes to the small tile.)"""
-    best = None
-    for i in range(1, 34):
-        for j in range(i, 66):
-            rows, out = 256 * (i - 1) + a, 256 * (j - 1) + b
-            if R.big_tile(rows, out, cu_count) and (best is None or rows * out < best[0] * best[1]):
-                best = (rows, out)
-    assert best and R.big_tile(best[0], best[1], cu_count), (a, b, cu_count)
-    return best
 
 
 def gemm_cases(tile, edge, cu_count):
@@ -345,6 +317,40 @@ def test_an_empty_inner_dimension_is_the_formula_on_zero_sums(cus):
         want = R.qlinear_ref(x, w, b, relu)
         assert same_bits(got, want) and untouched, (relu, got, want)
     assert same_bits(R.qlinear_ref(x, w, bias, True), np.tile(np.array([1.5, 0.0, 0.0], np.float32), (4, 1)))
+
+
+FUZZ_EMPTY_IN = (53, 271, 0)   # (rows, out, in) of the fuzz case that found it (tests/q8_fuzz.py: cases(64, 2026, 256)[9])
+
+
+def test_the_row_quantiser_takes_an_empty_inner_dimension_and_feeds_the_int8_output(cus):
+    """A (rows, 0) tensor has no bytes and torch gives it the address NULL: mmh_q8_quantize_rows took the NULL dQ for an argument
+    error, so quantize_rows, quantize and an int8-output qlinear on fp32 rows raised where in == 0.  Every scale is 1, nothing
+    of the window is written, and the layer is the requantised bias."""
+    import torch
+    import qchain_ref as Q
+    from how_to_optimize_gemm_amd import q8
+    rows, out, _ = FUZZ_EMPTY_IN
+    x = _padded(rows, 0, 4, 4)[1][:, :0]
+    window = torch.full((rows, 8), 0x55, dtype=torch.int8, device="cuda")
+    q, s, r = q8.quantize_rows(x, out=window[:, :0])
+    launched = q8.last_launch()
+    torch.cuda.synchronize()
+    assert launched.startswith("quantize_rows_s8_kernel<false>") and launched.endswith(f"{(rows + 3) // 4} workgroups"), launched
+    assert tuple(q.shape) == (rows, 0) and bool((window == 0x55).all())
+    ones = np.ones(rows, np.float32)
+    assert same_bits(s.cpu().numpy(), ones) and same_bits(r.cpu().numpy(), ones)
+    xq = q8.quantize(x)
+    assert (xq.rows, xq.cols) == (rows, 0) and same_bits(xq.inv_scale.cpu().numpy(), ones)
+    bias = np.random.default_rng(53).uniform(-4, 4, out).astype(np.float32)
+    bias[:4] = [0.25, -1.25, 63.75, -100.0]   # ties at the scale 2, and a value that clamps
+    qw = q8.QWeight(_padded(out, 0, 4, 4)[1][:, :0])
+    for relu in (False, True):
+        got = q8.qlinear(x, qw, torch.from_numpy(bias).cuda(), "relu" if relu else None, out_scale=2.0)
+        torch.cuda.synchronize()
+        want = Q.requant_ref(R.qlinear_ref(np.zeros((rows, 0), np.float32), np.zeros((out, 0), np.float32), bias, relu), np.full(rows, 2.0, np.float32))
+        assert np.array_equal(got.q.cpu().numpy(), want) and same_bits(got.inv_scale.cpu().numpy(), np.full(rows, 0.5, np.float32)), relu
+        assert (want[0, :4] == ([0, 0, 127, 0] if relu else [0, -2, 127, -127])).all()
+    qw.close()
 
 
 def test_large_sums_round_to_nearest_even(cus):
