@@ -57,133 +57,89 @@ def translation_units(ab: bool = False) -> list[str]:
     return tus
 
 
-def _build_shared(target: str, defines: list[str], objdir: str, force: bool, verbose: bool) -> str:
-    """hipcc -c every translation unit of csrc/ (in parallel: the kernel-heavy ones take a minute each),
-    then link them into `target`.  Objects live under build/<objdir>/ (git-ignored) and are reused while
-    neither their .hip nor any header has changed."""
+def _headers(*dirs: str, c_headers: tuple = ()) -> list[str]:
+    """What makes an object stale besides its .hip: csrc/'s headers and the first C header, the named C headers of include/,
+    and every .hpp of `dirs`."""
+    out = [s for s in library_sources() if s.endswith((".hpp", ".h", ".inc"))]
+    out += [os.path.join(REPO, "include", h) for h in c_headers]
+    for d in dirs:
+        out += [os.path.join(d, f) for f in sorted(os.listdir(d)) if f.endswith(".hpp")]
+    return out
+
+
+def _hip_sources(d: str) -> list[str]:
+    return sorted(os.path.join(d, f) for f in os.listdir(d) if f.endswith(".hip"))
+
+
+def _build_shared(target: str, tus: list[str], includes: list[str], headers: list[str], objdir: str, version_script: str,
+                  extra: tuple = (), link_flags: tuple = (), force: bool = False, verbose: bool = False) -> str:
+    """The one recipe of every library: hipcc -c each translation unit of `tus` with -I `includes` in that order, then `extra`
+    (defines, and what goes with them), at most 16 at a time (the kernel-heavy ones take a minute each), then link the objects
+    into `target` with `link_flags` and the version script.  Objects live under build/<objdir>/ (git-ignored) and are reused while
+    neither their .hip nor any of `headers` has changed."""
     from concurrent.futures import ThreadPoolExecutor
-    ab = "-DMMH_AB_BUILD" in defines
-    headers = [s for s in library_sources() if s.endswith((".hpp", ".h", ".inc"))]
-    if ab and os.path.isdir(AB_SRC):
-        headers += [os.path.join(AB_SRC, f) for f in sorted(os.listdir(AB_SRC)) if f.endswith((".hpp", ".inc"))]
     odir = os.path.join(PKG_DIR, "build", objdir)
     os.makedirs(odir, exist_ok=True)
-    flags = [f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-result", "-I" + CSRC] + defines
-    if ab:
-        flags.append("-I" + AB_SRC)
-    jobs = []
-    for tu in translation_units(ab):
-        obj = os.path.join(odir, os.path.basename(tu)[:-4] + ".o")
-        if force or _stale(obj, [tu] + headers):
-            jobs.append([hipcc()] + flags + ["-c", tu, "-o", obj])
+    flags = [f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-result"] + ["-I" + d for d in includes] + list(extra)
+    objs = [os.path.join(odir, os.path.basename(tu)[:-4] + ".o") for tu in tus]
+    jobs = [[hipcc()] + flags + ["-c", tu, "-o", obj] for tu, obj in zip(tus, objs) if force or _stale(obj, [tu] + headers)]
     def run(cmd):
         if verbose:
             print(" ".join(cmd))
         subprocess.check_call(cmd)
     if jobs:
-        with ThreadPoolExecutor(max_workers=min(len(jobs), os.cpu_count() or 4)) as pool:
+        with ThreadPoolExecutor(max_workers=min(len(jobs), os.cpu_count() or 4, 16)) as pool:
             list(pool.map(run, jobs))
-    objs = [os.path.join(odir, os.path.basename(tu)[:-4] + ".o") for tu in translation_units(ab)]
-    if force or jobs or _stale(target, objs + [os.path.join(CSRC, "exports.map")]):
-        run([hipcc(), f"--offload-arch={ARCH}", "-shared", "-fPIC"] + objs +
-            ["-o", target, "-ldl", "-Wl,--version-script=" + os.path.join(CSRC, "exports.map")])
+    if force or jobs or _stale(target, objs + [version_script]):
+        run([hipcc(), f"--offload-arch={ARCH}", "-shared", "-fPIC"] + objs + ["-o", target] + list(link_flags) + ["-Wl,--version-script=" + version_script])
     return target
+
+
+def _build_product(target: str, defines: list[str], objdir: str, force: bool, verbose: bool) -> str:
+    """csrc/*.hip with `defines` -> `target`; -DMMH_AB_BUILD adds tools/ab/'s translation units, headers and -I."""
+    ab = "-DMMH_AB_BUILD" in defines
+    headers = _headers()
+    if ab and os.path.isdir(AB_SRC):
+        headers += [os.path.join(AB_SRC, f) for f in sorted(os.listdir(AB_SRC)) if f.endswith((".hpp", ".inc"))]
+    return _build_shared(target, translation_units(ab), [CSRC], headers, objdir, os.path.join(CSRC, "exports.map"),
+                         defines + (["-I" + AB_SRC] if ab else []), ["-ldl"], force, verbose)
 
 
 def build_library(force: bool = False, verbose: bool = False) -> str:
     """hipcc --offload-arch=gfx950 -> how-to-optimize-gemm_amd/libmmult_hip.so"""
-    return _build_shared(LIB, [], "product", force, verbose)
+    return _build_product(LIB, [], "product", force, verbose)
 
 
 def build_q8_library(force: bool = False, verbose: bool = False) -> str:
-    """csrc_q8/*.hip -> how-to-optimize-gemm_amd/libmmult_hip_q8.so, with the product library's flags (-I csrc: its kernels sit
-    on csrc/'s int8 tile and quantisation rules).  Objects under build/q8/; an object is stale when its .hip, a header of
-    csrc_q8/ or of csrc/, or either C header has changed."""
-    from concurrent.futures import ThreadPoolExecutor
-    headers = [s for s in library_sources() if s.endswith((".hpp", ".h", ".inc"))]
-    headers += [os.path.join(REPO, "include", "mmult_hip_q8.h")]
-    headers += [os.path.join(CSRC_Q8, f) for f in sorted(os.listdir(CSRC_Q8)) if f.endswith(".hpp")]
-    tus = sorted(os.path.join(CSRC_Q8, f) for f in os.listdir(CSRC_Q8) if f.endswith(".hip"))
-    odir = os.path.join(PKG_DIR, "build", "q8")
-    os.makedirs(odir, exist_ok=True)
-    flags = [f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-result", "-I" + CSRC_Q8, "-I" + CSRC]
-    objs = [os.path.join(odir, os.path.basename(tu)[:-4] + ".o") for tu in tus]
-    jobs = [[hipcc()] + flags + ["-c", tu, "-o", obj] for tu, obj in zip(tus, objs) if force or _stale(obj, [tu] + headers)]
-    def run(cmd):
-        if verbose:
-            print(" ".join(cmd))
-        subprocess.check_call(cmd)
-    if jobs:
-        with ThreadPoolExecutor(max_workers=min(len(jobs), os.cpu_count() or 4)) as pool:
-            list(pool.map(run, jobs))
-    version_script = os.path.join(CSRC_Q8, "exports_q8.map")
-    if force or jobs or _stale(Q8_LIB, objs + [version_script]):
-        run([hipcc(), f"--offload-arch={ARCH}", "-shared", "-fPIC"] + objs + ["-o", Q8_LIB, "-Wl,--version-script=" + version_script])
-    return Q8_LIB
+    """csrc_q8/*.hip -> how-to-optimize-gemm_amd/libmmult_hip_q8.so, with the product library's flags (-I csrc_q8 -I csrc: its
+    kernels sit on csrc/'s int8 tile and quantisation rules).  Objects under build/q8/; an object is stale when its .hip, a header
+    of csrc_q8/ or of csrc/, or either C header has changed."""
+    return _build_shared(Q8_LIB, _hip_sources(CSRC_Q8), [CSRC_Q8, CSRC], _headers(CSRC_Q8, c_headers=("mmult_hip_q8.h",)), "q8",
+                         os.path.join(CSRC_Q8, "exports_q8.map"), force=force, verbose=verbose)
 
 
 def build_q8o_library(force: bool = False, verbose: bool = False) -> str:
-    """csrc_q8o/*.hip -> how-to-optimize-gemm_amd/libmmult_hip_q8o.so, with the q8 library's flags (-I csrc_q8o -I csrc_q8 -I csrc:
-    its kernels sit on csrc/'s int8 tile and quantisation rules).  Objects under build/q8o/; an object is stale when its .hip, a
-    header of csrc_q8o/, csrc_q8/ or csrc/, or a C header has changed.  At most 16 compile jobs at a time."""
-    from concurrent.futures import ThreadPoolExecutor
-    headers = [s for s in library_sources() if s.endswith((".hpp", ".h", ".inc"))]
-    headers += [os.path.join(REPO, "include", "mmult_hip_q8.h"), os.path.join(REPO, "include", "mmult_hip_q8o.h")]
-    for d in (CSRC_Q8, CSRC_Q8O):
-        headers += [os.path.join(d, f) for f in sorted(os.listdir(d)) if f.endswith(".hpp")]
-    tus = sorted(os.path.join(CSRC_Q8O, f) for f in os.listdir(CSRC_Q8O) if f.endswith(".hip"))
-    odir = os.path.join(PKG_DIR, "build", "q8o")
-    os.makedirs(odir, exist_ok=True)
-    flags = [f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-result", "-I" + CSRC_Q8O, "-I" + CSRC_Q8, "-I" + CSRC]
-    objs = [os.path.join(odir, os.path.basename(tu)[:-4] + ".o") for tu in tus]
-    jobs = [[hipcc()] + flags + ["-c", tu, "-o", obj] for tu, obj in zip(tus, objs) if force or _stale(obj, [tu] + headers)]
-    def run(cmd):
-        if verbose:
-            print(" ".join(cmd))
-        subprocess.check_call(cmd)
-    if jobs:
-        with ThreadPoolExecutor(max_workers=min(len(jobs), os.cpu_count() or 4, 16)) as pool:
-            list(pool.map(run, jobs))
-    version_script = os.path.join(CSRC_Q8O, "exports_q8o.map")
-    if force or jobs or _stale(Q8O_LIB, objs + [version_script]):
-        run([hipcc(), f"--offload-arch={ARCH}", "-shared", "-fPIC"] + objs + ["-o", Q8O_LIB, "-Wl,--version-script=" + version_script])
-    return Q8O_LIB
+    """csrc_q8o/*.hip -> how-to-optimize-gemm_amd/libmmult_hip_q8o.so: the q8 library's recipe with -I csrc_q8o in front (its host
+    side shares csrc_q8/q8_host.hpp).  Objects under build/q8o/; csrc_q8o/'s headers and mmult_hip_q8o.h make them stale too."""
+    return _build_shared(Q8O_LIB, _hip_sources(CSRC_Q8O), [CSRC_Q8O, CSRC_Q8, CSRC],
+                         _headers(CSRC_Q8, CSRC_Q8O, c_headers=("mmult_hip_q8.h", "mmult_hip_q8o.h")), "q8o",
+                         os.path.join(CSRC_Q8O, "exports_q8o.map"), force=force, verbose=verbose)
 
 
 def build_q8d_library(force: bool = False, verbose: bool = False) -> str:
-    """csrc_q8d/*.hip -> how-to-optimize-gemm_amd/libmmult_hip_q8d.so, with the q8o library's flags and -I csrc_q8d in front (its
-    kernels use csrc/'s LDS-DMA loader, plan rules and quantisation rules).  Objects under build/q8d/; an object is stale when its
-    .hip, a header of csrc_q8d/, csrc_q8o/, csrc_q8/ or csrc/, or a C header has changed.  At most 16 compile jobs at a time."""
-    from concurrent.futures import ThreadPoolExecutor
-    headers = [s for s in library_sources() if s.endswith((".hpp", ".h", ".inc"))]
-    headers += [os.path.join(REPO, "include", h) for h in ("mmult_hip_q8.h", "mmult_hip_q8o.h", "mmult_hip_q8d.h")]
-    for d in (CSRC_Q8, CSRC_Q8O, CSRC_Q8D):
-        headers += [os.path.join(d, f) for f in sorted(os.listdir(d)) if f.endswith(".hpp")]
-    tus = sorted(os.path.join(CSRC_Q8D, f) for f in os.listdir(CSRC_Q8D) if f.endswith(".hip"))
-    odir = os.path.join(PKG_DIR, "build", "q8d")
-    os.makedirs(odir, exist_ok=True)
-    flags = [f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-result", "-I" + CSRC_Q8D, "-I" + CSRC_Q8O, "-I" + CSRC_Q8,
-             "-I" + CSRC]
-    objs = [os.path.join(odir, os.path.basename(tu)[:-4] + ".o") for tu in tus]
-    jobs = [[hipcc()] + flags + ["-c", tu, "-o", obj] for tu, obj in zip(tus, objs) if force or _stale(obj, [tu] + headers)]
-    def run(cmd):
-        if verbose:
-            print(" ".join(cmd))
-        subprocess.check_call(cmd)
-    if jobs:
-        with ThreadPoolExecutor(max_workers=min(len(jobs), os.cpu_count() or 4, 16)) as pool:
-            list(pool.map(run, jobs))
-    version_script = os.path.join(CSRC_Q8D, "exports_q8d.map")
-    if force or jobs or _stale(Q8D_LIB, objs + [version_script]):
-        run([hipcc(), f"--offload-arch={ARCH}", "-shared", "-fPIC"] + objs + ["-o", Q8D_LIB, "-Wl,--version-script=" + version_script])
-    return Q8D_LIB
+    """csrc_q8d/*.hip -> how-to-optimize-gemm_amd/libmmult_hip_q8d.so: the q8o library's recipe with -I csrc_q8d in front (its
+    kernels use csrc/'s LDS-DMA loader, plan rules and quantisation rules).  Objects under build/q8d/; csrc_q8d/'s headers and
+    mmult_hip_q8d.h make them stale too."""
+    return _build_shared(Q8D_LIB, _hip_sources(CSRC_Q8D), [CSRC_Q8D, CSRC_Q8O, CSRC_Q8, CSRC],
+                         _headers(CSRC_Q8, CSRC_Q8O, CSRC_Q8D, c_headers=("mmult_hip_q8.h", "mmult_hip_q8o.h", "mmult_hip_q8d.h")), "q8d",
+                         os.path.join(CSRC_Q8D, "exports_q8d.map"), force=force, verbose=verbose)
 
 
 def build_timeline_library(force: bool = False) -> str:
     """-DMMH_AB_BUILD -DMMH_DMA_TIMELINE -> libmmult_hip_tl.so: the A/B library whose plain LDS-DMA kernels
     also write per-workgroup wall-clock stamps (tools/dma_timeline.py only; the stamps perturb the
     schedule of the big tiles, so no other tool measures with this build)."""
-    return _build_shared(os.path.join(PKG_DIR, "libmmult_hip_tl.so"), ["-DMMH_AB_BUILD", "-DMMH_DMA_TIMELINE"], "timeline",
+    return _build_product(os.path.join(PKG_DIR, "libmmult_hip_tl.so"), ["-DMMH_AB_BUILD", "-DMMH_DMA_TIMELINE"], "timeline",
                          force, False)
 
 
@@ -192,7 +148,7 @@ def build_ab_library(force: bool = False, verbose: bool = False) -> str:
     scheduling A/B variants and the timing-only ablation builds (wrong results).  Loaded by
     tools/ab_bench.py and tools/misc_bench.py only; never by the package, the harness or the tests
     of the product path."""
-    return _build_shared(AB_LIB, ["-DMMH_AB_BUILD"], "ab", force, verbose)
+    return _build_product(AB_LIB, ["-DMMH_AB_BUILD"], "ab", force, verbose)
 
 
 def build_harness(force: bool = False) -> str:

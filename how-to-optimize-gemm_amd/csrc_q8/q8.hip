@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "../../include/mmult_hip_q8.h"
+#include "q8_host.hpp"
 #include "qlinear_launch.hpp"
 #include "qlinear_plan.hpp"
 #include "quant_rows_s8.hpp"
@@ -29,44 +30,15 @@ struct mmh_q8_weight {
 
 namespace {
 
-thread_local std::string g_error, g_launch;
-
-int fail(int status, const std::string &text) {
-  g_error = text;
-  return status;
-}
-int hip_fail(hipError_t e, const char *what) { return fail(MMH_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e)); }
-#define Q8_TRY(expr)                                  \
-  do {                                                \
-    hipError_t e_ = (expr);                           \
-    if (e_ != hipSuccess) return hip_fail(e_, #expr); \
-  } while (0)
-
-struct DeviceGuard {
-  int prev = -1;
-  bool switched = false;
-  hipError_t enter(int device) {
-    hipError_t e = hipGetDevice(&prev);
-    if (e != hipSuccess || prev == device) return e;
-    e = hipSetDevice(device);
-    switched = e == hipSuccess;
-    return e;
-  }
-  ~DeviceGuard() {
-    if (switched) (void)hipSetDevice(prev);
-  }
-};
-
 bool capturing(hipStream_t s) {
   hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
   (void)hipStreamIsCapturing(s, &cap);
   return cap != hipStreamCaptureStatusNone;
 }
-int base16(const void *p) { return (int)(reinterpret_cast<uintptr_t>(p) & 15); }
 
 // quant_vec_ok's convention for the row quantiser's operands (q NULL: scales only)
 bool rows_vec_ok(const float *x, int ldx, const int8_t *q, int ldq) {
-  return base16(x) == 0 && ldx % 4 == 0 && (!q || ((reinterpret_cast<uintptr_t>(q) & 3) == 0 && ldq % 4 == 0));
+  return mod16(x) == 0 && ldx % 4 == 0 && (!q || (mod4(q) == 0 && ldq % 4 == 0));
 }
 
 hipError_t launch_row_quant(const RowQuantArgs &a, const RowQuantPlan &p, hipStream_t s) {
@@ -105,8 +77,6 @@ void release(mmh_q8_weight *w) {
   delete w;
 }
 
-bool act_ok(int activation) { return activation == MMH_ACT_NONE || activation == MMH_ACT_RELU; }
-
 int linear_args(const mmh_q8_weight *w, int rows, const float *dX, int ldx, int activation, const float *dY, int ldy) {
   if (!w || rows < 0 || !act_ok(activation)) return MMH_ERR_INVALID_ARG;
   if (rows == 0) return MMH_OK;
@@ -116,7 +86,7 @@ int linear_args(const mmh_q8_weight *w, int rows, const float *dX, int ldx, int 
 
 // mmh_q8_linear behind its argument checks, on the object's device
 int linear_on(mmh_q8_weight *w, int rows, const float *dX, int ldx, const float *dBias, int activation, float *dY, int ldy, hipStream_t s) {
-  const Q8Plan p = plan_qlinear(rows, w->out, w->in, ldx, ldy, base16(dX), base16(dY), w->cus, dBias != nullptr, activation == MMH_ACT_RELU);
+  const Q8Plan p = plan_qlinear(rows, w->out, w->in, ldx, ldy, mod16(dX), mod16(dY), w->cus, dBias != nullptr, activation == MMH_ACT_RELU);
   if (const int rc = reserve(w, p.scratch, s, "mmh_q8_linear"); rc != MMH_OK) return rc;
   char *base = static_cast<char *>(w->scratch);
   int8_t *xq = reinterpret_cast<int8_t *>(base);
@@ -125,8 +95,7 @@ int linear_on(mmh_q8_weight *w, int rows, const float *dX, int ldx, const float 
   Q8_TRY(launch_row_quant(qa, p.quant, s));
   const QlinearArgs g{rows, w->out, w->in, xq, p.pitch_k, w->q, w->pitch, rx, w->inv_scale, dBias, activation == MMH_ACT_RELU ? 1 : 0,
                       dY, ldy, p.nbm, p.nbn};
-  Q8_TRY(p.tile == 256 ? (p.edge ? launch_qlinear_256_edge(g, s) : launch_qlinear_256(g, s))
-                       : (p.edge ? launch_qlinear_128_edge(g, s) : launch_qlinear_128(g, s)));
+  Q8_TRY(launch_qlinear(p, g, s));
   g_launch = p.text;
   return MMH_OK;
 }
@@ -234,18 +203,17 @@ int mmh_q8_linear_s8(mmh_q8_weight_t w, int rows, const int8_t *dXq, int ldq, co
   if (!w || rows < 0 || !act_ok(activation)) return MMH_ERR_INVALID_ARG;
   if (rows == 0) return MMH_OK;
   if ((w->in > 0 && !dXq) || !d_inv_scale || !dY || ldq < w->in || ldy < w->out) return MMH_ERR_INVALID_ARG;   // (in == 0: xq is not read)
-  if (w->in > 0 && !i8_dword(ldq, base16(dXq)))
+  if (w->in > 0 && !i8_dword(ldq, mod16(dXq)))
     return fail(MMH_ERR_UNSUPPORTED, "mmh_q8_linear_s8: the tile reads the int8 rows in dwords -- ldq and dXq's address must be multiples of 4");
   if (!i8_window(ldq, w->pitch, w->in))
     return fail(MMH_ERR_UNSUPPORTED, "mmh_q8_linear_s8: the int8 rows lie beyond the GEMM's 2 GiB descriptor window");
   DeviceGuard guard;
   Q8_TRY(guard.enter(w->device));
   // the plan of the fp32 call on these rows, without its quantiser: the same tile, guard and grid, launched straight on dXq
-  const Q8Plan p = plan_qlinear(rows, w->out, w->in, w->in > 0 ? w->in : 1, ldy, 0, base16(dY), w->cus, dBias != nullptr, activation == MMH_ACT_RELU);
+  const Q8Plan p = plan_qlinear(rows, w->out, w->in, w->in > 0 ? w->in : 1, ldy, 0, mod16(dY), w->cus, dBias != nullptr, activation == MMH_ACT_RELU);
   const QlinearArgs g{rows, w->out, w->in, dXq, ldq, w->q, w->pitch, d_inv_scale, w->inv_scale, dBias, activation == MMH_ACT_RELU ? 1 : 0,
                       dY, ldy, p.nbm, p.nbn};
-  Q8_TRY(p.tile == 256 ? (p.edge ? launch_qlinear_256_edge(g, static_cast<hipStream_t>(stream)) : launch_qlinear_256(g, static_cast<hipStream_t>(stream)))
-                       : (p.edge ? launch_qlinear_128_edge(g, static_cast<hipStream_t>(stream)) : launch_qlinear_128(g, static_cast<hipStream_t>(stream))));
+  Q8_TRY(launch_qlinear(p, g, static_cast<hipStream_t>(stream)));
   const char *then = strstr(p.text, "then ");
   g_launch = then ? then + 5 : p.text;
   return MMH_OK;
@@ -280,24 +248,7 @@ int mmh_time_q8_linear(mmh_q8_weight_t w, int rows, const float *dX, int ldx, co
   DeviceGuard guard;
   Q8_TRY(guard.enter(w->device));
   hipStream_t s = static_cast<hipStream_t>(stream);
-  int rc = MMH_OK;
-  for (int i = 0; i < warmup && rc == MMH_OK; ++i) rc = linear_on(w, rows, dX, ldx, dBias, activation, dY, ldy, s);
-  if (rc != MMH_OK) return rc;
-  hipEvent_t t0 = nullptr, t1 = nullptr;
-  hipError_t e = hipEventCreate(&t0);
-  if (e == hipSuccess) e = hipEventCreate(&t1);
-  if (e == hipSuccess) e = hipEventRecord(t0, s);
-  for (int i = 0; i < reps && rc == MMH_OK && e == hipSuccess; ++i) rc = linear_on(w, rows, dX, ldx, dBias, activation, dY, ldy, s);
-  float ms = 0.f;
-  if (rc == MMH_OK && e == hipSuccess) e = hipEventRecord(t1, s);
-  if (rc == MMH_OK && e == hipSuccess) e = hipEventSynchronize(t1);
-  if (rc == MMH_OK && e == hipSuccess) e = hipEventElapsedTime(&ms, t0, t1);
-  if (t0) (void)hipEventDestroy(t0);
-  if (t1) (void)hipEventDestroy(t1);
-  if (rc != MMH_OK) return rc;
-  if (e != hipSuccess) return hip_fail(e, "mmh_time_q8_linear");
-  *ms_per_call = ms / reps;
-  return MMH_OK;
+  return timed("mmh_time_q8_linear", warmup, reps, s, ms_per_call, [&] { return linear_on(w, rows, dX, ldx, dBias, activation, dY, ldy, s); });
 }
 
 }  // extern "C"

@@ -24,6 +24,14 @@ hipError_t launch_qlinear_128_edge(const QlinearArgs &a, hipStream_t s);
 hipError_t launch_qlinear_256(const QlinearArgs &a, hipStream_t s);
 hipError_t launch_qlinear_256_edge(const QlinearArgs &a, hipStream_t s);
 
+// the one of the four that the plan (qlinear_plan.hpp, Q8Plan: tile, edge) names -- a template, so that the kernels' translation
+// units, which include this header, do not depend on the plan's
+template <class Plan>
+hipError_t launch_qlinear(const Plan &p, const QlinearArgs &a, hipStream_t s) {
+  return p.tile == 256 ? (p.edge ? launch_qlinear_256_edge(a, s) : launch_qlinear_256(a, s))
+                       : (p.edge ? launch_qlinear_128_edge(a, s) : launch_qlinear_128(a, s));
+}
+
 template <int TILE, bool EDGE>
 hipError_t launch_qlinear_tile(const QlinearArgs &a, hipStream_t s) {
   constexpr int TM = TILE / 32;

@@ -1,10 +1,10 @@
 // q8d.hip -- libmmult_hip_q8d.so: the extern "C" entry points of include/mmult_hip_q8d.h and the two kernels' launches.
 // Stateless: no object, no allocation; the split-K partials live in the caller's workspace.  Every argument is checked before the
 // first device call; every entry point that touches the device restores the caller's.
-#include <atomic>
 #include <string>
 
 #include "../../include/mmult_hip_q8d.h"
+#include "q8_host.hpp"
 #include "qdecode_plan.hpp"
 #include "qdecode_s8.hpp"
 
@@ -16,52 +16,7 @@ static_assert(kQdStrip == QD_STRIP && kQdSlice == IK && kQdMaxRows == QD_ROWS &&
 
 namespace {
 
-thread_local std::string g_error, g_launch;
-
-int fail(int status, const std::string &text) {
-  g_error = text;
-  return status;
-}
-int hip_fail(hipError_t e, const char *what) { return fail(MMH_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e)); }
-#define Q8D_TRY(expr)                                 \
-  do {                                                \
-    hipError_t e_ = (expr);                           \
-    if (e_ != hipSuccess) return hip_fail(e_, #expr); \
-  } while (0)
-
-struct DeviceGuard {
-  int prev = -1;
-  bool switched = false;
-  hipError_t enter(int device) {
-    hipError_t e = hipGetDevice(&prev);
-    if (e != hipSuccess || prev == device) return e;
-    e = hipSetDevice(device);
-    switched = e == hipSuccess;
-    return e;
-  }
-  ~DeviceGuard() {
-    if (switched) (void)hipSetDevice(prev);
-  }
-};
-
-int mod4(const void *p) { return (int)(reinterpret_cast<uintptr_t>(p) & 3); }
-int mod16(const void *p) { return (int)(reinterpret_cast<uintptr_t>(p) & 15); }
-bool act_ok(int activation) { return activation == MMH_ACT_NONE || activation == MMH_ACT_RELU; }
-
-// The shape's and the layout's rules, shared by the call and its plan (mods: the bases modulo 4): mmh_q8o_linear's, and the rows
-int shape_status(const char *who, int rows, int out, int in, int ldq, int pitch_n, int ldo, int xq4, int wq4) {
-  if (rows < 0 || out < 0 || in < 0) return MMH_ERR_INVALID_ARG;
-  if (rows == 0) return MMH_OK;
-  if (rows > kQdMaxRows)
-    return fail(MMH_ERR_UNSUPPORTED, std::string(who) + ": at most 16 rows (MMH_Q8D_MAX_ROWS) -- larger batches are the tile path's");
-  if (out == 0 || ldq < in || pitch_n < out || ldo < out) return MMH_ERR_INVALID_ARG;
-  if (in > 0 && !(i8_dword(ldq, xq4) && i8_dword(pitch_n, wq4)))
-    return fail(MMH_ERR_UNSUPPORTED, std::string(who) + ": the kernel reads the int8 rows and the weight image in dwords -- their pitches "
-                "and base addresses must be multiples of 4");
-  if (!i8_window(ldq, pitch_n, in))
-    return fail(MMH_ERR_UNSUPPORTED, std::string(who) + ": the operands lie beyond the kernel's 2 GiB descriptor window");
-  return MMH_OK;
-}
+constexpr ShapeRules kShape{"kernel", "kernel", kQdMaxRows};   // mmh_q8o_linear's rules, and at most 16 rows
 
 struct Call {
   int device, rows, out, in;
@@ -85,22 +40,13 @@ struct Call {
   const void *o() const { return out8() ? static_cast<const void *>(yq) : y; }
 };
 
-int cu_count(int device) {
-  static std::atomic<int> known[64];
-  if (device < 64 && known[device].load(std::memory_order_relaxed) > 0) return known[device].load(std::memory_order_relaxed);
-  int cus = 0;
-  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || cus <= 0) cus = 256;
-  if (device < 64) known[device].store(cus, std::memory_order_relaxed);
-  return cus;
-}
-
 // Everything that needs no device.  (The workspace's SIZE is held to the plan of the device's CU count: linear_on, before its
 // first launch.)
 int call_status(const char *who, const Call &c) {
   if (c.device < 0 || !act_ok(c.activation) || c.splits < 0 || c.rows < 0 || c.out < 0 || c.in < 0) return MMH_ERR_INVALID_ARG;
   if (c.rows == 0) return MMH_OK;   // (nothing is read, nothing launched)
   if ((c.y != nullptr) == (c.yq != nullptr) || c.out8() != (c.yq != nullptr)) return MMH_ERR_INVALID_ARG;   // exactly one, and the scale's
-  if (const int rc = shape_status(who, c.rows, c.out, c.in, c.ldq, c.pitch_n, c.ldo(), mod4(c.xq), mod4(c.wq)); rc != MMH_OK || c.rows == 0)
+  if (const int rc = shape_status(who, kShape, c.rows, c.out, c.in, c.ldq, c.pitch_n, c.ldo(), mod4(c.xq), mod4(c.wq)); rc != MMH_OK || c.rows == 0)
     return rc;
   if ((c.in > 0 && (!c.xq || !c.wq)) || !c.rx || !c.rw) return MMH_ERR_INVALID_ARG;
   if (c.in > 0) {
@@ -121,7 +67,7 @@ int linear_on(const char *who, const Call &c, hipStream_t s) {
   if (c.in > 0) {
     hipLaunchKernelGGL(qdecode_partial_kernel, dim3((unsigned)p.strips, (unsigned)p.splits), dim3(QD_WAVES * 64), 0, s, c.rows, c.out,
                        c.in, p.k_len, c.xq, c.ldq, c.wq, c.pitch_n, work, p.wp);
-    Q8D_TRY(hipGetLastError());
+    Q8_TRY(hipGetLastError());
   }
   const dim3 grid((unsigned)p.finish_x, (unsigned)c.rows);
   const int relu = c.activation == MMH_ACT_RELU ? 1 : 0;
@@ -131,7 +77,7 @@ int linear_on(const char *who, const Call &c, hipStream_t s) {
   else
     hipLaunchKernelGGL(qdecode_finish_kernel<false>, grid, dim3(QD_FINISH_THREADS), 0, s, c.rows, c.out, p.splits, work, p.wp, c.rx, c.rw,
                        c.bias, relu, c.so, static_cast<void *>(c.y), c.ldy, p.wide ? 1 : 0);
-  Q8D_TRY(hipGetLastError());
+  Q8_TRY(hipGetLastError());
   g_launch = p.text;
   return MMH_OK;
 }
@@ -150,7 +96,7 @@ int mmh_q8d_linear(int device, int rows, int out, int in, const int8_t *dXq, int
                dY,     ldy,  dYq,   ldyq, d_work, work_bytes, splits};
   if (const int rc = call_status("mmh_q8d_linear", c); rc != MMH_OK || rows == 0) return rc;
   DeviceGuard guard;
-  Q8D_TRY(guard.enter(device));
+  Q8_TRY(guard.enter(device));
   return linear_on("mmh_q8d_linear", c, static_cast<hipStream_t>(stream));
 }
 
@@ -159,7 +105,7 @@ int mmh_q8d_linear_plan(int rows, int out, int in, int ldq, int pitch_n, int out
   if (rows <= 0 || out <= 0 || ((xq_mod4 | wq_mod4) & ~3) || (o_mod16 & ~15) || (out8 & ~1) || splits < 0 || !text || text_bytes <= 0 ||
       !work_bytes)
     return MMH_ERR_INVALID_ARG;
-  if (const int rc = shape_status("mmh_q8d_linear_plan", rows, out, in, ldq, pitch_n, ldo, xq_mod4, wq_mod4); rc != MMH_OK) return rc;
+  if (const int rc = shape_status("mmh_q8d_linear_plan", kShape, rows, out, in, ldq, pitch_n, ldo, xq_mod4, wq_mod4); rc != MMH_OK) return rc;
   const QdPlan p = plan_qdecode(rows, out, in, out8 != 0, ldo, o_mod16, splits, cu_count > 0 ? cu_count : 256);
   if (!p.ok) return fail(MMH_ERR_INVALID_ARG, "mmh_q8d_linear_plan: the forced split count leaves a K range empty");
   snprintf(text, (size_t)text_bytes, "%s", p.text);
@@ -177,26 +123,9 @@ int mmh_time_q8d_linear(int device, int rows, int out, int in, const int8_t *dXq
   if (const int rc = call_status("mmh_time_q8d_linear", c); rc != MMH_OK) return rc;
   if (rows == 0) return MMH_ERR_INVALID_ARG;   // (nothing to time)
   DeviceGuard guard;
-  Q8D_TRY(guard.enter(device));
+  Q8_TRY(guard.enter(device));
   hipStream_t s = static_cast<hipStream_t>(stream);
-  int rc = MMH_OK;
-  for (int i = 0; i < warmup && rc == MMH_OK; ++i) rc = linear_on("mmh_time_q8d_linear", c, s);
-  if (rc != MMH_OK) return rc;
-  hipEvent_t t0 = nullptr, t1 = nullptr;
-  hipError_t e = hipEventCreate(&t0);
-  if (e == hipSuccess) e = hipEventCreate(&t1);
-  if (e == hipSuccess) e = hipEventRecord(t0, s);
-  for (int i = 0; i < reps && rc == MMH_OK && e == hipSuccess; ++i) rc = linear_on("mmh_time_q8d_linear", c, s);
-  float ms = 0.f;
-  if (rc == MMH_OK && e == hipSuccess) e = hipEventRecord(t1, s);
-  if (rc == MMH_OK && e == hipSuccess) e = hipEventSynchronize(t1);
-  if (rc == MMH_OK && e == hipSuccess) e = hipEventElapsedTime(&ms, t0, t1);
-  if (t0) (void)hipEventDestroy(t0);
-  if (t1) (void)hipEventDestroy(t1);
-  if (rc != MMH_OK) return rc;
-  if (e != hipSuccess) return hip_fail(e, "mmh_time_q8d_linear");
-  *ms_per_call = ms / reps;
-  return MMH_OK;
+  return timed("mmh_time_q8d_linear", warmup, reps, s, ms_per_call, [&] { return linear_on("mmh_time_q8d_linear", c, s); });
 }
 
 }  // extern "C"

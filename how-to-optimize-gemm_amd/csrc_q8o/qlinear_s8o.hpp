@@ -90,6 +90,14 @@ hipError_t launch_qlinear_s8o_128_edge(const QlinearS8oArgs &a, hipStream_t s);
 hipError_t launch_qlinear_s8o_256(const QlinearS8oArgs &a, hipStream_t s);
 hipError_t launch_qlinear_s8o_256_edge(const QlinearS8oArgs &a, hipStream_t s);
 
+// the one of the four that the plan (qlinear_s8o_plan.hpp, Q8oPlan: tile, edge) names -- a template, so that the kernels' translation
+// units, which include this header, do not depend on the plan's
+template <class Plan>
+hipError_t launch_qlinear_s8o(const Plan &p, const QlinearS8oArgs &a, hipStream_t s) {
+  return p.tile == 256 ? (p.edge ? launch_qlinear_s8o_256_edge(a, s) : launch_qlinear_s8o_256(a, s))
+                       : (p.edge ? launch_qlinear_s8o_128_edge(a, s) : launch_qlinear_s8o_128(a, s));
+}
+
 template <int TILE, bool EDGE>
 hipError_t launch_qlinear_s8o_tile(const QlinearS8oArgs &a, hipStream_t s) {
   constexpr int TM = TILE / 32;

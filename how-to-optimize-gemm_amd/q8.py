@@ -36,62 +36,68 @@ def tensor_args(t, rows, cols, what, dtype, device):
     overlap) -- for a tensor that belongs to no handle: (data_ptr, leading dimension)."""
     return MMult._tensor_args(_OnDevice(device), t, rows, cols, what, dtype)
 
-HEADER = os.path.join(os.path.dirname(_abi.HEADER), "mmult_hip_q8.h")
-LIB_PATH = os.path.join(_api.PKG_DIR, "libmmult_hip_q8.so")
-CONSTANTS, PROTOTYPES = _abi.parse(HEADER)
-EXPORTS = list(PROTOTYPES)   # every symbol include/mmult_hip_q8.h declares
 _STATUS_NAMES = {v: name for name, v in _abi.CONSTANTS.items() if name == "MMH_OK" or name.startswith("MMH_ERR_")}
 
-_lib = None
+
+class _Library:
+    """One of the layer's libraries (built in-tree by build.py): `header` under include/ is parsed now, `path` is loaded on
+    first use, on the HIP runtime torch and libmmult_hip.so share, and every prototype of the header is bound.  `prefix` names
+    its <prefix>_last_error and <prefix>_last_launch.  Fails loudly."""
+
+    def __init__(self, header: str, path: str, prefix: str):
+        self.header = os.path.join(os.path.dirname(_abi.HEADER), header)
+        self.path = os.path.join(_api.PKG_DIR, path)
+        self.prefix = prefix
+        self.constants, self.prototypes = _abi.parse(self.header)
+        self._lib = None
+
+    def lib(self) -> C.CDLL:
+        if self._lib is None:
+            _api._share_hip_runtime_with_torch()
+            if not os.path.exists(self.path):
+                raise MMultError(ERR_UNSUPPORTED, "load", f"{self.path} is missing -- run __graft_entry__.build(); there is no CPU fallback")
+            L = C.CDLL(self.path)
+            for name, (restype, argtypes) in self.prototypes.items():
+                fn = getattr(L, name)
+                fn.restype, fn.argtypes = restype, argtypes
+            self._lib = L
+        return self._lib
+
+    def check(self, status: int, where: str) -> None:
+        if status != OK:
+            last = getattr(self.lib(), self.prefix + "_last_error")().decode()
+            detail = _STATUS_NAMES.get(status, "unknown status")
+            raise MMultError(status, where, f"{detail}; {last}" if last else detail)
+
+    def last_launch(self) -> str:
+        return getattr(self.lib(), self.prefix + "_last_launch")().decode()
 
 
-def lib() -> C.CDLL:
-    """Load libmmult_hip_q8.so (built in-tree by build.py) on the HIP runtime torch and libmmult_hip.so share.  Fails loudly."""
-    global _lib
-    if _lib is not None:
-        return _lib
-    _api._share_hip_runtime_with_torch()
-    if not os.path.exists(LIB_PATH):
-        raise MMultError(ERR_UNSUPPORTED, "load", f"{LIB_PATH} is missing -- run __graft_entry__.build(); there is no CPU fallback")
-    L = C.CDLL(LIB_PATH)
-    for name, (restype, argtypes) in PROTOTYPES.items():
-        fn = getattr(L, name)
-        fn.restype, fn.argtypes = restype, argtypes
-    _lib = L
-    return L
+_q8 = _Library("mmult_hip_q8.h", "libmmult_hip_q8.so", "mmh_q8")       # fp32 out, the weight object, the row quantiser
+_q8o = _Library("mmult_hip_q8o.h", "libmmult_hip_q8o.so", "mmh_q8o")   # int8 out
+_q8d = _Library("mmult_hip_q8d.h", "libmmult_hip_q8d.so", "mmh_q8d")   # 1 - 16 rows, split-K
+HEADER, LIB_PATH, CONSTANTS, PROTOTYPES = _q8.header, _q8.path, _q8.constants, _q8.prototypes
+EXPORTS = list(PROTOTYPES)   # every symbol include/mmult_hip_q8.h declares
+Q8O_HEADER, Q8O_LIB_PATH = _q8o.header, _q8o.path
+Q8D_HEADER, Q8D_LIB_PATH = _q8d.header, _q8d.path
+Q8D_MAX_ROWS = _q8d.constants["MMH_Q8D_MAX_ROWS"]
+lib, lib_q8o, lib_q8d = _q8.lib, _q8o.lib, _q8d.lib   # the loaded ctypes libraries
+_check = _q8.check
 
 
-Q8O_HEADER = os.path.join(os.path.dirname(_abi.HEADER), "mmult_hip_q8o.h")
-Q8O_LIB_PATH = os.path.join(_api.PKG_DIR, "libmmult_hip_q8o.so")
-_lib_q8o = None
-
-
-def lib_q8o() -> C.CDLL:
-    """Load libmmult_hip_q8o.so (the int8-output layer) on first use, bound from its own header.  Fails loudly."""
-    global _lib_q8o
-    if _lib_q8o is not None:
-        return _lib_q8o
-    _api._share_hip_runtime_with_torch()
-    if not os.path.exists(Q8O_LIB_PATH):
-        raise MMultError(ERR_UNSUPPORTED, "load", f"{Q8O_LIB_PATH} is missing -- run __graft_entry__.build(); there is no CPU fallback")
-    L = C.CDLL(Q8O_LIB_PATH)
-    for name, (restype, argtypes) in _abi.parse(Q8O_HEADER)[1].items():
-        fn = getattr(L, name)
-        fn.restype, fn.argtypes = restype, argtypes
-    _lib_q8o = L
-    return L
-
-
-def _check_q8o(status: int, where: str) -> None:
-    if status != OK:
-        last = lib_q8o().mmh_q8o_last_error().decode()
-        detail = _STATUS_NAMES.get(status, "unknown status")
-        raise MMultError(status, where, f"{detail}; {last}" if last else detail)
+def last_launch() -> str:
+    """What the last qlinear / quantize_rows on this thread launched: the row quantiser's form and path, the GEMM's instantiation."""
+    return _q8.last_launch()
 
 
 def last_launch_q8o() -> str:
     """What the last int8-output qlinear on this thread launched."""
-    return lib_q8o().mmh_q8o_last_launch().decode()
+    return _q8o.last_launch()
+
+
+def last_launch_q8d() -> str:
+    """What the last qlinear_decode on this thread launched."""
+    return _q8d.last_launch()
 
 
 def qlinear_s8o_plan(rows: int, out_features: int, in_features: int, ldq: int = 0, pitch_n: int = 0, ldyq: int = 0, xq_mod4: int = 0,
@@ -100,44 +106,10 @@ def qlinear_s8o_plan(rows: int, out_features: int, in_features: int, ldq: int = 
     pitch (the length rounded up to 16)."""
     p16 = lambda n: (n + 15) & ~15
     text = C.create_string_buffer(128)
-    _check_q8o(lib_q8o().mmh_q8o_linear_plan(rows, out_features, in_features, ldq or p16(in_features), pitch_n or p16(out_features),
+    _q8o.check(lib_q8o().mmh_q8o_linear_plan(rows, out_features, in_features, ldq or p16(in_features), pitch_n or p16(out_features),
                                              ldyq or p16(out_features), xq_mod4, wq_mod4, yq_mod4, cu_count, text, len(text)),
                "mmh_q8o_linear_plan")
     return text.value.decode()
-
-
-Q8D_HEADER = os.path.join(os.path.dirname(_abi.HEADER), "mmult_hip_q8d.h")
-Q8D_LIB_PATH = os.path.join(_api.PKG_DIR, "libmmult_hip_q8d.so")
-Q8D_MAX_ROWS = _abi.parse(Q8D_HEADER)[0]["MMH_Q8D_MAX_ROWS"]
-_lib_q8d = None
-
-
-def lib_q8d() -> C.CDLL:
-    """Load libmmult_hip_q8d.so (the small-batch layer) on first use, bound from its own header.  Fails loudly."""
-    global _lib_q8d
-    if _lib_q8d is not None:
-        return _lib_q8d
-    _api._share_hip_runtime_with_torch()
-    if not os.path.exists(Q8D_LIB_PATH):
-        raise MMultError(ERR_UNSUPPORTED, "load", f"{Q8D_LIB_PATH} is missing -- run __graft_entry__.build(); there is no CPU fallback")
-    L = C.CDLL(Q8D_LIB_PATH)
-    for name, (restype, argtypes) in _abi.parse(Q8D_HEADER)[1].items():
-        fn = getattr(L, name)
-        fn.restype, fn.argtypes = restype, argtypes
-    _lib_q8d = L
-    return L
-
-
-def _check_q8d(status: int, where: str) -> None:
-    if status != OK:
-        last = lib_q8d().mmh_q8d_last_error().decode()
-        detail = _STATUS_NAMES.get(status, "unknown status")
-        raise MMultError(status, where, f"{detail}; {last}" if last else detail)
-
-
-def last_launch_q8d() -> str:
-    """What the last qlinear_decode on this thread launched."""
-    return lib_q8d().mmh_q8d_last_launch().decode()
 
 
 def qlinear_decode_plan(rows: int, out_features: int, in_features: int, ldq: int = 0, pitch_n: int = 0, out8: bool = False, ldo: int = 0,
@@ -147,22 +119,10 @@ def qlinear_decode_plan(rows: int, out_features: int, in_features: int, ldq: int
     rows of the default pitch."""
     p16 = lambda n: (n + 15) & ~15
     text, work = C.create_string_buffer(192), C.c_size_t(0)
-    _check_q8d(lib_q8d().mmh_q8d_linear_plan(rows, out_features, in_features, ldq or p16(in_features), pitch_n or p16(out_features),
+    _q8d.check(lib_q8d().mmh_q8d_linear_plan(rows, out_features, in_features, ldq or p16(in_features), pitch_n or p16(out_features),
                                              int(bool(out8)), ldo or (p16(out_features) if out8 else out_features), xq_mod4, wq_mod4,
                                              o_mod16, splits, cu_count, text, len(text), C.byref(work)), "mmh_q8d_linear_plan")
     return text.value.decode(), work.value
-
-
-def _check(status: int, where: str) -> None:
-    if status != OK:
-        last = lib().mmh_q8_last_error().decode()
-        detail = _STATUS_NAMES.get(status, "unknown status")
-        raise MMultError(status, where, f"{detail}; {last}" if last else detail)
-
-
-def last_launch() -> str:
-    """What the last qlinear / quantize_rows on this thread launched: the row quantiser's form and path, the GEMM's instantiation."""
-    return lib().mmh_q8_last_launch().decode()
 
 
 def _activation_id(activation, what: str) -> int:
@@ -350,6 +310,14 @@ def _bias_ptr(what, bias, qweight):
     return bias.data_ptr()
 
 
+def _float_rows(what, x, qweight) -> None:
+    """What every entry point asks of an fp32 x: (rows, in_features), and no gradient to lose."""
+    if x.dim() != 2 or x.shape[1] != qweight.in_features:
+        raise MMultError(ERR_INVALID_ARG, what, f"need a 2-D x (rows, {qweight.in_features})")
+    if x.requires_grad:
+        raise MMultError(ERR_INVALID_ARG, what, "the int8 layer has no backward: x requires grad")
+
+
 def _rows_args(what, x: QRows, qweight):
     if x.cols != qweight.in_features or x.device != qweight.device:
         raise MMultError(ERR_INVALID_ARG, what, f"need QRows of {qweight.in_features} columns on the weight's device")
@@ -388,38 +356,48 @@ def _scale_vectors(what, out_scale, rows, device):
     return torch.full((rows,), float(so), dtype=torch.float32, device=dev), torch.full((rows,), float(inv), dtype=torch.float32, device=dev)
 
 
+def _out_window(what, out, rows, n, out8, device):
+    """(out, address, leading dimension) of a (rows, n) result on `device`: the caller's `out`, or new rows -- int8 (out8) of
+    pitch n rounded up to 16, else dense fp32.  One row has no row stride to go by: its view's, where that holds the row."""
+    import torch
+    dtype = torch.int8 if out8 else torch.float32
+    if out is None:
+        out = torch.empty((rows, (n + 15) & ~15), dtype=dtype, device=f"cuda:{device}")[:, :n] if out8 else \
+            torch.empty((rows, n), dtype=dtype, device=f"cuda:{device}")
+    po, ldo = tensor_args(out, rows, n, what + "(out)", dtype, device)
+    if rows == 1 and out.stride(0) >= n:
+        ldo = out.stride(0)
+    return out, po, ldo
+
+
+def _run(library: _Library, name: str, args, device: int, time):
+    """time None: mmh_<name>(*args, stream).  time = (warmup, reps): mmh_time_<name>'s mean milliseconds per call."""
+    if time is None:
+        return library.check(getattr(library.lib(), "mmh_" + name)(*args, _stream(device)), "mmh_" + name)
+    ms = C.c_float(0.0)
+    library.check(getattr(library.lib(), "mmh_time_" + name)(*args, time[0], time[1], _stream(device), C.byref(ms)), "mmh_time_" + name)
+    return ms.value
+
+
 def _linear_s8o(what, x: QRows, qweight, bias, activation, so, inv, out=None, time=None):
     """mmh_q8o_linear (time = (warmup, reps): mmh_time_q8o_linear) on a QRows with the output scales `so` and their
     reciprocals `inv` (rows floats each): the QRows of the output, in `out` or in new rows of pitch out_features rounded up to 16."""
-    import torch
     act = _activation_id(activation, what)
     rows, pxq, ldq, prx = _rows_args(what, x, qweight)
     n = qweight.out_features
-    if out is None:
-        out = torch.empty((rows, (n + 15) & ~15), dtype=torch.int8, device=x.q.device)[:, :n]
-    pyq, ldyq = tensor_args(out, rows, n, what + "(out)", torch.int8, qweight.device)
-    if rows == 1 and out.stride(0) >= n:
-        ldyq = out.stride(0)
+    out, pyq, ldyq = _out_window(what, out, rows, n, True, qweight.device)
     pq, _, pr = qweight._ptrs
     args = (qweight.device, rows, n, qweight.in_features, pxq, ldq, prx, pq, qweight.pitch, pr, _bias_ptr(what, bias, qweight), act,
             so.data_ptr(), pyq, ldyq)
-    if time is not None:
-        ms = C.c_float(0.0)
-        _check_q8o(lib_q8o().mmh_time_q8o_linear(*args, time[0], time[1], _stream(qweight.device), C.byref(ms)), "mmh_time_q8o_linear")
-        return ms.value
-    if rows > 0:
-        _check_q8o(lib_q8o().mmh_q8o_linear(*args, _stream(qweight.device)), "mmh_q8o_linear")
-    return QRows._of_window(out, inv[:rows], pyq, ldyq)
+    ms = _run(_q8o, "q8o_linear", args, qweight.device, time) if time is not None or rows > 0 else None
+    return ms if time is not None else QRows._of_window(out, inv[:rows], pyq, ldyq)
 
 
 def _linear_args(what, x, qweight, bias, activation, out):
     """mmh_q8_linear's arguments between the object and the stream, and `out`."""
     import torch
     act = _activation_id(activation, what)
-    if x.dim() != 2 or x.shape[1] != qweight.in_features:
-        raise MMultError(ERR_INVALID_ARG, what, f"need a 2-D x (rows, {qweight.in_features})")
-    if x.requires_grad:
-        raise MMultError(ERR_INVALID_ARG, what, "the int8 layer has no backward: x requires grad")
+    _float_rows(what, x, qweight)
     rows, dev = x.shape[0], qweight.device
     if out is None:
         out = torch.empty((rows, qweight.out_features), dtype=torch.float32, device=x.device)
@@ -437,30 +415,25 @@ def qlinear(x, qweight: QWeight, bias=None, activation=None, out=None, out_scale
     fl(1 / out_scale) --, which the next qlinear reads in place."""
     if out_scale is not None:
         if not isinstance(x, QRows):
-            if x.dim() != 2 or x.shape[1] != qweight.in_features:
-                raise MMultError(ERR_INVALID_ARG, "qlinear", f"need a 2-D x (rows, {qweight.in_features})")
-            if x.requires_grad:
-                raise MMultError(ERR_INVALID_ARG, "qlinear", "the int8 layer has no backward: x requires grad")
+            _float_rows("qlinear", x, qweight)
             x = quantize(x)
         so, inv = _scale_vectors("qlinear", out_scale, x.rows, qweight.device)
         return _linear_s8o("qlinear", x, qweight, bias, activation, so, inv, out)
     if isinstance(x, QRows):
         args, out = _linear_s8_args("qlinear", x, qweight, bias, activation, out)
         if args[0] > 0:
-            _check(lib().mmh_q8_linear_s8(qweight._handle, *args, _stream(qweight.device)), "mmh_q8_linear_s8")
+            _run(_q8, "q8_linear_s8", (qweight._handle, *args), qweight.device, None)
         return out
     args, out = _linear_args("qlinear", x, qweight, bias, activation, out)
     if args[0] > 0:
-        _check(lib().mmh_q8_linear(qweight._handle, *args, _stream(qweight.device)), "mmh_q8_linear")
+        _run(_q8, "q8_linear", (qweight._handle, *args), qweight.device, None)
     return out
 
 
 def time_qlinear(x, qweight: QWeight, bias=None, activation=None, out=None, warmup: int = 1, reps: int = 20) -> float:
     """Mean milliseconds per qlinear call (one event pair around `reps` calls)."""
     args, _ = _linear_args("time_qlinear", x, qweight, bias, activation, out)
-    ms = C.c_float(0.0)
-    _check(lib().mmh_time_q8_linear(qweight._handle, *args, warmup, reps, _stream(qweight.device), C.byref(ms)), "mmh_time_q8_linear")
-    return ms.value
+    return _run(_q8, "q8_linear", (qweight._handle, *args), qweight.device, (warmup, reps))
 
 
 def time_qlinear_s8o(x: QRows, qweight: QWeight, bias=None, activation=None, out=None, out_scale=1.0, warmup: int = 1, reps: int = 20) -> float:
@@ -484,19 +457,13 @@ def _linear_q8d(what, x: QRows, qweight, bias, activation, so, inv, out=None, sp
     """mmh_q8d_linear (time = (warmup, reps): mmh_time_q8d_linear) on a QRows of at most 16 rows.  so None: the fp32 result in
     `out` or a new dense tensor; else the output scales `so` and their reciprocals `inv` (rows floats each) and the QRows of the
     output, in `out` or in new rows of pitch out_features rounded up to 16.  The partials go through the weight's workspace."""
-    import torch
     act = _activation_id(activation, what)
     rows, pxq, ldq, prx = _rows_args(what, x, qweight)
     if rows > Q8D_MAX_ROWS:
         raise MMultError(ERR_UNSUPPORTED, what, f"at most {Q8D_MAX_ROWS} rows -- larger batches are qlinear's")
     n, k = qweight.out_features, qweight.in_features
     out8 = so is not None
-    if out is None:
-        out = torch.empty((rows, (n + 15) & ~15), dtype=torch.int8, device=x.q.device)[:, :n] if out8 else \
-            torch.empty((rows, n), dtype=torch.float32, device=x.q.device)
-    po, ldo = tensor_args(out, rows, n, what + "(out)", torch.int8 if out8 else torch.float32, qweight.device)
-    if rows == 1 and out.stride(0) >= n:
-        ldo = out.stride(0)
+    out, po, ldo = _out_window(what, out, rows, n, out8, qweight.device)
     if rows == 0 or n == 0:
         if time is not None:
             raise MMultError(ERR_INVALID_ARG, what, "nothing to time")
@@ -509,11 +476,9 @@ def _linear_q8d(what, x: QRows, qweight, bias, activation, so, inv, out=None, sp
     args = (qweight.device, rows, n, k, pxq, ldq, prx, pq, qweight.pitch, pr, _bias_ptr(what, bias, qweight), act,
             so.data_ptr() if out8 else None, None if out8 else po, 0 if out8 else ldo, po if out8 else None, ldo if out8 else 0,
             work.data_ptr() if work is not None else None, work.numel() if work is not None else 0, splits)
+    ms = _run(_q8d, "q8d_linear", args, qweight.device, time)
     if time is not None:
-        ms = C.c_float(0.0)
-        _check_q8d(lib_q8d().mmh_time_q8d_linear(*args, time[0], time[1], _stream(qweight.device), C.byref(ms)), "mmh_time_q8d_linear")
-        return ms.value
-    _check_q8d(lib_q8d().mmh_q8d_linear(*args, _stream(qweight.device)), "mmh_q8d_linear")
+        return ms
     return QRows._of_window(out, inv[:rows], po, ldo) if out8 else out
 
 
@@ -521,10 +486,7 @@ def _decode_rows(what, x, qweight) -> QRows:
     """x as the QRows the decode kernels read: itself, or quantize(x) of an fp32 (rows <= 16, in_features) tensor."""
     if isinstance(x, QRows):
         return x
-    if x.dim() != 2 or x.shape[1] != qweight.in_features:
-        raise MMultError(ERR_INVALID_ARG, what, f"need a 2-D x (rows, {qweight.in_features})")
-    if x.requires_grad:
-        raise MMultError(ERR_INVALID_ARG, what, "the int8 layer has no backward: x requires grad")
+    _float_rows(what, x, qweight)
     if x.shape[0] > Q8D_MAX_ROWS:
         raise MMultError(ERR_UNSUPPORTED, what, f"at most {Q8D_MAX_ROWS} rows -- larger batches are qlinear's")
     return quantize(x)

@@ -5,6 +5,7 @@ import ctypes as C
 import functools
 import os
 import re
+import struct
 import sys
 
 import pytest
@@ -62,6 +63,24 @@ def plan(fn, *args):
     kern, tiles, grid = C.c_int(-9), C.c_long(-9), C.c_int(-9)
     rc = fn(*args, C.byref(kern), C.byref(tiles), C.byref(grid))
     return rc, (kern.value, tiles.value, grid.value)
+
+
+def dynamic_exports(path):
+    """Names of the defined global functions in an ELF64 shared object's dynamic symbol table."""
+    blob = open(path, "rb").read()
+    shoff, = struct.unpack_from("<Q", blob, 0x28)
+    shentsize, shnum = struct.unpack_from("<HH", blob, 0x3A)
+    sections = [struct.unpack_from("<IIQQQQIIQQ", blob, shoff + i * shentsize) for i in range(shnum)]
+    names = []
+    for _, sh_type, _, _, off, size, link, _, _, entsize in sections:
+        if sh_type != 11:   # SHT_DYNSYM
+            continue
+        stroff = sections[link][4]
+        for p in range(off, off + size, entsize):
+            st_name, st_info, _, st_shndx = struct.unpack_from("<IBBH", blob, p)
+            if st_shndx != 0 and (st_info & 15) == 2 and (st_info >> 4) in (1, 2):   # defined, FUNC, GLOBAL / WEAK
+                names.append(blob[stroff + st_name:blob.index(b"\0", stroff + st_name)].decode())
+    return sorted(names)
 
 
 # ---- instantiations and their NN twins: twins() yields (instantiation, NN twin, tile) ----------------------------------------

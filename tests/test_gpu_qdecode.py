@@ -463,6 +463,44 @@ def test_time_qlinear_decode_launches_the_plan_and_leaves_the_result(out8, cus):
     qw.close()
 
 
+@pytest.mark.parametrize("warmup,reps", [(1, 1), (0, 2)], ids=["in-the-warm-up", "between-the-events"])
+def test_the_timing_loop_unwinds_from_a_refused_call(warmup, reps, cus):
+    """mmh_time_q8d_linear on a valid call whose work_bytes is one byte short of the plan's: linear_on refuses it in the warm-up
+    (before the timer's events exist) or in the first timed call (after they do).  Either way the status and the message are the
+    call's, nothing is launched -- the output and the workspace keep their fill, the launch text is the earlier call's -- and a
+    correct timed call on the same rows and output follows.  (An argument refusal: nothing invalid reaches the device.)"""
+    import math
+    import torch
+    import how_to_optimize_gemm_amd as H
+    from how_to_optimize_gemm_amd import q8
+    rows, out, in_ = 3, 130, 257
+    p = D.problem(rows, out, in_)
+    qw = q8.QWeight(dev(p.w))
+    x, bias = qrows(p, 4), dev(p.bias)
+    text, work_bytes, _, _ = D.plan(rows, out, in_, cus=cus)
+    assert work_bytes > 1
+    q8.qlinear_decode(qrows(p, 4, 2), qw)   # (two rows: a launch text that is not this call's)
+    before = q8.last_launch_q8d()
+    assert before and before != text
+    y = torch.full((rows, out), 7.0, device="cuda")
+    work = torch.full((work_bytes,), WORK_FILL, dtype=torch.uint8, device="cuda")
+    L, ms = q8.lib_q8d(), C.c_float(-1.0)
+    pq, _, pr = qw._ptrs
+    rc = L.mmh_time_q8d_linear(0, rows, out, in_, x._ptr, x._ld, x.inv_scale.data_ptr(), pq, qw.pitch, pr, bias.data_ptr(), H.ACT_NONE, None,
+                               y.data_ptr(), out, None, 0, work.data_ptr(), work_bytes - 1, 0, warmup, reps,
+                               torch.cuda.current_stream().cuda_stream, C.byref(ms))
+    assert rc == H.ERR_INVALID_ARG, (rc, L.mmh_q8d_last_error())
+    assert L.mmh_q8d_last_error() == b"mmh_time_q8d_linear: the workspace is smaller than the plan's work_bytes"
+    torch.cuda.synchronize()
+    assert bool((y == 7.0).all()) and bool((work == WORK_FILL).all()) and ms.value == -1.0
+    assert q8.last_launch_q8d() == before
+    took = q8.time_qlinear_decode(x, qw, bias, out=y, warmup=1, reps=3)
+    assert isinstance(took, float) and math.isfinite(took) and took > 0, took
+    assert q8.last_launch_q8d() == text
+    assert same_bits(y.cpu().numpy(), Q.qlinear_s8_ref(p.xq, p.rx, p.w, p.bias))
+    qw.close()
+
+
 def test_the_workspace_grows_between_two_calls_that_nothing_separates(cus):
     """1 row, then 16 rows with no synchronise in between: the second call replaces the cached workspace while the first may
     still be running on it (the old tensor goes back to torch's allocator, which hands it to nobody ahead of the stream's

@@ -4,7 +4,6 @@ include/mmult_hip_q8.h declares, every prototype binds from the parsed header, m
 import ctypes as C
 import itertools
 import os
-import struct
 import threading
 
 import pytest
@@ -12,6 +11,7 @@ import pytest
 import how_to_optimize_gemm_amd as H
 from how_to_optimize_gemm_amd import abi_header, build, q8
 import qlinear_ref as R
+from built_lib import dynamic_exports
 from conftest import REPO
 
 
@@ -24,24 +24,6 @@ def test_build_all_builds_the_library_after_the_product_library(monkeypatch):
     monkeypatch.setattr(build, "build_harness", lambda force=False: calls.append("harness"))
     build.build_all()
     assert calls[:2] == ["product", "q8"], calls
-
-
-def dynamic_exports(path):
-    """Names of the defined global functions in an ELF64 shared object's dynamic symbol table."""
-    blob = open(path, "rb").read()
-    shoff, = struct.unpack_from("<Q", blob, 0x28)
-    shentsize, shnum = struct.unpack_from("<HH", blob, 0x3A)
-    sections = [struct.unpack_from("<IIQQQQIIQQ", blob, shoff + i * shentsize) for i in range(shnum)]
-    names = []
-    for _, sh_type, _, _, off, size, link, _, _, entsize in sections:
-        if sh_type != 11:   # SHT_DYNSYM
-            continue
-        stroff = sections[link][4]
-        for p in range(off, off + size, entsize):
-            st_name, st_info, _, st_shndx = struct.unpack_from("<IBBH", blob, p)
-            if st_shndx != 0 and (st_info & 15) == 2 and (st_info >> 4) in (1, 2):   # defined, FUNC, GLOBAL / WEAK
-                names.append(blob[stroff + st_name:blob.index(b"\0", stroff + st_name)].decode())
-    return sorted(names)
 
 
 def test_the_library_exports_exactly_the_headers_prototypes():

@@ -5,7 +5,6 @@ forced split counts, work_bytes is the header's formula, and argument errors are
 import ctypes as C
 import itertools
 import os
-import struct
 import threading
 
 import pytest
@@ -13,7 +12,7 @@ import pytest
 import how_to_optimize_gemm_amd as H
 from how_to_optimize_gemm_amd import abi_header, build, q8
 import qdecode_ref as D
-from built_lib import REPO
+from built_lib import REPO, dynamic_exports
 
 
 def test_build_all_builds_the_library_after_the_third(monkeypatch):
@@ -57,24 +56,11 @@ def test_the_recipe_is_the_third_librarys_with_its_own_directory_in_front(monkey
     assert "-shared" in link and link[link.index("-o") + 1] == build.Q8D_LIB
     assert "-Wl,--version-script=" + os.path.join(build.CSRC_Q8D, "exports_q8d.map") in link
     assert not [a for a in link if "libmmult_hip" in a and a != build.Q8D_LIB], "links nothing of the other libraries"
-
-
-def dynamic_exports(path):
-    """Names of the defined global functions in an ELF64 shared object's dynamic symbol table."""
-    blob = open(path, "rb").read()
-    shoff, = struct.unpack_from("<Q", blob, 0x28)
-    shentsize, shnum = struct.unpack_from("<HH", blob, 0x3A)
-    sections = [struct.unpack_from("<IIQQQQIIQQ", blob, shoff + i * shentsize) for i in range(shnum)]
-    names = []
-    for _, sh_type, _, _, off, size, link, _, _, entsize in sections:
-        if sh_type != 11:   # SHT_DYNSYM
-            continue
-        stroff = sections[link][4]
-        for p in range(off, off + size, entsize):
-            st_name, st_info, _, st_shndx = struct.unpack_from("<IBBH", blob, p)
-            if st_shndx != 0 and (st_info & 15) == 2 and (st_info >> 4) in (1, 2):   # defined, FUNC, GLOBAL / WEAK
-                names.append(blob[stroff + st_name:blob.index(b"\0", stroff + st_name)].decode())
-    return sorted(names)
+    # the one recipe caps every library's pool (cpu_count is 192 here): the second library's units, 16 of the first library's
+    del workers[:]
+    build.build_q8_library(force=True)
+    build.build_library(force=True)
+    assert len(workers) == 2 and max(workers) <= 16 and workers[1] == 16 < len(build.translation_units())
 
 
 def test_the_header_parses_and_the_library_exports_exactly_its_prototypes():

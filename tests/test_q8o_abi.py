@@ -5,7 +5,6 @@ operands the tile cannot read are refused before any device call -- and mmh_q8_l
 import ctypes as C
 import itertools
 import os
-import struct
 import threading
 
 import pytest
@@ -13,6 +12,7 @@ import pytest
 import how_to_optimize_gemm_amd as H
 from how_to_optimize_gemm_amd import abi_header, build, q8
 import qchain_ref as Q
+from built_lib import dynamic_exports
 from conftest import REPO
 
 
@@ -53,24 +53,11 @@ def test_the_recipe_is_the_second_librarys_with_its_own_directory(monkeypatch):
     assert "-shared" in link and link[link.index("-o") + 1] == build.Q8O_LIB
     assert "-Wl,--version-script=" + os.path.join(build.CSRC_Q8O, "exports_q8o.map") in link
     assert not [a for a in link if "libmmult_hip" in a and a != build.Q8O_LIB], "links nothing of the other libraries"
-
-
-def dynamic_exports(path):
-    """Names of the defined global functions in an ELF64 shared object's dynamic symbol table."""
-    blob = open(path, "rb").read()
-    shoff, = struct.unpack_from("<Q", blob, 0x28)
-    shentsize, shnum = struct.unpack_from("<HH", blob, 0x3A)
-    sections = [struct.unpack_from("<IIQQQQIIQQ", blob, shoff + i * shentsize) for i in range(shnum)]
-    names = []
-    for _, sh_type, _, _, off, size, link, _, _, entsize in sections:
-        if sh_type != 11:   # SHT_DYNSYM
-            continue
-        stroff = sections[link][4]
-        for p in range(off, off + size, entsize):
-            st_name, st_info, _, st_shndx = struct.unpack_from("<IBBH", blob, p)
-            if st_shndx != 0 and (st_info & 15) == 2 and (st_info >> 4) in (1, 2):   # defined, FUNC, GLOBAL / WEAK
-                names.append(blob[stroff + st_name:blob.index(b"\0", stroff + st_name)].decode())
-    return sorted(names)
+    # the one recipe caps every library's pool: the second library's five units, 16 of the first library's more than 16
+    del workers[:]
+    build.build_q8_library(force=True)
+    build.build_library(force=True)
+    assert len(build.translation_units()) > 16 and workers == [5, 16] and max(workers) <= 16
 
 
 def test_the_library_exports_exactly_the_headers_prototypes():
