@@ -159,9 +159,9 @@ int mmh_sgemm_host_timed(mmh_handle_t h, int m, int n, int k, const float *A, in
   // Device images are dense (lda=k, ldb=n, ldc=n) whatever the host strides.
   const size_t ab = (size_t)m * k * sizeof(float), bb = (size_t)k * n * sizeof(float),
                cb = (size_t)m * n * sizeof(float);
-  if ((rc = h->a.reserve(ab ? ab : 16)) != MMH_OK) return rc;
-  if ((rc = h->b.reserve(bb ? bb : 16)) != MMH_OK) return rc;
-  if ((rc = h->c.reserve(cb)) != MMH_OK) return rc;
+  if ((rc = alloc_status(h->a.reserve(ab ? ab : 16))) != MMH_OK) return rc;
+  if ((rc = alloc_status(h->b.reserve(bb ? bb : 16))) != MMH_OK) return rc;
+  if ((rc = alloc_status(h->c.reserve(cb))) != MMH_OK) return rc;
   float *dA = static_cast<float *>(h->a.p), *dB = static_cast<float *>(h->b.p),
         *dC = static_cast<float *>(h->c.p);
   // row-panel pipeline when the problem is large enough for the copies to matter (>= 2 panels of

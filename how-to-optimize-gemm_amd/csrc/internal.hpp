@@ -33,11 +33,13 @@
 #include <string.h>
 
 #include <initializer_list>
+#include <memory>
 #include <string>
 #include <utility>
 #include <vector>
 
 #include "ab_build.hpp"
+#include "device_memory.hpp"   // capturing, DeviceGuard, DevBuf / GraphBuf / Retired
 #include "../../include/mmult_hip.h"
 
 namespace mmh {
@@ -55,32 +57,14 @@ int hip_fail(hipError_t e, const char *what);
     if (e_ != hipSuccess) return ::mmh::hip_fail(e_, #expr); \
   } while (0)
 
-struct DevBuf {
-  void *p = nullptr;
-  size_t bytes = 0;
-  // keep_old: a launch captured into a hipGraph may point at the current allocation -- then a buffer
-  // that has to grow is RETIRED (freed with the handle), never freed under the graph
-  int reserve(size_t need, std::vector<void *> *retire_to = nullptr);
-  void release();
-};
+// A failed allocation of a handle-owned buffer (device_memory.hpp's reserve) as this library's status and text (state.hip)
+int alloc_status(hipError_t e);
 
-// Handle-owned scratch that is per handle, not per stream, and grows on demand: the int8 / quantisation images and the
-// partial rows of mmh_relu_grad_colsum.  It grows through reserve_scratch (state.hip) only, which holds the capture rule.
-struct Scratch : DevBuf {
-  bool captured = false;   // a captured launch points at p: retire on growth, never free under the graph
-};
+// Handle-owned scratch that is per handle, not per stream, and grows on demand -- the int8 / quantisation images and the partial
+// rows of mmh_relu_grad_colsum -- is a GraphBuf each.  It grows through reserve_scratch (state.hip) only.
 struct ScratchNeed {
-  Scratch *buf;
+  GraphBuf *buf;
   size_t bytes;            // 0: the call does not use buf
-};
-
-// Entry points run on the HANDLE's device and leave the caller's current device as they found it
-// (a torch process whose current device differs from the handle's must not find it changed).
-struct DeviceGuard {
-  int prev = -1;
-  bool switched = false;
-  hipError_t enter(int device);
-  ~DeviceGuard();
 };
 
 constexpr int kMaxHostPanels = 16;
@@ -140,28 +124,29 @@ struct mmh_context {
   int kernel = MMH_KERNEL_AUTO;
   int cu_count = 0;
   mmh::DevBuf a, b, c;     // staging for the host-pointer flavour
-  mmh::Scratch bt;         // int8 GEMM: packed (transposed, padded) B (tools build)
+  mmh::GraphBuf bt;        // int8 GEMM: packed (transposed, padded) B (tools build)
   int igemm_mode = 0;      // 0 auto, see MMH_OPT_IGEMM_MODE
   int i8_grid_cap = 0;     // test hook (environment MMH_I8_GRID_CAP, read at mmh_create): K3p's persistent grid, so that small shapes walk several tiles per workgroup
-  mmh::Scratch qa, qb, qc, qs;  // quantised GEMM workspace: int8 A, int8 B, int32 C, {amax bits, scales, a zero block}
+  mmh::GraphBuf qa, qb, qc, qs; // quantised GEMM workspace: int8 A, int8 B, int32 C, {amax bits, scales, a zero block}
   void *qs_zeros_of = nullptr;  // the allocation of qs whose zero block has been written (igemm.hip, zero_amax)
-  mmh::Scratch colsum_parts;    // mmh_relu_grad_colsum: the row blocks' partial column sums (ceil(rows / R) x cols floats)
+  mmh::GraphBuf colsum_parts;   // mmh_relu_grad_colsum: the row blocks' partial column sums (ceil(rows / R) x cols floats)
   // stream-K / split-K workspaces, one set PER STREAM the handle has launched on: launches on different streams
   // never share hand-off words or partial tiles, so nothing has to order one stream behind another and the handle
   // never touches a stream again after the call that used it returns (the caller may destroy it).
   struct StreamWs {
     hipStream_t stream = nullptr;
-    mmh::DevBuf flags;     // per-tile hand-off words; every launch leaves them ZERO (the last reader of a word
+    mmh::GraphBuf flags;   // per-tile hand-off words; every launch leaves them ZERO (the last reader of a word
                            // resets it), so only a fresh or suspect buffer is memset
     bool flags_dirty = true;
-    mmh::DevBuf parts;     // partial tiles
+    mmh::GraphBuf parts;   // partial tiles
     unsigned long stamp = 0;
-    bool captured = false; // a captured launch points at flags / parts: retire on growth, never evict
+    // a captured launch points at flags / parts (marked together): they retire on growth, and the set is never evicted
+    bool captured() const { return flags.captured; }
   };
-  std::vector<StreamWs *> ws;
+  std::vector<std::unique_ptr<StreamWs>> ws;
   unsigned long ws_stamp = 0;
   int *sk_stats = nullptr;           // device: [0] stream-K hand-overs finished by the head's owner (diagnostic)
-  std::vector<void *> retired;       // allocations a captured graph may still point at
+  mmh::Retired retired;              // allocations a captured graph may still point at: freed with the handle
   int streamk = 1;         // allow the persistent stream-K launch for ragged tile counts
   int splitk = 0;          // opt-in split-K: 0 off (default), 1 auto, >= 2 that many parts
   int host_panels = -1;    // host flavour: -1 auto, 0/1 the plain staged form, n pipelined row panels
@@ -200,8 +185,14 @@ struct mmh_context {
     bool pinned = false;       // a captured graph points at buf: never evicted
     bool uploaded = false;
     std::vector<hipStream_t> upload_streams;   // the streams in whose order an upload of these bytes already sits
+    void drop_host() {
+      if (host) (void)hipHostFree(host);
+      host = nullptr;
+      host_ints = 0;
+    }
+    ~SkTable() { drop_host(); }
   };
-  std::vector<SkTable *> sk_tables;
+  std::vector<std::unique_ptr<SkTable>> sk_tables;
   unsigned long sk_stamp = 0;
   // resident workgroups per CU of each persistent kernel, per handle (= per device)
   std::vector<std::pair<const void *, int>> per_cu;
@@ -227,11 +218,6 @@ void destroy_context(mmh_context *h);
 int warm_context(mmh_context *h);
 
 inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-inline bool capturing(hipStream_t s) {
-  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-  (void)hipStreamIsCapturing(s, &cap);
-  return cap != hipStreamCaptureStatusNone;
-}
 
 // whole tiles, 16-byte aligned operands: the unguarded instantiations
 inline bool fast_shape(int BM, int BN, int KB, const GemmArgs &g) {
@@ -283,7 +269,7 @@ void workspaces_suspect(mmh_context *ctx);   // a launch may have died half-way:
 // Everything ONE call needs of the handle's scratch, before the call launches or records anything.  On a capturing stream a
 // call that would have to allocate or grow any of it is MMH_ERR_UNSUPPORTED (`who` names the entry point in the message) with
 // nothing allocated, freed or marked; otherwise every buffer is at least its size when this returns MMH_OK.  From the first
-// captured call that uses a buffer, growth retires the old allocation to ctx->retired instead of freeing it.
+// captured call that uses a buffer, growth retires the old allocation to ctx->retired instead of freeing it (GraphBuf::reserve).
 int reserve_scratch(mmh_context *ctx, hipStream_t s, const char *who, std::initializer_list<ScratchNeed> needs);
 bool build_sk_tables(long tiles, int nk, int grid, int *order, int *place);
 int sk_tables_for(mmh_context *ctx, long tiles, int nk, int grid, hipStream_t s, const int **order, const int **place, int min10 = 0);

@@ -35,6 +35,7 @@ int probe_mfma_f32(int cu_count, float *tflops) {
   if (cu_count <= 0) cu_count = 256;
   float *d = nullptr;
   MMH_HIP_TRY(hipMalloc(&d, 64));
+  const DevBuf own(d, 64);   // freed on every way out
   const int iters = 20000, blocks = cu_count * 2;
   hipEvent_t t0, t1;
   MMH_HIP_TRY(hipEventCreate(&t0));
@@ -50,7 +51,6 @@ int probe_mfma_f32(int cu_count, float *tflops) {
   *tflops = (float)(flops / (ms * 1e-3) / 1e12);
   (void)hipEventDestroy(t0);
   (void)hipEventDestroy(t1);
-  (void)hipFree(d);
   return MMH_OK;
 }
 
@@ -199,6 +199,7 @@ int probe_mfma_i8(int cu_count, float *tops, int random_operands = 0,
   if (cu_count <= 0) cu_count = 256;
   int *d = nullptr;
   MMH_HIP_TRY(hipMalloc(&d, 64));
+  const DevBuf own(d, 64);
   const int iters = 40000, blocks = cu_count * 2;
   hipEvent_t t0, t1;
   MMH_HIP_TRY(hipEventCreate(&t0));
@@ -221,7 +222,6 @@ int probe_mfma_i8(int cu_count, float *tops, int random_operands = 0,
   *tops = (float)(ops / (ms * 1e-3) / 1e12);
   (void)hipEventDestroy(t0);
   (void)hipEventDestroy(t1);
-  (void)hipFree(d);
   return MMH_OK;
 }
 
@@ -262,11 +262,12 @@ int probe_hbm_copy(size_t bytes, float *gbps, int cu_count = 256, int mode = 0) 
   const size_t n = bytes / sizeof(f32x4);
   f32x4 *src = nullptr, *dst = nullptr;
   MMH_HIP_TRY(hipMalloc(&src, n * sizeof(f32x4)));
+  const DevBuf own_src(src, n * sizeof(f32x4));
   if (hipMalloc(&dst, mode == 0 ? n * sizeof(f32x4) : 64) != hipSuccess) {
-    (void)hipFree(src);
     set_last_error("hipMalloc(dst) failed");
     return MMH_ERR_ALLOC;
   }
+  const DevBuf own_dst(dst, mode == 0 ? n * sizeof(f32x4) : 64);
   MMH_HIP_TRY(hipMemset(src, 1, n * sizeof(f32x4)));
   hipEvent_t t0, t1;
   MMH_HIP_TRY(hipEventCreate(&t0));
@@ -289,8 +290,6 @@ int probe_hbm_copy(size_t bytes, float *gbps, int cu_count = 256, int mode = 0) 
   *gbps = (float)((mode == 0 ? 2.0 : 1.0) * n * sizeof(f32x4) * reps / (ms * 1e-3) / 1e9);
   (void)hipEventDestroy(t0);
   (void)hipEventDestroy(t1);
-  (void)hipFree(src);
-  (void)hipFree(dst);
   return MMH_OK;
 }
 
@@ -342,6 +341,7 @@ __global__ void __launch_bounds__(512) probe_lds_read_kernel(float *__restrict__
 int probe_lds_read(int width, float *gbps, int cu_count) {
   float *out = nullptr;
   MMH_HIP_TRY(hipMalloc(&out, 64));
+  const DevBuf own(out, 64);
   hipEvent_t t0, t1;
   MMH_HIP_TRY(hipEventCreate(&t0));
   MMH_HIP_TRY(hipEventCreate(&t1));
@@ -366,7 +366,6 @@ int probe_lds_read(int width, float *gbps, int cu_count) {
   *gbps = (float)((double)blocks * 512 * 8 * w * iters * reps / (ms * 1e-3) / 1e9);
   (void)hipEventDestroy(t0);
   (void)hipEventDestroy(t1);
-  (void)hipFree(out);
   return MMH_OK;
 }
 

@@ -61,6 +61,7 @@ int mmh_shard_destroy(mmh_shard_t sh) {
   for (int d = 0; d < (int)sh->devices.size(); ++d) {
     (void)hipSetDevice(sh->devices[d]);
     if (d < (int)sh->comms.size() && sh->comms[d]) rccl_api().comm_destroy(sh->comms[d]);
+    // (freed by hand, not with sh: on their own device, and hipFree waits for it -- before its events and streams go)
     if (d < (int)sh->a.size()) { sh->a[d].release(); sh->b[d].release(); sh->c[d].release(); }
     if (d < (int)sh->events.size())
       for (hipEvent_t e : sh->events[d])
@@ -278,9 +279,9 @@ int mmh_shard_sgemm_streamed(mmh_shard_t sh, int m, int n, int k, const float *A
     mmh_shard_rows(m, G, d, &row0[d], &rows[d]);
     HIP_TRY(hipSetDevice(sh->devices[d]));
     const size_t r = rows[d] > 0 ? rows[d] : 1;
-    if ((rc = sh->a[d].reserve(r * kk * sizeof(float))) != MMH_OK) return rc;
-    if ((rc = sh->b[d].reserve(kk * n * sizeof(float))) != MMH_OK) return rc;
-    if ((rc = sh->c[d].reserve(r * n * sizeof(float))) != MMH_OK) return rc;
+    if ((rc = alloc_status(sh->a[d].reserve(r * kk * sizeof(float)))) != MMH_OK) return rc;
+    if ((rc = alloc_status(sh->b[d].reserve(kk * n * sizeof(float)))) != MMH_OK) return rc;
+    if ((rc = alloc_status(sh->c[d].reserve(r * n * sizeof(float)))) != MMH_OK) return rc;
   }
   // One host thread per device for the host <-> device phases: a copy from/to pageable memory blocks
   // its calling thread, and every device has a PCIe link of its own.

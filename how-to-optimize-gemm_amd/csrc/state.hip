@@ -23,62 +23,32 @@ int hip_fail(hipError_t e, const char *what) {
   return MMH_ERR_HIP;
 }
 
-int DevBuf::reserve(size_t need, std::vector<void *> *retire_to) {
-  if (need <= bytes) return MMH_OK;
-  if (p) {
-    if (retire_to) retire_to->push_back(p);
-    else (void)hipFree(p);
-  }
-  p = nullptr;
-  bytes = 0;
-  hipError_t e = hipMalloc(&p, need);
-  if (e != hipSuccess) {
-    set_last_error(std::string("hipMalloc: ") + hipGetErrorString(e));
-    return MMH_ERR_ALLOC;
-  }
-  bytes = need;
-  return MMH_OK;
+int alloc_status(hipError_t e) {
+  if (e == hipSuccess) return MMH_OK;
+  set_last_error(std::string("hipMalloc: ") + hipGetErrorString(e));
+  return MMH_ERR_ALLOC;
 }
 
-void DevBuf::release() {
-  if (p) (void)hipFree(p);
-  p = nullptr;
-  bytes = 0;
-}
-
-// The rule of the stream-K sets (workspace_for) for the scratch that is per handle: nothing is allocated while a stream is
-// capturing, and what a graph points at is never freed under it.  All of a call's needs are looked at before any is met, so a
-// refusal leaves the handle exactly as it was.
+// The capture rule (device_memory.hpp, GraphBuf) for the scratch that is per handle.  All of a call's needs are looked at before
+// any is met, so a refusal leaves the handle exactly as it was.
 int reserve_scratch(mmh_context *ctx, hipStream_t s, const char *who, std::initializer_list<ScratchNeed> needs) {
   bool any = false;
   for (const ScratchNeed &n : needs) any = any || n.bytes > 0;
   if (!any) return MMH_OK;
   const bool cap = capturing(s);
-  if (cap)
-    for (const ScratchNeed &n : needs)
-      if (n.bytes > n.buf->bytes) {
-        set_last_error(std::string(who) + ": a handle-owned workspace would have to be allocated or grown while the stream is "
-                       "capturing -- make one uncaptured call at the largest size first");
-        return MMH_ERR_UNSUPPORTED;
-      }
+  for (const ScratchNeed &n : needs)
+    if (n.buf->growth(n.bytes, cap) == Growth::Refused) {
+      set_last_error(std::string(who) + ": a handle-owned workspace would have to be allocated or grown while the stream is "
+                     "capturing -- make one uncaptured call at the largest size first");
+      return MMH_ERR_UNSUPPORTED;
+    }
   for (const ScratchNeed &n : needs) {
     if (n.bytes == 0) continue;
-    if (cap) n.buf->captured = true;
-    if (const int rc = n.buf->reserve(n.bytes, n.buf->captured ? &ctx->retired : nullptr); rc != MMH_OK) return rc;
+    hipError_t e;
+    n.buf->reserve(n.bytes, cap, ctx->retired, &e);
+    if (e != hipSuccess) return alloc_status(e);
   }
   return MMH_OK;
-}
-
-hipError_t DeviceGuard::enter(int device) {
-  hipError_t e = hipGetDevice(&prev);
-  if (e != hipSuccess) return e;
-  if (prev == device) return hipSuccess;
-  e = hipSetDevice(device);
-  switched = e == hipSuccess;
-  return e;
-}
-DeviceGuard::~DeviceGuard() {
-  if (switched) (void)hipSetDevice(prev);
 }
 
 int check_sticky(mmh_context *h) {
@@ -116,10 +86,10 @@ int check_gemm_args(int m, int n, int k, const void *A, int lda, const void *B, 
 int workspace_for(mmh_context *ctx, hipStream_t s, long tiles, size_t parts_bytes, int **flags, float **parts) {
   const bool cap = capturing(s);
   mmh_context::StreamWs *w = nullptr;
-  for (auto *e : ctx->ws)
-    if (e->stream == s) w = e;
-  const size_t need_flags = (size_t)tiles * sizeof(int);
-  if (cap && (!w || need_flags > w->flags.bytes || parts_bytes > w->parts.bytes || w->flags_dirty)) {
+  for (auto &e : ctx->ws)
+    if (e->stream == s) w = e.get();
+  const size_t need = (size_t)tiles * sizeof(int);
+  if (cap && (!w || w->flags.growth(need, cap) == Growth::Refused || w->parts.growth(parts_bytes, cap) == Growth::Refused || w->flags_dirty)) {
     // Nothing may be allocated (or cleared outside the graph) while a stream is capturing, and a graph must not share
     // hand-off words and partial-tile slots with launches it is not ordered against: a captured stream-K launch uses
     // the CAPTURE STREAM'S OWN set or nothing.  (Round 3 borrowed the most recently used set of any stream -- a replay
@@ -132,11 +102,11 @@ int workspace_for(mmh_context *ctx, hipStream_t s, long tiles, size_t parts_byte
   }
   if (!w) {
     size_t evictable = 0;
-    for (auto *e : ctx->ws) evictable += e->captured ? 0 : 1;
+    for (auto &e : ctx->ws) evictable += e->captured() ? 0 : 1;
     if (evictable >= 8 && !cap) {
       mmh_context::StreamWs *old = nullptr;
-      for (auto *e : ctx->ws)
-        if (!e->captured && (!old || e->stamp < old->stamp)) old = e;
+      for (auto &e : ctx->ws)
+        if (!e->captured() && (!old || e->stamp < old->stamp)) old = e.get();
       HIP_TRY(hipDeviceSynchronize());   // whatever still uses the set -- on a stream that may no longer exist
       old->flags.release();
       old->parts.release();
@@ -145,18 +115,17 @@ int workspace_for(mmh_context *ctx, hipStream_t s, long tiles, size_t parts_byte
     } else {
       w = new (std::nothrow) mmh_context::StreamWs;
       if (!w) return MMH_ERR_ALLOC;
-      ctx->ws.push_back(w);
+      ctx->ws.emplace_back(w);
     }
     w->stream = s;
   }
   w->stamp = ++ctx->ws_stamp;
-  if (cap) w->captured = true;
-  std::vector<void *> *retire = w->captured ? &ctx->retired : nullptr;
-  const size_t need = (size_t)tiles * sizeof(int);
+  if (cap) w->flags.captured = w->parts.captured = true;   // (a capturing call gets here only where both fit)
+  hipError_t e = hipSuccess;
   if (need > w->flags.bytes) {
     // (growing a set whose stream still runs a launch: hipFree waits for the device, so freeing is safe eagerly)
-    const int rc = w->flags.reserve(std::max(need, (size_t)(256u << 10)), retire);
-    if (rc != MMH_OK) return rc;
+    w->flags.reserve(std::max(need, (size_t)(256u << 10)), cap, ctx->retired, &e);
+    if (e != hipSuccess) return alloc_status(e);
     w->flags_dirty = true;
   }
   if (w->flags_dirty) {
@@ -166,8 +135,8 @@ int workspace_for(mmh_context *ctx, hipStream_t s, long tiles, size_t parts_byte
     if (!cap) w->flags_dirty = false;   // a fill recorded into a graph does not clean the buffer NOW
   }
   if (parts_bytes > w->parts.bytes) {
-    const int rc = w->parts.reserve(std::max(parts_bytes, (size_t)(16u << 20)), retire);
-    if (rc != MMH_OK) return rc;
+    w->parts.reserve(std::max(parts_bytes, (size_t)(16u << 20)), cap, ctx->retired, &e);
+    if (e != hipSuccess) return alloc_status(e);
   }
   *flags = static_cast<int *>(w->flags.p);
   *parts = static_cast<float *>(w->parts.p);
@@ -175,7 +144,7 @@ int workspace_for(mmh_context *ctx, hipStream_t s, long tiles, size_t parts_byte
 }
 
 void workspaces_suspect(mmh_context *ctx) {
-  for (auto *e : ctx->ws) e->flags_dirty = true;
+  for (auto &e : ctx->ws) e->flags_dirty = true;
 }
 
 // mmh_reserve_stream: `s` gets a workspace set of its own that is large enough for any stream-K launch MMH_KERNEL_AUTO
@@ -251,7 +220,7 @@ int sk_tables_for(mmh_context *ctx, long tiles, int nk, int grid, hipStream_t s,
   if (min10 <= 0 || ctx->sk_order_min10 != 18) min10 = ctx->sk_order_min10;   // (tools build, option 104: one threshold for all)
   if (!ctx->sk_order || tiles > (1L << 20) || tiles * 10 < (long)grid * min10) return MMH_OK;
   const bool cap = capturing(s);
-  for (auto *t : ctx->sk_tables)
+  for (auto &t : ctx->sk_tables)
     if (t->tiles == tiles && t->nk == nk && t->grid == grid && t->uploaded) {
       t->stamp = ++ctx->sk_stamp;
       if (cap) t->pinned = true;   // the entry must outlive the graph
@@ -279,38 +248,28 @@ int sk_tables_for(mmh_context *ctx, long tiles, int nk, int grid, hipStream_t s,
   // entries pinned ones only make the cache grow
   mmh_context::SkTable *slot = nullptr;
   size_t unpinned = 0;
-  for (auto *t : ctx->sk_tables) {
+  for (auto &t : ctx->sk_tables) {
     unpinned += t->pinned ? 0 : 1;
     // an entry whose build failed (no pinned memory, a shape the builder declines) holds nothing and nobody reads it:
     // it is the first to be reused -- round 3 left such entries in the list, counted against the 32
-    if (!t->pinned && !t->uploaded && !slot) slot = t;
+    if (!t->pinned && !t->uploaded && !slot) slot = t.get();
   }
   if (slot) {
     // reuse the dead entry as it is
   } else if (unpinned < 32) {
     slot = new (std::nothrow) mmh_context::SkTable;
     if (!slot) return MMH_ERR_ALLOC;
-    ctx->sk_tables.push_back(slot);
+    ctx->sk_tables.emplace_back(slot);
   } else {
-    for (auto *t : ctx->sk_tables)
-      if (!t->pinned && (!slot || t->stamp < slot->stamp)) slot = t;
-    // the evicted tables may still be read by a launch in flight on any stream
-    if (!cap) {
-      HIP_TRY(hipDeviceSynchronize());
-    } else {
-      // nothing may synchronise during capture: take a fresh entry instead
-      slot = new (std::nothrow) mmh_context::SkTable;
-      if (!slot) return MMH_ERR_ALLOC;
-      ctx->sk_tables.push_back(slot);
-    }
+    for (auto &t : ctx->sk_tables)
+      if (!t->pinned && (!slot || t->stamp < slot->stamp)) slot = t.get();
+    HIP_TRY(hipDeviceSynchronize());   // the evicted tables may still be read by a launch in flight on any stream
   }
   const size_t ints = (size_t)grid + (size_t)tiles;
   slot->uploaded = false;
   slot->tiles = 0;
   if (ints > slot->host_ints) {
-    if (slot->host) (void)hipHostFree(slot->host);
-    slot->host = nullptr;
-    slot->host_ints = 0;
+    slot->drop_host();
     void *hp = nullptr;
     if (hipHostMalloc(&hp, ints * sizeof(int), hipHostMallocDefault) != hipSuccess) {
       (void)hipGetLastError();
@@ -320,8 +279,8 @@ int sk_tables_for(mmh_context *ctx, long tiles, int nk, int grid, hipStream_t s,
     slot->host_ints = ints;
   }
   if (!build_sk_tables(tiles, nk, grid, slot->host, slot->host + grid)) return MMH_OK;   // identity is always right
-  const int rc = slot->buf.reserve(ints * sizeof(int), cap ? &ctx->retired : nullptr);
-  if (rc != MMH_OK) return rc;
+  // (no graph points at an entry that is rewritten -- a pinned one never is --, so what it outgrows is freed)
+  if (const int rc = alloc_status(slot->buf.reserve(ints * sizeof(int))); rc != MMH_OK) return rc;
   HIP_TRY(hipMemcpyAsync(slot->buf.p, slot->host, ints * sizeof(int), hipMemcpyHostToDevice, s));
   slot->host_ints = std::max(slot->host_ints, ints);
   slot->tiles = tiles;
@@ -329,9 +288,7 @@ int sk_tables_for(mmh_context *ctx, long tiles, int nk, int grid, hipStream_t s,
   slot->grid = grid;
   slot->stamp = ++ctx->sk_stamp;
   slot->uploaded = true;
-  slot->upload_streams.clear();
-  if (!cap) slot->upload_streams.push_back(s);
-  slot->pinned = cap;
+  slot->upload_streams.assign(1, s);
   *order = static_cast<const int *>(slot->buf.p);
   *place = *order + grid;
   return MMH_OK;
@@ -406,7 +363,7 @@ int warm_context(mmh_context *h) {
   if (h->warmed) return MMH_OK;
   // scratch: a 128 K-float buffer every kernel family runs ONE tile of itself on (contents irrelevant)
   DevBuf scratch;
-  int rc = scratch.reserve((size_t)(1u << 17) * sizeof(float) + (1u << 20));
+  int rc = alloc_status(scratch.reserve((size_t)(1u << 17) * sizeof(float) + (1u << 20)));
   if (rc != MMH_OK) return rc;
   HIP_TRY(hipMemsetAsync(scratch.p, 0, scratch.bytes, nullptr));
   float *p = static_cast<float *>(scratch.p);
@@ -425,7 +382,7 @@ int warm_context(mmh_context *h) {
     float *parts = nullptr;
     if (workspace_for(h, nullptr, 1 << 16, (size_t)(64u << 20), &flags, &parts) != MMH_OK) {   // the null stream's set
       (void)hipGetLastError();
-      for (auto *e : h->ws)
+      for (auto &e : h->ws)
         if (e->stream == nullptr) {
           e->flags.release();
           e->parts.release();
@@ -433,8 +390,7 @@ int warm_context(mmh_context *h) {
         }
     }
   }
-  const hipError_t e = hipStreamSynchronize(nullptr);
-  scratch.release();
+  const hipError_t e = hipStreamSynchronize(nullptr);   // ... before the scratch goes, on every way out from here
   if (rc != MMH_OK) return rc;
   if (e != hipSuccess) return hip_fail(e, "mmh_warm: hipStreamSynchronize");
   h->warmed = true;
@@ -447,26 +403,6 @@ void destroy_context(mmh_context *h) {
   DeviceGuard guard;
   (void)guard.enter(h->device);
   (void)hipDeviceSynchronize();
-  h->a.release();
-  h->b.release();
-  h->c.release();
-  for (auto *e : h->ws) {
-    e->flags.release();
-    e->parts.release();
-    delete e;
-  }
-  h->bt.release();
-  h->qa.release();
-  h->qb.release();
-  h->qc.release();
-  h->qs.release();
-  h->colsum_parts.release();
-  for (void *p : h->retired) (void)hipFree(p);
-  for (auto *t : h->sk_tables) {
-    t->buf.release();
-    if (t->host) (void)hipHostFree(t->host);
-    delete t;
-  }
   if (h->pipeline_ready) {
     for (int i = 0; i < kMaxHostPanels; ++i) {
       if (h->ev_in[i]) (void)hipEventDestroy(h->ev_in[i]);
@@ -483,7 +419,7 @@ void destroy_context(mmh_context *h) {
   if (h->sk_stats) (void)hipFree(h->sk_stats);
   rocblas_release(h->rocblas);
   hipblaslt_release(h->blaslt);
-  delete h;
+  delete h;   // every buffer, stream set, table and retired allocation goes with its owner -- behind the synchronisation, under the guard
 }
 
 }  // namespace mmh

@@ -165,8 +165,7 @@ void hipblaslt_release(void *&state) {
     for (auto &p : st->plans) destroy_plan(api, p);
     if (st->handle) api.destroy(st->handle);
   }
-  st->workspace.release();
-  delete st;
+  delete st;   // (and its workspace)
   state = nullptr;
 }
 
@@ -186,7 +185,7 @@ int hipblaslt_sgemm_rowmajor(void **state, int m, int n, int k, const float *dA,
       set_last_error("hipblasLtCreate failed");
       return MMH_ERR_UNSUPPORTED;
     }
-    if (st->workspace.reserve(kBlasLtWorkspace) != MMH_OK) {
+    if (alloc_status(st->workspace.reserve(kBlasLtWorkspace)) != MMH_OK) {
       api.destroy(st->handle);
       delete st;
       return MMH_ERR_ALLOC;

@@ -5,7 +5,6 @@
 
 #include <new>
 #include <string>
-#include <vector>
 
 #include "../../include/mmult_hip_q8.h"
 #include "q8_host.hpp"
@@ -19,22 +18,13 @@ static_assert(kQrWaveCols == QR_WAVE_COLS, "qlinear_plan.hpp restates the kernel
 
 struct mmh_q8_weight {
   int device = 0, out = 0, in = 0, pitch = 0, cus = 256;
-  int8_t *q = nullptr;                          // in x pitch
-  float *scale = nullptr, *inv_scale = nullptr; // out floats each
-  // the activations' image and row scales of the call in flight: grown on demand, under the capture rule
-  void *scratch = nullptr;
-  size_t scratch_bytes = 0;
-  bool captured = false;                        // a captured launch points at scratch: retire on growth, never free
-  std::vector<void *> retired;
+  DevBuf q;                  // int8, in x pitch
+  DevBuf scale, inv_scale;   // out floats each
+  GraphBuf scratch;          // the activations' image and row scales of the call in flight: grown on demand, under the capture rule
+  Retired retired;
 };
 
 namespace {
-
-bool capturing(hipStream_t s) {
-  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-  (void)hipStreamIsCapturing(s, &cap);
-  return cap != hipStreamCaptureStatusNone;
-}
 
 // quant_vec_ok's convention for the row quantiser's operands (q NULL: scales only)
 bool rows_vec_ok(const float *x, int ldx, const int8_t *q, int ldq) {
@@ -51,30 +41,12 @@ hipError_t launch_row_quant(const RowQuantArgs &a, const RowQuantPlan &p, hipStr
 // The object's scratch holds `need` bytes when this returns MMH_OK; refused, with the object as it was, where that takes an
 // allocation on a capturing stream
 int reserve(mmh_q8_weight *w, size_t need, hipStream_t s, const char *who) {
-  const bool cap = capturing(s);
-  if (need <= w->scratch_bytes) {
-    w->captured = w->captured || cap;
-    return MMH_OK;
-  }
-  if (cap)
+  hipError_t e;
+  if (w->scratch.reserve(need, capturing(s), w->retired, &e) == Growth::Refused)
     return fail(MMH_ERR_UNSUPPORTED, std::string(who) + ": the weight object's scratch would have to be allocated or grown while the "
                 "stream is capturing -- make one uncaptured call at the largest size, or mmh_q8_linear_reserve, first");
-  void *p = nullptr;
-  if (const hipError_t e = hipMalloc(&p, need); e != hipSuccess) return fail(MMH_ERR_ALLOC, std::string("hipMalloc: ") + hipGetErrorString(e));
-  if (w->scratch) {
-    if (w->captured) w->retired.push_back(w->scratch);
-    else (void)hipFree(w->scratch);
-  }
-  w->scratch = p;
-  w->scratch_bytes = need;
+  if (e != hipSuccess) return fail(MMH_ERR_ALLOC, std::string("hipMalloc: ") + hipGetErrorString(e));
   return MMH_OK;
-}
-
-void release(mmh_q8_weight *w) {
-  for (void *p : {static_cast<void *>(w->q), static_cast<void *>(w->scale), static_cast<void *>(w->inv_scale), w->scratch})
-    if (p) (void)hipFree(p);
-  for (void *p : w->retired) (void)hipFree(p);
-  delete w;
 }
 
 int linear_args(const mmh_q8_weight *w, int rows, const float *dX, int ldx, int activation, const float *dY, int ldy) {
@@ -88,12 +60,12 @@ int linear_args(const mmh_q8_weight *w, int rows, const float *dX, int ldx, int 
 int linear_on(mmh_q8_weight *w, int rows, const float *dX, int ldx, const float *dBias, int activation, float *dY, int ldy, hipStream_t s) {
   const Q8Plan p = plan_qlinear(rows, w->out, w->in, ldx, ldy, mod16(dX), mod16(dY), w->cus, dBias != nullptr, activation == MMH_ACT_RELU);
   if (const int rc = reserve(w, p.scratch, s, "mmh_q8_linear"); rc != MMH_OK) return rc;
-  char *base = static_cast<char *>(w->scratch);
+  char *base = w->scratch.as<char>();
   int8_t *xq = reinterpret_cast<int8_t *>(base);
   float *sx = reinterpret_cast<float *>(base + p.off_scale), *rx = reinterpret_cast<float *>(base + p.off_inv);
   const RowQuantArgs qa{dX, rows, w->in, ldx, xq, p.pitch_k, p.pitch_k, sx, rx, p.quant.vec ? 1 : 0};
   Q8_TRY(launch_row_quant(qa, p.quant, s));
-  const QlinearArgs g{rows, w->out, w->in, xq, p.pitch_k, w->q, w->pitch, rx, w->inv_scale, dBias, activation == MMH_ACT_RELU ? 1 : 0,
+  const QlinearArgs g{rows, w->out, w->in, xq, p.pitch_k, w->q.as<int8_t>(), w->pitch, rx, w->inv_scale.as<float>(), dBias, activation == MMH_ACT_RELU ? 1 : 0,
                       dY, ldy, p.nbm, p.nbn};
   Q8_TRY(launch_qlinear(p, g, s));
   g_launch = p.text;
@@ -123,28 +95,28 @@ int mmh_q8_weight_create(mmh_q8_weight_t *weight, int device, int out, int in, c
   int cus = 0;
   if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && cus > 0) w->cus = cus;
   const size_t image = (size_t)in * w->pitch, floats = (size_t)w->pitch * sizeof(float);
-  hipError_t e = hipMalloc(reinterpret_cast<void **>(&w->q), image ? image : 16);
-  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&w->scale), floats);
-  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&w->inv_scale), floats);
+  hipError_t e = w->q.reserve(image ? image : 16);
+  if (e == hipSuccess) e = w->scale.reserve(floats);
+  if (e == hipSuccess) e = w->inv_scale.reserve(floats);
   if (e != hipSuccess) {
-    release(w);
+    delete w;
     return fail(MMH_ERR_ALLOC, std::string("hipMalloc: ") + hipGetErrorString(e));
   }
   // the channel scales: the row quantiser without an image; then the image, tile by tile
   const bool vec = rows_vec_ok(dW, ldw, nullptr, 0);
-  const RowQuantArgs qa{dW, out, in, ldw, nullptr, 0, 0, w->scale, w->inv_scale, vec ? 1 : 0};
+  const RowQuantArgs qa{dW, out, in, ldw, nullptr, 0, 0, w->scale.as<float>(), w->inv_scale.as<float>(), vec ? 1 : 0};
   e = launch_row_quant(qa, plan_row_quant(out, in, vec), s);
   if (e == hipSuccess && in > 0) {
     const dim3 grid((unsigned)((w->pitch + PW_TILE - 1) / PW_TILE), (unsigned)((in + PW_TILE - 1) / PW_TILE));
     if (grid.y > 65535u) e = hipErrorInvalidValue;
     else {
-      hipLaunchKernelGGL(prepare_weight_s8_kernel, grid, dim3(256), 0, s, dW, out, in, ldw, w->scale, w->q, w->pitch, vec ? 1 : 0);
+      hipLaunchKernelGGL(prepare_weight_s8_kernel, grid, dim3(256), 0, s, dW, out, in, ldw, w->scale.as<float>(), w->q.as<int8_t>(), w->pitch, vec ? 1 : 0);
       e = hipGetLastError();
     }
   }
   if (e != hipSuccess) {
     (void)hipStreamSynchronize(s);
-    release(w);
+    delete w;
     return hip_fail(e, "mmh_q8_weight_create");
   }
   *weight = w;
@@ -155,7 +127,7 @@ int mmh_q8_weight_destroy(mmh_q8_weight_t w) {
   if (!w) return MMH_OK;
   DeviceGuard guard;
   Q8_TRY(guard.enter(w->device));
-  release(w);   // (hipFree waits for the device: no launch still reads what goes)
+  delete w;   // (its buffers' hipFree waits for the device: no launch still reads what goes)
   return MMH_OK;
 }
 
@@ -165,9 +137,9 @@ int mmh_q8_weight_info(mmh_q8_weight_t w, int *out, int *in, int *pitch, const i
   if (out) *out = w->out;
   if (in) *in = w->in;
   if (pitch) *pitch = w->pitch;
-  if (dQ) *dQ = w->q;
-  if (d_scale) *d_scale = w->scale;
-  if (d_inv_scale) *d_inv_scale = w->inv_scale;
+  if (dQ) *dQ = w->q.as<int8_t>();
+  if (d_scale) *d_scale = w->scale.as<float>();
+  if (d_inv_scale) *d_inv_scale = w->inv_scale.as<float>();
   return MMH_OK;
 }
 
@@ -211,7 +183,7 @@ int mmh_q8_linear_s8(mmh_q8_weight_t w, int rows, const int8_t *dXq, int ldq, co
   Q8_TRY(guard.enter(w->device));
   // the plan of the fp32 call on these rows, without its quantiser: the same tile, guard and grid, launched straight on dXq
   const Q8Plan p = plan_qlinear(rows, w->out, w->in, w->in > 0 ? w->in : 1, ldy, 0, mod16(dY), w->cus, dBias != nullptr, activation == MMH_ACT_RELU);
-  const QlinearArgs g{rows, w->out, w->in, dXq, ldq, w->q, w->pitch, d_inv_scale, w->inv_scale, dBias, activation == MMH_ACT_RELU ? 1 : 0,
+  const QlinearArgs g{rows, w->out, w->in, dXq, ldq, w->q.as<int8_t>(), w->pitch, d_inv_scale, w->inv_scale.as<float>(), dBias, activation == MMH_ACT_RELU ? 1 : 0,
                       dY, ldy, p.nbm, p.nbn};
   Q8_TRY(launch_qlinear(p, g, static_cast<hipStream_t>(stream)));
   const char *then = strstr(p.text, "then ");

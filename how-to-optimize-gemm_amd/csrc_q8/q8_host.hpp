@@ -1,7 +1,7 @@
 // q8_host.hpp -- what the host sides of the int8 layer libraries share: q8.hip, q8o.hip and q8d.hip each include it once, after
-// their C header.  The per-thread error and launch texts, the device guard, the argument rules that need no device, the cached
-// CU count and the timing loop.  Everything here has internal linkage: each .so keeps its own state, and an error in one
-// library never shows in another's mmh_*_last_error.
+// their C header.  The per-thread error and launch texts, the argument rules that need no device, the cached CU count and the
+// timing loop; csrc/device_memory.hpp's device guard and owners come with it.  Everything here has internal linkage: each .so
+// keeps its own state, and an error in one library never shows in another's mmh_*_last_error.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -10,6 +10,7 @@
 #include <string>
 
 #include "../../include/mmult_hip.h"   // the statuses, MMH_ACT_*
+#include "device_memory.hpp"           // mmh::capturing, DeviceGuard, DevBuf / GraphBuf / Retired
 #include "igemm_plan.hpp"              // i8_dword, i8_window
 
 namespace {
@@ -26,22 +27,6 @@ int hip_fail(hipError_t e, const char *what) { return fail(MMH_ERR_HIP, std::str
     hipError_t e_ = (expr);                           \
     if (e_ != hipSuccess) return hip_fail(e_, #expr); \
   } while (0)
-
-// The caller's device is current again when the entry point returns
-struct DeviceGuard {
-  int prev = -1;
-  bool switched = false;
-  hipError_t enter(int device) {
-    hipError_t e = hipGetDevice(&prev);
-    if (e != hipSuccess || prev == device) return e;
-    e = hipSetDevice(device);
-    switched = e == hipSuccess;
-    return e;
-  }
-  ~DeviceGuard() {
-    if (switched) (void)hipSetDevice(prev);
-  }
-};
 
 [[maybe_unused]] int mod4(const void *p) { return (int)(reinterpret_cast<uintptr_t>(p) & 3); }
 [[maybe_unused]] int mod16(const void *p) { return (int)(reinterpret_cast<uintptr_t>(p) & 15); }
