@@ -527,17 +527,22 @@ class MMult:
             self.sgemm_op(ta, tb, m, n, k, pa, lda, pb, ldb, pc, ldc, accumulate, stream)
         return out
 
-    def _ex(self, what, a, b, out, alpha, beta, bias, bias_mode, activation):
-        """out = act(alpha a @ b + beta out + bias) through mmh_sgemm_ex on torch's current stream; a / b as matmul takes them."""
+    def _ex_args(self, what, a, b, out):
+        """_ex's operands after its checks: (m, n, k, pa, lda, ta, pb, ldb, tb, pc, ldc).  addmm asks before it copies `input` into
+        `out`: nothing is written to the `out` of a call that will be refused."""
         import torch
         if a.dtype != torch.float32 or b.dtype != torch.float32:
             raise MMultError(ERR_INVALID_ARG, what, "fp32 only")
         if a.dim() != 2 or b.dim() != 2 or a.shape[1] != b.shape[0]:
             raise MMultError(ERR_INVALID_ARG, what, "need 2-D operands whose inner dimensions agree")
         (m, k), n = a.shape, b.shape[1]
-        pa, lda, ta = self._operand_args(a, m, k, what + "(A)")
-        pb, ldb, tb = self._operand_args(b, k, n, what + "(B)")
-        pc, ldc = self._tensor_args(out, m, n, what + "(C)", torch.float32)
+        return (m, n, k) + self._operand_args(a, m, k, what + "(A)") + self._operand_args(b, k, n, what + "(B)") + \
+            self._tensor_args(out, m, n, what + "(C)", torch.float32)
+
+    def _ex(self, what, a, b, out, alpha, beta, bias, bias_mode, activation):
+        """out = act(alpha a @ b + beta out + bias) through mmh_sgemm_ex on torch's current stream; a / b as matmul takes them."""
+        import torch
+        m, n, k, pa, lda, ta, pb, ldb, tb, pc, ldc = self._ex_args(what, a, b, out)
         pbias = 0
         if bias is not None:
             if not bias.is_cuda or bias.device.index != self.device or bias.dtype != torch.float32 or bias.dim() != 1 or \
@@ -545,9 +550,10 @@ class MMult:
                 raise MMultError(ERR_INVALID_ARG, what, "the bias is a dense 1-D fp32 tensor on the handle's device, one float per "
                                  "output column")
             pbias = bias.data_ptr()
+        # (a bias of no floats -- no output column -- has nothing to add, and no pointer to pass: torch gives an empty tensor NULL)
         stream = torch.cuda.current_stream(a.device).cuda_stream
-        self.sgemm_ex(ta, tb, m, n, k, alpha, pa, lda, pb, ldb, beta, pc, ldc, pbias, bias_mode if bias is not None else BIAS_NONE,
-                      activation, stream)
+        self.sgemm_ex(ta, tb, m, n, k, alpha, pa, lda, pb, ldb, beta, pc, ldc, pbias, bias_mode if pbias else BIAS_NONE, activation,
+                      stream)
         return out
 
     def addmm(self, input, a, b, *, beta=1.0, alpha=1.0, out=None):
@@ -569,6 +575,7 @@ class MMult:
             out = torch.empty((m, n), dtype=torch.float32, device=a.device)
         if out is not input:
             if float(beta) != 0.0:
+                self._ex_args("addmm", a, b, out)   # (nothing is copied into the `out` of a call that will be refused)
                 out.copy_(input)   # (1-D: broadcast over the rows)
         return self._ex("addmm", a, b, out, alpha, beta, None, BIAS_NONE, ACT_NONE)
 
@@ -729,19 +736,24 @@ class MMult:
         self.sgemm_batched(ta, tb, m, n, k, pa, lda, sa, pb, ldb, sb, pc, ldc, sc, batch, accumulate, stream)
         return out
 
-    def _batched_ex(self, what, a, b, out, alpha, beta, bias, stride_bias, activation):
-        """out[i] = act(alpha a[i] @ b[i] + beta out[i] + bias_i) through mmh_sgemm_batched_ex on torch's current stream; a / b /
-        out as bmm takes them; bias: None, or a column bias -- a tensor whose n floats per matrix are dense, matrix i's
-        stride_bias elements behind matrix i - 1's."""
+    def _batched_ex_args(self, what, a, b, out):
+        """_batched_ex's operands after its checks: (batch, m, n, k) and _batched_args of a, b and out.  baddbmm asks before it
+        copies `input` into `out`."""
         import torch
         if a.dtype != torch.float32 or b.dtype != torch.float32:
             raise MMultError(ERR_INVALID_ARG, what, "fp32 only")
         if a.dim() != 3 or b.dim() != 3 or a.shape[0] != b.shape[0] or a.shape[2] != b.shape[1]:
             raise MMultError(ERR_INVALID_ARG, what, "need 3-D operands whose batch and inner dimensions agree")
         (batch, m, k), n = a.shape, b.shape[2]
-        pa, lda, ta, sa = self._batched_args(a, batch, m, k, what + "(A)", True)
-        pb, ldb, tb, sb = self._batched_args(b, batch, k, n, what + "(B)", True)
-        pc, ldc, _, sc = self._batched_args(out, batch, m, n, what + "(C)", False)
+        return (batch, m, n, k), self._batched_args(a, batch, m, k, what + "(A)", True), \
+            self._batched_args(b, batch, k, n, what + "(B)", True), self._batched_args(out, batch, m, n, what + "(C)", False)
+
+    def _batched_ex(self, what, a, b, out, alpha, beta, bias, stride_bias, activation):
+        """out[i] = act(alpha a[i] @ b[i] + beta out[i] + bias_i) through mmh_sgemm_batched_ex on torch's current stream; a / b /
+        out as bmm takes them; bias: None, or a column bias -- a tensor whose n floats per matrix are dense, matrix i's
+        stride_bias elements behind matrix i - 1's."""
+        import torch
+        (batch, m, n, k), (pa, lda, ta, sa), (pb, ldb, tb, sb), (pc, ldc, _, sc) = self._batched_ex_args(what, a, b, out)
         pbias = 0
         if bias is not None:
             if not bias.is_cuda or bias.device.index != self.device or bias.dtype != torch.float32 or stride_bias < 0 or \
@@ -752,8 +764,9 @@ class MMult:
         if batch == 0:
             return out
         stream = torch.cuda.current_stream(a.device).cuda_stream
+        # (a bias of no floats -- no output column -- has nothing to add, and no pointer to pass: torch gives an empty tensor NULL)
         self.sgemm_batched_ex(ta, tb, m, n, k, alpha, pa, lda, sa, pb, ldb, sb, beta, pc, ldc, sc, batch, pbias, stride_bias,
-                              BIAS_COL if bias is not None else BIAS_NONE, activation, stream)
+                              BIAS_COL if pbias else BIAS_NONE, activation, stream)
         return out
 
     def baddbmm(self, input, a, b, *, beta=1.0, alpha=1.0, out=None):
@@ -782,8 +795,9 @@ class MMult:
             if not fits:
                 raise MMultError(ERR_INVALID_ARG, "baddbmm", f"input must broadcast to ({batch},{m},{n})")
             if float(beta) != 0.0:
-                # (nothing is copied into an `out` the call will refuse: a CPU tensor, matrices that overlap)
-                _, ldc, _, sc = self._batched_args(out, batch, m, n, "baddbmm(C)", False)
+                # (nothing is copied into the `out` of a call that will be refused: a CPU tensor, matrices that overlap, operands
+                # that disagree or cannot be read)
+                _, _, _, (_, ldc, _, sc) = self._batched_ex_args("baddbmm", a, b, out)
                 if batch > 1 and sc < (m - 1) * ldc + n:
                     raise MMultError(ERR_INVALID_ARG, "baddbmm(C)", "the matrices of out overlap")
                 if input.device != out.device:

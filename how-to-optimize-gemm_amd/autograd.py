@@ -35,7 +35,8 @@ class _LinearFn(torch.autograd.Function):
         # an expanded gradient (y.sum().backward(): every stride 0) or any other view the kernels cannot address
         if grad_out.dim() != 2 or (grad_out.shape[1] > 1 and grad_out.stride(1) != 1) or \
                 (grad_out.shape[0] > 1 and grad_out.stride(0) < max(grad_out.shape[1], 1)):
-            grad_out = grad_out.contiguous()
+            # (an empty tensor is contiguous to torch whatever its strides: .contiguous() would hand the expanded one back)
+            grad_out = grad_out.contiguous() if grad_out.numel() else grad_out.new_empty(grad_out.shape)
         need = (ctx.needs_input_grad[2], ctx.needs_input_grad[3], ctx.has_bias and ctx.needs_input_grad[4])
         dx, dw, db = ctx.mm.linear_backward(grad_out, x, w, y, need=need)
         return None, None, dx, dw, db

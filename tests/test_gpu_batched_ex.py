@@ -517,6 +517,14 @@ def test_baddbmm(h, oracle):
         with pytest.raises(H.MMultError) as e:
             call()
         assert e.value.status == H.ERR_INVALID_ARG
+    # a refused call copies nothing into its `out` first (the front end's fuzz found the copy ahead of the operands' checks)
+    kept = torch.full((batch, m, n), float("nan"), device="cuda")
+    for call in (lambda: h.baddbmm(inp, a, b[:, :k - 1], beta=0.5, out=kept), lambda: h.baddbmm(inp, a[:2], b, beta=0.5, out=kept),
+                 lambda: h.baddbmm(inp, a, b.cpu(), out=kept), lambda: h.baddbmm(inp, a[:, :, ::2], b[:, :(k + 1) // 2], out=kept)):
+        with pytest.raises(H.MMultError) as e:
+            call()
+        assert e.value.status == H.ERR_INVALID_ARG
+    assert bool(kept.isnan().all())
 
 
 def test_batched_linear(h, oracle):
@@ -550,6 +558,9 @@ def test_batched_linear(h, oracle):
     out = torch.full((batch, rows + 1, fout + 2), float("nan"), device="cuda")
     assert same_bits(h.batched_linear(x, w, bias, out=out[:, :rows, :fout]).cpu().numpy(), want(s, lambda i: bias_h[i], 0))
     assert bool(out[:, rows:, :].isnan().all()) and bool(out[:, :, fout:].isnan().all())
+    # no output feature: a bias of no floats has the address NULL and nothing to add (found by the front end's fuzz)
+    assert h.batched_linear(x, w[:, :0], bias[:, :0], "relu").shape == (batch, rows, 0)
+    assert h.batched_linear(x, w[0, :0], bias[0, :0]).shape == (batch, rows, 0)
     for call in (lambda: h.batched_linear(x, w, bias, "gelu"),
                  lambda: h.batched_linear(x[0], w),
                  lambda: h.batched_linear(x, w[:2]),

@@ -387,6 +387,19 @@ def test_addmm_and_linear(h, oracle):
             h.linear(x, w, dev(bias_n)[:n - 1])
         with pytest.raises(H.MMultError):
             h.addmm(dev(c0)[:, :n - 1], ta_, tb_)
+        # a refused call copies nothing into its `out` first (the front end's fuzz found the copy ahead of the checks): operands
+        # whose inner dimensions disagree, an operand without a unit stride, an `out` whose rows overlap
+        kept = torch.full((m + 1, n), float("nan"), device="cuda")
+        for pa, pb, out in ((ta_[:, :k - 1], tb_, kept[:m]), (ta_[:, ::2], tb_[:k // 2], kept[:m]), (ta_.cpu(), tb_, kept[:m]),
+                            (ta_, tb_, torch.as_strided(kept, (m, n), (n - 1, 1)))):
+            with pytest.raises(H.MMultError) as e:
+                h.addmm(dev(c0), pa, pb, beta=0.5, out=out)
+            assert e.value.status == H.ERR_INVALID_ARG
+        assert bool(kept.isnan().all())
+        # no output column: a bias of no floats has the address NULL and nothing to add (found by the front end's fuzz)
+        none = torch.empty((0,), device="cuda")
+        assert h.linear(x, w[:0], none, activation="relu").shape == (m, 0)
+        assert h.addmm(none, ta_, tb_[:, :0]).shape == (m, 0)
     torch.cuda.synchronize()
 
 

@@ -152,6 +152,24 @@ def test_a_kernel_without_op_forms_refuses_before_anything_is_launched():
             a.linear_backward(g, x, w[:, :-1], y)
 
 
+def test_an_expanded_gradient_of_no_rows_or_no_columns_goes_through_the_backward(amm):
+    """y.sum().backward() hands back an expanded gradient (strides 0, 0); with no rows, or no output features, torch calls it
+    contiguous and .contiguous() returns it as it is -- the backward raised on its strides (found by the front end's fuzz).  The
+    bias gradient of no rows is +0."""
+    import torch
+    from how_to_optimize_gemm_amd import autograd
+    for rows, n_in, n_out in ((0, 5, 7), (6, 5, 0)):
+        x = torch.rand((rows, n_in), device="cuda").requires_grad_()
+        w = torch.rand((n_out, n_in), device="cuda").requires_grad_()
+        b = torch.rand((n_out,), device="cuda").requires_grad_()
+        y = autograd.linear(amm, x, w, b, "relu")
+        assert y.shape == (rows, n_out)
+        y.sum().backward()
+        assert x.grad.shape == x.shape and w.grad.shape == w.shape and b.grad.shape == b.shape
+        assert not bool(x.grad.any()) and not bool(w.grad.any())
+        assert torch.equal(b.grad.view(torch.int32), torch.zeros(n_out, dtype=torch.int32, device="cuda"))
+
+
 def test_mm_linear_itself_stays_outside_autograd(amm):
     import torch
     x = torch.randn((9, 6), device="cuda", requires_grad=True)
