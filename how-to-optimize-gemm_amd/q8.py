@@ -9,6 +9,8 @@
     hq = q8.qlinear(xq, qw, bias, "relu", out_scale=s) # int8 out (libmmult_hip_q8o.so): the next layer's QRows, no fp32 round trip
     mlp = q8.QMLP.from_float([fc1, fc2]); mlp.calibrate(x); y = mlp(x)    # one quantiser, int8 -> int8 hidden layers, fp32 out
     y = q8.qlinear_decode(xq, qw, bias)                # 1 - 16 rows (libmmult_hip_q8d.so): split-K strips, the same bits as qlinear
+    qw4 = q8.QWeight4(linear.weight.detach())          # 4-bit weights (W4A8, libmmult_hip_q4d.so): packed nibbles, half the bytes
+    y = q8.qlinear_decode(xq, qw4, bias)               # ... for 1 - 16 rows only: there are no 4-bit tiles
 
 The binding is read from include/mmult_hip_q8.h (abi_header.parse); the numeric contract is in that header.  The int8-output
 library is loaded on first use, its binding read from include/mmult_hip_q8o.h.  Everything runs
@@ -76,12 +78,15 @@ class _Library:
 _q8 = _Library("mmult_hip_q8.h", "libmmult_hip_q8.so", "mmh_q8")       # fp32 out, the weight object, the row quantiser
 _q8o = _Library("mmult_hip_q8o.h", "libmmult_hip_q8o.so", "mmh_q8o")   # int8 out
 _q8d = _Library("mmult_hip_q8d.h", "libmmult_hip_q8d.so", "mmh_q8d")   # 1 - 16 rows, split-K
+_q4d = _Library("mmult_hip_q4d.h", "libmmult_hip_q4d.so", "mmh_q4d")   # 1 - 16 rows on packed 4-bit weights
 HEADER, LIB_PATH, CONSTANTS, PROTOTYPES = _q8.header, _q8.path, _q8.constants, _q8.prototypes
 EXPORTS = list(PROTOTYPES)   # every symbol include/mmult_hip_q8.h declares
 Q8O_HEADER, Q8O_LIB_PATH = _q8o.header, _q8o.path
 Q8D_HEADER, Q8D_LIB_PATH = _q8d.header, _q8d.path
+Q4D_HEADER, Q4D_LIB_PATH = _q4d.header, _q4d.path
 Q8D_MAX_ROWS = _q8d.constants["MMH_Q8D_MAX_ROWS"]
-lib, lib_q8o, lib_q8d = _q8.lib, _q8o.lib, _q8d.lib   # the loaded ctypes libraries
+Q4D_MAX_ROWS = _q4d.constants["MMH_Q4D_MAX_ROWS"]
+lib, lib_q8o, lib_q8d, lib_q4d = _q8.lib, _q8o.lib, _q8d.lib, _q4d.lib   # the loaded ctypes libraries
 _check = _q8.check
 
 
@@ -98,6 +103,11 @@ def last_launch_q8o() -> str:
 def last_launch_q8d() -> str:
     """What the last qlinear_decode on this thread launched."""
     return _q8d.last_launch()
+
+
+def last_launch_q4d() -> str:
+    """What the last qlinear_decode on a QWeight4 on this thread launched."""
+    return _q4d.last_launch()
 
 
 def qlinear_s8o_plan(rows: int, out_features: int, in_features: int, ldq: int = 0, pitch_n: int = 0, ldyq: int = 0, xq_mod4: int = 0,
@@ -122,6 +132,18 @@ def qlinear_decode_plan(rows: int, out_features: int, in_features: int, ldq: int
     _q8d.check(lib_q8d().mmh_q8d_linear_plan(rows, out_features, in_features, ldq or p16(in_features), pitch_n or p16(out_features),
                                              int(bool(out8)), ldo or (p16(out_features) if out8 else out_features), xq_mod4, wq_mod4,
                                              o_mod16, splits, cu_count, text, len(text), C.byref(work)), "mmh_q8d_linear_plan")
+    return text.value.decode(), work.value
+
+
+def qlinear_decode4_plan(rows: int, out_features: int, in_features: int, ldq: int = 0, pitch_n: int = 0, out8: bool = False, ldo: int = 0,
+                         xq_mod4: int = 0, wp_mod4: int = 0, o_mod16: int = 0, splits: int = 0, cu_count: int = 256):
+    """qlinear_decode_plan for a QWeight4: (text, work bytes) of the call, what last_launch_q4d() says after it.  The same
+    arguments and defaults; pitch_n is the packed image's."""
+    p16 = lambda n: (n + 15) & ~15
+    text, work = C.create_string_buffer(192), C.c_size_t(0)
+    _q4d.check(lib_q4d().mmh_q4d_linear_plan(rows, out_features, in_features, ldq or p16(in_features), pitch_n or p16(out_features),
+                                             int(bool(out8)), ldo or (p16(out_features) if out8 else out_features), xq_mod4, wp_mod4,
+                                             o_mod16, splits, cu_count, text, len(text), C.byref(work)), "mmh_q4d_linear_plan")
     return text.value.decode(), work.value
 
 
@@ -155,7 +177,34 @@ def _stream(device: int) -> int:
     return torch.cuda.current_stream(device).cuda_stream
 
 
-class QWeight:
+class _DecodeWork:
+    """qlinear_decode's split-K partials of a prepared weight: a torch uint8 tensor cached on the weight, grown outside capture
+    only.  The weight says what a call needs through _decode_plan (its library's plan)."""
+
+    _decode_work = None
+    _decode_plan = staticmethod(qlinear_decode_plan)
+
+    def _decode_workspace(self, nbytes: int):
+        """The cached workspace of qlinear_decode, at least nbytes long (torch's allocations are 16-byte aligned)."""
+        import torch
+        if self._decode_work is None or self._decode_work.numel() < nbytes:
+            if torch.cuda.is_current_stream_capturing():
+                raise MMultError(ERR_UNSUPPORTED, "qlinear_decode", "the workspace would have to grow while the stream is capturing -- "
+                                 f"call {type(self).__name__}.reserve_decode() first")
+            self._decode_work = torch.empty((max(int(nbytes), 16),), dtype=torch.uint8, device=f"cuda:{self.device}")
+        return self._decode_work
+
+    def reserve_decode(self, splits: int = 0) -> None:
+        """Size qlinear_decode's workspace for every call of 1 - 16 rows on this weight (before capturing a graph): the plan's
+        own split count, or a forced one."""
+        if self.in_features == 0 or self.out_features == 0:
+            return
+        cus = _cu_count(self.device)
+        self._decode_workspace(max(self._decode_plan(rows, self.out_features, self.in_features, pitch_n=self.pitch, splits=splits,
+                                                     cu_count=cus)[1] for rows in range(1, Q8D_MAX_ROWS + 1)))
+
+
+class QWeight(_DecodeWork):
     """A layer's weight prepared once: `w` (out_features, in_features) fp32 on a GPU, torch's layout, read in place (any row
     stride).  Holds the int8 image transposed -- (in_features, pitch) with pitch = out_features rounded up to 16, pad columns
     0 --, one scale per output channel and the scales' reciprocals.  The preparation is enqueued on torch's current stream."""
@@ -203,25 +252,6 @@ class QWeight:
         """Size the object's scratch for calls of up to max_rows rows (before capturing a graph of larger calls than were run)."""
         _check(lib().mmh_q8_linear_reserve(self._handle, int(max_rows), _stream(self.device)), "mmh_q8_linear_reserve")
 
-    def _decode_workspace(self, nbytes: int):
-        """The cached workspace of qlinear_decode, at least nbytes long (torch's allocations are 16-byte aligned)."""
-        import torch
-        if self._decode_work is None or self._decode_work.numel() < nbytes:
-            if torch.cuda.is_current_stream_capturing():
-                raise MMultError(ERR_UNSUPPORTED, "qlinear_decode", "the workspace would have to grow while the stream is capturing -- "
-                                 "call QWeight.reserve_decode() first")
-            self._decode_work = torch.empty((max(int(nbytes), 16),), dtype=torch.uint8, device=f"cuda:{self.device}")
-        return self._decode_work
-
-    def reserve_decode(self, splits: int = 0) -> None:
-        """Size qlinear_decode's workspace for every call of 1 - 16 rows on this weight (before capturing a graph): the plan's
-        own split count, or a forced one."""
-        if self.in_features == 0 or self.out_features == 0:
-            return
-        cus = _cu_count(self.device)
-        self._decode_workspace(max(qlinear_decode_plan(rows, self.out_features, self.in_features, pitch_n=self.pitch, splits=splits,
-                                                       cu_count=cus)[1] for rows in range(1, Q8D_MAX_ROWS + 1)))
-
     def close(self) -> None:
         self._decode_work = None
         if self._handle is not None:
@@ -233,6 +263,87 @@ class QWeight:
             self.close()
         except Exception:
             pass
+
+
+class QWeight4(_DecodeWork):
+    """A layer's weight at FOUR bits per element (W4A8), prepared once: `w` (out_features, in_features) fp32 on a GPU, torch's
+    layout, read in place (any row stride).  Owns three torch tensors: `p`, the packed uint8 image (packed_rows, pitch) -- pitch =
+    out_features rounded up to 16, 64 rows per 128 input features, a byte's low nibble the first half of its slice and its high
+    nibble the second (include/mmult_hip_q4d.h has the layout) --, `scale` (out_features,) = 7 / max|w[j, :]| and `inv_scale` =
+    fl(1 / scale).  Read by qlinear_decode only: 1 - 16 rows.  The preparation is enqueued on torch's current stream."""
+
+    _decode_plan = staticmethod(qlinear_decode4_plan)
+
+    def __init__(self, w, device=None):
+        import torch
+        if w.dim() != 2:
+            raise MMultError(ERR_INVALID_ARG, "QWeight4", "need a 2-D weight (out_features, in_features)")
+        self.device = w.device.index if device is None else int(device)
+        self.out_features, self.in_features = int(w.shape[0]), int(w.shape[1])
+        pw, ldw = tensor_args(w.detach(), self.out_features, self.in_features, "QWeight4(w)", torch.float32, self.device)
+        self.pitch, packed_rows, _ = weight4_layout(self.out_features, self.in_features)
+        dev = f"cuda:{self.device}"
+        self.p = torch.empty((packed_rows, self.pitch), dtype=torch.uint8, device=dev)
+        self.scale = torch.empty((self.out_features,), dtype=torch.float32, device=dev)
+        self.inv_scale = torch.empty((self.out_features,), dtype=torch.float32, device=dev)
+        _q4d.check(lib_q4d().mmh_q4d_pack_weight(self.device, self.out_features, self.in_features, pw, ldw, self.p.data_ptr(), self.pitch,
+                                                 self.scale.data_ptr(), self.inv_scale.data_ptr(), _stream(self.device)), "mmh_q4d_pack_weight")
+
+    @classmethod
+    def from_image(cls, p, inv_scale, out_features: int, in_features: int):
+        """Adopt a caller-made packed image: `p` uint8 (64 * ceil(in_features / 128), pitch >= out_features) on a GPU with unit
+        column stride, a row stride that is a multiple of 4 and a 4-byte aligned base, every nibble of an input feature >=
+        in_features zero (-8 is allowed); `inv_scale` a dense (out_features,) fp32 tensor, one factor per output channel.  `scale`
+        is None."""
+        import torch
+        self = cls.__new__(cls)
+        self.out_features, self.in_features = int(out_features), int(in_features)
+        packed_rows = weight4_layout(self.out_features, self.in_features)[1]
+        if not (torch.is_tensor(p) and p.is_cuda and p.dtype == torch.uint8 and p.dim() == 2 and p.shape[0] == packed_rows
+                and p.shape[1] >= self.out_features):
+            raise MMultError(ERR_INVALID_ARG, "QWeight4.from_image", f"p is a ({packed_rows}, >= {self.out_features}) uint8 tensor on a GPU")
+        self.device = p.device.index
+        self.pitch = int(p.shape[1])
+        if packed_rows:
+            _, self.pitch = tensor_args(p, packed_rows, int(p.shape[1]), "QWeight4.from_image(p)", torch.uint8, self.device)
+            if self.pitch % 4 or p.data_ptr() % 4:
+                raise MMultError(ERR_INVALID_ARG, "QWeight4.from_image", "the kernel reads p in dwords: a row stride that is a multiple of 4 "
+                                 "and a 4-byte aligned base")
+        if not (torch.is_tensor(inv_scale) and inv_scale.is_cuda and inv_scale.device.index == self.device and inv_scale.dtype == torch.float32
+                and inv_scale.dim() == 1 and inv_scale.shape[0] == self.out_features and (self.out_features <= 1 or inv_scale.stride(0) == 1)):
+            raise MMultError(ERR_INVALID_ARG, "QWeight4.from_image", "inv_scale is a dense (out_features,) fp32 tensor on p's device")
+        self.p, self.scale, self.inv_scale = p, None, inv_scale
+        return self
+
+    @property
+    def _ptrs(self):
+        """(image, scale, inv_scale) addresses, as QWeight's."""
+        return (self.p.data_ptr() if self.p.numel() else None, None if self.scale is None else self.scale.data_ptr(), self.inv_scale.data_ptr())
+
+    @property
+    def nbytes(self) -> int:
+        """The packed image's bytes."""
+        return int(self.p.shape[0]) * self.pitch
+
+    def unpack(self):
+        """The int8 image QWeight.q would be, (in_features, pitch): values in -8 .. 7.  torch ops on the packed tensor."""
+        import torch
+        slices = self.p.shape[0] // 64
+        p = self.p.view(slices, 64, self.p.shape[1]).to(torch.int16)
+        lo, hi = p & 15, p >> 4
+        w = torch.stack([lo, hi], 1).reshape(slices * 128, self.p.shape[1])
+        return torch.where(w >= 8, w - 16, w).to(torch.int8)[:self.in_features]
+
+    def close(self) -> None:
+        self._decode_work = None
+
+
+def weight4_layout(out_features: int, in_features: int):
+    """(pitch, packed rows, bytes) of the library's own packed 4-bit image.  Host arithmetic only."""
+    pitch, rows, nbytes = C.c_int(0), C.c_int(0), C.c_size_t(0)
+    _q4d.check(lib_q4d().mmh_q4d_weight_layout(int(out_features), int(in_features), C.byref(pitch), C.byref(rows), C.byref(nbytes)),
+               "mmh_q4d_weight_layout")
+    return pitch.value, rows.value, nbytes.value
 
 
 def quantize_rows(x, out=None):
@@ -406,6 +517,12 @@ def _linear_args(what, x, qweight, bias, activation, out):
     return (rows, px, ldx, _bias_ptr(what, bias, qweight), act, py, ldy), out
 
 
+def _no_tiles4(what, qweight) -> None:
+    if isinstance(qweight, QWeight4):
+        raise MMultError(ERR_UNSUPPORTED, what, "a QWeight4 has no tile path: 4-bit weights run through qlinear_decode, 1 - "
+                         f"{Q4D_MAX_ROWS} rows per call")
+
+
 def qlinear(x, qweight: QWeight, bias=None, activation=None, out=None, out_scale=None):
     """y = act(x @ w.t() + bias) in int8 (the headers' contracts).  x: (rows, in_features) fp32, quantised per row on the way
     in, or a QRows, read as it is (no quantiser pass; one QRows may feed any number of weights).  bias (out_features,) or
@@ -413,6 +530,7 @@ def qlinear(x, qweight: QWeight, bias=None, activation=None, out=None, out_scale
     out_scale a Python float or a (rows,) fp32 device tensor: y is quantised with that scale per row and returned as a QRows
     -- q in `out`, an int8 (rows, out_features) window of any pitch and base, or in new rows of pitch out_features rounded up to 16; inv_scale =
     fl(1 / out_scale) --, which the next qlinear reads in place."""
+    _no_tiles4("qlinear", qweight)
     if out_scale is not None:
         if not isinstance(x, QRows):
             _float_rows("qlinear", x, qweight)
@@ -432,12 +550,14 @@ def qlinear(x, qweight: QWeight, bias=None, activation=None, out=None, out_scale
 
 def time_qlinear(x, qweight: QWeight, bias=None, activation=None, out=None, warmup: int = 1, reps: int = 20) -> float:
     """Mean milliseconds per qlinear call (one event pair around `reps` calls)."""
+    _no_tiles4("time_qlinear", qweight)
     args, _ = _linear_args("time_qlinear", x, qweight, bias, activation, out)
     return _run(_q8, "q8_linear", (qweight._handle, *args), qweight.device, (warmup, reps))
 
 
 def time_qlinear_s8o(x: QRows, qweight: QWeight, bias=None, activation=None, out=None, out_scale=1.0, warmup: int = 1, reps: int = 20) -> float:
     """Mean milliseconds per int8-output qlinear call on a QRows (one event pair around `reps` calls)."""
+    _no_tiles4("time_qlinear_s8o", qweight)
     so, inv = _scale_vectors("time_qlinear_s8o", out_scale, x.rows, qweight.device)
     return _linear_s8o("time_qlinear_s8o", x, qweight, bias, activation, so, inv, out, time=(warmup, reps))
 
@@ -459,8 +579,9 @@ def _linear_q8d(what, x: QRows, qweight, bias, activation, so, inv, out=None, sp
     output, in `out` or in new rows of pitch out_features rounded up to 16.  The partials go through the weight's workspace."""
     act = _activation_id(activation, what)
     rows, pxq, ldq, prx = _rows_args(what, x, qweight)
+    four = isinstance(qweight, QWeight4)
     if rows > Q8D_MAX_ROWS:
-        raise MMultError(ERR_UNSUPPORTED, what, f"at most {Q8D_MAX_ROWS} rows -- larger batches are qlinear's")
+        raise MMultError(ERR_UNSUPPORTED, what, _too_many_rows(qweight))
     n, k = qweight.out_features, qweight.in_features
     out8 = so is not None
     out, po, ldo = _out_window(what, out, rows, n, out8, qweight.device)
@@ -471,15 +592,21 @@ def _linear_q8d(what, x: QRows, qweight, bias, activation, so, inv, out=None, sp
     pq, _, pr = qweight._ptrs
     work_bytes = 0
     if k > 0:
-        work_bytes = qlinear_decode_plan(rows, n, k, ldq, qweight.pitch, out8, ldo, 0, pq % 4, po % 16, splits, _cu_count(qweight.device))[1]
+        work_bytes = qweight._decode_plan(rows, n, k, ldq, qweight.pitch, out8, ldo, 0, pq % 4, po % 16, splits, _cu_count(qweight.device))[1]
     work = qweight._decode_workspace(work_bytes) if k > 0 else None
     args = (qweight.device, rows, n, k, pxq, ldq, prx, pq, qweight.pitch, pr, _bias_ptr(what, bias, qweight), act,
             so.data_ptr() if out8 else None, None if out8 else po, 0 if out8 else ldo, po if out8 else None, ldo if out8 else 0,
             work.data_ptr() if work is not None else None, work.numel() if work is not None else 0, splits)
-    ms = _run(_q8d, "q8d_linear", args, qweight.device, time)
+    ms = _run(_q4d, "q4d_linear", args, qweight.device, time) if four else _run(_q8d, "q8d_linear", args, qweight.device, time)
     if time is not None:
         return ms
     return QRows._of_window(out, inv[:rows], po, ldo) if out8 else out
+
+
+def _too_many_rows(qweight) -> str:
+    if isinstance(qweight, QWeight4):
+        return f"at most {Q4D_MAX_ROWS} rows -- there are no 4-bit tiles for larger batches"
+    return f"at most {Q8D_MAX_ROWS} rows -- larger batches are qlinear's"
 
 
 def _decode_rows(what, x, qweight) -> QRows:
@@ -488,12 +615,13 @@ def _decode_rows(what, x, qweight) -> QRows:
         return x
     _float_rows(what, x, qweight)
     if x.shape[0] > Q8D_MAX_ROWS:
-        raise MMultError(ERR_UNSUPPORTED, what, f"at most {Q8D_MAX_ROWS} rows -- larger batches are qlinear's")
+        raise MMultError(ERR_UNSUPPORTED, what, _too_many_rows(qweight))
     return quantize(x)
 
 
 def qlinear_decode(x, qweight: QWeight, bias=None, activation=None, out=None, out_scale=None, splits: int = 0):
-    """qlinear for 1 - 16 rows (libmmult_hip_q8d.so): the same arguments, the same bits -- the weight is streamed once by
+    """qlinear for 1 - 16 rows (libmmult_hip_q8d.so; a QWeight4: libmmult_hip_q4d.so, the same arguments, the bits of the int8
+    layer on the unpacked image): the same arguments, the same bits -- the weight is streamed once by
     strips x K ranges of workgroups (split-K; int32 partials add up exactly), a second kernel applies the epilogue.  x fp32 is
     quantised first with quantize(); a QRows is read in place.  More than 16 rows raise MMultError.  splits: 0 the plan's
     choice, > 0 that many K ranges.  The partials live in a workspace cached on `qweight`: it grows on demand, but not under
@@ -641,9 +769,13 @@ def _make_qlinear_class():
         """torch.nn.Linear (+ ReLU) in int8, inference only: the weight is a QWeight (set_weight / from_float), the bias an
         fp32 buffer.  forward flattens leading dimensions to rows; an input that requires grad raises."""
 
-        def __init__(self, in_features: int, out_features: int, bias: bool = True, activation=None, decode: bool = False):
+        def __init__(self, in_features: int, out_features: int, bias: bool = True, activation=None, decode: bool = False,
+                     weight_bits: int = 8):
             super().__init__()
             self.decode = bool(decode)   # batches of at most 16 rows go through qlinear_decode (the same bits)
+            if weight_bits not in (8, 4) or (weight_bits == 4 and not decode):
+                raise MMultError(ERR_INVALID_ARG, "QLinear", "weight_bits is 8, or 4 with decode=True (4-bit weights have no tile path)")
+            self.weight_bits = weight_bits   # 4: a QWeight4 -- every call goes through qlinear_decode, more than 16 rows are refused
             _activation_id(activation, "QLinear")
             self.in_features, self.out_features, self.activation = in_features, out_features, activation
             self.qweight = None
@@ -653,15 +785,15 @@ def _make_qlinear_class():
             """Prepare `w` (out_features, in_features) fp32 on a GPU; `bias` replaces the bias buffer's values."""
             if tuple(w.shape) != (self.out_features, self.in_features):
                 raise MMultError(ERR_INVALID_ARG, "QLinear.set_weight", f"need a ({self.out_features},{self.in_features}) weight")
-            self.qweight = QWeight(w)
+            self.qweight = QWeight4(w) if self.weight_bits == 4 else QWeight(w)
             if self.bias is not None:
                 self.bias = (torch.zeros(self.out_features) if bias is None else bias.detach().to(torch.float32)).to(w.device).contiguous()
             return self
 
         @classmethod
-        def from_float(cls, linear, activation=None, decode=False):
-            """The int8 layer of a torch.nn.Linear whose weight lives on a GPU."""
-            return cls(linear.in_features, linear.out_features, linear.bias is not None, activation, decode).set_weight(
+        def from_float(cls, linear, activation=None, decode=False, weight_bits=8):
+            """The int8 layer of a torch.nn.Linear whose weight lives on a GPU (weight_bits=4 with decode=True: 4-bit weights)."""
+            return cls(linear.in_features, linear.out_features, linear.bias is not None, activation, decode, weight_bits).set_weight(
                 linear.weight.detach(), None if linear.bias is None else linear.bias.detach())
 
         def forward(self, x):
@@ -672,7 +804,7 @@ def _make_qlinear_class():
             rows = x.reshape(-1, self.in_features)
             if rows.shape[0] > 1 and rows.shape[1] > 1 and rows.stride(1) != 1:
                 rows = rows.contiguous()
-            layer = qlinear_decode if self.decode and rows.shape[0] <= Q8D_MAX_ROWS else qlinear
+            layer = qlinear_decode if self.weight_bits == 4 or (self.decode and rows.shape[0] <= Q8D_MAX_ROWS) else qlinear
             y = layer(rows, self.qweight, self.bias, self.activation)
             return y.reshape(*x.shape[:-1], self.out_features)
 
@@ -692,4 +824,5 @@ def __getattr__(name):   # QLinear / QMLP are torch.nn.Modules: made when first 
 __all__ = ["QWeight", "QLinear", "QRows", "QMLP", "quantize_rows", "quantize", "qlinear", "time_qlinear", "time_qlinear_s8o", "qlinear_plan",
            "qlinear_s8o_plan", "scale_of_amax", "last_launch", "last_launch_q8o", "lib", "lib_q8o", "EXPORTS", "LIB_PATH", "HEADER",
            "Q8O_LIB_PATH", "Q8O_HEADER", "qlinear_decode", "time_qlinear_decode", "qlinear_decode_plan", "last_launch_q8d", "lib_q8d",
-           "Q8D_LIB_PATH", "Q8D_HEADER", "Q8D_MAX_ROWS"]
+           "Q8D_LIB_PATH", "Q8D_HEADER", "Q8D_MAX_ROWS", "QWeight4", "weight4_layout", "qlinear_decode4_plan", "last_launch_q4d", "lib_q4d",
+           "Q4D_LIB_PATH", "Q4D_HEADER", "Q4D_MAX_ROWS"]
