@@ -8,8 +8,9 @@ qlinear_s8_ref takes behind its quantiser -- qlinear_ref.epilogue_ref on the exa
 the UNPACKED int8 image, with the channels' factors the image came with.  The sums are numpy's own (float64 products of
 integers below 2^53: exact), so nothing here needs a compiled helper.
 
-Also here: the tables tests/test_gpu_q4decode.py runs (tests/test_q4d_coverage.py holds the classes they promise, on the CPU)
-and their inputs."""
+Also here: the tables tests/test_gpu_q4decode.py runs -- cases() and wide_deep_cases(), the second at the grids, split counts
+and row counts the first stops short of -- (tests/test_q4d_coverage.py holds the classes they promise, on the CPU) and their
+inputs, ceiling_problem() among them: ranges of exactly MAX_RANGE_K k that end with the accumulator at +2^30."""
 import collections
 import functools
 
@@ -136,6 +137,24 @@ def largest_pitch_n(in_):
     return (D.WINDOW - 256 - 1) // (layout(1, in_)[1] + 128) & ~3
 
 
+def furthest_slice(nk):
+    """The last slice q4decode_partial_kernel's two-stage ring requests in a range of nk slices: 0 and 1 ahead of the loop,
+    then one behind each slice consumed, and the loop consumes in pairs -- nk + 2 behind an odd count, nk + 1 behind an even."""
+    return nk + 2 if nk % 2 else nk + 1
+
+
+def weight_offsets(in_, pitch_n, splits=1):
+    """Per K range of a forced split count: (ext_w of strip 0, the largest scalar offset -- the kernel's `int` product
+    kt * 64 * pitch_n --, the largest unsigned sum voff_w + soff, with voff_w <= 63 pitch_n + 112 and 16 bytes read)."""
+    k_len, rs = D.ranges(in_, splits)
+    got = []
+    for begin, end in rs:
+        nk = -(-(end - begin) // SLICE)
+        soff = furthest_slice(nk) * HALF * pitch_n
+        got.append(((HALF * nk - 1) * pitch_n + STRIP, soff, soff + (HALF - 1) * pitch_n + STRIP - 1))
+    return got
+
+
 # ---- the GPU tables ---------------------------------------------------------------------------------------------------------
 ROWS = (1, 2, 15, 16)
 INS = (1, 63, 64, 65, 127, 128, 129, 384, 385, 1153)
@@ -177,6 +196,54 @@ def cases():
 
 
 case_id = D.case_id
+
+# ---- the second table: where the kernel differs from the int8 one it was copied from -----------------------------------------
+WIDE_OUTS, WIDE_ROWS, SHALLOW = D.WIDE_OUTS, D.WIDE_ROWS, D.SHALLOW   # the finish grid: qdecode_ref's, behind in <= 385
+MANY_RANGES_INS = (1153, 1280)                                         # forced counts above 3, up to one range per slice
+OWN_CHOICE = ((1, 130, 8192), (2, 130, 8192), (1, D.FINISH_COLS + 1, 4224))   # splits == 0: one slice per range at 256 CUs
+WIDE_DEEP = ((4224, 1), (11008, 2))                                    # (in, forced ranges) at 16 rows, 130 columns: 33, 43 slices
+LADDER = (130, 257, 2)                                                 # (out, in, forced ranges) at every row count 1 - 16
+RESERVE_SHAPE = (257, 1153)                                            # (out, in) whose own split count varies with the rows
+
+
+@functools.lru_cache(maxsize=None)
+def wide_deep_cases():
+    """qdecode_ref.wide_deep_cases() for the packed image: the finish grid (every WIDE_OUTS at two row counts behind two to four
+    shallow ranges, then 1027 columns on the two layouts whose stores are wide although out is no multiple of 4), every forced
+    count above 3 that leaves no range of MANY_RANGES_INS empty, the plan's own choice where it is one slice per range (every
+    range consumes a zero second stage), the deep ranges (the second on a caller-made image) and LADDER at every row count.
+    Layouts, weights and epilogues rotate as in cases()."""
+    out = []
+
+    def add(rows, n, in_, s, **fixed):
+        out.append(D._case(len(out), rows, n, in_, s)._replace(**fixed))
+
+    for j, n in enumerate(WIDE_OUTS):
+        for r in (0, 1):
+            add(WIDE_ROWS[(2 * j + r) % len(WIDE_ROWS)], n, *SHALLOW[len(out) % len(SHALLOW)])
+    # ldy = out + 1 at a 16-byte base, ldyq = out + 5 at a 4-byte base: whole rows of dwords, the last three columns one by one
+    add(16, D.FINISH_COLS + 3, 257, 2, y=D.Y_LAYOUTS.index((1, 0)), yq=D.YQ_LAYOUTS.index((5, 0)))
+    add(1, D.FINISH_COLS + 3, 129, 2, y=D.Y_LAYOUTS.index((1, 0)), yq=D.YQ_LAYOUTS.index((5, 0)))
+    for in_ in MANY_RANGES_INS:
+        for s in range(FORCED[-1] + 1, -(-in_ // SLICE) + 1):
+            if D.valid_splits(in_, s):
+                add(ROWS[len(out) % 4], OUTS[len(out) % len(OUTS)], in_, s)
+    for rows, n, in_ in OWN_CHOICE:
+        add(rows, n, in_, 0)
+    for j, (in_, s) in enumerate(WIDE_DEEP):
+        add(MAX_ROWS, 130, in_, s, weight="image" if j == 1 else "qweight")
+    for rows in range(1, MAX_ROWS + 1):
+        add(rows, *LADDER)
+    return tuple(out)
+
+
+def range_slices(c, cus=256):
+    """[(slices of the range, is it the last one) ...] of a case's K ranges: what the two-stage ring goes through per workgroup.
+    An odd count consumes its second stage as zeros."""
+    _, _, splits, k_len = plan(c.rows, c.out, c.in_, splits=c.splits, cus=cus)
+    ends = [min((s + 1) * k_len, c.in_) - s * k_len for s in range(splits)]
+    return [(-(-kr // SLICE), s == splits - 1) for s, kr in enumerate(ends)]
+
 
 # xq int8 (rows, in); rx; w: the fp32 weight or None; W: the int8 image (in, out) in -8 .. 7; rw; bias; so; acc
 Problem = collections.namedtuple("Problem", "xq rx w W rw bias so acc")
@@ -255,6 +322,57 @@ def large_sums_problem():
     inexact = acc.astype(np.float32).astype(np.int64) != acc
     assert inexact.sum() > 250 and inexact[acc > 1 << 24].sum() > 25 and inexact[acc < -(1 << 24)].sum() > 25
     bias = rng.uniform(-4, 4, out).astype(np.float32)
+    return Problem(xq, rx, None, W, rw, bias, D.out_scales(R.epilogue_ref(acc, rx, rw, bias, False)), acc)
+
+
+CEILING_SHAPE = (16, 130)   # rows, out: two strips, the second of 2 columns
+CEILING_CELLS = 4           # rows {0, 1} x channels {0, 1}: the saturated sums, all that the half-slice check may leave out
+
+
+def partial_of_range(xq, W, begin, end):
+    """What q4decode_partial_kernel writes for the K range [begin, end): its int32 accumulator holds 16 x the sum (the
+    nibbles arrive as int8 bytes 16 W), then `acc >> 4`, ARITHMETIC.  The accumulator has to fit: that is MAX_RANGE_K."""
+    acc16 = 16 * (np.asarray(xq[:, begin:end], np.float64) @ np.asarray(W[begin:end], np.float64))
+    assert np.abs(acc16).max(initial=0) <= 1 << 30, (begin, end)   # (+2^30 from -128 x -8; the negative extreme is smaller)
+    return acc16.astype(np.int32) >> 4
+
+
+@functools.lru_cache(maxsize=None)
+def ceiling_problem(in_):
+    """(16, 130, in_) with in_ a multiple of MAX_RANGE_K, to run in ranges of exactly MAX_RANGE_K k (512 slices): rows over
+    the full int8 range with row 0 all -128 and row 1 all 127, a caller-made image over -8 .. 7 with channel 0 all -8 and
+    channel 1 all 7; factors, bias and output scales as in image_problem.  In every range the accumulator of cell (0, 0) is
+    +2^30 exactly -- all the contract admits -- and that of cell (1, 0) is -1 065 353 216; the shifted accumulator is the sum;
+    every other sum keeps all its bits in fp32, and each half of each slice moves them."""
+    rows, out = CEILING_SHAPE
+    assert in_ > 0 and in_ % MAX_RANGE_K == 0
+    rng = np.random.default_rng(7)
+    xq = D.int8_full_range(rng, (rows, in_))
+    xq[0], xq[1] = -128, 127
+    W = rng.integers(-8, 8, (in_, out), dtype=np.int8)
+    W[:, 0], W[:, 1] = -8, 7
+    rx = rng.uniform(0.01, 0.05, rows).astype(np.float32)
+    rw = rng.uniform(0.01, 0.04, out).astype(np.float32)
+    bias = rng.uniform(-4, 4, out).astype(np.float32)
+    acc = int_sums(xq, W)
+    total = np.zeros((rows, out), np.int64)
+    for begin in range(0, in_, MAX_RANGE_K):
+        part = partial_of_range(xq, W, begin, begin + MAX_RANGE_K)
+        assert 16 * int(part[0, 0]) == 1 << 30 and 16 * int(part[1, 0]) == -1065353216, (begin, part[:2, :2])
+        assert np.array_equal(part, int_sums(xq[:, begin:begin + MAX_RANGE_K], W[begin:begin + MAX_RANGE_K])), begin
+        total += part
+    assert np.array_equal(total, acc)
+    plain = np.ones((rows, out), bool)
+    plain[:2, :2] = False
+    assert plain.size - int(plain.sum()) == CEILING_CELLS
+    assert np.abs(acc[plain]).max() < 1 << 24 and np.abs(acc[~plain]).min() > 1 << 24
+    # each 64-k half of each slice, at once: (halves, rows, 64) @ (halves, 64, out) in float32 (|sum| <= 64 * 1024: exact)
+    halves = in_ // HALF
+    moved = np.matmul(xq.reshape(rows, halves, HALF).transpose(1, 0, 2).astype(np.float32), W.reshape(halves, HALF, out).astype(np.float32))
+    share = (moved[:, plain] != 0).mean(axis=1)
+    assert share.shape == (halves,) and float(share.min()) >= 0.9, (int(share.argmin()), float(share.min()))
+    low, high = W.reshape(in_ // SLICE, 2, HALF, out)[:, 0], W.reshape(in_ // SLICE, 2, HALF, out)[:, 1]
+    assert (low != high).any(axis=(1, 2)).all()   # swapping the halves of any slice would change the sums
     return Problem(xq, rx, None, W, rw, bias, D.out_scales(R.epilogue_ref(acc, rx, rw, bias, False)), acc)
 
 

@@ -6,8 +6,12 @@ x's int8 rows at a pitch of `in` rounded up to 4 plus 0 - 12 bytes and a base 0 
 beyond `in`, between the rows and in the (16 - rows) rows' worth of memory behind the last row poisoned with 0x55; a weight that
 is QWeight4's own image or a caller-made one (its own pitch and base, pad columns poisoned); the output inside a buffer of 0x55
 that is compared WHOLE with what the reference says it holds afterwards; the workspace pre-filled with 0x7f and followed by 64
-guard bytes.  The launch text is held to the Python plan at the device's CU count.  tests/q4_ref.py has the case table,
-tests/test_q4d_coverage.py what it promises."""
+guard bytes.  The launch text is held to the Python plan at the device's CU count.  tests/q4_ref.py has the two case tables --
+cases(), thorough in the small, and wide_deep_cases(): outputs wider than one finish workgroup, up to one K range per slice,
+deep ranges, every row count --, tests/test_q4d_coverage.py what they promise.  Two calls run ranges of exactly
+MMH_Q4D_MAX_RANGE_K k, where the accumulator ends at +2^30; three more run operands at the edge of the descriptor window (the
+largest pitch_n and ldq shape_status4 admits), built on the device inside one 1.07 GB buffer of 0x55; the Python layer's timer,
+its cached workspace under QWeight4's own plan and from_image's refusals follow at the end."""
 import numpy as np
 import pytest
 
@@ -73,9 +77,9 @@ class Weight:
         self.qweight.close()
 
 
-def run(p, weight, bias, relu, out8, splits, cus, x_pad=0, x_off=0, o_pad=0, o_off=0):
+def run(p, weight, bias, relu, out8, splits, cus, x_pad=0, x_off=0, o_pad=0, o_off=0, x_rows=None):
     """One mmh_q4d_linear call on the layouts above; asserts the status, the launch text, the whole output buffer, the
-    workspace's guard.  Returns the launch text."""
+    workspace's guard.  Returns the launch text.  x_rows: device_rows' triple where the caller has laid x out itself."""
     import torch
     import how_to_optimize_gemm_amd as H
     from how_to_optimize_gemm_amd import q8
@@ -84,7 +88,7 @@ def run(p, weight, bias, relu, out8, splits, cus, x_pad=0, x_off=0, o_pad=0, o_o
     out = p.W.shape[1]
     item = 1 if out8 else 4
     ldo = out + o_pad
-    keep_x, pxq, ldq = device_rows(p.xq, x_pad, x_off)
+    keep_x, pxq, ldq = x_rows or device_rows(p.xq, x_pad, x_off)
     rx, so, db = dev(p.rx), dev(p.so), dev(p.bias)
     planned = F.plan(rows, out, in_, out8, ldo, (item * o_off) % 16, splits, cus)
     assert planned not in (None, "long"), "the table forces a split count the plan refuses"
@@ -116,9 +120,9 @@ def run(p, weight, bias, relu, out8, splits, cus, x_pad=0, x_off=0, o_pad=0, o_o
     return launched
 
 
-def run_both(p, weight, bias, relu, splits, cus, x_pad=0, x_off=0, y=0, yq=0):
-    a = run(p, weight, bias, relu, False, splits, cus, x_pad, x_off, *D.Y_LAYOUTS[y])
-    b = run(p, weight, bias, relu, True, splits, cus, x_pad, x_off, *D.YQ_LAYOUTS[yq])
+def run_both(p, weight, bias, relu, splits, cus, x_pad=0, x_off=0, y=0, yq=0, x_rows=None):
+    a = run(p, weight, bias, relu, False, splits, cus, x_pad, x_off, *D.Y_LAYOUTS[y], x_rows=x_rows)
+    b = run(p, weight, bias, relu, True, splits, cus, x_pad, x_off, *D.YQ_LAYOUTS[yq], x_rows=x_rows)
     return a, b
 
 
@@ -176,6 +180,42 @@ def test_every_case_of_the_table_is_the_contract_on_both_outputs(index, cus):
         w.close()
 
 
+@pytest.mark.parametrize("index", range(len(F.wide_deep_cases())), ids=[F.case_id(c) for c in F.wide_deep_cases()])
+def test_every_case_of_the_second_table_is_the_contract_on_both_outputs(index, cus):
+    """More than one finish workgroup per row (this library's own build of the finish kernels, blockIdx.x > 0), up to 33
+    strips, up to one K range per slice -- the plan's own choice at one and two rows included, whatever it is on this device:
+    every range then consumes a zero second stage --, ranges of 33 and 43 slices, every row count 1 - 16."""
+    c = F.wide_deep_cases()[index]
+    p = (F.problem if c.weight == "qweight" else F.image_problem)(c.rows, c.out, c.in_)
+    w = Weight(p, c.weight, index)
+    try:
+        run_both(p, w, c.bias, c.relu, c.splits, cus, c.x_pad, c.x_off, c.y, c.yq)
+    finally:
+        w.close()
+
+
+# ---- 2b. the 65536-k ceiling of a range -------------------------------------------------------------------------------------
+@pytest.mark.parametrize("in_,ranges", [(F.MAX_RANGE_K, 1), (2 * F.MAX_RANGE_K, 2)], ids=["one-range", "two-ranges"])
+def test_ranges_of_exactly_65536_k_fill_the_accumulator_to_2_to_the_30(in_, ranges, cus):
+    """F.ceiling_problem: every range is MMH_Q4D_MAX_RANGE_K long, 512 slices; the accumulator of cell (0, 0) ends at +2^30
+    exactly (x = -128 against W = -8), that of cell (1, 0) at -1 065 353 216, and `acc >> 4` has to be arithmetic.  With two
+    ranges the finish kernel adds two partials of 2^26.  One k more in a forced range is refused (no launch): the run sits ON
+    the boundary."""
+    import how_to_optimize_gemm_amd as H
+    from how_to_optimize_gemm_amd import q8
+    with pytest.raises(H.MMultError) as e:
+        q8.qlinear_decode4_plan(16, 130, F.MAX_RANGE_K + 1, splits=1, cu_count=cus)
+    assert e.value.status == H.ERR_INVALID_ARG and "65536" in str(e.value)
+    assert F.plan(16, 130, in_, splits=ranges, cus=cus)[2:] == (ranges, F.MAX_RANGE_K)
+    p = F.ceiling_problem(in_)
+    w = Weight(p, "image", 6)
+    try:
+        for launched in run_both(p, w, True, False, ranges, cus, 4, 8, 2, 2):
+            assert f"2 strips x {ranges} splits of {F.MAX_RANGE_K} k" in launched
+    finally:
+        w.close()
+
+
 def test_the_plans_own_choice_splits_on_the_devices_cu_count(cus):
     rows, out, in_ = F.PLAN_SHAPE
     _, _, splits, k_len = F.plan(rows, out, in_, cus=cus)
@@ -196,6 +236,144 @@ def test_bias_and_relu_all_four(bias, relu, cus):
     w = Weight(p, "qweight")
     try:
         run_both(p, w, bias, relu, 2, cus, 12, 4, 1, 1)
+    finally:
+        w.close()
+
+
+# ---- 2c. operands at the edge of the descriptor window ----------------------------------------------------------------------
+EDGE_OUT = 130
+EDGE_BYTES = 16 + 12 + (F.layout(EDGE_OUT, 129)[1] - 1) * F.largest_pitch_n(129) + EDGE_OUT + 64   # the largest operand below: 1.07 GB
+
+
+@pytest.fixture(scope="module")
+def edge():
+    """The flat 0x55 buffer the operands at the window's edge are strided views of: they are written on the device, there is
+    never a host array of that size."""
+    import torch
+    buf = torch.full((EDGE_BYTES,), POISON, dtype=torch.uint8, device="cuda")
+    yield buf
+    del buf
+    torch.cuda.empty_cache()
+
+
+def edge_operand(buf, values, ld, off, rows_behind=0):
+    """(keep-alive, the operand as a strided view of buf, ld) of one-byte `values` as rows of pitch ld, 16 + off bytes into
+    buf; everything else of the max(its rows, rows_behind) rows' worth of bytes and 64 behind them is 0x55 (again)."""
+    import torch
+    rows, cols = values.shape
+    end = 16 + off + max((rows - 1) * ld + cols, rows_behind * ld) + 64
+    assert values.dtype.itemsize == 1 and off % 4 == 0 and ld % 4 == 0 and end <= buf.numel(), (values.shape, ld, off, buf.numel())
+    buf[:end].fill_(POISON)
+    view = torch.as_strided(buf, (rows, cols), (ld, 1), 16 + off)
+    view.copy_(dev(values.view(np.uint8)))
+    return buf, view, ld
+
+
+class EdgeImage:
+    """Weight's interface for a caller-made packed image of pitch `pitch` inside the edge buffer, adopted by from_image."""
+
+    def __init__(self, buf, p, pitch, off):
+        from how_to_optimize_gemm_amd import q8
+        in_, out = p.W.shape
+        _, view, _ = edge_operand(buf, F.pack_ref(p.W), pitch, off)
+        self.qweight = q8.QWeight4.from_image(view, dev(p.rw), out, in_)
+        self.ptr, _, self.rw = self.qweight._ptrs
+        self.pitch = self.qweight.pitch
+        assert self.pitch == pitch and self.ptr == buf.data_ptr() + 16 + off
+
+    def close(self):
+        self.qweight.close()
+
+
+@pytest.mark.parametrize("splits", [0, 1])
+def test_one_slice_at_the_largest_image_pitch_inside_the_window(edge, cus, splits):
+    """in 1, out 130, 2 rows, pitch_n = P = 11 184 784: the largest multiple of 4 that shape_status4 admits for one slice (the
+    next one is refused: tests/test_q4d_abi.py).  The image is one slice of 64 packed rows spanning 63 P + 130 bytes = 0.70 GB,
+    of which 130 per packed row are written (row 0 holds k = 0 in its low nibbles; the rest of the slice is zero nibbles).
+
+    The offsets of q4decode_partial_kernel's weight descriptor, written down before the first run.  A lane's offset is
+    voff_w + soff with voff_w = r P + 16 slot, r <= 63, slot <= 7 -- at most 63 P + 112, its 16 bytes end at 63 P + 127 =
+    704 641 519 -- and the scalar soff = kt 64 P, an `int` product; the extent is ext_w = (64 nk - 1) P + 128 (strip 0; 4 for
+    strip 1, whose base is 128 bytes further).  One range, kr = 1, nk = 1 -- odd --, ext_w = 63 P + 128 = 704 641 520, and the
+    slices issued are 0 - 3 = nk + 2:
+      slice 0   offsets 0 .. 63 P + 127 < ext_w: packed rows 0 - 63, all inside the image;
+      slice 1   soff 64 P = 715 826 176 >= ext_w; offsets up to 127 P + 127 = 1 420 467 695: zeros, and CONSUMED -- the second
+                ring stage of an odd slice count;
+      slice 2   soff 128 P = 1 431 652 352; offsets up to 191 P + 127 = 2 136 293 871 < 2^31: zeros, never consumed;
+      slice 3   soff 192 P = 2 147 478 528 < 2^31 = 2 147 483 648 by 5 120 (the int product does not overflow: with one more
+                ring stage, 256 P, it would); offsets 192 P .. 255 P + 127 = 2 852 120 047: above 2^31, below 2^32 -- an
+                unsigned 32-bit sum that does not wrap --, all > ext_w: zeros, never consumed.
+    Nothing beyond slice 0 is fetched.  x is 2 dense rows: its offsets stay below 15 ldq + 48 + 448.  The case is one the
+    contract admits; every offset beyond ext_w must read zeros, and the asserts below are the arithmetic."""
+    pitch, nk = F.largest_pitch_n(1), 1
+    assert pitch == 11184784 and F.window_ok(4, pitch, 1) and not F.window_ok(4, pitch + 4, 1)
+    ext_w = (64 * nk - 1) * pitch + 128
+    assert 63 * pitch + 127 < ext_w <= 64 * pitch
+    assert (nk + 2) * 64 * pitch == 2147478528 < 1 << 31 <= (nk + 3) * 64 * pitch
+    assert (1 << 31) < (nk + 2) * 64 * pitch + 63 * pitch + 127 < 1 << 32
+    assert F.weight_offsets(1, pitch) == [(ext_w, 2147478528, 2852120047)] and F.furthest_slice(nk) == 3
+    assert F.plan(2, EDGE_OUT, 1, cus=cus)[2:] == (1, 128)
+    p = F.image_problem(2, EDGE_OUT, 1)
+    w = EdgeImage(edge, p, pitch, 12)
+    try:
+        run_both(p, w, False, True, splits, cus, 0, 4, 1, 1)
+    finally:
+        w.close()
+
+
+@pytest.mark.parametrize("splits", [1, 2])
+def test_the_largest_image_pitch_of_two_slices_inside_the_window(edge, cus, splits):
+    """in 129, out 130, 16 rows, pitch_n = P = 8 388 588: the largest multiple of 4 admitted for 128 packed rows.  The image
+    spans 127 P + 130 bytes = 1.065 GB, of which 130 per packed row are written.
+
+    voff_w = r P + 16 slot, r <= 63 (its 16 bytes end at most at 63 P + 127 = 528 481 171); soff = kt 64 P;
+    ext_w = (64 nk - 1) P + 128 (strip 0).  With ONE range kr = 129, nk = 2 -- even --, ext_w = 127 P + 128 = 1 065 350 804,
+    and the slices issued are 0 - 3 = nk + 1:
+      slice 0   offsets 0 .. 63 P + 127: packed rows 0 - 63, inside the image;
+      slice 1   soff 64 P = 536 869 632; offsets .. 127 P + 127 = 1 065 350 803 < ext_w: packed rows 64 - 127, inside the image;
+      slice 2   soff 128 P = 1 073 739 264 >= ext_w; offsets .. 191 P + 127: zeros, never consumed;
+      slice 3   soff 192 P = 1 610 608 896 < 2^31; offsets .. 255 P + 127 = 2 139 090 067 < 2^31: zeros, never consumed.
+    With TWO ranges (k_len 128) range 0 has kr = 128, nk = 1, ext_w = 63 P + 128 = 528 481 172: its slice 1 (soff 64 P >=
+    ext_w) is consumed as zeros although the image's second slice lies AT those addresses -- the extent, not the memory, makes
+    it zero --, and slices 2 and 3 = nk + 2 follow up to 255 P + 127 as above.  Range 1's base is 64 P further (a 64-bit
+    pointer sum), kr = 1, nk = 1, ext_w = 63 P + 128: slice 0 is the image's packed rows 64 - 127, slices 1 - 3 reach
+    255 P + 127 past THAT base, all beyond its extent.  x is 16 dense rows.  Every case is inside the contract."""
+    pitch = F.largest_pitch_n(129)
+    assert pitch == 8388588 and F.window_ok(132, pitch, 129) and not F.window_ok(132, pitch + 4, 129)
+    k_len = F.plan(16, EDGE_OUT, 129, splits=splits)[3]
+    assert k_len == (256, 128)[splits - 1]
+    for kr in ((129,), (128, 1))[splits - 1]:
+        nk = -(-kr // 128)
+        last = F.furthest_slice(nk)
+        ext_w = (64 * nk - 1) * pitch + 128
+        assert (64 * nk - 1) * pitch + 127 < ext_w <= 64 * nk * pitch
+        assert last == 3 and last * 64 * pitch == 1610608896 < 1 << 31
+        assert last * 64 * pitch + 63 * pitch + 127 == 2139090067 < 1 << 31   # (so below 2^32 too)
+    assert 127 * pitch + EDGE_OUT + 16 + 4 + 64 <= EDGE_BYTES
+    p = F.image_problem(16, EDGE_OUT, 129)
+    w = EdgeImage(edge, p, pitch, 4)
+    try:
+        run_both(p, w, True, False, splits, cus, 4, 8, 2, 2)
+    finally:
+        w.close()
+
+
+def test_the_largest_row_pitch_inside_the_window(edge, cus):
+    """in 129, out 130, 16 rows of x at ldq = 8 388 588, the largest multiple of 4 with 256 ldq + in < 2^31 - 4096: x spans
+    134 MB; the image is QWeight4's own.  The x descriptor's extent is 15 ldq + 132 = 125 828 952; a lane's offset is
+    li ldq + k_begin + 16 g + 128 kt (+ 64) <= 15 ldq + 128 + 48 + 448 = 125 829 444 with the slices issued up to 3: far
+    below 2^31, and beyond the extent only in the last row's bytes past `in` (zeros).  The weight's offsets are those of a
+    pitch of 144."""
+    ldq = D.largest_ldq(129)
+    assert ldq == 8388588 and F.window_ok(ldq, 144, 129) and not F.window_ok(ldq + 4, 144, 129)
+    assert 15 * ldq + 128 + 48 + 3 * 128 + 64 < 1 << 31
+    p = F.problem(16, EDGE_OUT, 129)
+    w = Weight(p, "qweight")
+    assert w.pitch == 144
+    try:
+        keep, view, _ = edge_operand(edge, p.xq, ldq, 8, F.MAX_ROWS)
+        for splits in (1, 2):
+            run_both(p, w, True, True, splits, cus, y=3, yq=3, x_rows=(keep, view.data_ptr(), ldq))
     finally:
         w.close()
 
@@ -376,3 +554,174 @@ def test_the_module_with_four_bit_weights_and_the_refusals(cus):
     # the timer goes through the same entry
     ms = q8.time_qlinear_decode(xq, layer.qweight, layer.bias, "relu", warmup=1, reps=3)
     assert isinstance(ms, float) and ms > 0 and q8.last_launch_q4d() == F.plan(16, 130, 192, cus=cus)[0]
+
+
+# ---- 7. the Python layer: QWeight4's own plan behind the shared workspace, the timer, from_image's refusals -----------------------
+@pytest.mark.parametrize("out8", [False, True], ids=["fp32", "int8"])
+def test_time_qlinear_decode_launches_the_plan_and_leaves_the_result(out8, cus):
+    """mmh_time_q4d_linear behind its argument checks: one warm-up and three timed calls; no bound on the time itself."""
+    import math
+    import torch
+    from how_to_optimize_gemm_amd import q8
+    rows, out, in_ = 16, 257, 385
+    p = F.problem(rows, out, in_)
+    qw = q8.QWeight4(dev(p.w))
+    x, bias = qrows(p, 4), dev(p.bias)
+    ldo = (out + 15) & ~15 if out8 else out
+    y = torch.full((rows, ldo), POISON, dtype=torch.int8, device="cuda") if out8 else torch.full((rows, ldo), float("nan"), device="cuda")
+    ms = q8.time_qlinear_decode(x, qw, bias, "relu", out=y[:, :out], out_scale=dev(p.so) if out8 else None, warmup=1, reps=3)
+    assert isinstance(ms, float) and math.isfinite(ms) and ms > 0, ms
+    assert q8.last_launch_q4d() == F.plan(rows, out, in_, out8, ldo, cus=cus)[0]
+    got, want = y.cpu().numpy(), F.want_of(p, True, True, out8)
+    if out8:
+        assert np.array_equal(got[:, :out], want) and bool((got[:, out:] == POISON).all())
+    else:
+        assert same_bits(got, want)
+    qw.close()
+
+
+@pytest.mark.parametrize("refusal", ["in-the-warm-up", "between-the-events", "an-empty-range", "a-long-range"])
+def test_the_timing_loop_unwinds_from_a_refused_call(refusal, cus):
+    """mmh_time_q4d_linear on calls it has to refuse.  A workspace one byte short of the plan's, where the plan's own count is
+    above one range (so that the device-free checks, which know no CU count, let it pass): linear_on refuses it in the warm-up
+    (before the timer's events exist) or in the first timed call (after they do).  A forced count that leaves a range empty,
+    and one range of 65536 + 128 k (a zero image: it is never read), are refused before the loop.  Every time the status and
+    the message are the call's, nothing is launched -- the output and the workspace keep their fill, the launch text is the
+    earlier call's -- and a correct timed call on the same rows and output follows.  (Argument refusals: nothing invalid
+    reaches the device.)"""
+    import ctypes as C
+    import math
+    import torch
+    import how_to_optimize_gemm_amd as H
+    from how_to_optimize_gemm_amd import q8
+    rows, out, in_ = 3, 130, 1153
+    p = F.problem(rows, out, in_)
+    qw = q8.QWeight4(dev(p.w))
+    x, bias = qrows(p, 4), dev(p.bias)
+    text, work_bytes, own, _ = F.plan(rows, out, in_, cus=cus)
+    assert own > 1 and work_bytes - 1 >= D.work_bytes(1, rows, out)
+    assert F.plan(rows, out, in_, splits=6) is None and F.plan(rows, out, F.MAX_RANGE_K + 128, splits=1) == "long"
+    q8.qlinear_decode(qrows(p, 4, 2), qw)   # (two rows: a launch text that is not this call's)
+    before = q8.last_launch_q4d()
+    assert before and before != text
+    y = torch.full((rows, out), 7.0, device="cuda")
+    work = torch.full((work_bytes,), WORK_FILL, dtype=torch.uint8, device="cuda")
+    pq, _, pr = qw._ptrs
+    k, ldq, pxq, pitch, splits, given, warmup, reps = in_, x._ld, x._ptr, qw.pitch, 0, work_bytes - 1, 1, 1
+    message = b"the workspace is smaller than the plan's work_bytes"
+    if refusal == "between-the-events":
+        warmup, reps = 0, 2
+    elif refusal == "an-empty-range":
+        splits, given, message = 6, work_bytes, b"the forced split count leaves a K range empty"
+    elif refusal == "a-long-range":
+        k = ldq = F.MAX_RANGE_K + 128
+        long_x = torch.zeros((rows, k), dtype=torch.int8, device="cuda")
+        long_p = torch.zeros((F.layout(out, k)[1], pitch), dtype=torch.uint8, device="cuda")
+        pxq, pq, splits, given = long_x.data_ptr(), long_p.data_ptr(), 1, work_bytes
+        message = b"the forced split count leaves a K range longer than 65536 k (MMH_Q4D_MAX_RANGE_K)"
+    L, ms = q8.lib_q4d(), C.c_float(-1.0)
+    rc = L.mmh_time_q4d_linear(0, rows, out, k, pxq, ldq, x.inv_scale.data_ptr(), pq, pitch, pr, bias.data_ptr(), H.ACT_NONE, None,
+                               y.data_ptr(), out, None, 0, work.data_ptr(), given, splits, warmup, reps,
+                               torch.cuda.current_stream().cuda_stream, C.byref(ms))
+    assert rc == H.ERR_INVALID_ARG, (rc, L.mmh_q4d_last_error())
+    assert L.mmh_q4d_last_error() == b"mmh_time_q4d_linear: " + message
+    torch.cuda.synchronize()
+    assert bool((y == 7.0).all()) and bool((work == WORK_FILL).all()) and ms.value == -1.0
+    assert q8.last_launch_q4d() == before
+    took = q8.time_qlinear_decode(x, qw, bias, out=y, warmup=1, reps=3)
+    assert isinstance(took, float) and math.isfinite(took) and took > 0, took
+    assert q8.last_launch_q4d() == text
+    assert same_bits(y.cpu().numpy(), F.want_of(p, True, False, False))
+    qw.close()
+
+
+def test_the_workspace_grows_between_two_calls_that_nothing_separates(cus):
+    """1 row, then 16 rows with no synchronise in between: the second call replaces the cached workspace while the first may
+    still be running on it (the old tensor goes back to torch's allocator, which hands it to nobody ahead of the stream's
+    work).  Then 1 row again: what is large enough stays.  (in 385 has no 3 ranges without an empty one: 4, one per slice.)"""
+    import torch
+    from how_to_optimize_gemm_amd import q8
+    out, in_, splits = D.FINISH_COLS + 1, 385, 4
+    assert D.valid_splits(in_, splits) and not D.valid_splits(in_, 3)
+    assert D.work_bytes(splits, 1, out) < D.work_bytes(splits, 16, out)
+    p = F.problem(16, out, in_)
+    qw = q8.QWeight4(dev(p.w))
+    bias = dev(p.bias)
+    x1, x16 = qrows(p, 4, 1), qrows(p, 4)
+    torch.cuda.synchronize()
+    assert qw._decode_work is None
+    y1 = q8.qlinear_decode(x1, qw, bias, splits=splits)
+    first = qw._decode_work
+    assert first.numel() >= D.work_bytes(splits, 1, out) and first.numel() < D.work_bytes(splits, 16, out)
+    y16 = q8.qlinear_decode(x16, qw, bias, splits=splits)
+    second = qw._decode_work
+    assert second is not first and second.numel() >= D.work_bytes(splits, 16, out)
+    assert q8.last_launch_q4d() == F.plan(16, out, in_, splits=splits, cus=cus)[0]
+    torch.cuda.synchronize()
+    want = F.want_of(p, True, False, False)
+    assert same_bits(y1.cpu().numpy(), want[:1]) and same_bits(y16.cpu().numpy(), want)
+    again = q8.qlinear_decode(x1, qw, bias, splits=splits)
+    assert qw._decode_work is second
+    assert same_bits(again.cpu().numpy(), want[:1])
+    qw.close()
+
+
+@pytest.mark.parametrize("splits", [0, 3], ids=["own-choice", "forced-3"])
+def test_reserve_decode_is_enough_for_every_row_count_on_both_outputs(splits, cus):
+    """After reserve_decode() no call of 1 - 16 rows replaces the workspace, on a shape whose own split count -- and with it
+    the plan's work_bytes -- varies with the rows, and is not the int8 plan's (tests/test_q4d_coverage.py): QWeight4 shares
+    the workspace code with QWeight and has to bring its own plan to it."""
+    from how_to_optimize_gemm_amd import q8
+    out, in_ = F.RESERVE_SHAPE
+    mine = [F.plan(rows, out, in_, splits=splits, cus=cus)[1] for rows in range(1, F.MAX_ROWS + 1)]
+    assert len(set(mine)) >= 4
+    if splits == 0:
+        assert mine != [D.plan(rows, out, in_, cus=cus)[1] for rows in range(1, F.MAX_ROWS + 1)]
+    p = F.problem(F.MAX_ROWS, out, in_)
+    P = F.pack_ref(p.W)
+    qw = q8.QWeight4(dev(p.w))
+    bias = dev(p.bias)
+    assert qw._decode_work is None
+    qw.reserve_decode(splits=splits)
+    reserved = qw._decode_work
+    assert reserved.numel() >= max(mine)
+    for rows in range(1, F.MAX_ROWS + 1):
+        x = qrows(p, 8, rows)
+        y = q8.qlinear_decode(x, qw, bias, splits=splits)
+        assert q8.last_launch_q4d() == F.plan(rows, out, in_, splits=splits, cus=cus)[0]
+        yq = q8.qlinear_decode(x, qw, bias, out_scale=dev(p.so[:rows]), splits=splits)
+        assert q8.last_launch_q4d() == F.plan(rows, out, in_, True, (out + 15) & ~15, splits=splits, cus=cus)[0]
+        assert qw._decode_work is reserved and qw._decode_work.data_ptr() == reserved.data_ptr(), rows
+        assert same_bits(y.cpu().numpy(), F.want(p.xq[:rows], p.rx[:rows], P, in_, p.rw, p.bias))
+        assert np.array_equal(yq.q.cpu().numpy(), F.want(p.xq[:rows], p.rx[:rows], P, in_, p.rw, p.bias, False, p.so[:rows]))
+    qw.close()
+
+
+def test_from_image_refuses_what_the_kernel_cannot_read():
+    """QWeight4.from_image on a wrong packed row count, a row pitch that is no multiple of 4, a base 2 bytes off, and factors
+    on the host, of another dtype or strided: ERR_INVALID_ARG each, nothing launched; the same memory laid out right is taken."""
+    import torch
+    import how_to_optimize_gemm_amd as H
+    from how_to_optimize_gemm_amd import q8
+    out, in_ = 130, 129
+    prow = F.layout(out, in_)[1]
+    flat = torch.zeros((16 + (prow + 1) * 136,), dtype=torch.uint8, device="cuda")
+    rw = torch.ones((2 * out,), dtype=torch.float32, device="cuda")
+
+    def image(rows=prow, pitch=136, base=16):
+        return torch.as_strided(flat, (rows, out), (pitch, 1), base)
+
+    assert prow == 128 and flat.data_ptr() % 16 == 0
+    good = q8.QWeight4.from_image(image(), rw[:out], out, in_)
+    assert (good.pitch, good.scale, good._ptrs[0]) == (136, None, flat.data_ptr() + 16)
+    for what, p, r in (("a packed row too many", image(rows=prow + 1), rw[:out]),
+                       ("a packed row short", image(rows=prow - 1), rw[:out]),
+                       ("a pitch of 134", image(pitch=134), rw[:out]),
+                       ("a base off by 2", image(base=18), rw[:out]),
+                       ("factors on the host", image(), rw[:out].cpu()),
+                       ("float64 factors", image(), rw[:out].double()),
+                       ("strided factors", image(), rw[::2]),
+                       ("too few factors", image(), rw[:out - 1])):
+        with pytest.raises(H.MMultError) as e:
+            q8.QWeight4.from_image(p, r, out, in_)
+        assert e.value.status == H.ERR_INVALID_ARG, (what, str(e.value))
