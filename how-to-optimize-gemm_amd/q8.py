@@ -11,6 +11,8 @@
     y = q8.qlinear_decode(xq, qw, bias)                # 1 - 16 rows (libmmult_hip_q8d.so): split-K strips, the same bits as qlinear
     qw4 = q8.QWeight4(linear.weight.detach())          # 4-bit weights (W4A8, libmmult_hip_q4d.so): packed nibbles, half the bytes
     y = q8.qlinear_decode(xq, qw4, bias)               # ... for 1 - 16 rows only: there are no 4-bit tiles
+    mlp4 = q8.QMLP([qw4a, qw4b], biases, decode=True)  # a stack may hold QWeight4s (mixed with QWeights) with decode=True only:
+                                                       # calibrate / forward take 1 - 16 rows, more raise ERR_UNSUPPORTED
 
 The binding is read from include/mmult_hip_q8.h (abi_header.parse); the numeric contract is in that header.  The int8-output
 library is loaded on first use, its binding read from include/mmult_hip_q8o.h.  Everything runs
@@ -493,6 +495,7 @@ def _run(library: _Library, name: str, args, device: int, time):
 def _linear_s8o(what, x: QRows, qweight, bias, activation, so, inv, out=None, time=None):
     """mmh_q8o_linear (time = (warmup, reps): mmh_time_q8o_linear) on a QRows with the output scales `so` and their
     reciprocals `inv` (rows floats each): the QRows of the output, in `out` or in new rows of pitch out_features rounded up to 16."""
+    _no_tiles4(what, qweight)   # (its packed image is not the (in_features, pitch) image this kernel reads)
     act = _activation_id(activation, what)
     rows, pxq, ldq, prx = _rows_args(what, x, qweight)
     n = qweight.out_features
@@ -660,7 +663,8 @@ def _make_qmlp_class():
         """A stack of linear layers in int8, inference only: one row quantiser, then int8 -> int8 for every hidden layer (the
         GEMM's epilogue writes the next layer's rows: no fp32 activation ever reaches memory), then int8 -> fp32 for the last.
         The hidden activations are quantised with one static scale per layer (`out_scales`): calibrate(x) measures them, or
-        set them by hand.  `activation` follows every hidden layer, `last_activation` the last."""
+        set them by hand.  `activation` follows every hidden layer, `last_activation` the last.  A stack that holds a QWeight4
+        needs decode=True and takes at most 16 rows per call, in forward and in calibrate: 4-bit weights have no tile path."""
 
         def __init__(self, qweights, biases=None, activation="relu", last_activation=None, decode=False):
             super().__init__()
@@ -670,6 +674,9 @@ def _make_qmlp_class():
             self.qweights = list(qweights)
             if not self.qweights:
                 raise MMultError(ERR_INVALID_ARG, "QMLP", "need at least one QWeight")
+            self._four = any(isinstance(q, QWeight4) for q in self.qweights)   # every call goes through qlinear_decode
+            if self._four and not self.decode:
+                raise MMultError(ERR_INVALID_ARG, "QMLP", "a QWeight4 in the stack needs decode=True (4-bit weights have no tile path)")
             biases = list(biases) if biases is not None else [None] * len(self.qweights)
             for a, b in zip(self.qweights, self.qweights[1:]):
                 if a.out_features != b.in_features or a.device != b.device:
@@ -712,6 +719,9 @@ def _make_qmlp_class():
             if x.requires_grad:
                 raise MMultError(ERR_INVALID_ARG, "QMLP", "the int8 layers have no backward: x requires grad")
             rows = x.reshape(-1, self.in_features)
+            if self._four and rows.shape[0] > Q4D_MAX_ROWS:   # before anything is launched
+                raise MMultError(ERR_UNSUPPORTED, "QMLP", f"the stack holds 4-bit weights: at most {Q4D_MAX_ROWS} rows per call -- there "
+                                 "are no 4-bit tiles for larger batches")
             if rows.shape[0] > 1 and rows.shape[1] > 1 and rows.stride(1) != 1:
                 rows = rows.contiguous()
             return rows
@@ -729,11 +739,13 @@ def _make_qmlp_class():
 
         def calibrate(self, x):
             """Run the layers with fp32 outputs on `x` and set each hidden layer's output scale to scale_of_amax of the
-            largest finite |h| it produced.  Returns the scales."""
+            largest finite |h| it produced.  Returns the scales.  At most 16 rows of a decode=True stack go through
+            qlinear_decode (the same bits; the only route of a QWeight4)."""
             h = self._rows(x)
+            layer = qlinear_decode if self.decode and h.shape[0] <= Q8D_MAX_ROWS else qlinear
             scales = []
             for i, qw in enumerate(self.qweights[:-1]):
-                h = qlinear(h, qw, self._bias(i), self.activation)
+                h = layer(h, qw, self._bias(i), self.activation)
                 a = h.abs()
                 amax = torch.where(torch.isfinite(a), a, torch.zeros_like(a)).max().item() if h.numel() else 0.0
                 scales.append(scale_of_amax(amax))

@@ -1,6 +1,7 @@
-"""A seeded, stratified differential fuzz of the three int8 layer libraries (libmmult_hip_q8.so, _q8o.so, _q8d.so) and the Python
-objects above them (q8.QWeight, QRows, qlinear, qlinear_decode) against the numpy contracts the tables already use:
-tests/qlinear_ref.py, tests/qchain_ref.py, tests/qdecode_ref.py.  (Shared test code: see tests/bitcmp.py.)
+"""A seeded, stratified differential fuzz of the three int8 layer libraries (libmmult_hip_q8.so, _q8o.so, _q8d.so), of the 4-bit
+decode library (libmmult_hip_q4d.so) and of the Python objects above them (q8.QWeight, QWeight4, QRows, qlinear, qlinear_decode)
+against the numpy contracts the tables already use: tests/qlinear_ref.py, tests/qchain_ref.py, tests/qdecode_ref.py,
+tests/q4_ref.py.  (Shared test code: see tests/bitcmp.py.)
 
 The tables (tests/test_gpu_qlinear.py, test_gpu_qchain.py, test_gpu_q8o_table.py, test_gpu_qdecode.py) are thorough along each
 axis but rotate their axes in lock-step; here the axes meet: shapes, the layouts of five windows, epilogues, forced split
@@ -20,6 +21,12 @@ The forms of a case (run_case):
   F4  q8.qlinear(QRows, ..., out=int8 window, out_scale) requant_ref and inv_scale_ref; on quantize(x)'s default rows and on F1's
   F5  F4's QRows in place into QWeight(w2)               qlinear_s8_ref of the reference's bytes -- or _rows_args' refusal
   F6  q8.qlinear_decode (rows <= 16), both outputs       the same bits; a forced split count with an empty range is refused
+  F7  the 4-bit weight (rows <= 16, libmmult_hip_q4d.so), on F6's rows, windows and split count:
+      pack   q8.QWeight4(w) -- w a row-strided window in every second decode case -- every byte of the image, scale, inv_scale
+      fp32 / int8   q8.qlinear_decode on it              tests/q4_ref.py's contract on the reference's packed image; the int8
+                                                         output under out_scales() of the 4-bit reference's OWN fp32 result
+      image  the packed bytes in a poisoned uint8 window through QWeight4.from_image: F7 fp32's and int8's bits, the window
+             unchanged -- or from_image's refusal of a pitch or base the kernel cannot read in dwords
 After every launching call the library's last_launch text is the text of its own plan function for that layout."""
 import collections
 import types
@@ -27,6 +34,7 @@ import zlib
 
 import numpy as np
 
+import q4_ref as P4
 import qchain_ref as Q
 import qdecode_ref as D
 import qlinear_ref as R
@@ -180,10 +188,16 @@ def layout(c):
     L.decode = c.rows <= D.MAX_ROWS
     L.splits_ok = not (c.in_ > 0 and c.splits > 0 and not D.valid_splits(c.in_, c.splits))
     L.decode_ld = L.rows_ld if L.rows_ok else L.default_ld
+    # F7: QWeight4 reads w in a row-strided window (x's: ldx_pad, off_x) in every second decode case -- strata 4 and 5 draw their
+    # row counts 1, 8, 15, 6, ... in turn, so an even count is every second of them; the packed image goes into a uint8 window
+    # of the int8 output's pitch and base, which from_image adopts where the kernel can read it in dwords (in == 0: no packed
+    # rows, nothing is read, any window is taken)
+    L.w4_strided = L.decode and c.rows % 2 == 0
+    L.image_ok = c.in_ == 0 or (L.ldyq % 4 == 0 and c.off_yq % 4 == 0)
     return L
 
 
-# form: F1 ... F6 and which call of it; lib: "q8" / "q8o" / "q8d"; args: the plan function's; part: "quantiser" / "gemm" / "all" of
+# form: F1 ... F7 and which call of it; lib: "q8" / "q8o" / "q8d" / "q4d"; args: the plan function's; part: "quantiser" / "gemm" / "all" of
 # mmh_q8_linear_plan's text
 Call = collections.namedtuple("Call", "form lib args part")
 
@@ -204,7 +218,10 @@ def calls(c):
         out.append(Call("F5", "q8", (c.rows, c.out2, c.out, c.out, L.ldy2_call, 0, L.y16, c.bias, c.relu), "gemm"))
     if L.decode and L.splits_ok:
         out += [Call("F6 fp32", "q8d", (c.rows, c.out, c.in_, L.decode_ld, False, L.ldy, L.y16, c.splits), "all"),
-                Call("F6 int8", "q8d", (c.rows, c.out, c.in_, L.decode_ld, True, L.ldyq, L.yq16, c.splits), "all")]
+                Call("F6 int8", "q8d", (c.rows, c.out, c.in_, L.decode_ld, True, L.ldyq, L.yq16, c.splits), "all"),
+                # (the image F7 runs a second time on has its own pitch; the plan's text does not depend on it)
+                Call("F7 fp32", "q4d", (c.rows, c.out, c.in_, L.decode_ld, False, L.ldy, L.y16, c.splits), "all"),
+                Call("F7 int8", "q4d", (c.rows, c.out, c.in_, L.decode_ld, True, L.ldyq, L.yq16, c.splits), "all")]
     return out
 
 
@@ -221,29 +238,35 @@ def library_plan(call, cus):
         return _part(text, call.part), scratch
     if call.lib == "q8o":
         return q8.qlinear_s8o_plan(a[0], a[1], a[2], ldq=a[3], ldyq=a[4], yq_mod4=a[5], cu_count=cus), None
-    return q8.qlinear_decode_plan(a[0], a[1], a[2], ldq=a[3], out8=a[4], ldo=a[5], o_mod16=a[6], splits=a[7], cu_count=cus)
+    plan = q8.qlinear_decode4_plan if call.lib == "q4d" else q8.qlinear_decode_plan
+    return plan(a[0], a[1], a[2], ldq=a[3], out8=a[4], ldo=a[5], o_mod16=a[6], splits=a[7], cu_count=cus)
 
 
 def python_plan(call, cus):
-    """library_plan from the Python restatements: qlinear_ref.plan_text, qchain_ref.plan_text_s8o, qdecode_ref.plan."""
+    """library_plan from the Python restatements: qlinear_ref.plan_text, qchain_ref.plan_text_s8o, qdecode_ref.plan, q4_ref.plan."""
     a = call.args
     if call.lib == "q8":
         text, scratch = R.plan_text(*a, cus)
         return _part(text, call.part), scratch
     if call.lib == "q8o":
         return Q.plan_text_s8o(a[0], a[1], a[4], a[5], cus), None
-    return D.plan(a[0], a[1], a[2], a[4], a[5], a[6], a[7], cus)[:2]
+    return (P4.plan if call.lib == "q4d" else D.plan)(a[0], a[1], a[2], a[4], a[5], a[6], a[7], cus)[:2]
 
 
 # ---- inputs and expectations ------------------------------------------------------------------------------------------------------
-Inputs = collections.namedtuple("Inputs", "x w w2 bias bias2 planted")   # planted: special name -> the row / channel / positions
+# planted: special name -> the row / channel / positions; ties4: the channel of w that holds W4_TIES, or None
+Inputs = collections.namedtuple("Inputs", "x w w2 bias bias2 planted ties4")
+# a channel of w for the 4-bit quantiser (decode cases of in >= 4): its maximum 3.5, so that the scale is 7 / 3.5 = 2 exactly, and
+# values that come to halves -- 0.5 and 2.5, where round-half-even and round-half-away part, and -1.5, where they agree
+W4_TIES = (3.5, 0.25, -0.75, 1.25)
 
 
 def inputs(c):
     """x ~ 3 N(0, 1), w and w2 ~ U(-0.5, 0.5), the biases ~ U(-4, 4) (test_gpu_qlinear.problem's distributions), seeded by the case's
     fields; then c.specials at random positions: "x:<kind>" / "w:<kind>" one of qlinear_ref.special_rows as a row of x / a channel of
     w; "bias:NaN", "bias:+-inf", "bias:-0.0", "bias:+-1e6" those values in the bias; "bias:ties" (in == 0, where y is the bias) 127
-    and values that scale_factor brings to halves."""
+    and values that scale_factor brings to halves.  Last, drawing nothing: W4_TIES in the first columns of one other channel of w
+    where the case runs F7 (rows <= 16, in >= 4, a channel free of the "w:" special)."""
     rng = np.random.default_rng(zlib.crc32(repr(tuple(c)).encode()))
     x = (rng.standard_normal((c.rows, c.in_)) * 3).astype(np.float32)
     w = rng.uniform(-0.5, 0.5, (c.out, c.in_)).astype(np.float32)
@@ -265,12 +288,19 @@ def inputs(c):
             at = [free.pop() for _ in values[:len(free)]]
             bias[at] = values[:len(at)]
             planted[name] = at
-    return Inputs(x, w, w2, bias, bias2, planted)
+    ties4 = None
+    if c.rows <= D.MAX_ROWS and c.in_ >= len(W4_TIES):
+        taken = [r for n, r in planted.items() if n.startswith("w:")]
+        ties4 = next((ch for ch in (free[::-1] if free else range(c.out)) if ch not in taken), None)
+        if ties4 is not None:
+            w[ties4, :len(W4_TIES)] = W4_TIES
+    return Inputs(x, w, w2, bias, bias2, planted, ties4)
 
 
 # the reference's rules, by name: a test swaps one for a wrong one to show that the case list tells the two apart
 RULES = types.SimpleNamespace(quantize_rows_ref=R.quantize_rows_ref, int_sums=R.int_sums, epilogue_ref=R.epilogue_ref,
-                              requant_ref=Q.requant_ref, inv_scale_ref=Q.inv_scale_ref, qlinear_s8_ref=Q.qlinear_s8_ref)
+                              requant_ref=Q.requant_ref, inv_scale_ref=Q.inv_scale_ref, qlinear_s8_ref=Q.qlinear_s8_ref,
+                              quantize4_ref=P4.quantize4_ref, pack_ref=P4.pack_ref, unpack_ref=P4.unpack_ref)
 
 
 def _sums(rules, qx, qw):
@@ -290,7 +320,9 @@ def out_scales(c, y):
 
 def expected(c, inp, rules=RULES):
     """One entry per form: F1 (q, scale, inv_scale); F2 y, F3 the same array; F4 (yq, inv_scale, so); F5 y2; F6 (y, yq) -- decode
-    promises the tile path's bits -- or None above 16 rows."""
+    promises the tile path's bits -- or None above 16 rows; F7 (image uint8 (packed rows, out), scale, inv_scale, y4, yq4, so4) or
+    None above 16 rows: q4_ref.want's steps, rule by rule (tests/test_q8_fuzz_cases.py holds the two to each other), on the
+    reference's rows and the reference's packed image, so4 = out_scales() of y4 itself."""
     qx, sx, rx = rules.quantize_rows_ref(inp.x)
     qw, _, rw = rules.quantize_rows_ref(inp.w)
     y = rules.epilogue_ref(_sums(rules, qx, qw), rx, rw, inp.bias if c.bias else None, c.relu)
@@ -298,7 +330,15 @@ def expected(c, inp, rules=RULES):
     yq, inv = rules.requant_ref(y, so), rules.inv_scale_ref(so)
     w2, b2 = (inp.w2, inp.bias2) if c.out2 != 1 else (np.concatenate([inp.w2, inp.w2]), np.concatenate([inp.bias2, inp.bias2]))
     y2 = rules.qlinear_s8_ref(yq, inv, w2, b2 if c.bias else None, c.relu)[:, :c.out2].copy()
-    return {"F1": (qx, sx, rx), "F2": y, "F3": y, "F4": (yq, inv, so), "F5": y2, "F6": (y, yq) if c.rows <= D.MAX_ROWS else None}
+    f7 = None
+    if c.rows <= D.MAX_ROWS:
+        q4, s4, r4 = rules.quantize4_ref(inp.w)
+        image = rules.pack_ref(np.ascontiguousarray(q4.T))
+        w4 = np.ascontiguousarray(rules.unpack_ref(image, c.in_).T)   # (out, in): int_sums' layout
+        y4 = rules.epilogue_ref(_sums(rules, qx, w4), rx, r4, inp.bias if c.bias else None, c.relu)
+        so4 = out_scales(c, y4)
+        f7 = (image, s4, r4, y4, rules.requant_ref(y4, so4), so4)
+    return {"F1": (qx, sx, rx), "F2": y, "F3": y, "F4": (yq, inv, so), "F5": y2, "F6": (y, yq) if c.rows <= D.MAX_ROWS else None, "F7": f7}
 
 
 # ---- the GPU runner ---------------------------------------------------------------------------------------------------------------
@@ -341,7 +381,8 @@ def _bytes_differ(got, want):
 
 def run_case(c, cus, tally=None):
     """Run every form of the case on the current device.  Returns the list of failures (strings), never stopping at the first;
-    tally, a dict, counts "forms" run and "refusals" checked.  A HIP error is not a failure of a form: it is raised."""
+    tally, a dict, counts "forms" run, "F7" those of them that are a layer call on a 4-bit weight, and "refusals" checked.  A HIP
+    error is not a failure of a form: it is raised."""
     import torch
     import how_to_optimize_gemm_amd as H
     from how_to_optimize_gemm_amd import q8
@@ -358,12 +399,12 @@ def run_case(c, cus, tally=None):
     def ran(n=1, key="forms"):
         tally[key] = tally.get(key, 0) + n
 
-    def launched(form, text):
-        if text != plans[form]:
-            fail(form, f"launched {text!r}, the plan says {plans[form]!r}")
+    def launched(form, text, plan=None):
+        if text != plans[plan or form]:
+            fail(form, f"launched {text!r}, the plan says {plans[plan or form]!r}")
 
     def refusal(form, call, texts_before):
-        """`call` must raise MMultError(ERR_INVALID_ARG) and launch nothing: texts_before are the three last_launch texts."""
+        """`call` must raise MMultError(ERR_INVALID_ARG) and launch nothing: texts_before are the four last_launch texts."""
         ran(key="refusals")
         try:
             call()
@@ -374,7 +415,7 @@ def run_case(c, cus, tally=None):
                 fail(form, f"refused with status {e.status}, not MMH_ERR_INVALID_ARG: {e}")
         else:
             fail(form, "was not refused")
-        if (q8.last_launch(), q8.last_launch_q8o(), q8.last_launch_q8d()) != texts_before:
+        if texts() != texts_before:
             fail(form, "a refused call changed a last_launch text")
 
     def attempt(form, call):
@@ -388,7 +429,7 @@ def run_case(c, cus, tally=None):
             return None
 
     def texts():
-        return q8.last_launch(), q8.last_launch_q8o(), q8.last_launch_q8d()
+        return q8.last_launch(), q8.last_launch_q8o(), q8.last_launch_q8d(), q8.last_launch_q4d()
 
     def device_bias(values, n):
         if not c.bias:
@@ -410,6 +451,10 @@ def run_case(c, cus, tally=None):
             fail(form, "wrote outside the window")
         return got
 
+    def f7_ran():
+        ran()
+        ran(key="F7")
+
     def check_i8(form, flat, view, got_rows, want, want_inv, same_as=None):
         if got_rows.q.data_ptr() != view.data_ptr():
             fail(form, "the returned QRows is not the window")
@@ -424,7 +469,7 @@ def run_case(c, cus, tally=None):
             fail(form, "wrote outside the window")
         return got
 
-    qw = qw2 = None
+    qw = qw2 = qw4 = None
     try:
         empty = lambda n: torch.full((n, 4), float("nan"), device="cuda")[:, :0]   # an (n, 0) window with a row stride
         qw = q8.QWeight(torch.from_numpy(inp.w).cuda() if c.in_ else empty(c.out))
@@ -539,8 +584,82 @@ def run_case(c, cus, tally=None):
                 torch.cuda.synchronize()
                 if not bool(torch.isnan(yflat).all()) or not bool((oflat == POISON).all()):
                     fail("F6", "a refused call wrote to its output")
+
+        # F7: the 4-bit weight -- the packer, the layer on F6's rows and windows, the same image adopted from a poisoned window
+        if L.decode:
+            image, want_s4, want_r4, want_y4, want_yq4, so4 = exp["F7"]
+            want_inv4 = RULES.inv_scale_ref(so4)
+            if c.in_ == 0:
+                w_dev = empty(c.out)
+            elif L.w4_strided:
+                w_dev = _f32_window(c.out, c.in_, L.ldx, c.off_x, inp.w)[1][:, :c.in_]
+            else:
+                w_dev = torch.from_numpy(inp.w).cuda()
+            qw4 = attempt("F7 pack", lambda: q8.QWeight4(w_dev))
+            if qw4 is not None:
+                ran()
+                torch.cuda.synchronize()
+                pitch, prow, nbytes = P4.layout(c.out, c.in_)
+                want_p = np.zeros((prow, pitch), np.uint8)
+                want_p[:, :c.out] = image
+                if (qw4.pitch, tuple(qw4.p.shape), qw4.nbytes) != (pitch, (prow, pitch), nbytes):
+                    fail("F7 pack", f"pitch {qw4.pitch}, image {tuple(qw4.p.shape)}, {qw4.nbytes} bytes; the layout is {(pitch, prow, nbytes)}")
+                elif not np.array_equal(qw4.p.cpu().numpy(), want_p):
+                    fail("F7 pack", _bytes_differ(qw4.p.cpu().numpy(), want_p))
+                for name, g, w_ in (("scale", qw4.scale, want_s4), ("inv_scale", qw4.inv_scale, want_r4)):
+                    if not same_bits(g.cpu().numpy(), w_):
+                        fail("F7 pack", f"{name}:", first_difference(g.cpu().numpy()[None, :], w_[None, :]))
+
+            # the same bytes as a caller's image: from_image takes a window the kernel can read in dwords, and no other
+            prow = image.shape[0]
+            host = np.full(16 + c.off_yq + prow * L.ldyq + 64, POISON, np.uint8)
+            host[16 + c.off_yq:16 + c.off_yq + prow * L.ldyq].reshape(prow, L.ldyq)[:, :c.out] = image
+            pflat = torch.from_numpy(host).cuda()
+            assert pflat.data_ptr() % 16 == 0
+            pview = pflat[16 + c.off_yq:16 + c.off_yq + prow * L.ldyq].view(prow, L.ldyq)[:, :c.out]
+            r4_dev = torch.from_numpy(want_r4).cuda()
+            adopted = None
+            if L.image_ok:
+                adopted = attempt("F7 image", lambda: q8.QWeight4.from_image(pview, r4_dev, c.out, c.in_))
+            else:
+                refusal("F7 image", lambda: q8.QWeight4.from_image(pview, r4_dev, c.out, c.in_), texts())
+
+            def decode4(weight, out8):
+                if out8:
+                    return q8.qlinear_decode(rows_in, weight, db, act, out=ov[:, :c.out], out_scale=scale_arg(so4), splits=c.splits)
+                return q8.qlinear_decode(rows_in, weight, db, act, out=yv[:, :c.out], splits=c.splits)
+
+            first = {}   # F7 fp32's and F7 int8's bits: the adopted image has to give the same
+            for form, weight in (("F7", qw4), ("F7 image", adopted)):
+                if weight is None or rows_in is None:
+                    continue
+                if L.splits_ok:
+                    if attempt(form + " fp32", lambda: decode4(weight, False)) is not None:
+                        f7_ran()
+                        launched(form + " fp32", q8.last_launch_q4d(), "F7 fp32")
+                        torch.cuda.synchronize()
+                        got = check_f32(form + " fp32", yflat, yv, c.out, want_y4, first.get("fp32"))
+                        first.setdefault("fp32", ("F7 fp32", got))
+                    ov[:, :c.out] = POISON
+                    got = attempt(form + " int8", lambda: decode4(weight, True))
+                    if got is not None:
+                        f7_ran()
+                        launched(form + " int8", q8.last_launch_q4d(), "F7 int8")
+                        torch.cuda.synchronize()
+                        got = check_i8(form + " int8", oflat, ov, got, want_yq4, want_inv4, first.get("int8"))
+                        first.setdefault("int8", ("F7 int8", got))
+                elif weight is qw4:   # include/mmult_hip_q4d.h: MMH_ERR_INVALID_ARG where a range would be empty, no output touched
+                    ov[:, :c.out] = POISON
+                    refusal("F7 fp32", lambda: decode4(weight, False), texts())
+                    refusal("F7 int8", lambda: decode4(weight, True), texts())
+                    torch.cuda.synchronize()
+                    if not bool(torch.isnan(yflat).all()) or not bool((oflat == POISON).all()):
+                        fail("F7", "a refused call wrote to its output")
+            torch.cuda.synchronize()
+            if not np.array_equal(pflat.cpu().numpy(), host):
+                fail("F7 image", "the image's window changed")
     finally:
-        for weight in (qw, qw2):
+        for weight in (qw, qw2, qw4):
             if weight is not None:
                 weight.close()
     return fails

@@ -1,7 +1,8 @@
 """The int8 layers' differential fuzz on the GPU: tests/q8_fuzz.py's run_case on the seeded list cases(64, 2026, cus), one test per
 stratum (eight cases each), and tools/fuzz_q8.py once as a child process on another seed.  What the list reaches and what its
 oracle tells apart is held on the CPU by tests/test_q8_fuzz_cases.py; run_case holds every launch's last_launch text to the
-library's plan function, so the coverage proved there is the coverage reached here."""
+library's plan function, so the coverage proved there is the coverage reached here.  The cases of at most 16 rows run the 4-bit
+weight too (F7: libmmult_hip_q4d.so through q8.QWeight4 and qlinear_decode)."""
 import pytest
 
 import q8_fuzz as F
@@ -26,6 +27,8 @@ def test_every_case_of_the_stratum_is_the_contract_in_every_form(stratum, cus):
         failures += [f"case {F.STRATA * i + stratum}: {f}\n  {c}" for f in F.run_case(c, cus, tally)]
     assert not failures, f"{len(failures)} failures\n" + "\n".join(failures)
     assert tally["forms"] >= 3 * len(cases), tally   # F1, F2 and F4 at the least, in every case
+    if stratum in (4, 5):                             # F7: the 4-bit weight's layer on both outputs wherever the split count is valid
+        assert tally.get("F7", 0) >= 2 * sum(F.layout(c).splits_ok for c in cases), tally
 
 
 def test_the_tool_on_another_seed():

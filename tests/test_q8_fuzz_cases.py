@@ -14,7 +14,16 @@ Cases of the 64 whose expectation differs, per mutant, at 256 / 304 / 64 compute
     requant clamps at -128                                     16 / 16 / 16
     decode sums only the first split                           13 / 13 / 13
     inv_scale kept as a double reciprocal of the rounded scale 58 / 58 / 58
-The last one is read as: rx = 1 / (double)sx used unrounded in the epilogue's first product.  Rounded to float32 first, the double
+    4-bit: clamp to -8 .. 7                                     2 /  2 /  2    (of the 22 cases of at most 16 rows, which run F7)
+    4-bit: scale 8 / amax                                      20 / 20 / 20
+    4-bit: round half away from zero                           20 / 20 / 20    (q8_fuzz.W4_TIES; 2 without that channel)
+    4-bit: the nibble halves of a slice swapped in the image   20 / 20 / 20
+    4-bit: nibbles zero-extended                               20 / 20 / 20
+    4-bit: inf quantised to 0                                   2 /  2 /  2
+    4-bit: abs-max over non-finite elements too                 6 /  6 /  6
+F7 -- the 4-bit weight (libmmult_hip_q4d.so) on the list's decode cases -- has its own section at the end: the launch forms its
+texts reach, the two weight windows and both answers of QWeight4.from_image, its expectation against tests/q4_ref.py's want.
+The inv_scale mutant is read as: rx = 1 / (double)sx used unrounded in the epilogue's first product.  Rounded to float32 first, the double
 reciprocal IS the float32 quotient (53 >= 2 * 24 + 2 bits: the second rounding is innocuous) -- q8._scale_vectors relies on it --
 and that reading is asserted to differ nowhere."""
 import types
@@ -23,6 +32,7 @@ import numpy as np
 import pytest
 
 import built_lib
+import q4_ref as P4
 import q8_fuzz as F
 import qchain_ref as Q
 import qdecode_ref as D
@@ -278,8 +288,45 @@ def _epilogue_on_double_rx(acc, rx, rw, bias=None, relu=False):
 
 def _differs(a, b):
     """Two expectations differ in some form's bits."""
-    flat = lambda e: [np.asarray(v) for f in ("F1", "F2", "F4", "F5", "F6") if e[f] is not None for v in (e[f] if isinstance(e[f], tuple) else (e[f],))]
-    return any(not (np.array_equal(p, q) if p.dtype == np.int8 else same_bits(p, q)) for p, q in zip(flat(a), flat(b)))
+    flat = lambda e: [np.asarray(v) for f in ("F1", "F2", "F4", "F5", "F6", "F7") if e[f] is not None for v in (e[f] if isinstance(e[f], tuple) else (e[f],))]
+    return any(not (np.array_equal(p, q) if p.dtype in (np.int8, np.uint8) else same_bits(p, q)) for p, q in zip(flat(a), flat(b)))
+
+
+# ---- mutants of the 4-bit rules (tests/q4_ref.py: quantize4_ref, pack_ref, unpack_ref) ----------------------------------------------
+def _quantize4(low=-7.0, numerator=7.0, rounding=np.rint, inf_to_zero=False, finite_amax=True):
+    """quantize4_ref with one rule changed."""
+    def quantize(w):
+        w = np.ascontiguousarray(w, dtype=np.float32)
+        a = np.abs(w)
+        if finite_amax:
+            a = np.where(np.isfinite(a), a, np.float32(0))
+        with np.errstate(all="ignore"):
+            amax = [np.float32(r.max()) if r.size else np.float32(0) for r in a]
+            s = np.array([np.minimum(np.float32(numerator) / m, R.F32_MAX) if m > 0 else np.float32(1) for m in amax], np.float32)
+            t = w * s[:, None]
+            t = np.where(np.isnan(w) | (np.isinf(w) & inf_to_zero), np.float32(0), t)
+            r = np.fmin(np.fmax(rounding(t), np.float32(low)), np.float32(7))
+            inv = np.float32(1.0) / s
+        q = np.empty(w.shape, np.int8)
+        q[...] = r
+        return q, s, inv
+    return quantize
+
+
+def _pack_halves_swapped(W):
+    """pack_ref with the low nibble holding the second half of each slice."""
+    W = np.asarray(W, np.int8)
+    in_, n = W.shape
+    full = np.zeros((-(-in_ // P4.SLICE) * P4.SLICE, n), np.int8)
+    full[:in_] = W
+    swapped = full.reshape(-1, 2, P4.HALF, n)[:, ::-1].reshape(-1, n)
+    return P4.pack_ref(swapped)
+
+
+def _unpack_zero_extended(P, in_):
+    P = np.asarray(P, np.uint8)
+    p = P.reshape(P.shape[0] // P4.HALF, 1, P4.HALF, P.shape[1])
+    return np.concatenate([p & 15, p >> 4], 1).reshape(-1, P.shape[1]).astype(np.int8)[:in_]
 
 
 MUTANTS = {
@@ -289,7 +336,15 @@ MUTANTS = {
     "requant rounds half away from zero": lambda r: dict(requant_ref=_requant(_half_away, -127.0)),
     "requant clamps at -128": lambda r: dict(requant_ref=_requant(np.rint, -128.0)),
     "inv_scale kept as a double reciprocal of the rounded scale": lambda r: dict(quantize_rows_ref=_double_reciprocal(False), epilogue_ref=_epilogue_on_double_rx),
+    "4-bit: clamp to -8 .. 7": lambda r: dict(quantize4_ref=_quantize4(low=-8.0)),
+    "4-bit: scale 8 / amax": lambda r: dict(quantize4_ref=_quantize4(numerator=8.0)),
+    "4-bit: round half away from zero": lambda r: dict(quantize4_ref=_quantize4(rounding=_half_away)),
+    "4-bit: the nibble halves of a slice swapped in the image": lambda r: dict(pack_ref=_pack_halves_swapped),
+    "4-bit: nibbles zero-extended": lambda r: dict(unpack_ref=_unpack_zero_extended),
+    "4-bit: inf quantised to 0": lambda r: dict(quantize4_ref=_quantize4(inf_to_zero=True)),
+    "4-bit: abs-max over non-finite elements too": lambda r: dict(quantize4_ref=_quantize4(finite_amax=False)),
 }
+RULES_4BIT = {"quantize4_ref", "pack_ref", "unpack_ref"}   # a mutant of these alone changes F7 only: cases without F7 are not recomputed
 
 
 def _first_split_only(c, inp, rules, cus):
@@ -307,7 +362,8 @@ def _first_split_only(c, inp, rules, cus):
 def test_every_mutant_of_the_reference_differs_from_it_in_some_case(cus, table):
     counts = {}
     for name, swap in MUTANTS.items():
-        counts[name] = sum(_differs(F.expected(c, inp, mutate(rules, **swap(rules))), exp) for c, inp, rules, exp in table)
+        rows = [t for t in table if t[3]["F7"] is not None] if set(swap(None)) <= RULES_4BIT else table
+        counts[name] = sum(_differs(F.expected(c, inp, mutate(rules, **swap(rules))), exp) for c, inp, rules, exp in rows)
     name = "decode sums only the first split"
     counts[name] = 0
     for c, inp, rules, exp in table:
@@ -326,3 +382,135 @@ def test_every_mutant_of_the_reference_differs_from_it_in_some_case(cus, table):
         if "bias:ties" in c.specials:
             wrong = F.expected(c, inp, mutate(rules, requant_ref=_requant(_half_away, -127.0)))
             assert not np.array_equal(wrong["F4"][0], exp["F4"][0]), c
+
+
+# ---- F7: the 4-bit weight on the decode cases ----------------------------------------------------------------------------------------
+def _eligible(rows):
+    """The cases (or table rows) that run F7: at most 16 rows."""
+    return [r for r in rows if (r if isinstance(r, F.Case) else r[0]).rows <= D.MAX_ROWS]
+
+
+def test_the_4_bit_launches_reach_every_form_of_their_library(cus):
+    """The F7 launch texts of the list (q4_ref.plan; the test above holds it to mmh_q4d_linear_plan on every call): both finish
+    kernels, both store forms, the finish kernel alone, forced counts 1 - 3 and the plan's own choice above one range."""
+    el = _eligible(F.cases(N, SEED, cus))
+    assert len(el) >= 16 and all(c.rows <= 16 for c in el)                  # strata 4 and 5 whole, and what stratum 6 draws
+    q4d = [(c, k, t) for c in el for k, t in launching(c, cus) if k.lib == "q4d"]
+    assert all(k.form in ("F7 fp32", "F7 int8") for _, k, _ in q4d) and not any(k.lib == "q4d" for c in F.cases(N, SEED, cus)
+                                                                               if c.rows > 16 for k in F.calls(c))
+    splits_of = lambda t: int(t.split(" strips x ")[1].split(" splits")[0]) if "partial" in t else 0
+    want = {}
+    for out8 in ("false", "true"):
+        for stores in ("wide", "single"):
+            want[f"qdecode_finish_kernel<{out8}>, {stores} stores"] = any(
+                f"qdecode_finish_kernel<{out8}>," in t and t.endswith(f"{stores} stores") for _, _, t in q4d)
+        want[f"qdecode_finish_kernel<{out8}> alone"] = any(f"qdecode_finish_kernel<{out8}> alone" in t and c.in_ == 0 for c, _, t in q4d)
+    for forced in (1, 2, 3):
+        want[f"{forced} ranges forced"] = any(c.splits == forced and splits_of(t) == forced for c, _, t in q4d)
+    want["q4decode_partial_kernel"] = any(t.startswith("q4decode_partial_kernel, ") for _, _, t in q4d)
+    want["several strips"] = any("partial" in t and not t.startswith("q4decode_partial_kernel, 1 strips") for _, _, t in q4d)
+    missing = [name for name, reached in want.items() if not reached]
+    assert not missing, f"{cus} CUs: F7 does not reach {missing}"
+    own = {c for c, _, t in q4d if c.splits == 0 and splits_of(t) > 1}
+    assert len(own) >= 4, (cus, len(own))
+    both = [c for c in el if {k.form for k in F.calls(c)} >= {"F7 fp32", "F7 int8"}]
+    assert len(both) >= 16 and all(F.layout(c).splits_ok for c in both), len(both)
+    assert all(("F7 fp32" in {k.form for k in F.calls(c)}) == F.layout(c).splits_ok for c in el)
+
+
+def test_the_4_bit_forms_meet_both_weight_windows_and_both_answers_of_from_image(cus):
+    el = _eligible(F.cases(N, SEED, cus))
+    adopted = [c for c in el if F.layout(c).image_ok]
+    assert 2 * len(adopted) >= len(el) and len(el) - len(adopted) >= 4, (len(el), len(adopted))
+    # a refused window has a pitch or a base that is no multiple of 4; an adopted one of in > 0 has neither
+    for c in el:
+        L = F.layout(c)
+        assert L.image_ok == (c.in_ == 0 or ((c.out + c.ldyq_pad) % 4 == 0 and c.off_yq % 4 == 0)), c
+    assert any((c.out + c.ldyq_pad) % 4 and c.off_yq % 4 == 0 for c in el) and any(c.off_yq % 4 and (c.out + c.ldyq_pad) % 4 == 0 for c in el)
+    # the weight is read dense in one half and through a row-strided window in the other: exactly in turn in strata 4 and 5
+    decode = [c for i, c in enumerate(F.cases(N, SEED, cus)) if i % F.STRATA in (4, 5)]
+    assert [F.layout(c).w4_strided for c in decode] == [False, True] * (len(decode) // 2)
+    strided = [c for c in el if F.layout(c).w4_strided and c.in_ > 0]
+    assert len(strided) >= 6 and any(c.off_x % 4 for c in strided) and any(c.ldx_pad % 4 for c in strided) and \
+        any(c.off_x % 4 == 0 and (c.in_ + c.ldx_pad) % 4 == 0 for c in strided)
+    assert not any(F.layout(c).w4_strided for c in F.cases(N, SEED, cus) if c.rows > 16)
+
+
+def test_the_4_bit_expectation_is_q4_refs_want_on_the_references_image(cus, table):
+    """expected()'s F7 takes q4_ref.want's steps through the named rules, so that mutants can replace them; with the true rules it
+    IS q4_ref.want of the reference's rows and packed image (the int8 output under the scales of the 4-bit fp32 result), and its
+    image is the packed quantise4_ref of w."""
+    el = _eligible(table)
+    for c, inp, rules, exp in el:
+        qx, _, rx = exp["F1"]
+        image, s4, r4, y4, yq4, so4 = exp["F7"]
+        q, s, inv = P4.quantize4_ref(inp.w)
+        assert np.array_equal(image, P4.pack_ref(np.ascontiguousarray(q.T))) and image.dtype == np.uint8, c
+        assert image.shape == (P4.layout(c.out, c.in_)[1], c.out) and same_bits(s4, s) and same_bits(r4, inv), c
+        bias = inp.bias if c.bias else None
+        assert same_bits(y4, P4.want(qx, rx, image, c.in_, r4, bias, c.relu)), c
+        assert same_bits(so4, F.out_scales(c, y4)) and np.isfinite(so4).all() and (so4 > 0).all(), c
+        assert np.array_equal(yq4, P4.want(qx, rx, image, c.in_, r4, bias, c.relu, so4)) and yq4.dtype == np.int8, c
+        assert int(np.abs(q).max(initial=0)) <= 7, c
+    assert all(exp["F7"] is None for c, _, _, exp in table if c.rows > 16)
+    # the 4-bit result is not the 8-bit one: its own scales matter
+    assert sum(not same_bits(exp["F7"][5], exp["F4"][2]) for *_, exp in el) >= len(el) // 2
+    # the mutants' common base is the reference
+    for c, inp, _, exp in el[:6]:
+        q, s, inv = _quantize4()(inp.w)
+        assert np.array_equal(q, P4.unpack_ref(exp["F7"][0], c.in_).T) and same_bits(s, exp["F7"][1]) and same_bits(inv, exp["F7"][2])
+
+
+def test_the_4_bit_int8_expectation_saturates_where_the_scale_factor_says(cus, table):
+    """so4 is scale_factor x 127 / (the largest finite |y4| of the row or the matrix): at a factor of 1 or more that maximum
+    lands on +-127 (or is clamped there), at 0.5 no finite value passes 64.  A row (matrix) without a finite non-zero value has
+    no maximum to land anywhere, and a scale that was clamped to FLT_MAX brings it nowhere near."""
+    el = _eligible(table)
+    holds_127 = []
+    for c, _, _, exp in el:
+        y4, yq4 = exp["F7"][3], exp["F7"][4]
+        top = int(np.abs(yq4.astype(np.int16)).max())
+        holds_127.append(top == 127)
+        assert not (yq4 == -128).any(), c
+        if not (np.isfinite(y4) & (y4 != 0)).any() or (exp["F7"][5] == R.F32_MAX).any():
+            continue
+        if c.scale_factor >= 1:
+            assert top == 127, (c, top)
+        elif not np.isinf(y4).any():
+            assert top <= 64, (c, top)
+    assert sum(holds_127) >= 4 and holds_127.count(False) >= 2, holds_127
+
+
+def test_the_4_bit_special_values_reach_the_packed_image(cus, table):
+    """The case's "w:<kind>" channel and the W4_TIES channel as quantize4_ref must leave them, read back out of the image."""
+    seen, ties = set(), 0
+    for c, inp, _, exp in _eligible(table):
+        image, s4 = exp["F7"][0], exp["F7"][1]
+        W = P4.unpack_ref(image, c.in_)   # (in, out)
+        for name, at in inp.planted.items():
+            where, kind = name.split(":")
+            if where != "w":
+                continue
+            seen.add(kind)
+            q, v = W[:, at], inp.w[at]
+            finite = np.abs(np.where(np.isfinite(v), v, np.float32(0))).max()
+            assert same_bits(s4[at:at + 1], [P4.q4_scale_of_amax(finite)]), (c, name)
+            if kind == "all zero":
+                assert not q.any() and s4[at] == 1
+            elif kind == "NaN":
+                assert q[1] == 0 and np.abs(q).max() == 7
+            elif kind == "+-inf":
+                assert q[0] == 7 and q[2] == -7
+            elif kind == "max 1e-38":   # rint(1e-38 * FLT_MAX) = rint(3.4)
+                assert s4[at] == R.F32_MAX and q[3] == 3 and not np.delete(q, 3).any()
+            else:
+                assert kind == "-max" and (q == -7).all()
+        if inp.ties4 is not None:
+            ties += 1
+            assert inp.ties4 not in [r for n, r in inp.planted.items() if n.startswith("w:")] and s4[inp.ties4] == 2, c
+            assert W[:4, inp.ties4].tolist() == [7, 0, -2, 2], (c, W[:4, inp.ties4])      # 7, 0.5, -1.5, 2.5: half to even
+        else:
+            assert c.in_ < len(F.W4_TIES) or c.out == 1, c
+    assert seen == set(F.ROW_KINDS), set(F.ROW_KINDS) - seen
+    assert ties >= 12, ties
+    assert all(inp.ties4 is None for c, inp, _, _ in table if c.rows > 16)

@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
-"""Differential fuzz of the int8 linear layers on one GPU: libmmult_hip_q8.so, libmmult_hip_q8o.so, libmmult_hip_q8d.so and
-q8.QWeight / QRows / qlinear / qlinear_decode against the numpy contracts (tests/qlinear_ref.py, qchain_ref.py, qdecode_ref.py),
-bit for bit, on the seeded, stratified case list of tests/q8_fuzz.py: six forms per case (the row quantiser alone, the layer on
-fp32 rows, on quantised rows, with an int8 output, two layers chained in place, the small-batch layer on both outputs), guard
+"""Differential fuzz of the int8 linear layers on one GPU: libmmult_hip_q8.so, libmmult_hip_q8o.so, libmmult_hip_q8d.so,
+libmmult_hip_q4d.so and q8.QWeight / QWeight4 / QRows / qlinear / qlinear_decode against the numpy contracts (tests/qlinear_ref.py,
+qchain_ref.py, qdecode_ref.py, q4_ref.py), bit for bit, on the seeded, stratified case list of tests/q8_fuzz.py: seven forms per
+case (the row quantiser alone, the layer on fp32 rows, on quantised rows, with an int8 output, two layers chained in place, the
+small-batch layer on both outputs, and the same on 4-bit weights: the packer, both outputs, a caller-made image), guard
 bands around every window, the refusals the headers state, and after every launch the library's last_launch text against its own
 plan function at the device's CU count.  tests/test_gpu_q8_fuzz.py runs the same runner on cases(64, 2026, cus).
 usage: python tools/fuzz_q8.py [cases] [seed]   (cases: a multiple of 8; exit 1: failures, exit 2: a HIP error stopped the run)"""
@@ -28,5 +29,6 @@ for i, case in enumerate(q8_fuzz.cases(cases, seed, cus)):
     for f in failures:
         print(f"case {i} (stratum {i % q8_fuzz.STRATA}): {f}\n  {case}")
     bad += len(failures)
-print(f"int8 layer fuzz: {cases} cases, {tally.get('forms', 0)} forms run, {tally.get('refusals', 0)} refusals checked, {bad} failures")
+print(f"int8 layer fuzz: {cases} cases, {tally.get('forms', 0)} forms run ({tally.get('F7', 0)} of them on 4-bit weights), "
+      f"{tally.get('refusals', 0)} refusals checked, {bad} failures")
 sys.exit(1 if bad else 0)
