@@ -23,6 +23,8 @@ CSRC_Q8D = os.path.join(PKG_DIR, "csrc_q8d")
 Q8D_LIB = os.path.join(PKG_DIR, "libmmult_hip_q8d.so")   # the fourth: the int8 layer for 1 - 16 rows, split-K (include/mmult_hip_q8d.h)
 CSRC_Q4D = os.path.join(PKG_DIR, "csrc_q4d")
 Q4D_LIB = os.path.join(PKG_DIR, "libmmult_hip_q4d.so")   # the fifth: the 1 - 16 row layer on packed 4-bit weights (include/mmult_hip_q4d.h)
+CSRC_Q4G = os.path.join(PKG_DIR, "csrc_q4g")
+Q4G_LIB = os.path.join(PKG_DIR, "libmmult_hip_q4g.so")   # the sixth: the 4-bit layer with one scale per group of 128 (include/mmult_hip_q4g.h)
 HARNESS = os.path.join(PKG_DIR, "harness")
 ARCH = "gfx950"
 
@@ -147,6 +149,16 @@ def build_q4d_library(force: bool = False, verbose: bool = False) -> str:
                          os.path.join(CSRC_Q4D, "exports_q4d.map"), force=force, verbose=verbose)
 
 
+def build_q4g_library(force: bool = False, verbose: bool = False) -> str:
+    """csrc_q4g/*.hip -> how-to-optimize-gemm_amd/libmmult_hip_q4g.so: the q4d library's recipe with -I csrc_q4g in front (its
+    kernels sit on csrc_q8d/'s ring geometry and csrc_q4d/'s quantisation rules and plan geometry).  Objects under build/q4g/;
+    csrc_q4g/'s headers and mmult_hip_q4g.h make them stale too."""
+    return _build_shared(Q4G_LIB, _hip_sources(CSRC_Q4G), [CSRC_Q4G, CSRC_Q4D, CSRC_Q8D, CSRC_Q8O, CSRC_Q8, CSRC],
+                         _headers(CSRC_Q8, CSRC_Q8O, CSRC_Q8D, CSRC_Q4D, CSRC_Q4G,
+                                  c_headers=("mmult_hip_q8.h", "mmult_hip_q8o.h", "mmult_hip_q8d.h", "mmult_hip_q4d.h", "mmult_hip_q4g.h")),
+                         "q4g", os.path.join(CSRC_Q4G, "exports_q4g.map"), force=force, verbose=verbose)
+
+
 def build_timeline_library(force: bool = False) -> str:
     """-DMMH_AB_BUILD -DMMH_DMA_TIMELINE -> libmmult_hip_tl.so: the A/B library whose plain LDS-DMA kernels
     also write per-workgroup wall-clock stamps (tools/dma_timeline.py only; the stamps perturb the
@@ -179,6 +191,7 @@ def build_all(force: bool = False) -> None:
     build_q8o_library(force)
     build_q8d_library(force)
     build_q4d_library(force)
+    build_q4g_library(force)
     if os.path.isdir(HARNESS):
         build_harness(force)
 

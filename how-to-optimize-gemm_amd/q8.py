@@ -11,6 +11,8 @@
     y = q8.qlinear_decode(xq, qw, bias)                # 1 - 16 rows (libmmult_hip_q8d.so): split-K strips, the same bits as qlinear
     qw4 = q8.QWeight4(linear.weight.detach())          # 4-bit weights (W4A8, libmmult_hip_q4d.so): packed nibbles, half the bytes
     y = q8.qlinear_decode(xq, qw4, bias)               # ... for 1 - 16 rows only: there are no 4-bit tiles
+    qw4g = q8.QWeight4G(linear.weight.detach())        # ... with one scale per group of 128 input features (libmmult_hip_q4g.so):
+    y = q8.qlinear_decode(xq, qw4g, bias, splits=4)    # its own bit contract, which depends on the K partition -- force it to pin the bits
     mlp4 = q8.QMLP([qw4a, qw4b], biases, decode=True)  # a stack may hold QWeight4s (mixed with QWeights) with decode=True only:
                                                        # calibrate / forward take 1 - 16 rows, more raise ERR_UNSUPPORTED
 
@@ -81,14 +83,17 @@ _q8 = _Library("mmult_hip_q8.h", "libmmult_hip_q8.so", "mmh_q8")       # fp32 ou
 _q8o = _Library("mmult_hip_q8o.h", "libmmult_hip_q8o.so", "mmh_q8o")   # int8 out
 _q8d = _Library("mmult_hip_q8d.h", "libmmult_hip_q8d.so", "mmh_q8d")   # 1 - 16 rows, split-K
 _q4d = _Library("mmult_hip_q4d.h", "libmmult_hip_q4d.so", "mmh_q4d")   # 1 - 16 rows on packed 4-bit weights
+_q4g = _Library("mmult_hip_q4g.h", "libmmult_hip_q4g.so", "mmh_q4g")   # ... with one scale per group of 128 input features
 HEADER, LIB_PATH, CONSTANTS, PROTOTYPES = _q8.header, _q8.path, _q8.constants, _q8.prototypes
 EXPORTS = list(PROTOTYPES)   # every symbol include/mmult_hip_q8.h declares
 Q8O_HEADER, Q8O_LIB_PATH = _q8o.header, _q8o.path
 Q8D_HEADER, Q8D_LIB_PATH = _q8d.header, _q8d.path
 Q4D_HEADER, Q4D_LIB_PATH = _q4d.header, _q4d.path
+Q4G_HEADER, Q4G_LIB_PATH = _q4g.header, _q4g.path
 Q8D_MAX_ROWS = _q8d.constants["MMH_Q8D_MAX_ROWS"]
 Q4D_MAX_ROWS = _q4d.constants["MMH_Q4D_MAX_ROWS"]
-lib, lib_q8o, lib_q8d, lib_q4d = _q8.lib, _q8o.lib, _q8d.lib, _q4d.lib   # the loaded ctypes libraries
+Q4G_GROUP = _q4g.constants["MMH_Q4G_GROUP"]
+lib, lib_q8o, lib_q8d, lib_q4d, lib_q4g = _q8.lib, _q8o.lib, _q8d.lib, _q4d.lib, _q4g.lib   # the loaded ctypes libraries
 _check = _q8.check
 
 
@@ -110,6 +115,11 @@ def last_launch_q8d() -> str:
 def last_launch_q4d() -> str:
     """What the last qlinear_decode on a QWeight4 on this thread launched."""
     return _q4d.last_launch()
+
+
+def last_launch_q4g() -> str:
+    """What the last qlinear_decode on a QWeight4G on this thread launched."""
+    return _q4g.last_launch()
 
 
 def qlinear_s8o_plan(rows: int, out_features: int, in_features: int, ldq: int = 0, pitch_n: int = 0, ldyq: int = 0, xq_mod4: int = 0,
@@ -146,6 +156,21 @@ def qlinear_decode4_plan(rows: int, out_features: int, in_features: int, ldq: in
     _q4d.check(lib_q4d().mmh_q4d_linear_plan(rows, out_features, in_features, ldq or p16(in_features), pitch_n or p16(out_features),
                                              int(bool(out8)), ldo or (p16(out_features) if out8 else out_features), xq_mod4, wp_mod4,
                                              o_mod16, splits, cu_count, text, len(text), C.byref(work)), "mmh_q4d_linear_plan")
+    return text.value.decode(), work.value
+
+
+def qlinear_decode4g_plan(rows: int, out_features: int, in_features: int, ldq: int = 0, pitch_n: int = 0, out8: bool = False, ldo: int = 0,
+                          xq_mod4: int = 0, wp_mod4: int = 0, o_mod16: int = 0, splits: int = 0, cu_count: int = 256, pitch_s: int = 0,
+                          gs_mod16: int = 0):
+    """qlinear_decode_plan for a QWeight4G: (text, work bytes) of the call, what last_launch_q4g() says after it -- the K
+    partition its bits depend on.  The same arguments and defaults; pitch_n is the packed image's, pitch_s the group scales'
+    (0: out_features rounded up to 16), gs_mod16 their base modulo 16."""
+    p16 = lambda n: (n + 15) & ~15
+    text, work = C.create_string_buffer(192), C.c_size_t(0)
+    _q4g.check(lib_q4g().mmh_q4g_linear_plan(rows, out_features, in_features, ldq or p16(in_features), pitch_n or p16(out_features),
+                                             pitch_s or p16(out_features), int(bool(out8)),
+                                             ldo or (p16(out_features) if out8 else out_features), xq_mod4, wp_mod4, gs_mod16, o_mod16,
+                                             splits, cu_count, text, len(text), C.byref(work)), "mmh_q4g_linear_plan")
     return text.value.decode(), work.value
 
 
@@ -292,25 +317,33 @@ class QWeight4(_DecodeWork):
                                                  self.scale.data_ptr(), self.inv_scale.data_ptr(), _stream(self.device)), "mmh_q4d_pack_weight")
 
     @classmethod
-    def from_image(cls, p, inv_scale, out_features: int, in_features: int):
-        """Adopt a caller-made packed image: `p` uint8 (64 * ceil(in_features / 128), pitch >= out_features) on a GPU with unit
-        column stride, a row stride that is a multiple of 4 and a 4-byte aligned base, every nibble of an input feature >=
-        in_features zero (-8 is allowed); `inv_scale` a dense (out_features,) fp32 tensor, one factor per output channel.  `scale`
-        is None."""
+    def _adopt_image(cls, p, out_features: int, in_features: int):
+        """from_image's first half: a new object that holds the caller's packed image `p`, its device and its pitch."""
         import torch
         self = cls.__new__(cls)
         self.out_features, self.in_features = int(out_features), int(in_features)
         packed_rows = weight4_layout(self.out_features, self.in_features)[1]
         if not (torch.is_tensor(p) and p.is_cuda and p.dtype == torch.uint8 and p.dim() == 2 and p.shape[0] == packed_rows
                 and p.shape[1] >= self.out_features):
-            raise MMultError(ERR_INVALID_ARG, "QWeight4.from_image", f"p is a ({packed_rows}, >= {self.out_features}) uint8 tensor on a GPU")
+            raise MMultError(ERR_INVALID_ARG, cls.__name__ + ".from_image", f"p is a ({packed_rows}, >= {self.out_features}) uint8 tensor on a GPU")
         self.device = p.device.index
         self.pitch = int(p.shape[1])
         if packed_rows:
-            _, self.pitch = tensor_args(p, packed_rows, int(p.shape[1]), "QWeight4.from_image(p)", torch.uint8, self.device)
+            _, self.pitch = tensor_args(p, packed_rows, int(p.shape[1]), cls.__name__ + ".from_image(p)", torch.uint8, self.device)
             if self.pitch % 4 or p.data_ptr() % 4:
-                raise MMultError(ERR_INVALID_ARG, "QWeight4.from_image", "the kernel reads p in dwords: a row stride that is a multiple of 4 "
-                                 "and a 4-byte aligned base")
+                raise MMultError(ERR_INVALID_ARG, cls.__name__ + ".from_image", "the kernel reads p in dwords: a row stride that is a multiple "
+                                 "of 4 and a 4-byte aligned base")
+        self.p = p
+        return self
+
+    @classmethod
+    def from_image(cls, p, inv_scale, out_features: int, in_features: int):
+        """Adopt a caller-made packed image: `p` uint8 (64 * ceil(in_features / 128), pitch >= out_features) on a GPU with unit
+        column stride, a row stride that is a multiple of 4 and a 4-byte aligned base, every nibble of an input feature >=
+        in_features zero (-8 is allowed); `inv_scale` a dense (out_features,) fp32 tensor, one factor per output channel.  `scale`
+        is None."""
+        import torch
+        self = cls._adopt_image(p, out_features, in_features)
         if not (torch.is_tensor(inv_scale) and inv_scale.is_cuda and inv_scale.device.index == self.device and inv_scale.dtype == torch.float32
                 and inv_scale.dim() == 1 and inv_scale.shape[0] == self.out_features and (self.out_features <= 1 or inv_scale.stride(0) == 1)):
             raise MMultError(ERR_INVALID_ARG, "QWeight4.from_image", "inv_scale is a dense (out_features,) fp32 tensor on p's device")
@@ -338,6 +371,86 @@ class QWeight4(_DecodeWork):
 
     def close(self) -> None:
         self._decode_work = None
+
+
+class QWeight4G(QWeight4):
+    """A QWeight4 with ONE SCALE PER GROUP of 128 consecutive input features of every output channel (GPTQ / AWQ style), prepared
+    once from `w` (out_features, in_features) fp32 on a GPU.  Owns `p`, QWeight4's packed image byte for byte in layout, and
+    `group_scale` / `group_inv_scale`, fp32 (groups, pitch_s) with groups = ceil(in_features / 128) and pitch_s = out_features
+    rounded up to 16 (pad columns 0): 7 / max|w[j, 128 g : 128 g + 128]| and its reciprocal.  `scale` and `inv_scale` are None.
+    Read by qlinear_decode only, 1 - 16 rows, under include/mmult_hip_q4g.h's contract."""
+
+    _decode_plan = staticmethod(qlinear_decode4g_plan)
+
+    def __init__(self, w, group_size: int = 128, device=None):
+        import torch
+        if group_size != Q4G_GROUP:
+            raise MMultError(ERR_INVALID_ARG, "QWeight4G", f"group_size is {Q4G_GROUP}: a group is one slice of the packed image")
+        if w.dim() != 2:
+            raise MMultError(ERR_INVALID_ARG, "QWeight4G", "need a 2-D weight (out_features, in_features)")
+        self.group_size = Q4G_GROUP
+        self.device = w.device.index if device is None else int(device)
+        self.out_features, self.in_features = int(w.shape[0]), int(w.shape[1])
+        pw, ldw = tensor_args(w.detach(), self.out_features, self.in_features, "QWeight4G(w)", torch.float32, self.device)
+        self.pitch, packed_rows, groups, self.pitch_s, _, _ = weight4g_layout(self.out_features, self.in_features)
+        dev = f"cuda:{self.device}"
+        self.p = torch.empty((packed_rows, self.pitch), dtype=torch.uint8, device=dev)
+        self.group_scale = torch.empty((groups, self.pitch_s), dtype=torch.float32, device=dev)
+        self.group_inv_scale = torch.empty((groups, self.pitch_s), dtype=torch.float32, device=dev)
+        self.scale = self.inv_scale = None
+        _q4g.check(lib_q4g().mmh_q4g_pack_weight(self.device, self.out_features, self.in_features, pw, ldw, self.p.data_ptr(), self.pitch,
+                                                 self.group_scale.data_ptr(), self.group_inv_scale.data_ptr(), self.pitch_s,
+                                                 _stream(self.device)), "mmh_q4g_pack_weight")
+
+    @classmethod
+    def from_image(cls, p, group_inv_scale, out_features: int, in_features: int):
+        """Adopt caller-made operands: `p` as QWeight4.from_image takes it; `group_inv_scale` an fp32 (ceil(in_features / 128),
+        >= out_features) tensor on p's device with unit column stride, a row stride that is a multiple of 4 floats and a 16-byte
+        aligned base (the kernel reads four factors as one vector), one factor per group and output channel.  `group_scale` is None."""
+        import torch
+        self = cls._adopt_image(p, out_features, in_features)
+        groups = -(-self.in_features // Q4G_GROUP)
+        g = group_inv_scale
+        if not (torch.is_tensor(g) and g.is_cuda and g.device.index == self.device and g.dtype == torch.float32 and g.dim() == 2
+                and g.shape[0] == groups and g.shape[1] >= self.out_features):
+            raise MMultError(ERR_INVALID_ARG, "QWeight4G.from_image", f"group_inv_scale is a ({groups}, >= {self.out_features}) fp32 tensor on p's device")
+        self.pitch_s = int(g.shape[1])
+        if groups:
+            _, self.pitch_s = tensor_args(g, groups, int(g.shape[1]), "QWeight4G.from_image(group_inv_scale)", torch.float32, self.device)
+            if groups == 1 and g.stride(0) >= g.shape[1]:
+                self.pitch_s = int(g.stride(0))
+            if self.pitch_s % 4 or g.data_ptr() % 16:
+                raise MMultError(ERR_INVALID_ARG, "QWeight4G.from_image", "the kernel reads four group scales as one vector: a row stride that "
+                                 "is a multiple of 4 floats and a 16-byte aligned base")
+        self.group_size = Q4G_GROUP
+        self.scale = self.inv_scale = self.group_scale = None
+        self.group_inv_scale = g
+        return self
+
+    @property
+    def _ptrs(self):
+        """(image, None, group_inv_scale) addresses, as QWeight4's."""
+        return (self.p.data_ptr() if self.p.numel() else None, None, self.group_inv_scale.data_ptr() if self.group_inv_scale.numel() else None)
+
+    @property
+    def nbytes(self) -> int:
+        """The packed image's bytes plus the group scales' (the reciprocals: what the layer reads)."""
+        return int(self.p.shape[0]) * self.pitch + int(self.group_inv_scale.shape[0]) * self.pitch_s * 4
+
+    def dequantize(self):
+        """The fp32 (out_features, in_features) weight the layer multiplies by: unpack() times the groups' factors.  torch ops."""
+        import torch
+        n, k = self.out_features, self.in_features
+        r = self.group_inv_scale[:, :n].repeat_interleave(Q4G_GROUP, dim=0)[:k]
+        return (self.unpack()[:, :n].to(torch.float32) * r).t().contiguous()
+
+
+def weight4g_layout(out_features: int, in_features: int):
+    """(pitch, packed rows, groups, pitch_s, image bytes, scale bytes) of the library's own grouped 4-bit layout.  Host arithmetic only."""
+    pitch, rows, groups, pitch_s, image, scales = C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0), C.c_size_t(0), C.c_size_t(0)
+    _q4g.check(lib_q4g().mmh_q4g_weight_layout(int(out_features), int(in_features), C.byref(pitch), C.byref(rows), C.byref(groups),
+                                               C.byref(pitch_s), C.byref(image), C.byref(scales)), "mmh_q4g_weight_layout")
+    return pitch.value, rows.value, groups.value, pitch_s.value, image.value, scales.value
 
 
 def weight4_layout(out_features: int, in_features: int):
@@ -582,7 +695,7 @@ def _linear_q8d(what, x: QRows, qweight, bias, activation, so, inv, out=None, sp
     output, in `out` or in new rows of pitch out_features rounded up to 16.  The partials go through the weight's workspace."""
     act = _activation_id(activation, what)
     rows, pxq, ldq, prx = _rows_args(what, x, qweight)
-    four = isinstance(qweight, QWeight4)
+    four, grouped = isinstance(qweight, QWeight4), isinstance(qweight, QWeight4G)
     if rows > Q8D_MAX_ROWS:
         raise MMultError(ERR_UNSUPPORTED, what, _too_many_rows(qweight))
     n, k = qweight.out_features, qweight.in_features
@@ -595,12 +708,18 @@ def _linear_q8d(what, x: QRows, qweight, bias, activation, so, inv, out=None, sp
     pq, _, pr = qweight._ptrs
     work_bytes = 0
     if k > 0:
-        work_bytes = qweight._decode_plan(rows, n, k, ldq, qweight.pitch, out8, ldo, 0, pq % 4, po % 16, splits, _cu_count(qweight.device))[1]
+        extra = {"pitch_s": qweight.pitch_s, "gs_mod16": pr % 16} if grouped else {}
+        work_bytes = qweight._decode_plan(rows, n, k, ldq, qweight.pitch, out8, ldo, 0, pq % 4, po % 16, splits, _cu_count(qweight.device),
+                                          **extra)[1]
     work = qweight._decode_workspace(work_bytes) if k > 0 else None
-    args = (qweight.device, rows, n, k, pxq, ldq, prx, pq, qweight.pitch, pr, _bias_ptr(what, bias, qweight), act,
+    scales = (pr, qweight.pitch_s) if grouped else (pr,)   # one factor per group and channel, or one per channel
+    args = (qweight.device, rows, n, k, pxq, ldq, prx, pq, qweight.pitch, *scales, _bias_ptr(what, bias, qweight), act,
             so.data_ptr() if out8 else None, None if out8 else po, 0 if out8 else ldo, po if out8 else None, ldo if out8 else 0,
             work.data_ptr() if work is not None else None, work.numel() if work is not None else 0, splits)
-    ms = _run(_q4d, "q4d_linear", args, qweight.device, time) if four else _run(_q8d, "q8d_linear", args, qweight.device, time)
+    if grouped:
+        ms = _run(_q4g, "q4g_linear", args, qweight.device, time)
+    else:
+        ms = _run(_q4d, "q4d_linear", args, qweight.device, time) if four else _run(_q8d, "q8d_linear", args, qweight.device, time)
     if time is not None:
         return ms
     return QRows._of_window(out, inv[:rows], po, ldo) if out8 else out
@@ -628,7 +747,12 @@ def qlinear_decode(x, qweight: QWeight, bias=None, activation=None, out=None, ou
     strips x K ranges of workgroups (split-K; int32 partials add up exactly), a second kernel applies the epilogue.  x fp32 is
     quantised first with quantize(); a QRows is read in place.  More than 16 rows raise MMultError.  splits: 0 the plan's
     choice, > 0 that many K ranges.  The partials live in a workspace cached on `qweight`: it grows on demand, but not under
-    graph capture -- QWeight.reserve_decode() sizes it first."""
+    graph capture -- QWeight.reserve_decode() sizes it first.
+    A QWeight4G (libmmult_hip_q4g.so) has a bit contract of its own (include/mmult_hip_q4g.h): its partials are fp32 sums of
+    group terms, added in group order inside a K range and in range order across ranges, so THE BITS DEPEND ON THE PARTITION
+    (splits, k_len).  The partition is the plan's (qlinear_decode4g_plan: host arithmetic, no device needed); with splits=0 it
+    depends on the row count and on the device's CU count, so force `splits` to get the same bits at every batch size and on
+    every part."""
     x = _decode_rows("qlinear_decode", x, qweight)
     so = inv = None
     if out_scale is not None:
@@ -782,12 +906,15 @@ def _make_qlinear_class():
         fp32 buffer.  forward flattens leading dimensions to rows; an input that requires grad raises."""
 
         def __init__(self, in_features: int, out_features: int, bias: bool = True, activation=None, decode: bool = False,
-                     weight_bits: int = 8):
+                     weight_bits: int = 8, group_size=None):
             super().__init__()
             self.decode = bool(decode)   # batches of at most 16 rows go through qlinear_decode (the same bits)
             if weight_bits not in (8, 4) or (weight_bits == 4 and not decode):
                 raise MMultError(ERR_INVALID_ARG, "QLinear", "weight_bits is 8, or 4 with decode=True (4-bit weights have no tile path)")
+            if group_size is not None and (weight_bits != 4 or group_size != Q4G_GROUP):
+                raise MMultError(ERR_INVALID_ARG, "QLinear", f"group_size is None, or {Q4G_GROUP} with weight_bits=4 (a QWeight4G)")
             self.weight_bits = weight_bits   # 4: a QWeight4 -- every call goes through qlinear_decode, more than 16 rows are refused
+            self.group_size = group_size     # 128: a QWeight4G, one scale per group of 128 input features
             _activation_id(activation, "QLinear")
             self.in_features, self.out_features, self.activation = in_features, out_features, activation
             self.qweight = None
@@ -797,15 +924,16 @@ def _make_qlinear_class():
             """Prepare `w` (out_features, in_features) fp32 on a GPU; `bias` replaces the bias buffer's values."""
             if tuple(w.shape) != (self.out_features, self.in_features):
                 raise MMultError(ERR_INVALID_ARG, "QLinear.set_weight", f"need a ({self.out_features},{self.in_features}) weight")
-            self.qweight = QWeight4(w) if self.weight_bits == 4 else QWeight(w)
+            self.qweight = (QWeight4G(w, self.group_size) if self.group_size else QWeight4(w)) if self.weight_bits == 4 else QWeight(w)
             if self.bias is not None:
                 self.bias = (torch.zeros(self.out_features) if bias is None else bias.detach().to(torch.float32)).to(w.device).contiguous()
             return self
 
         @classmethod
-        def from_float(cls, linear, activation=None, decode=False, weight_bits=8):
-            """The int8 layer of a torch.nn.Linear whose weight lives on a GPU (weight_bits=4 with decode=True: 4-bit weights)."""
-            return cls(linear.in_features, linear.out_features, linear.bias is not None, activation, decode, weight_bits).set_weight(
+        def from_float(cls, linear, activation=None, decode=False, weight_bits=8, group_size=None):
+            """The int8 layer of a torch.nn.Linear whose weight lives on a GPU (weight_bits=4 with decode=True: 4-bit weights;
+            group_size=128 with them: one scale per group of 128 input features)."""
+            return cls(linear.in_features, linear.out_features, linear.bias is not None, activation, decode, weight_bits, group_size).set_weight(
                 linear.weight.detach(), None if linear.bias is None else linear.bias.detach())
 
         def forward(self, x):
@@ -837,4 +965,5 @@ __all__ = ["QWeight", "QLinear", "QRows", "QMLP", "quantize_rows", "quantize", "
            "qlinear_s8o_plan", "scale_of_amax", "last_launch", "last_launch_q8o", "lib", "lib_q8o", "EXPORTS", "LIB_PATH", "HEADER",
            "Q8O_LIB_PATH", "Q8O_HEADER", "qlinear_decode", "time_qlinear_decode", "qlinear_decode_plan", "last_launch_q8d", "lib_q8d",
            "Q8D_LIB_PATH", "Q8D_HEADER", "Q8D_MAX_ROWS", "QWeight4", "weight4_layout", "qlinear_decode4_plan", "last_launch_q4d", "lib_q4d",
-           "Q4D_LIB_PATH", "Q4D_HEADER", "Q4D_MAX_ROWS"]
+           "Q4D_LIB_PATH", "Q4D_HEADER", "Q4D_MAX_ROWS", "QWeight4G", "weight4g_layout", "qlinear_decode4g_plan", "last_launch_q4g", "lib_q4g",
+           "Q4G_LIB_PATH", "Q4G_HEADER", "Q4G_GROUP"]
